@@ -8,9 +8,11 @@ Workload (BASELINE.json configs[4], "C5"): 100 000 protein pairs, both lengths i
 core local semantics (SimpleLocalAligner), BLOSUM62, del 11 / ext 2.  The batch is fixed; with N > 1 the pairs are
 sharded over the ranks by balanced cells (LPT), so scaling is STRONG (total work fixed), as north_star asks
 ("scaling at 8 GPUs on a 100k-pair batch").  `--pairs` shrinks the batch for quick runs.
-At N = 1 the line also carries "end_to_end" (the same batch through aln_align_batch: host buffers in, host buffers out),
-the single-pair configuration (configs[3], 10k x 10k) as "single_pair", configs[1] and [2] as "configs", and the CPU oracle
+A plain run sets up, warms up, times `--steps` steps and prints the headline.  With `--full` and N = 1 the line also carries
+"end_to_end" (the same batch through aln_align_batch: host buffers in, host buffers out), the single-pair configuration
+(configs[3], 10k x 10k) as "single_pair", configs[1] and [2] as "configs", a fresh process's "cold_start", and the CPU oracle
 timed on a bounded sample ("cpu_baseline", all cores and one core; its results also check the GPU's on that sample).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 Launch: `python bench.py` (N=1) or
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N`.
@@ -35,6 +37,39 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.3 TB/s measured-achievable)
 ALG_BYTES_PER_CELL = 0.25      # one 2-bit direction per cell is the only per-cell datum that must leave the chip
+
+# --dump-outputs: the alignment fields of every pair's 48-byte summary (passes and flags say how the library got there, not
+# what it found), and the aligned strings of a seeded sample of pairs -- all strings of C5 would be ~0.9 GB as float32.
+# At most 2^17 pairs x 9 float64 arrays + 2 x 6 Mi float32 codes + 4096 float64 indices: under 60 MB.
+DUMP_FIELDS = ("f", "score", "end_y", "end_x", "start_y", "start_x", "aln_len", "status")
+DUMP_SUMMARY_PAIRS = 1 << 17
+DUMP_STRING_PAIRS = 4096
+DUMP_STRING_CODES = 6 << 20
+DUMP_SEED = 0xA11C0D0
+
+
+def dump_outputs(path, summaries, fetched, mine):
+    """Writes what the timed path computed in its last step: `summaries` are the records of the whole batch in global pair
+    order, `fetched` is this rank's BatchResult (summaries + both aligned strings) and `mine` the global indices of its pairs.
+    Every array is float64 or float32; the samples depend on the arguments alone."""
+    os.makedirs(path, exist_ok=True)
+    n = len(summaries)
+    pairs = np.arange(n)
+    if n > DUMP_SUMMARY_PAIRS:
+        pairs = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SUMMARY_PAIRS, replace=False))
+    np.save(os.path.join(path, "pair_index.npy"), pairs.astype(np.float64))
+    for name in DUMP_FIELDS:
+        np.save(os.path.join(path, name + ".npy"), summaries[name][pairs].astype(np.float64))
+    # aligned query and target codes (gaps as the blank code) of the sampled pairs, concatenated; lengths are aln_len
+    local = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(len(mine), min(len(mine), DUMP_STRING_PAIRS), replace=False))
+    qa, ta = [np.zeros(0, np.uint8)], [np.zeros(0, np.uint8)]
+    for j in local:
+        a, b = fetched.aligned(j)
+        qa.append(a)
+        ta.append(b)
+    np.save(os.path.join(path, "aligned_pair_index.npy"), np.asarray(mine)[local].astype(np.float64))
+    np.save(os.path.join(path, "aligned_query.npy"), np.concatenate(qa)[:DUMP_STRING_CODES].astype(np.float32))
+    np.save(os.path.join(path, "aligned_target.npy"), np.concatenate(ta)[:DUMP_STRING_CODES].astype(np.float32))
 
 
 def cpu_baseline(batch, S, gpu_results, target_seconds=12.0):
@@ -353,6 +388,9 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--pairs", type=int, default=100000, help="size of the C5 batch (default: the full 100 000)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also the host-buffer call, the other configurations, the cold start and the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-single-pair", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true")
@@ -361,6 +399,8 @@ def main():
                     help="world size 1 only: run the RCCL process group and the summary gather of the N > 1 path anyway")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "hbm_traffic.json"))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # stdout carries ONE JSON line.  Libraries print there too (RCCL writes a five-line version banner to fd 1 when the
     # process group comes up), so fd 1 is pointed at stderr for the whole run and the line goes to the saved descriptor.
@@ -443,12 +483,15 @@ def main():
     fetched = sb.fetch(want_traceback=True)              # D2H of the 48-byte summaries and both aligned strings of every pair
     t_fetch = time.perf_counter() - t_fetch
     res = fetched.results
-    del fetched
     ok = int((res["status"] == 0).sum())
     refills = int((res["passes"] > 1).sum())
+    everyone = res
     if use_dist:
         everyone = gather.unpack(shards, args.pairs)
         assert (everyone[mine] == res).all() and int((everyone["status"] == 0).sum()) >= ok
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, everyone, fetched, mine)
+    del fetched
 
     line = None
     if rank == 0:
@@ -506,9 +549,9 @@ def main():
                                "gcups_rank0": round(batch.cells / (t_stage + elapsed / args.steps + t_fetch) / 1e9, 2)},
         }
 
-    # ---- N = 1 extras: the host-buffer call, the single-pair configuration, the small configurations, the CPU baseline
+    # ---- --full, N = 1: the host-buffer call, the single-pair configuration, the small configurations, the CPU baseline
     sb.close()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         e2e_res = None
         if not args.no_end_to_end:
             line["end_to_end"], e2e_res = end_to_end(batch, S, local_rank)
