@@ -22,9 +22,10 @@ ERR_OOM = 6
 ERR_INVALID_ARGUMENT = 7
 ERR_UNSUPPORTED = 8
 ERR_MATRIX_SHAPE = 9
+ERR_CAPACITY = 10
 STATUS_NAMES = {0: "OK", 1: "ERR_UNNECESSARY_ARGUMENT", 2: "ERR_EMPTY_SEQUENCE", 3: "ERR_CODE_OUT_OF_RANGE",
                 4: "ERR_NO_POSITIVE_CELL", 5: "ERR_DEVICE", 6: "ERR_OOM", 7: "ERR_INVALID_ARGUMENT",
-                8: "ERR_UNSUPPORTED", 9: "ERR_MATRIX_SHAPE"}
+                8: "ERR_UNSUPPORTED", 9: "ERR_MATRIX_SHAPE", 10: "ERR_CAPACITY"}
 # enum aln_outputs
 OUT_SCORE, OUT_TRACEBACK, OUT_DIRECTIONS, OUT_H_MATRIX = 1, 2, 4, 8
 
@@ -34,6 +35,8 @@ EXPORTS = [
     "aln_align_batch", "aln_plan_chunks", "aln_batch_create", "aln_batch_run", "aln_batch_sync", "aln_batch_fetch",
     "aln_batch_destroy", "aln_batch_cells", "aln_batch_size", "aln_batch_results_device",
     "aln_batch_direction_bytes", "aln_batch_timing", "aln_batch_enable_timing",
+    "aln_scan_create", "aln_scan_destroy", "aln_scan_windows", "aln_scan_score", "aln_scan_select", "aln_scan_string_stride",
+    "aln_scan_stats",
 ]
 
 
@@ -52,6 +55,11 @@ class PairResult(C.Structure):
 
 
 assert C.sizeof(PairResult) == 48
+
+
+class ScanGeometry(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("step", C.c_uint64), ("width", C.c_uint64), ("reverse", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 _lib = None
 
@@ -110,6 +118,22 @@ def load():
     lib.aln_batch_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     lib.aln_batch_enable_timing.restype = None
     lib.aln_batch_enable_timing.argtypes = [vp, i]
+    gp = C.POINTER(ScanGeometry)
+    lib.aln_scan_create.restype = vp
+    lib.aln_scan_create.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int)]
+    lib.aln_scan_destroy.restype = None
+    lib.aln_scan_destroy.argtypes = [vp]
+    lib.aln_scan_windows.restype = C.c_size_t
+    lib.aln_scan_windows.argtypes = [vp, gp]
+    lib.aln_scan_score.restype = i
+    lib.aln_scan_score.argtypes = [vp, C.POINTER(Params), gp, vp]
+    lib.aln_scan_select.restype = i
+    lib.aln_scan_select.argtypes = [vp, C.POINTER(Params), gp, C.c_double, C.c_double, C.c_double, C.c_size_t,
+                                    C.POINTER(C.c_uint64), vp, vp, vp]
+    lib.aln_scan_string_stride.restype = C.c_uint64
+    lib.aln_scan_string_stride.argtypes = [vp, C.c_uint32, gp]
+    lib.aln_scan_stats.restype = i
+    lib.aln_scan_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 

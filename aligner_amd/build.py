@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libaligner_hip.so")
-SOURCES = ["aln_kernels.hip", "aln_host.hip"]
+SOURCES = ["aln_kernels.hip", "aln_host.hip", "aln_scan.hip"]
 # aln_kernels.hip is compiled as several translation units side by side (-DALN_TU=<mask of its ALN_PART_* families>): the fast
 # core-local batch kernel alone is half of the compile time
 KERNEL_UNITS = [("generic", 1), ("fast_cl", 2), ("fast_rest", 4), ("single", 8), ("tb", 16), ("fast_cl_solo", 32), ("fast_rest_solo", 64)]
@@ -79,6 +79,7 @@ def _build_lib(force=False, remarks=False):
     jobs = [(base + ["-DALN_TU=%d" % mask, "-c", os.path.join(CSRC, "aln_kernels.hip"), "-o", os.path.join(objdir, "aln_kernels_%s.o" % name)])
             for name, mask in KERNEL_UNITS]
     jobs.append(base + ["-c", os.path.join(CSRC, "aln_host.hip"), "-o", os.path.join(objdir, "aln_host.o")])
+    jobs.append(base + ["-c", os.path.join(CSRC, "aln_scan.hip"), "-o", os.path.join(objdir, "aln_scan.o")])
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as pool:
         for rc, cmd in zip(pool.map(subprocess.call, jobs), jobs):

@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <numeric>
 #include <string>
@@ -773,7 +774,8 @@ struct Need {
 };
 
 // device buffers of a slot for this chunk (grow-only; nothing happens once the pool is warm)
-static int slot_ensure(Slot &s, const Call &c, const Chunk &k, const Need *need = nullptr)
+// small_meta (window scans): the descriptors and the queue are built on the device, so the pinned staging holds the matrix only
+static int slot_ensure(Slot &s, const Call &c, const Chunk &k, const Need *need = nullptr, bool small_meta = false)
 {
     int st;
     const bool sl = s.pooled;
@@ -827,10 +829,36 @@ static int slot_ensure(Slot &s, const Call &c, const Chunk &k, const Need *need 
     }
 #undef ENS
     // pinned staging of the small tables: descs | order | matrix | pwm words
-    const size_t meta = std::max<size_t>(k.n, need ? need->n : 0) * (sizeof(PairDesc) + 4) + (size_t)c.rows * c.cols * 8 + (size_t)c.cols * 4 + 256;
+    const size_t meta = (small_meta ? 0 : std::max<size_t>(k.n, need ? need->n : 0) * (sizeof(PairDesc) + 4)) + (size_t)c.rows * c.cols * 8 + (size_t)c.cols * 4 + 256;
     if ((st = pin_ensure(s.h_meta, meta)) != ALN_OK) return st;
-    if (!k.seq_direct && (st = pin_ensure(s.h_in, k.seq_span + 64)) != ALN_OK) return st;
+    if (!small_meta && !k.seq_direct && (st = pin_ensure(s.h_in, k.seq_span + 64)) != ALN_OK) return st;
     return slot_init(s);
+}
+
+// H2D of the call's matrix (and of the PWM column words of the fast kernels) through pinned staging at `m`
+static int upload_matrix(Slot &s, const Call &c, uint8_t *m, hipStream_t st)
+{
+    size_t o = 0;
+    const size_t nm = c.md.size();
+    if (c.is_int) {
+        int32_t *mi = reinterpret_cast<int32_t *>(m + o);
+        for (size_t i = 0; i < nm; ++i) mi[i] = (int32_t)c.md[i];
+        HIPCHK(hipMemcpyAsync(s.matrix.p, mi, nm * 4, hipMemcpyHostToDevice, st));
+    } else {
+        memcpy(m + o, c.md.data(), nm * 8);
+        HIPCHK(hipMemcpyAsync(s.matrix.p, m + o, nm * 8, hipMemcpyHostToDevice, st));
+    }
+    o += nm * 8;
+    if (c.pwm && c.fast) {
+        uint32_t *words = reinterpret_cast<uint32_t *>(m + o);
+        for (uint32_t x = 0; x < c.cols; ++x) {
+            uint32_t wv = 0;
+            for (uint32_t r = 0; r < 4; ++r) wv |= ((uint32_t)(int32_t)(4 * (int32_t)c.md[(size_t)r * c.cols + x] - 2) & 0xffu) << (8 * r);
+            words[x] = wv;
+        }
+        HIPCHK(hipMemcpyAsync(s.pwm_words.p, words, (size_t)c.cols * 4, hipMemcpyHostToDevice, st));
+    }
+    return ALN_OK;
 }
 
 // H2D of one chunk on the slot's stream.  The residues come straight out of the caller's buffer (one span); the small tables
@@ -851,25 +879,8 @@ static int slot_upload(Slot &s, const Call &c, const Chunk &k, const uint8_t *se
         o += k.n * 4;
     }
     o = (o + 15) & ~(size_t)15;
-    const size_t nm = c.md.size();
-    if (c.is_int) {
-        int32_t *mi = reinterpret_cast<int32_t *>(m + o);
-        for (size_t i = 0; i < nm; ++i) mi[i] = (int32_t)c.md[i];
-        HIPCHK(hipMemcpyAsync(s.matrix.p, mi, nm * 4, hipMemcpyHostToDevice, st));
-    } else {
-        memcpy(m + o, c.md.data(), nm * 8);
-        HIPCHK(hipMemcpyAsync(s.matrix.p, m + o, nm * 8, hipMemcpyHostToDevice, st));
-    }
-    o += nm * 8;
-    if (c.pwm && c.fast) {
-        uint32_t *words = reinterpret_cast<uint32_t *>(m + o);
-        for (uint32_t x = 0; x < c.cols; ++x) {
-            uint32_t wv = 0;
-            for (uint32_t r = 0; r < 4; ++r) wv |= ((uint32_t)(int32_t)(4 * (int32_t)c.md[(size_t)r * c.cols + x] - 2) & 0xffu) << (8 * r);
-            words[x] = wv;
-        }
-        HIPCHK(hipMemcpyAsync(s.pwm_words.p, words, (size_t)c.cols * 4, hipMemcpyHostToDevice, st));
-    }
+    int e = upload_matrix(s, c, m + o, st);
+    if (e != ALN_OK) return e;
     if (k.seq_span && !seqs_there) {
         if (k.seq_direct) {
             HIPCHK(hipMemcpyAsync(s.seqs.p, seqs + k.seq_lo, k.seq_span, hipMemcpyHostToDevice, st));
@@ -1664,4 +1675,329 @@ extern "C" int aln_align_pair(aln_ctx *ctx, const aln_params *params, const uint
         }
     }
     return out->status;
+}
+
+// ---------------------------------------------------------------- window scan: one chromosome resident in HBM
+// The repeat search (latent-repeat-search, engine/calc.rs:19-147) aligns one PWM against every window j = first + k * step of a
+// chromosome, rows seq[j .. min(j + width, len)), again and again.  A scan uploads the residues once; a pass is a geometry, not
+// arrays: the descriptors are expanded on the device (aln_scan.hip) and handed to the same fill / traceback launches as a staged
+// batch (slot_launch), planned by the same chunk_plan from the window lengths -- once per geometry and kind of call, then kept.
+// A select pass tests z on the device, compacts the hits in window order and re-fills only those with directions, all on one
+// stream; what comes back is the hit count, the hits' summaries and strings.
+extern "C" void aln_scan_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t first, uint64_t step, uint64_t width,
+                                       uint64_t len, uint64_t base, uint32_t cols, hipStream_t s);
+extern "C" void aln_scan_launch_f(const aln_pair_result *res, double *f, uint64_t n, int32_t *bad, hipStream_t s);
+extern "C" uint64_t aln_scan_tiles(uint64_t n);
+extern "C" void aln_scan_launch_select(const aln_pair_result *res, uint64_t n, double mean, double sd, double z_min, uint32_t *tile_count,
+                                       uint32_t *tile_off, uint32_t *count, uint32_t *idx, uint32_t cap, hipStream_t s);
+extern "C" void aln_scan_launch_hits(PairDesc *descs, uint32_t *order, uint32_t n_slots, const uint32_t *idx, const uint32_t *count,
+                                     uint32_t cap, uint64_t first, uint64_t step, uint64_t width, uint64_t len, uint64_t base,
+                                     uint32_t cols, uint64_t dir_stride, uint64_t tb_stride, uint64_t tag_stride, hipStream_t s);
+extern "C" void aln_scan_launch_reverse(uint8_t *seq, uint64_t len, hipStream_t s);
+
+// the re-fill of a select pass has room for at least this many hits: a chunk of <= 4 pairs would take the one-workgroup route,
+// whose plan reads the pairs' shapes on the host
+#define ALN_SCAN_MIN_SLOTS 8u
+
+struct ScanPlan {
+    std::vector<uint64_t> key;
+    Chunk k;
+    uint64_t dir_stride = 0, tb_stride = 0, tag_stride = 0;
+};
+
+// Plans are shared by every scan of the process: the starting values' shuffled copy, the cycles and the reverse pass of a record
+// (same length, same geometry) use one plan per kind of call.  Least recently used first.
+static std::mutex g_scan_plans_mu;
+static std::vector<std::shared_ptr<ScanPlan>> g_scan_plans;
+
+struct aln_scan {
+    DevCtx *ctx = nullptr;            // one device: the context's first (as a staged batch)
+    Slot *slot = nullptr;             // private slot; slot->seqs holds the forward strand at 0 and, once needed, the reversed one at len
+    uint64_t len = 0;
+    bool rev_ready = false;
+    DevBuf fbuf, tiles, idx, misc;    // f of every window; tile counts + offsets; hit indices; [0] hit count, [1] failed-status flag
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double ms[4] = {0, 0, 0, 0};      // last pass: fill, selection, hit re-fill + walk (kernel time), download (wall)
+    uint64_t bytes[2] = {0, 0};       // last pass: host -> device, device -> host
+};
+
+static uint64_t scan_windows(uint64_t len, const aln_scan_geometry *g)
+{
+    return g->first < len ? (len - 1 - g->first) / g->step + 1 : 0;
+}
+
+extern "C" size_t aln_scan_windows(const aln_scan *sc, const aln_scan_geometry *g)
+{
+    if (!sc || !g || g->step == 0) return 0;
+    return (size_t)scan_windows(sc->len, g);
+}
+
+extern "C" void aln_scan_destroy(aln_scan *sc)
+{
+    if (!sc) return;
+    (void)hipSetDevice(sc->ctx->device);
+    for (hipEvent_t e : sc->ev) if (e) (void)hipEventDestroy(e);
+    dev_free(sc->fbuf); dev_free(sc->tiles); dev_free(sc->idx); dev_free(sc->misc);
+    slot_destroy(sc->slot);
+    delete sc;
+}
+
+extern "C" aln_scan *aln_scan_create(aln_ctx *ctx, const uint8_t *seq, size_t len, int *status)
+{
+    int st = ALN_OK;
+    aln_scan *sc = nullptr;
+    if (!ctx || (len && !seq)) { g_err = "null argument"; st = ALN_ERR_INVALID_ARGUMENT; }
+    else if ((uint64_t)len > 0x7FFFFFF0ull) { g_err = "sequence too long"; st = ALN_ERR_UNSUPPORTED; }
+    else {
+        // residue codes: a PWM has 4 rows (pwm/mod.rs:40-42), so every code must be below 4 -- checked once here instead of per pass
+        for (size_t i = 0; i < len; ++i)
+            if (seq[i] >= 4) { g_err = "residue code outside the position-weight matrix"; st = ALN_ERR_CODE_OUT_OF_RANGE; break; }
+    }
+    if (st == ALN_OK) {
+        sc = new aln_scan();
+        sc->ctx = ctx->devs[0];
+        sc->len = len;
+        sc->slot = new Slot();
+        sc->slot->pooled = false;
+        hipError_t e = hipSetDevice(sc->ctx->device);
+        if (e != hipSuccess) st = fail(e, "hipSetDevice");
+        // both strands' room at once: the buffer never moves afterwards (slot_ensure asks for at most len + 64)
+        if (st == ALN_OK) st = dev_ensure(sc->slot->seqs, 2 * (uint64_t)len + 256, false);
+        if (st == ALN_OK) st = dev_ensure(sc->misc, 256, false);
+        if (st == ALN_OK) st = slot_init(*sc->slot);
+        for (int i = 0; i < 4 && st == ALN_OK; ++i) { e = hipEventCreate(&sc->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
+        if (st == ALN_OK && len) {
+            e = hipMemcpyAsync(sc->slot->seqs.p, seq, len, hipMemcpyHostToDevice, sc->slot->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(sc->slot->stream);
+            if (e != hipSuccess) st = fail(e, "upload");
+        }
+        if (st != ALN_OK) { aln_scan_destroy(sc); sc = nullptr; }
+    }
+    if (status) *status = st;
+    return sc;
+}
+
+// the plan of n windows of geometry g (hits == 0), or of a re-fill with `hits` slots of the geometry's widest window
+// (the strand does not enter the plan: the descriptors' offsets are the device's business)
+static int scan_plan(aln_scan *sc, const Call &c, const aln_scan_geometry *g, uint64_t n, uint64_t hits, std::shared_ptr<ScanPlan> &out)
+{
+    const uint64_t wmax = std::min<uint64_t>(g->width, sc->len);
+    std::vector<uint64_t> key = {(uint64_t)sc->ctx->device, sc->len, n, g->first, g->step, g->width, hits, c.cols, (uint64_t)c.is_int,
+                                 (uint64_t)c.fast, (uint64_t)c.store_dirs, (uint64_t)c.want_tb, (uint64_t)c.semantics,
+                                 (uint64_t)(c.p.del != c.p.ext), (uint64_t)c.p.force_serial, (uint64_t)c.p.force_generic,
+                                 (uint64_t)c.p.max_passes};
+    {
+        std::lock_guard<std::mutex> lk(g_scan_plans_mu);
+        for (size_t i = 0; i < g_scan_plans.size(); ++i)
+            if (g_scan_plans[i]->key == key) {
+                out = g_scan_plans[i];
+                g_scan_plans.erase(g_scan_plans.begin() + (ptrdiff_t)i);
+                g_scan_plans.push_back(out);
+                return ALN_OK;
+            }
+    }
+    std::shared_ptr<ScanPlan> plp = std::make_shared<ScanPlan>();
+    ScanPlan &pl = *plp;
+    pl.key = key;
+    const uint64_t m = hits ? hits : n;
+    int st;
+    {
+        std::vector<uint64_t> q_off(m, 0), q_len(m, c.cols), t_off(m), t_len(m);
+        for (uint64_t k = 0; k < m; ++k) {
+            if (hits) { t_off[k] = 0; t_len[k] = wmax; continue; }
+            const uint64_t j = g->first + k * g->step;
+            t_off[k] = j;
+            t_len[k] = std::min<uint64_t>(g->width, sc->len - j);
+        }
+        st = chunk_plan(sc->ctx, c, q_off.data(), q_len.data(), t_off.data(), t_len.data(), 0, m, true, pl.k);
+    }
+    if (st != ALN_OK) return st;
+    if (hits) {
+        // every slot gets the room of the largest window of the geometry (the last windows are shorter)
+        uint64_t dmax = aln_dir_bytes(c.cols, (uint32_t)wmax);
+        for (uint64_t k = n; k-- > 0;) {
+            const uint64_t j = g->first + k * g->step;
+            if (sc->len - j >= g->width) break;
+            dmax = std::max<uint64_t>(dmax, aln_dir_bytes(c.cols, (uint32_t)(sc->len - j)));
+        }
+        const uint64_t cap = (uint64_t)c.cols + wmax + 2;
+        pl.dir_stride = (dmax + 255) & ~255ull;
+        pl.tb_stride = (5 * cap + 3) & ~3ull;
+        pl.tag_stride = (cap + 3) & ~3ull;
+        pl.k.dir_bytes = hits * pl.dir_stride; pl.k.tb_bytes = hits * pl.tb_stride; pl.k.tag_bytes = hits * pl.tag_stride;
+    }
+    // The device writes the descriptors, and the queue as the window order.  Windows routed elsewhere (<= 4 windows, real-valued
+    // PWM: the one-workgroup route takes the long ones) leave the batch kernel a queue of the others only: the plan's own queue is
+    // uploaded over the identity then (scan_fill), and the host keeps the descriptors those launches read.
+    if (pl.k.single_pairs.empty() && pl.k.wg_pairs.empty()) {
+        pl.k.descs.clear(); pl.k.descs.shrink_to_fit();
+        pl.k.order.clear(); pl.k.order.shrink_to_fit();
+    }
+    {
+        std::lock_guard<std::mutex> lk(g_scan_plans_mu);
+        if (g_scan_plans.size() >= 8) g_scan_plans.erase(g_scan_plans.begin());
+        g_scan_plans.push_back(plp);
+    }
+    out = plp;
+    return ALN_OK;
+}
+
+static int scan_call(aln_scan *sc, const aln_params *params, const aln_scan_geometry *g, uint32_t outputs, Call &c)
+{
+    if (!sc || !params || !g) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (params->semantics != ALN_PWM_LOCAL) { g_err = "a window scan aligns a position-weight matrix (ALN_PWM_LOCAL) only"; return ALN_ERR_UNSUPPORTED; }
+    if (g->step == 0 || g->width == 0) { g_err = "geometry: step and width must be positive"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (scan_windows(sc->len, g) > 0xFFFFFFF0ull) { g_err = "too many windows"; return ALN_ERR_UNSUPPORTED; }
+    aln_params p = *params;
+    p.outputs = outputs;
+    const uint64_t q1 = 0, t1 = std::min<uint64_t>(g->width, sc->len);      // the widest window decides the kernels (call_init)
+    int st = call_init(c, &p, &q1, &t1, 1, false);
+    if (st != ALN_OK) return st;
+    HIPCHK(hipSetDevice(sc->ctx->device));
+    Slot &s = *sc->slot;
+    if (g->reverse && !sc->rev_ready && sc->len) {
+        aln_scan_launch_reverse(s.seqs.as<uint8_t>(), sc->len, s.stream);
+        HIPCHK(hipGetLastError());
+        sc->rev_ready = true;
+    }
+    return ALN_OK;
+}
+
+// fill every window of g (score only) into the slot's results; f of every window into fbuf, a failed status into misc[1]
+static int scan_fill(aln_scan *sc, const Call &c, const aln_scan_geometry *g, const ScanPlan *pl, uint64_t n)
+{
+    Slot &s = *sc->slot;
+    hipStream_t st = s.stream;
+    aln_scan_launch_expand(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), n, g->first, g->step, g->width, sc->len, g->reverse ? sc->len : 0,
+                           c.cols, st);
+    HIPCHK(hipGetLastError());
+    if (pl->k.n_small != n && pl->k.n_small)               // some windows take another route: the batch kernel's queue is the plan's
+        HIPCHK(hipMemcpyAsync(s.order.p, pl->k.order.data(), 4 * pl->k.n_small, hipMemcpyHostToDevice, st));
+    int e = slot_launch(sc->ctx, s, c, pl->k, st, nullptr, nullptr);
+    if (e != ALN_OK) return e;
+    HIPCHK(hipMemsetAsync(sc->misc.p, 0, 8, st));
+    aln_scan_launch_f(s.results.as<aln_pair_result>(), sc->fbuf.as<double>(), n, sc->misc.as<int32_t>() + 1, st);
+    HIPCHK(hipGetLastError());
+    return ALN_OK;
+}
+
+static double ev_ms(hipEvent_t a, hipEvent_t b)
+{
+    float v = 0;
+    return hipEventElapsedTime(&v, a, b) == hipSuccess ? (double)v : 0.0;
+}
+
+extern "C" int aln_scan_score(aln_scan *sc, const aln_params *params, const aln_scan_geometry *g, double *f)
+{
+    Call c;
+    int st = scan_call(sc, params, g, ALN_OUT_SCORE, c);
+    if (st != ALN_OK) return st;
+    const uint64_t n = scan_windows(sc->len, g);
+    if (n && !f) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    for (double &v : sc->ms) v = 0;
+    sc->bytes[0] = sc->bytes[1] = 0;
+    if (n == 0) return ALN_OK;
+    Slot &s = *sc->slot;
+    std::shared_ptr<ScanPlan> pl;
+    if ((st = scan_plan(sc, c, g, n, 0, pl)) != ALN_OK) return st;
+    if ((st = slot_ensure(s, c, pl->k, nullptr, true)) != ALN_OK) return st;
+    if ((st = dev_ensure(sc->fbuf, 8 * n, false)) != ALN_OK) return st;
+    HIPCHK(hipEventRecord(sc->ev[0], s.stream));
+    if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), s.stream)) != ALN_OK) return st;
+    if ((st = scan_fill(sc, c, g, pl.get(), n)) != ALN_OK) { (void)hipStreamSynchronize(s.stream); return st; }
+    HIPCHK(hipEventRecord(sc->ev[1], s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    int32_t misc[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(f, sc->fbuf.p, 8 * n, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipMemcpyAsync(misc, sc->misc.p, 8, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    sc->ms[0] = ev_ms(sc->ev[0], sc->ev[1]);
+    sc->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    sc->bytes[0] = c.md.size() * (c.is_int ? 4 : 8) + (c.pwm && c.fast ? 4ull * c.cols : 0);
+    sc->bytes[1] = 8 * n + 8;
+    if (misc[1] != ALN_OK) { g_err = "a window failed"; return misc[1]; }
+    return ALN_OK;
+}
+
+extern "C" int aln_scan_select(aln_scan *sc, const aln_params *params, const aln_scan_geometry *g, double mean, double sd, double z_min,
+                               size_t cap, uint64_t *count, uint32_t *indices, aln_pair_result *results, uint8_t *tb_buf)
+{
+    Call c, ct;
+    int st = scan_call(sc, params, g, ALN_OUT_SCORE, c);
+    if (st != ALN_OK) return st;
+    if (!count || (cap && (!indices || !results))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (cap > 0xFFFFFFF0ull) { g_err = "capacity too large"; return ALN_ERR_UNSUPPORTED; }
+    aln_params pt = *params;
+    pt.outputs = ALN_OUT_SCORE | ALN_OUT_TRACEBACK;
+    const uint64_t q1 = 0, t1 = std::min<uint64_t>(g->width, sc->len);
+    if ((st = call_init(ct, &pt, &q1, &t1, 1, false)) != ALN_OK) return st;
+    *count = 0;
+    for (double &v : sc->ms) v = 0;
+    sc->bytes[0] = sc->bytes[1] = 0;
+    const uint64_t n = scan_windows(sc->len, g);
+    if (n == 0) return ALN_OK;
+    Slot &s = *sc->slot;
+    const uint64_t slots = std::max<uint64_t>(std::min<uint64_t>(cap, n), ALN_SCAN_MIN_SLOTS);
+    std::shared_ptr<ScanPlan> pl, ph;
+    if ((st = scan_plan(sc, c, g, n, 0, pl)) != ALN_OK) return st;
+    if ((st = scan_plan(sc, ct, g, n, slots, ph)) != ALN_OK) return st;
+    // every buffer is sized before anything is queued: a buffer that grew later would be freed under a running kernel
+    if ((st = slot_ensure(s, c, pl->k, nullptr, true)) != ALN_OK) return st;
+    if ((st = slot_ensure(s, ct, ph->k, nullptr, true)) != ALN_OK) return st;
+    const uint64_t tiles = aln_scan_tiles(n);
+    if ((st = dev_ensure(sc->fbuf, 8 * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(sc->tiles, 8 * tiles, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(sc->idx, 4 * slots, false)) != ALN_OK) return st;
+    hipStream_t q = s.stream;
+    HIPCHK(hipEventRecord(sc->ev[0], q));
+    if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) return st;
+    if ((st = scan_fill(sc, c, g, pl.get(), n)) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    HIPCHK(hipEventRecord(sc->ev[1], q));
+    uint32_t *misc = sc->misc.as<uint32_t>();
+    aln_scan_launch_select(s.results.as<aln_pair_result>(), n, mean, sd, z_min, sc->tiles.as<uint32_t>(), sc->tiles.as<uint32_t>() + tiles,
+                           misc, sc->idx.as<uint32_t>(), (uint32_t)slots, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(sc->ev[2], q));
+    aln_scan_launch_hits(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), (uint32_t)slots, sc->idx.as<uint32_t>(), misc, (uint32_t)slots,
+                         g->first, g->step, g->width, sc->len, g->reverse ? sc->len : 0, c.cols, ph->dir_stride, ph->tb_stride, ph->tag_stride, q);
+    HIPCHK(hipGetLastError());
+    if ((st = slot_launch(sc->ctx, s, ct, ph->k, q, nullptr, nullptr)) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    HIPCHK(hipEventRecord(sc->ev[3], q));
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t hm[2] = {0, 0};
+    HIPCHK(hipMemcpy(hm, misc, 8, hipMemcpyDeviceToHost));
+    *count = hm[0];
+    const uint64_t got = std::min<uint64_t>(hm[0], cap);
+    if (got) {
+        HIPCHK(hipMemcpyAsync(indices, sc->idx.p, 4 * got, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(results, s.results.p, sizeof(aln_pair_result) * got, hipMemcpyDeviceToHost, q));
+        if (tb_buf) HIPCHK(hipMemcpyAsync(tb_buf, s.tb.p, ph->tb_stride * got, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+    }
+    sc->ms[0] = ev_ms(sc->ev[0], sc->ev[1]);
+    sc->ms[1] = ev_ms(sc->ev[1], sc->ev[2]);
+    sc->ms[2] = ev_ms(sc->ev[2], sc->ev[3]);
+    sc->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    sc->bytes[0] = c.md.size() * (c.is_int ? 4 : 8) + (c.pwm && c.fast ? 4ull * c.cols : 0);
+    sc->bytes[1] = 8 + got * (4 + sizeof(aln_pair_result) + (tb_buf ? ph->tb_stride : 0));
+    if (hm[1] != ALN_OK) { g_err = "a window failed"; return (int)hm[1]; }
+    if (hm[0] > cap) { g_err = "more windows passed than the capacity holds"; return ALN_ERR_CAPACITY; }
+    return ALN_OK;
+}
+
+extern "C" uint64_t aln_scan_string_stride(const aln_scan *sc, uint32_t cols, const aln_scan_geometry *g)
+{
+    if (!sc || !g) return 0;
+    const uint64_t cap = (uint64_t)cols + std::min<uint64_t>(g->width, sc->len) + 2;
+    return (5 * cap + 3) & ~3ull;
+}
+
+extern "C" int aln_scan_stats(const aln_scan *sc, double *ms, uint64_t *bytes)
+{
+    if (!sc) return ALN_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < 4 && ms; ++i) ms[i] = sc->ms[i];
+    for (int i = 0; i < 2 && bytes; ++i) bytes[i] = sc->bytes[i];
+    return ALN_OK;
 }

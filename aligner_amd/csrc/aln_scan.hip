@@ -1,0 +1,200 @@
+// aln_scan.hip -- device side of the window scan (aln_scan_*, include/aligner_hip.h): the kernels that stand between a resident
+// chromosome and the existing fill / traceback machinery of aln_kernels.hip.
+//
+//   expand     window k of a geometry (first, step, width, reverse) -> PairDesc k (+ queue entry k): the descriptors the batch
+//              fill kernels read, built where they are used instead of on the host
+//   f          the f of every window out of the 48-byte summaries (8 bytes per window go back instead of 48)
+//   select     z = (f - mean) / sd >= z_min per window, compacted in ascending window order by a two-level prefix sum
+//              (tile counts, one workgroup's scan over the tiles, tile-local scans): the same indices every run
+//   hits       the selected windows -> PairDesc[cap] of the re-fill with directions (unused entries are skipped by the kernels)
+//   reverse    the reversed strand, written once behind the forward one in the scan's own buffer
+//
+// Every store is a plain C++ store of a thread (vector memory instructions).  The z test is a true IEEE division and compare
+// (-ffp-contract=off, no reciprocal): NaN fails it, +inf passes it.
+#include <hip/hip_runtime.h>
+
+#include "aln_device.h"
+
+#define SCAN_THREADS 256u
+#define SCAN_PER_THREAD 8u
+#define SCAN_TILE (SCAN_THREADS * SCAN_PER_THREAD)
+
+// ---- window expansion: descriptor k = window j = first + k * step, rows seq[j .. min(j + width, len)) of the strand at `base`
+__global__ __launch_bounds__(256) void aln_scan_expand_kernel(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t first,
+                                                              uint64_t step, uint64_t width, uint64_t len, uint64_t base,
+                                                              uint32_t cols)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint64_t j = first + k * step;
+    const uint64_t rem = len - j;
+    PairDesc d;
+    d.q_off = 0;
+    d.t_off = base + j;
+    d.N = cols;
+    d.M = (uint32_t)(width < rem ? width : rem);
+    d.dir_off = 0; d.tb_off = 0; d.tag_off = 0; d.h_off = 0;
+    d.status = ALN_OK;
+    d.layout = 0;
+    descs[k] = d;
+    order[k] = (uint32_t)k;
+}
+
+// ---- f of every window (+ the first status that is not ALN_OK, as a flag word: the pass failed)
+__global__ __launch_bounds__(256) void aln_scan_f_kernel(const aln_pair_result *res, double *f, uint64_t n, int32_t *bad)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const aln_pair_result r = res[k];
+    f[k] = r.f;
+    if (r.status != ALN_OK) atomicMax(bad, r.status);
+}
+
+__device__ __forceinline__ bool scan_keep(double f, double mean, double sd, double z_min)
+{
+    const double z = (f - mean) / sd;     // IEEE quotient (no contraction: -ffp-contract=off); a NaN z compares false
+    return z >= z_min;
+}
+
+// block-wide exclusive prefix sum of one value per thread (256 threads); returns the thread's offset, *total the block's sum
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *lds, uint32_t *total)
+{
+    const uint32_t t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (uint32_t o = 1; o < SCAN_THREADS; o <<= 1) {
+        const uint32_t add = t >= o ? lds[t - o] : 0u;
+        __syncthreads();
+        lds[t] += add;
+        __syncthreads();
+    }
+    const uint32_t incl = lds[t];
+    *total = lds[SCAN_THREADS - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+// ---- selection, step 1: kept windows per tile of SCAN_TILE windows (thread t looks at windows t*8 .. t*8+7 of the tile)
+__global__ __launch_bounds__(256) void aln_scan_count_kernel(const aln_pair_result *res, uint64_t n, double mean, double sd,
+                                                             double z_min, uint32_t *tile_count)
+{
+    __shared__ uint32_t lds[SCAN_THREADS];
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_PER_THREAD;
+    uint32_t c = 0;
+    for (uint32_t i = 0; i < SCAN_PER_THREAD; ++i)
+        if (base + i < n && scan_keep(res[base + i].f, mean, sd, z_min)) ++c;
+    uint32_t total;
+    (void)block_exclusive_scan(c, lds, &total);
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
+}
+
+// ---- selection, step 2: one workgroup turns the tile counts into tile offsets; count[0] = kept windows in all
+__global__ __launch_bounds__(256) void aln_scan_offsets_kernel(const uint32_t *tile_count, uint32_t *tile_off, uint64_t tiles,
+                                                               uint32_t *count)
+{
+    __shared__ uint32_t lds[SCAN_THREADS];
+    uint32_t carry = 0;
+    for (uint64_t b = 0; b < tiles; b += SCAN_THREADS) {
+        const uint64_t i = b + threadIdx.x;
+        const uint32_t v = i < tiles ? tile_count[i] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_exclusive_scan(v, lds, &total);
+        if (i < tiles) tile_off[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) count[0] = carry;
+}
+
+// ---- selection, step 3: every tile writes its kept window indices at its offset, in ascending order (the first `cap` of all)
+__global__ __launch_bounds__(256) void aln_scan_compact_kernel(const aln_pair_result *res, uint64_t n, double mean, double sd,
+                                                               double z_min, const uint32_t *tile_off, uint32_t *idx, uint32_t cap)
+{
+    __shared__ uint32_t lds[SCAN_THREADS];
+    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_PER_THREAD;
+    uint32_t keep = 0, c = 0;
+    for (uint32_t i = 0; i < SCAN_PER_THREAD; ++i)
+        if (base + i < n && scan_keep(res[base + i].f, mean, sd, z_min)) { keep |= 1u << i; ++c; }
+    uint32_t total;
+    uint32_t o = tile_off[blockIdx.x] + block_exclusive_scan(c, lds, &total);
+    for (uint32_t i = 0; i < SCAN_PER_THREAD; ++i)
+        if (keep & (1u << i)) {
+            if (o < cap) idx[o] = (uint32_t)(base + i);
+            ++o;
+        }
+}
+
+// ---- the re-fill's descriptors: entry h < min(count, cap) is window idx[h], laid out at h * stride in dirs / strings / tags;
+// the others are skipped by every kernel (ALN_PRE_EMPTY_OK: nothing to align)
+__global__ __launch_bounds__(256) void aln_scan_hits_kernel(PairDesc *descs, uint32_t *order, uint32_t n_slots, const uint32_t *idx,
+                                                            const uint32_t *count, uint32_t cap, uint64_t first, uint64_t step,
+                                                            uint64_t width, uint64_t len, uint64_t base, uint32_t cols,
+                                                            uint64_t dir_stride, uint64_t tb_stride, uint64_t tag_stride)
+{
+    const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= n_slots) return;
+    const uint32_t live = count[0] < cap ? count[0] : cap;
+    PairDesc d;
+    d.q_off = 0;
+    d.N = cols;
+    d.dir_off = (uint64_t)h * dir_stride; d.tb_off = (uint64_t)h * tb_stride; d.tag_off = (uint64_t)h * tag_stride; d.h_off = 0;
+    d.layout = 0;
+    if (h < live) {
+        const uint64_t j = first + (uint64_t)idx[h] * step;
+        const uint64_t rem = len - j;
+        d.t_off = base + j;
+        d.M = (uint32_t)(width < rem ? width : rem);
+        d.status = ALN_OK;
+    } else {
+        d.t_off = base;
+        d.M = 0;
+        d.status = ALN_PRE_EMPTY_OK;
+    }
+    descs[h] = d;
+    order[h] = h;
+}
+
+// ---- the reversed strand: seq[len + i] = seq[len - 1 - i]
+__global__ __launch_bounds__(256) void aln_scan_reverse_kernel(uint8_t *seq, uint64_t len)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < len) seq[len + i] = seq[len - 1 - i];
+}
+
+static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+
+extern "C" void aln_scan_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t first, uint64_t step, uint64_t width,
+                                       uint64_t len, uint64_t base, uint32_t cols, hipStream_t s)
+{
+    if (n) hipLaunchKernelGGL(aln_scan_expand_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, descs, order, n, first, step, width, len,
+                              base, cols);
+}
+
+extern "C" void aln_scan_launch_f(const aln_pair_result *res, double *f, uint64_t n, int32_t *bad, hipStream_t s)
+{
+    if (n) hipLaunchKernelGGL(aln_scan_f_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, res, f, n, bad);
+}
+
+extern "C" uint64_t aln_scan_tiles(uint64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
+
+extern "C" void aln_scan_launch_select(const aln_pair_result *res, uint64_t n, double mean, double sd, double z_min, uint32_t *tile_count,
+                                       uint32_t *tile_off, uint32_t *count, uint32_t *idx, uint32_t cap, hipStream_t s)
+{
+    const uint64_t tiles = aln_scan_tiles(n);
+    if (tiles) hipLaunchKernelGGL(aln_scan_count_kernel, dim3((uint32_t)tiles), dim3(SCAN_THREADS), 0, s, res, n, mean, sd, z_min, tile_count);
+    hipLaunchKernelGGL(aln_scan_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, tile_count, tile_off, tiles, count);
+    if (tiles) hipLaunchKernelGGL(aln_scan_compact_kernel, dim3((uint32_t)tiles), dim3(SCAN_THREADS), 0, s, res, n, mean, sd, z_min, tile_off,
+                                  idx, cap);
+}
+
+extern "C" void aln_scan_launch_hits(PairDesc *descs, uint32_t *order, uint32_t n_slots, const uint32_t *idx, const uint32_t *count,
+                                     uint32_t cap, uint64_t first, uint64_t step, uint64_t width, uint64_t len, uint64_t base,
+                                     uint32_t cols, uint64_t dir_stride, uint64_t tb_stride, uint64_t tag_stride, hipStream_t s)
+{
+    if (n_slots) hipLaunchKernelGGL(aln_scan_hits_kernel, dim3(blocks_of(n_slots, 256)), dim3(256), 0, s, descs, order, n_slots, idx, count,
+                                    cap, first, step, width, len, base, cols, dir_stride, tb_stride, tag_stride);
+}
+
+extern "C" void aln_scan_launch_reverse(uint8_t *seq, uint64_t len, hipStream_t s)
+{
+    if (len) hipLaunchKernelGGL(aln_scan_reverse_kernel, dim3(blocks_of(len, 256)), dim3(256), 0, s, seq, len);
+}

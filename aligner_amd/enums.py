@@ -25,6 +25,20 @@ POS = 99     # Protein::Pos / DNA::Pos     (enums.rs:82,145)
 ANY = 100    # Protein::Any / DNA::Any (next discriminant after Pos)
 
 
+class Index:
+    """enums.rs Index { coord, offset, local_offset }: where a run of skipped (non-ACGT) bytes ended."""
+    __slots__ = ("coord", "offset", "local_offset")
+
+    def __init__(self, coord, offset, local_offset):
+        self.coord, self.offset, self.local_offset = int(coord), int(offset), int(local_offset)
+
+    def __eq__(self, other):
+        return (self.coord, self.offset, self.local_offset) == (other.coord, other.offset, other.local_offset)
+
+    def __repr__(self):
+        return "Index(coord=%d, offset=%d, local_offset=%d)" % (self.coord, self.offset, self.local_offset)
+
+
 class _Alphabet:
     """Shared BioData behaviour (enums.rs:181-199); subclasses fix the letters."""
     letters = ""
@@ -116,6 +130,46 @@ class _Alphabet:
         # reference indexes freqs[v as usize]; '_' / '+' (98/99) would panic there -- same here
         np.add.at(freqs, out.astype(np.int64), 1.0)
         return out.copy(), freqs / float(len(out))
+
+    @classmethod
+    def from_u8_vec_with_freqs_and_indices(cls, raw):
+        """enums.rs:489-522 -- unknown bytes are skipped; every run of them that a kept residue ends leaves an
+        Index(coord = position in the kept sequence, offset = bytes skipped so far, local_offset = length of the run); the
+        list comes back reversed (last run first).  A run at the very end leaves nothing."""
+        from .errors import ReferencePanic
+        enc, _ = cls._tables()
+        raw = np.frombuffer(bytes(raw), dtype=np.uint8)
+        out = enc[raw]
+        keep = out != 255
+        codes = out[keep].copy()
+        if (codes >= cls.volume()).any():          # freqs[v as usize] with v = Blank / Pos: index out of bounds
+            raise ReferencePanic(-1, "ndarray: index out of bounds (freqs of a Blank / Pos residue)")
+        freqs = np.bincount(codes.astype(np.int64), minlength=cls.volume()).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            freqs = freqs / np.float64(len(codes))
+        indices = []
+        count = local = 0
+        passing = True
+        for i in np.flatnonzero(np.diff(np.concatenate(([1], keep.view(np.int8)))) != 0):
+            # i: the first byte of a run of skipped bytes (keep drops) or of kept bytes (keep rises)
+            if keep[i]:
+                if not passing:
+                    indices.append(Index(int(i) - count, count, local))
+                    local = 0
+                    passing = True
+            else:
+                run = int(np.argmax(keep[i:])) if keep[i:].any() else len(keep) - int(i)
+                count += run
+                local += run
+                passing = False
+        indices.reverse()
+        return codes, freqs, indices
+
+    @classmethod
+    def random_seq_with_freqs(cls, length, rng=None):
+        """enums.rs:540-551 -- the freqs are the COUNTS of each code (not divided by the length)."""
+        seq = cls.random_seq(length, rng)
+        return seq, np.bincount(seq.astype(np.int64), minlength=cls.volume()).astype(np.float64)
 
     @classmethod
     def random_seq(cls, length, rng=None):

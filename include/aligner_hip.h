@@ -48,7 +48,8 @@ enum aln_status {
     ALN_ERR_OOM = 6,
     ALN_ERR_INVALID_ARGUMENT = 7,
     ALN_ERR_UNSUPPORTED = 8,
-    ALN_ERR_MATRIX_SHAPE = 9         /* Err(Error::MatrixShapeError): PWM without exactly 4 rows, pwm/mod.rs:40-42 */
+    ALN_ERR_MATRIX_SHAPE = 9,        /* Err(Error::MatrixShapeError): PWM without exactly 4 rows, pwm/mod.rs:40-42 */
+    ALN_ERR_CAPACITY = 10            /* aln_scan_select: more windows passed than the caller's capacity holds (the count is the true one) */
 };
 
 /* What the caller wants back (bitmask in aln_params.outputs). */
@@ -159,6 +160,37 @@ uint64_t aln_batch_direction_bytes(const aln_batch *b);       /* bytes of packed
  * around the fill kernel and the traceback kernel (last 256 runs; call after aln_batch_sync) */
 int aln_batch_timing(aln_batch *b, double *fill_ms, double *traceback_ms, uint32_t *fill_launches);
 void aln_batch_enable_timing(aln_batch *b, int on);
+
+/* ---- window scan (the repeat search's loop, latent-repeat-search engine/calc.rs:19-147): one residue array resident in HBM
+ * (one device: the context's first), scanned again and again by ONE position-weight matrix (ALN_PWM_LOCAL only; anything else is
+ * ALN_ERR_UNSUPPORTED).  A pass is a geometry: window k starts at j = first + k * step (every j < len) and holds the rows
+ * seq[j .. min(j + width, len)) -- the last windows are truncated, not dropped; reverse = 1 reads the reversed strand (built on
+ * the device from the resident one; the residues are uploaded once).  The window descriptors are expanded on the device and
+ * filled by the same kernels aln_align_batch takes for the same windows.
+ * create: residue codes must be < 4 (else ALN_ERR_CODE_OUT_OF_RANGE).  windows: their number for a geometry.
+ * score: f of every window into f[windows] (8 bytes per window come back).
+ * select: the same fill, then on the device z = (f - mean) / sd (IEEE division; NaN fails, +inf passes) and the windows with
+ * z >= z_min in ascending window order; those are filled again with directions and walked on the same stream.  Returns the true
+ * number of hits in *count and the first min(count, cap) of them: window indices, summaries and (tb_buf optional) strings, hit h's
+ * at h * aln_scan_string_stride(...) in the ALN_PWM_LOCAL layout of aln_align_batch (u32 column numbers, then the residues at
+ * 4 * (cols + that window's length + 2)).  count > cap: ALN_ERR_CAPACITY.  params->outputs is ignored.
+ * stats: the last pass's kernel times in ms (fill, selection, hit re-fill + walk) + its download's wall time, and the bytes it
+ * moved (host -> device, device -> host). ---- */
+typedef struct aln_scan aln_scan;
+typedef struct aln_scan_geometry {
+    uint64_t first, step, width;
+    uint32_t reverse;
+    uint32_t reserved;
+} aln_scan_geometry;
+
+aln_scan *aln_scan_create(aln_ctx *ctx, const uint8_t *seq, size_t len, int *status);
+void aln_scan_destroy(aln_scan *scan);
+size_t aln_scan_windows(const aln_scan *scan, const aln_scan_geometry *geometry);
+int aln_scan_score(aln_scan *scan, const aln_params *params, const aln_scan_geometry *geometry, double *f);
+int aln_scan_select(aln_scan *scan, const aln_params *params, const aln_scan_geometry *geometry, double mean, double sd,
+                    double z_min, size_t cap, uint64_t *count, uint32_t *indices, aln_pair_result *results, uint8_t *tb_buf);
+uint64_t aln_scan_string_stride(const aln_scan *scan, uint32_t cols, const aln_scan_geometry *geometry);
+int aln_scan_stats(const aln_scan *scan, double *ms, uint64_t *bytes);
 
 #ifdef __cplusplus
 }
