@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "aln_device.h"
+#include "aln_plan_rules.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -450,6 +451,7 @@ struct Chunk {
     bool overlap = false;             // walk waves beside the fill (in-kernel overlapped traceback)
     // cooperative passes of the fast batch kernel (CoopRec, aln_device.h): hint ring capacities, bytes of the control block
     bool coop = false, coop_linger = false;
+    bool coop_lean = false;           // the chunk would share, but so little that the kernel build without the machinery runs it (aln_coop_lean)
     uint32_t coop_tail = 0;
     uint64_t coop_bytes = 0;
     // sequences: either one contiguous span of the caller's buffer, or gathered pair by pair into pinned staging
@@ -466,6 +468,21 @@ struct Chunk {
         descs = std::move(d); order = std::move(o); single_pairs = std::move(sp); single_r = std::move(sr); wg_pairs = std::move(wp); wg_r = std::move(wr);
     }
 };
+
+// ALN_COOP_LEAN (read once): unset = aln_coop_lean_plan decides, 0 = the cooperative build wherever a chunk could share, 1 = the
+// lean build there.  Unlike ALN_NO_COOP (no cooperative passes at all, which also routes large pairs as if nothing could be shared)
+// it only picks the kernel build: routing, grid, claim runs and two pairs per wave are decided as without it.
+static int coop_lean_setting()
+{
+    static const int v = [] { const char *e = getenv("ALN_COOP_LEAN"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+    return v;
+}
+// ALN_TRACE_PLAN=1 (read once): one stderr line per chunk that could share -- which build it runs, and the figures that decided it
+static bool trace_plan()
+{
+    static const bool v = getenv("ALN_TRACE_PLAN") != nullptr;
+    return v;
+}
 
 // allow_overlap: the chunk has the device to itself (a single-chunk call, a staged batch).  many_chunks: one of more than four
 // chunks of a pipelined call.
@@ -623,12 +640,14 @@ static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, c
         for (size_t i = 0; i < n; ++i) if (!is_single[i]) k.order.push_back((uint32_t)i);
     }
     k.n_small = k.order.size();
+    double cost_sum = 0;                  // pair_cost over the queue (aln_coop_lean)
     {
         // sort keys packed in one u64: cells descending, then index ascending (a stable order without a stable_sort)
         std::vector<uint64_t> key(k.n_small);
         bool packable = n < (1u << 24);
         for (size_t j = 0; j < k.n_small && packable; ++j) {
             const uint64_t pc = pair_cost(k.descs[k.order[j]]);
+            cost_sum += (double)pc;
             key[j] = ((~pc & ((1ull << 40) - 1)) << 24) | k.order[j];
         }
         if (packable) {
@@ -654,6 +673,7 @@ static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, c
             for (size_t j = 0; j < k.n_small; ++j) k.order[j] = (uint32_t)(key[j] & 0xffffffu);
         } else {
             std::stable_sort(k.order.begin(), k.order.end(), [&](uint32_t a, uint32_t b) { return pair_cost(k.descs[a]) > pair_cost(k.descs[b]); });
+            for (uint32_t i : k.order) cost_sum += (double)pair_cost(k.descs[i]);
         }
     }
     k.max_cells = 0;
@@ -699,6 +719,21 @@ static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, c
     // (one of many chunks of a pipelined call: its tail hides behind the chunks after it, and sharing re-fills only cost -- measured on
     // C5 through aln_align_batch, eight chunks: 51.2 ms without, 52.0 with; three chunks of the 12 500-pair shard: 10.3 without, 9.3 with)
     k.coop = coop_on && k.n_small != 0 && multi != 0 && !many_chunks;
+    // Many pairs per wave and a queue whose tail is short pairs: next to nothing would be shared -- the lean build (aln_plan_rules.h).
+    // (C5, 100 000 pairs: 33 per resident wave, the tail's longest re-fill 0.7 % of a wave's share)
+    // (k.grid as the kernel will run it: the overlapped traceback above has already cut it to the resident workgroups)
+    if (k.coop) {
+        const AlnLeanPlan lp = aln_coop_lean_plan(k.n_small, k.grid, (uint32_t)ctx->cus, cost_sum,
+                                                  [&](size_t j) { return pair_cost(k.descs[k.order[j]]); }, coop_lean_setting());
+        if (trace_plan())
+            fprintf(stderr, "aln plan: pairs %zu waves %llu resident %llu tail %llu share %.4g tail_cost %llu max_cost %llu build %s\n", k.n_small,
+                    (unsigned long long)lp.waves, (unsigned long long)lp.resident, (unsigned long long)lp.tail, lp.share,
+                    (unsigned long long)pair_cost(k.descs[k.order[lp.tail]]), (unsigned long long)pair_cost(k.descs[k.order[0]]), lp.lean ? "lean" : "coop");
+        if (lp.lean) {
+            k.coop = false;
+            k.coop_lean = true;
+        }
+    }
     if (k.coop) {
         const uint32_t resident = (uint32_t)ctx->cus * 3u;
         // (allow_overlap == false: a chunk of a pipelined call -- the chunks before and after it share the chip with this one, so its
@@ -746,7 +781,7 @@ static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, c
     // columns, more pairs than resident waves (with fewer, a wave per pair is through sooner), nothing shared, no walk waves beside
     // the fill, and the staged queries fit beside the profiles with three workgroups per CU.  ALN_NO_DUO=1: off.
     k.duo_qo = 0;
-    if (c.fast && !pwm && c.semantics == ALN_CORE_GLOBAL && !k.coop && !k.overlap && !getenv("ALN_NO_DUO") &&
+    if (c.fast && !pwm && c.semantics == ALN_CORE_GLOBAL && !k.coop && !k.coop_lean && !k.overlap && !getenv("ALN_NO_DUO") &&
         k.n_small > (uint64_t)ctx->cus * 12u) {
         uint32_t max_rows = 0, max_cols = 0;
         for (size_t j = 0; j < k.n_small; ++j) { const PairDesc &d = k.descs[k.order[j]]; max_rows = std::max(max_rows, d.M); max_cols = std::max(max_cols, d.N); }
@@ -944,7 +979,7 @@ static int slot_launch(DevCtx *ctx, Slot &s, const Call &c, const Chunk &k, hipS
     // runs of queue positions per atomic: only where pairs are many, short and alike (one strip, <= 2^18 cells), nothing is shared
     // and the queue is not two-ended; about 1.6 runs per wave or more, so that the last round stays as even as with single pairs
     fa.claim = 1;
-    if (c.fast && !k.coop && !fa.back_waves && k.max_cells <= (1ull << 18) && k.n_small != 0) {
+    if (c.fast && !k.coop && !k.coop_lean && !fa.back_waves && k.max_cells <= (1ull << 18) && k.n_small != 0) {
         // (queue units per resident wave; two pairs per wave: a unit is two pairs)
         const double per_wave = (double)(k.duo_qo ? (k.n_small + 1) / 2 : k.n_small) / ((double)std::min(k.grid, (uint32_t)ctx->cus * 3u) * 4.0);
         // (measured: C3, 3.3 pairs per wave: runs of 2 fill 0.232 -> 0.204 ms, runs of 3 / 4 0.218 / 0.222 -- the last round gets uneven;
