@@ -56,6 +56,12 @@ class PairResult(C.Structure):
 
 assert C.sizeof(PairResult) == 48
 
+# PairResult.flags / RESULT_DTYPE["flags"] (include/aligner_hip.h): which kernels filled the pair
+FLAG_INTEGER = 1        # integer kernels (also a dyadic real-valued scheme, filled scaled by 2^k)
+FLAG_SINGLE = 2         # the strip-pipelined single-pair route
+FLAG_WORKGROUP = 4      # generic kernels, one workgroup per pair
+FLAG_FAST = 8           # the fast integer kernels (i32 keys 4*H + tag, int8 query profile)
+
 
 class ScanGeometry(C.Structure):
     _fields_ = [("first", C.c_uint64), ("step", C.c_uint64), ("width", C.c_uint64), ("reverse", C.c_uint32),

@@ -40,6 +40,7 @@
 
 #include "aln_device.h"
 #include "aln_plan_rules.h"
+#include "aln_scheme_rules.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -347,8 +348,6 @@ struct Call {
     int semantics = 0;                // what the kernels run (PWM runs as CORE_LOCAL with position-specific scoring)
 };
 
-static bool integral(double v) { return std::isfinite(v) && v == std::floor(v) && std::fabs(v) < 1e9; }
-
 // bytes of the single-pair kernel's advice array and of its bottom-row record (one direction dword per block of the last
 // strip, at most (N + 63) / 2 + 4 blocks at R = 8), equal sizes, 256-aligned
 static inline uint64_t single_advice_bytes(uint64_t N)
@@ -371,7 +370,7 @@ static int call_init(Call &c, const aln_params *p, const uint64_t *q_len, const 
     if (c.pwm && p->rows != 4) return ALN_ERR_MATRIX_SHAPE;                    // pwm/mod.rs:40-42
     // the matrix lives in LDS: 32 KiB next to the query profiles; a position-weight matrix (no profiles in LDS) may be
     // 4 x 2000 wide (62.5 KiB as f64)
-    if ((uint64_t)p->rows * p->cols > (c.pwm ? 8000u : 4096u)) {
+    if (!aln_matrix_fits(c.pwm, p->rows, p->cols)) {
         g_err = c.pwm ? "position-weight matrix larger than 8000 entries (4 x 2000)" : "substitution matrix larger than 4096 entries";
         return ALN_ERR_UNSUPPORTED;
     }
@@ -379,17 +378,10 @@ static int call_init(Call &c, const aln_params *p, const uint64_t *q_len, const 
     c.rows = p->rows; c.cols = p->cols;
     const int64_t rs = p->row_stride ? p->row_stride : (int64_t)c.cols;
     c.md.resize((size_t)c.rows * c.cols);
-    c.maxabs = std::max(std::fabs(p->del), std::fabs(p->ext));
-    c.all_int = integral(p->del) && (c.core ? integral(p->ext) : true);
-    c.smin = 0; c.smax = 0;
     for (uint32_t r = 0; r < c.rows; ++r)
-        for (uint32_t k = 0; k < c.cols; ++k) {
-            const double v = p->matrix[(int64_t)r * rs + k];
-            c.md[(size_t)r * c.cols + k] = v;
-            c.all_int = c.all_int && integral(v);
-            c.maxabs = std::max(c.maxabs, std::fabs(v));
-            c.smin = std::min(c.smin, v); c.smax = std::max(c.smax, v);
-        }
+        for (uint32_t k = 0; k < c.cols; ++k) c.md[(size_t)r * c.cols + k] = p->matrix[(int64_t)r * rs + k];
+    AlnScheme sch = aln_scheme_scan(c.core, p->del, p->ext, c.md.data(), c.md.size());
+    c.all_int = sch.all_int;
     if (!c.core && !c.all_int) { g_err = "legacy semantics are i32: del and matrix must be integral"; return ALN_ERR_INVALID_ARGUMENT; }
     if (!c.core && p->force_f64) { g_err = "legacy semantics have no f64 form"; return ALN_ERR_UNSUPPORTED; }
     c.outs = p->outputs ? p->outputs : (ALN_OUT_SCORE | ALN_OUT_TRACEBACK);
@@ -407,31 +399,23 @@ static int call_init(Call &c, const aln_params *p, const uint64_t *q_len, const 
     // multiple of 2^-k, two candidates differ by 0 or by >= 2^-k > f64::EPSILON, and H == 0 means the same -- so the integer kernels
     // fill it (three times the f64 kernels' rate) and the two scores of every summary are scaled back, exactly, by one small kernel
     // behind the traceback.  Not with the H output (the dump is what the kernels computed), not when f64 is asked for.
-    // ALN_NO_DYADIC=1: off.
-    if (c.core && !c.all_int && !p->force_f64 && !want_h && !getenv("ALN_NO_DYADIC")) {
-        for (int kk = 1; kk <= 8; ++kk) {
-            const double sc = (double)(1 << kk);
-            bool ok = integral(p->del * sc) && integral(p->ext * sc);
-            for (size_t i = 0; ok && i < c.md.size(); ++i) ok = integral(c.md[i] * sc);
-            if (!ok) continue;
-            if (c.maxabs * sc * (double)max_span < 1073741824.0) {
-                for (double &v : c.md) v *= sc;
-                c.p.del *= sc; c.p.ext *= sc;
-                c.maxabs *= sc; c.smin *= sc; c.smax *= sc;
-                c.all_int = true;
-                c.unscale = 1.0 / sc;
-            }
-            break;
-        }
+    // ALN_NO_DYADIC=1: off.  The classification itself (bounds included) is aln_scheme_rules.h.
+    aln_scheme_dyadic(sch, c.core, p->force_f64, want_h, getenv("ALN_NO_DYADIC") != nullptr, p->del, p->ext, c.md.data(), c.md.size(),
+                      max_span);
+    if (sch.scale != 1.0) {
+        for (double &v : c.md) v *= sch.scale;
+        c.p.del *= sch.scale; c.p.ext *= sch.scale;
+        c.unscale = 1.0 / sch.scale;
     }
-    // integer kernels are exact iff every value is integral and |H| cannot leave i32
-    c.is_int = c.all_int && !p->force_f64 && c.maxabs * (double)max_span < 1073741824.0;
+    // integer kernels are exact iff every value is integral and |H| cannot leave i32; fast integer kernels: keys are
+    // 4*H + tag in i32, the profile holds 4*s - 2 as int8, and S + four waves' profiles (cols x 512 B each) have to fit the 64 KiB
+    // of LDS a workgroup gets without an opt-in
+    aln_scheme_route(sch, c.pwm, c.rows, c.cols, max_span, p->force_f64, want_h, p->force_serial, p->force_generic, ALN_FULL_R);
+    c.all_int = sch.all_int;
+    c.maxabs = sch.maxabs; c.smin = sch.smin; c.smax = sch.smax;
+    c.is_int = sch.is_int;
     if (!c.core && !c.is_int) { g_err = "legacy scores overflow i32 for these lengths"; return ALN_ERR_UNSUPPORTED; }
-    // fast integer kernels: keys are 4*H + tag in i32, the profile holds 4*s - 2 as int8, and S + four waves' profiles
-    // (cols x 512 B each) have to fit the 64 KiB of LDS a workgroup gets without an opt-in
-    const uint64_t fast_lds = (((uint64_t)c.rows * c.cols * 4 + 15) & ~15ull) + (c.pwm ? 0ull : 4ull * c.cols * 64u * ALN_FULL_R);
-    c.fast = c.is_int && !want_h && !p->force_serial && !p->force_generic && fast_lds <= 65536 && c.smin >= -31.0 && c.smax <= 32.0 &&
-             c.maxabs * (double)max_span < 268435456.0;
+    c.fast = sch.fast;
     return ALN_OK;
 }
 

@@ -1565,14 +1565,14 @@ __device__ __forceinline__ bool fast_work(FastIn in, const FastScratch &fs, cons
         __threadfence();                                 // (ordinary stores, also into the rows other waves' granules land in later: none stays dirty here)
         if (lane == 0) {
             desc.layout = ALN_LAYOUT_ROWMAJOR;
-            write_result<SEM>(res, (double)c.bv, c.by, c.bx, (double)c.corner, N, M, passes | 0x80u, 1u, in.pwm);
+            write_result<SEM>(res, (double)c.bv, c.by, c.bx, (double)c.corner, N, M, passes | 0x80u, 1u | 8u, in.pwm);
         }
         return true;                                     // directions written with ordinary stores
     }
     if (is_local<SEM>()) reduce_best<SEM>(o);
     if (lane == 0) {
         desc.layout = Ru ? (ALN_LAYOUT_UBATCH | (Ru << 8)) : ALN_LAYOUT_SKEW;
-        write_result<SEM>(res, (double)(o.bv >> 2), o.by, o.bx, (double)(o.corner >> 2), N, M, passes, 1u, in.pwm);
+        write_result<SEM>(res, (double)(o.bv >> 2), o.by, o.bx, (double)(o.corner >> 2), N, M, passes, 1u | 8u, in.pwm);
     }
     return false;
 }
@@ -2095,7 +2095,7 @@ __global__ __launch_bounds__(1024) void aln_single_finalize_kernel(SingleArgs a)
     if (lane == 0) {
         const int corner = a.cand[4 * (a.ns - 1) + 3] >> 2;
         desc.layout = ALN_LAYOUT_UNIFORM | (a.R << 8);
-        write_result<SEM>(res, (double)(o.bv >> 2), o.by, o.bx, (double)corner, N, M, a.pass + 1, 1u | 2u);
+        write_result<SEM>(res, (double)(o.bv >> 2), o.by, o.bx, (double)corner, N, M, a.pass + 1, 1u | 2u | 8u);
         if (aborted) res.status = ALN_ERR_DEVICE;
     }
 }
@@ -2152,7 +2152,7 @@ __global__ __launch_bounds__(1024) void aln_single_repair_finalize_kernel(Single
     if (lane == 0) {
         const int corner = a.cand[4 * (a.ns - 1) + 3] >> 2;
         desc.layout = ALN_LAYOUT_UNIFORM | (a.R << 8);
-        write_result<SEM>(res, (double)(o.bv >> 2), o.by, o.bx, (double)corner, desc.N, desc.M, 1u | 0x100u, 1u | 2u);
+        write_result<SEM>(res, (double)(o.bv >> 2), o.by, o.bx, (double)corner, desc.N, desc.M, 1u | 0x100u, 1u | 2u | 8u);
         a.ctrl[8] = 0;
     }
 }
@@ -2179,7 +2179,7 @@ __global__ __launch_bounds__(64) void aln_single_serial_kernel(SingleArgs a)
     w.hmat = nullptr; w.store_dirs = a.store_dirs != 0; w.pwm = false;
     serial_fill_impl<int, SEM>(w);
     desc.layout = ALN_LAYOUT_ROWMAJOR;
-    write_result<SEM>(res, (double)w.bv, w.by, w.bx, (double)w.corner, desc.N, desc.M, a.ctrl[15] | 0x80u, 1u | 2u);
+    write_result<SEM>(res, (double)w.bv, w.by, w.bx, (double)w.corner, desc.N, desc.M, a.ctrl[15] | 0x80u, 1u | 2u | 8u);
 }
 
 // arms pass 0 and clears the advice / bottom-row bytes.  A pair the validation kernel rejected (a residue code outside the
@@ -3100,7 +3100,7 @@ void aln_fill_duo_kernel(FillArgs a)
             if (!ok) skip_invalid(res, st, 0);
             else {
                 a.descs[pair].layout = ALN_LAYOUT_UBATCH | (R << 8);
-                write_result<ALN_CORE_GLOBAL>(res, 0.0, 0, 0, (double)(corner >> 2), N, M, 1u, 1u);
+                write_result<ALN_CORE_GLOBAL>(res, 0.0, 0, 0, (double)(corner >> 2), N, M, 1u, 1u | 8u);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // the LDS of this item is reused by the next

@@ -91,7 +91,9 @@ typedef struct aln_pair_result {
                                    bottom row moved, 3 no re-convergence, 4 repair limit); diagnostics only */
     uint32_t flags;             /* bit0: integer kernels were used (also for a real-valued scheme whose numbers are all multiples of
                                    2^-k, k <= 8: it is filled as the integer scheme times 2^k and f / score are scaled back, exactly); bit1: the strip-pipelined single-pair route;
-                                   bit2: generic kernels, one workgroup per pair (real-valued matrix / H output, <= 4 pairs per call) */
+                                   bit2: generic kernels, one workgroup per pair (real-valued matrix / H output, <= 4 pairs per call);
+                                   bit3: the fast integer kernels (i32 keys 4*H + tag, int8 query profile) filled this pair -- the
+                                   batch kernel, two pairs per wave, the single-pair route and their strict-order fallbacks */
 } aln_pair_result;
 
 typedef struct aln_ctx aln_ctx;      /* one per process: one GPU or a list of GPUs; thread-safe */

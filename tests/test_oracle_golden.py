@@ -147,3 +147,51 @@ def test_oracle_pwm_matches_python_restatement(orc, seed):
     assert got["f"] == ref["f"] and got["coords"] == ref["coords"]
     assert orc.align_pwm(seq, dele, ext, M[:3])["status"] == orc.ERR_MATRIX_SHAPE
     assert orc.align_pwm(seq, dele, ext, M, heuristics_present=True)["status"] == orc.ERR_UNNECESSARY_ARGUMENT
+
+
+TENTHS = np.array([[0.3, -0.1, -0.2, -0.2], [-0.1, 0.3, -0.2, -0.2], [-0.2, -0.2, 0.3, -0.1], [-0.2, -0.2, -0.1, 0.3]])
+
+
+@pytest.mark.parametrize("case", ["tenths", "blosum62x0.3", "big_penalty", "negative_penalty"])
+def test_oracle_matches_python_restatement_at_the_edges(orc, blosum62, case):
+    """The GPU tests at the limits trust the oracle exactly where its rules bite: schemes whose f64 cells hold candidates within
+    f64::EPSILON of the maximum and H within 1e-12 of zero (the literal EPS rule, Beginning on H == 0 exactly), and integer
+    schemes with the last integer penalty of a lopsided pair and with a negative one (f64 and i32 borders).  H and D cell by
+    cell against the restatement."""
+    from scheme_limits import INT_BOUND, last_below, span, tie_counts
+    rng = np.random.default_rng(len(case))
+    near = tiny = 0
+    for trial in range(4):
+        if case in ("tenths", "blosum62x0.3"):
+            S, dele, ext, A = (TENTHS, 0.2, 0.1, 4) if case == "tenths" else (blosum62 * 0.3, 3.3, 0.6, 20)
+            N, M = int(rng.integers(30, 60)), int(rng.integers(30, 60))
+        elif case == "big_penalty":
+            N, M = 120, 6
+            S, A = blosum62, 20
+            dele = ext = last_below(INT_BOUND, span(N, M))
+        else:
+            S, dele, ext, A = blosum62, -1, 2 if trial % 2 else -1, 20
+            N, M = int(rng.integers(10, 40)), int(rng.integers(10, 40))
+        q = rng.integers(0, A, N).astype(np.uint8)
+        t = rng.integers(0, A, M).astype(np.uint8)
+        for sem, local in ((orc.CORE_GLOBAL, False), (orc.CORE_LOCAL, True)):
+            ref = pyref.core(q.tolist(), t.tolist(), float(dele), float(ext), S.tolist(), local)
+            got = orc.align(sem, q, t, dele, ext, S, want_matrices=True)
+            if ref.get("panic"):
+                assert got["status"] == orc.ERR_NO_POSITIVE_CELL
+                continue
+            assert (got["H"] == _H(ref["H"], M, N)).all() and (got["D"] == _H(ref["D"], M, N)).all()
+            assert got["qa"].tolist() == ref["qa"] and got["ta"].tolist() == ref["ta"]
+            assert got["f"] == ref["f"] and got["coords"] == ref["coords"] and got["score"] == ref["score"]
+            n_, t_ = tie_counts(got["H"], got["D"], q, t, dele, ext, S, local)
+            near, tiny = near + n_, tiny + t_
+            if case == "big_penalty" and not local:
+                assert abs(got["H"]).max() == (N + 1) * dele > 0.9 * INT_BOUND          # the border -(N + 1) del
+        if case in ("big_penalty", "negative_penalty"):
+            for sem, local in ((orc.LEGACY_GLOBAL, False), (orc.LEGACY_LOCAL, True)):
+                ref = pyref.legacy(q.tolist(), t.tolist(), int(dele), S.tolist(), local)
+                got = orc.align(sem, q, t, dele, dele, S, want_matrices=True)
+                assert (got["H"] == _H(ref["H"], M, N)).all() and (got["D"] == _H(ref["D"], M, N)).all()
+                assert got["qa"].tolist() == ref["qa"] and got["ta"].tolist() == ref["ta"] and got["score"] == ref["score"]
+    if case in ("tenths", "blosum62x0.3"):
+        assert near > 0 and tiny > 0, (near, tiny)
