@@ -36,7 +36,7 @@ EXPORTS = [
     "aln_batch_destroy", "aln_batch_cells", "aln_batch_size", "aln_batch_results_device",
     "aln_batch_direction_bytes", "aln_batch_timing", "aln_batch_enable_timing",
     "aln_scan_create", "aln_scan_destroy", "aln_scan_windows", "aln_scan_score", "aln_scan_select", "aln_scan_string_stride",
-    "aln_scan_stats",
+    "aln_scan_stats", "aln_shuffle_scores", "aln_shuffle_targets",
 ]
 
 
@@ -66,6 +66,14 @@ FLAG_FAST = 8           # the fast integer kernels (i32 keys 4*H + tag, int8 que
 class ScanGeometry(C.Structure):
     _fields_ = [("first", C.c_uint64), ("step", C.c_uint64), ("width", C.c_uint64), ("reverse", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+
+class ShuffleSpec(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("pair_base", C.c_uint64), ("per_pair", C.c_uint32), ("max_trim", C.c_uint32)]
+
+
+assert C.sizeof(ShuffleSpec) == 24
 
 _lib = None
 
@@ -140,6 +148,11 @@ def load():
     lib.aln_scan_string_stride.argtypes = [vp, C.c_uint32, gp]
     lib.aln_scan_stats.restype = i
     lib.aln_scan_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    sp = C.POINTER(ShuffleSpec)
+    lib.aln_shuffle_scores.restype = i
+    lib.aln_shuffle_scores.argtypes = [vp, C.POINTER(Params), sp, vp, u64p, u64p, u64p, u64p, C.c_size_t, vp, vp, vp]
+    lib.aln_shuffle_targets.restype = i
+    lib.aln_shuffle_targets.argtypes = [vp, sp, vp, u64p, u64p, C.c_size_t, vp, u64p]
     _lib = lib
     return lib
 

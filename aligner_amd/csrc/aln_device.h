@@ -53,6 +53,17 @@ struct PairDesc {
 // the loops do not run, argmax is (0, 0), the traceback stops at once, f = 0).  The kernels skip the pair and report ALN_OK.
 #define ALN_PRE_EMPTY_OK (-1)
 
+// one pair of a shuffle call (aln_shuffle_*, aln_shuffle.hip): where its residues and its copies lie in the slot's residue buffer
+struct ShufflePair {
+    uint64_t q_off;          // the query (aln_shuffle_scores)
+    uint64_t t_off;          // the original target
+    uint64_t out_off;        // copy 0 in the call's shuffled region; copy s at out_off + s * t_len (L - trim bytes of it written)
+    uint32_t q_len, t_len;
+};
+// copies of at most this many residues are shuffled in LDS: 64 threads x 2 KiB = 128 KiB of a CU's 160
+#define ALN_SHUFFLE_LDS_MAX 2048u
+#define ALN_SHUFFLE_THREADS 64u
+
 struct FillArgs {
     const uint8_t *seqs;
     PairDesc *descs;

@@ -41,6 +41,7 @@
 #include "aln_device.h"
 #include "aln_plan_rules.h"
 #include "aln_scheme_rules.h"
+#include "aln_shuffle_rules.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -137,6 +138,7 @@ struct Slot {
     bool pooled = true;       // pool slots keep some slack when they grow; a staged batch's private slot is sized exactly
     DevBuf seqs, descs, order, counter, walked, dirs, results, tb, tags, scratch, matrix, pwm_words, hmat;
     DevBuf granules, advice1, cand, ctrl, tbmap, unpack, repair, coop;
+    DevBuf shuffle;           // shuffle calls (aln_shuffle_*): pair table | f of every copy | first failed copy per pair
     PinBuf h_meta;            // descs + order + matrix + pwm words (small, truly asynchronous H2D)
     PinBuf h_in, h_out;       // fallback staging: sequences gathered from scattered offsets / strings for a foreign tb layout
     hipStream_t stream = nullptr;
@@ -181,7 +183,8 @@ static void slot_destroy(Slot *s)
 {
     if (!s) return;
     DevBuf *d[] = {&s->seqs, &s->descs, &s->order, &s->counter, &s->walked, &s->dirs, &s->results, &s->tb, &s->tags, &s->scratch,
-                   &s->matrix, &s->pwm_words, &s->hmat, &s->granules, &s->advice1, &s->cand, &s->ctrl, &s->tbmap, &s->unpack, &s->repair, &s->coop};
+                   &s->matrix, &s->pwm_words, &s->hmat, &s->granules, &s->advice1, &s->cand, &s->ctrl, &s->tbmap, &s->unpack, &s->repair, &s->coop,
+                   &s->shuffle};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(s->h_meta); pin_free(s->h_in); pin_free(s->h_out);
     if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
@@ -2018,5 +2021,299 @@ extern "C" int aln_scan_stats(const aln_scan *sc, double *ms, uint64_t *bytes)
     if (!sc) return ALN_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < 4 && ms; ++i) ms[i] = sc->ms[i];
     for (int i = 0; i < 2 && bytes; ++i) bytes[i] = sc->bytes[i];
+    return ALN_OK;
+}
+
+// ---------------------------------------------------------------- shuffled copies: calculate_p_value's batch on the device
+// calculate_p_value (statistics/mod.rs:240-320) aligns a query against 4 999 trimmed and shuffled copies of its target.  A shuffle
+// call uploads every pair's query and original target once; per chunk of whole pairs the copies are drawn on the device
+// (aln_shuffle.hip: one thread per copy), expanded into descriptors there, filled score only by the same launches a batch call
+// makes (slot_launch, planned by chunk_plan from the copies' lengths, which the host computes with aln_shuffle_rules.h), and
+// their f gathered into one array: 8 bytes per copy and 4 per pair come back.  Every chunk is queued on one stream behind the
+// one before it; the host waits once, at the end.
+extern "C" void aln_shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
+                                   uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t out_base, uint32_t slot, hipStream_t s);
+extern "C" void aln_shuffle_launch_expand(PairDesc *descs, uint32_t *order, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
+                                          uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t region, uint64_t out_base, hipStream_t s);
+extern "C" void aln_shuffle_launch_gather(const aln_pair_result *res, double *f, uint64_t n, uint32_t per_pair, uint32_t *first, hipStream_t s);
+
+#define ALN_SHUFFLE_MAX_COPIES (1u << 20)          // per pair
+#define ALN_SHUFFLE_CHUNK_COPIES (1ull << 22)      // per chunk: the pair limit of a chunk of aln_align_batch
+#define ALN_SHUFFLE_CHUNK_BYTES (1ull << 30)       // shuffled residues per chunk
+
+static inline uint64_t align256(uint64_t v) { return (v + 255) & ~255ull; }
+
+static int shuffle_check(aln_ctx *ctx, const aln_shuffle_spec *sp, const uint8_t *seqs, const uint64_t *t_off, const uint64_t *t_len, size_t n)
+{
+    if (!ctx || !sp || (n && (!seqs || !t_off || !t_len))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->per_pair == 0 || sp->per_pair > ALN_SHUFFLE_MAX_COPIES) { g_err = "per_pair must be 1 .. 2^20"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n > 0xFFFFFFF0ull) { g_err = "too many pairs"; return ALN_ERR_UNSUPPORTED; }
+    for (size_t i = 0; i < n; ++i) {
+        if (t_len[i] > 0x7FFFFFF0ull) { g_err = "sequence too long"; return ALN_ERR_UNSUPPORTED; }
+        // statistics/mod.rs:312-314 slices target[..len - lock]: a trim draw longer than the target panics there
+        if (t_len[i] < sp->max_trim) { g_err = "a target is shorter than max_trim"; return ALN_ERR_INVALID_ARGUMENT; }
+    }
+    return ALN_OK;
+}
+
+// what a shuffle call uploads: one span of the caller's buffer, or -- offsets scattered far beyond what the pairs use -- the ranges
+// packed back to back; and the pair table with every pair's offsets in those bytes and its copies' place in the shuffled region
+struct ShuffleStage {
+    std::vector<ShufflePair> pairs;
+    bool direct = true;
+    uint64_t lo = 0, bytes = 0;       // direct: seqs[lo .. lo + bytes)
+    std::vector<uint8_t> packed;
+};
+
+static void shuffle_stage(const uint8_t *seqs, const uint64_t *q_off, const uint64_t *q_len, const uint64_t *t_off, const uint64_t *t_len,
+                          size_t n, uint32_t per_pair, ShuffleStage &g)
+{
+    uint64_t lo = ~0ull, hi = 0, sum = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (q_len && q_len[i]) { lo = std::min(lo, q_off[i]); hi = std::max(hi, q_off[i] + q_len[i]); sum += q_len[i]; }
+        if (t_len[i]) { lo = std::min(lo, t_off[i]); hi = std::max(hi, t_off[i] + t_len[i]); sum += t_len[i]; }
+    }
+    if (lo == ~0ull) { lo = 0; hi = 0; }
+    g.direct = hi - lo <= 2 * sum + 65536;
+    g.lo = lo;
+    g.pairs.resize(n);
+    if (!g.direct) g.packed.resize(sum);
+    uint64_t pos = 0, out = 0;
+    for (size_t i = 0; i < n; ++i) {
+        ShufflePair &P = g.pairs[i];
+        P.q_len = q_len ? (uint32_t)q_len[i] : 0u;
+        P.t_len = (uint32_t)t_len[i];
+        if (g.direct) {
+            P.q_off = P.q_len ? q_off[i] - lo : 0;
+            P.t_off = P.t_len ? t_off[i] - lo : 0;
+        } else {
+            P.q_off = pos;
+            if (P.q_len) memcpy(g.packed.data() + pos, seqs + q_off[i], P.q_len);
+            pos += P.q_len;
+            P.t_off = pos;
+            if (P.t_len) memcpy(g.packed.data() + pos, seqs + t_off[i], P.t_len);
+            pos += P.t_len;
+        }
+        P.out_off = out;
+        out += (uint64_t)per_pair * P.t_len;
+    }
+    g.bytes = g.direct ? hi - lo : pos;
+}
+
+// chunks of whole pairs: at most ALN_SHUFFLE_CHUNK_COPIES copies and ALN_SHUFFLE_CHUNK_BYTES shuffled residues (a single pair may
+// exceed the latter), and -- cells given -- cut once they reach `target` cells, as make_chunks cuts
+static void shuffle_chunks(const ShuffleStage &g, uint32_t per_pair, const std::vector<double> *cells, double target,
+                           std::vector<std::pair<size_t, size_t>> &out)
+{
+    out.clear();
+    const size_t n = g.pairs.size();
+    size_t first = 0;
+    double acc = 0;
+    uint64_t copies = 0, bytes = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t b = (uint64_t)per_pair * g.pairs[i].t_len;
+        if (i > first && (copies + per_pair > ALN_SHUFFLE_CHUNK_COPIES || bytes + b > ALN_SHUFFLE_CHUNK_BYTES)) {
+            out.emplace_back(first, i - first);
+            first = i; acc = 0; copies = 0; bytes = 0;
+        }
+        copies += per_pair; bytes += b;
+        if (cells && (acc += (*cells)[i]) >= target) {
+            out.emplace_back(first, i + 1 - first);
+            first = i + 1; acc = 0; copies = 0; bytes = 0;
+        }
+    }
+    if (first < n) out.emplace_back(first, n - first);
+}
+
+// LDS bytes per thread of the shuffle kernel for pairs [p0, p0 + np): the longest target that fits ALN_SHUFFLE_LDS_MAX, 16-aligned
+static uint32_t shuffle_lds_slot(const ShuffleStage &g, size_t p0, size_t np)
+{
+    uint32_t m = 0;
+    for (size_t i = p0; i < p0 + np; ++i)
+        if (g.pairs[i].t_len <= ALN_SHUFFLE_LDS_MAX) m = std::max(m, g.pairs[i].t_len);
+    return (m + 15u) & ~15u;
+}
+
+static uint64_t chunk_region_bytes(const ShuffleStage &g, uint32_t per_pair, size_t p0, size_t np)
+{
+    uint64_t b = 0;
+    for (size_t i = p0; i < p0 + np; ++i) b += (uint64_t)per_pair * g.pairs[i].t_len;
+    return b;
+}
+
+// H2D of the staged residues (at 0 of the slot's residue buffer) and of the pair table (at 0 of its shuffle buffer)
+static int shuffle_upload(Slot &s, const ShuffleStage &g, const uint8_t *seqs, hipStream_t st)
+{
+    if (g.bytes) HIPCHK(hipMemcpyAsync(s.seqs.p, g.direct ? seqs + g.lo : g.packed.data(), g.bytes, hipMemcpyHostToDevice, st));
+    if (!g.pairs.empty()) HIPCHK(hipMemcpyAsync(s.shuffle.p, g.pairs.data(), g.pairs.size() * sizeof(ShufflePair), hipMemcpyHostToDevice, st));
+    return ALN_OK;
+}
+
+extern "C" int aln_shuffle_scores(aln_ctx *ctx, const aln_params *params, const aln_shuffle_spec *spec, const uint8_t *seqs,
+                                  const uint64_t *q_off, const uint64_t *q_len, const uint64_t *t_off, const uint64_t *t_len,
+                                  size_t n_pairs, double *f, uint32_t *lengths, int32_t *status)
+{
+    int st = shuffle_check(ctx, spec, seqs, t_off, t_len, n_pairs);
+    if (st != ALN_OK) return st;
+    if (!params || (n_pairs && (!q_off || !q_len || !f))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (params->semantics == ALN_PWM_LOCAL) { g_err = "shuffled copies are aligned with the substitution-matrix semantics only"; return ALN_ERR_UNSUPPORTED; }
+    const uint32_t per = spec->per_pair;
+    const uint64_t total = (uint64_t)n_pairs * per;
+    // every copy's length: the plan needs them, the caller gets them; the longest copy of each pair decides the routes as in
+    // aln_align_batch over the copies (call_init)
+    std::vector<uint32_t> own_lens;
+    uint32_t *lens = lengths;
+    if (!lens) { own_lens.resize(total); lens = own_lens.data(); }
+    std::vector<uint64_t> lmax(n_pairs, 0);
+    std::vector<double> cells(n_pairs, 0.0);
+    for (size_t i = 0; i < n_pairs; ++i) {
+        uint64_t sum = 0;
+        for (uint32_t s = 0; s < per; ++s) {
+            const uint32_t L = (uint32_t)t_len[i] - aln_shuffle_trim_of(spec->seed, spec->pair_base + i, s, spec->max_trim);
+            lens[(uint64_t)i * per + s] = L;
+            lmax[i] = std::max<uint64_t>(lmax[i], L);
+            sum += L;
+        }
+        cells[i] = (double)q_len[i] * (double)sum;
+    }
+    aln_params p = *params;
+    p.outputs = ALN_OUT_SCORE;
+    Call c;
+    if ((st = call_init(c, &p, q_len, lmax.data(), n_pairs, false)) != ALN_OK) return st;
+    if (n_pairs == 0) return ALN_OK;
+
+    ShuffleStage g;
+    shuffle_stage(seqs, q_off, q_len, t_off, t_len, n_pairs, per, g);
+    // chunks: the cell bounds of make_chunks (1.6e10, three times that for the generic kernels; ALN_CHUNK_CELLS overrides)
+    double target = c.fast ? 1.6e10 : 4.8e10;
+    if (const char *e = getenv("ALN_CHUNK_CELLS")) target = std::max(1.0, atof(e));
+    std::vector<std::pair<size_t, size_t>> ranges;
+    shuffle_chunks(g, per, &cells, target, ranges);
+    const uint64_t region = align256(g.bytes);        // the shuffled copies of a chunk lie behind the uploaded residues
+    DevCtx *dev = ctx->devs[0];
+    HIPCHK(hipSetDevice(dev->device));
+    // the plans of every chunk first: the copies' lengths and offsets in the residue buffer, routed and laid out by chunk_plan
+    std::vector<Chunk> plans(ranges.size());
+    uint64_t region_max = 0, seq_need = 0;
+    {
+        std::vector<uint64_t> qo, ql, to, tl;
+        for (size_t j = 0; j < ranges.size(); ++j) {
+            const size_t p0 = ranges[j].first, np = ranges[j].second;
+            const uint64_t m = (uint64_t)np * per, out_base = g.pairs[p0].out_off;
+            qo.resize(m); ql.resize(m); to.resize(m); tl.resize(m);
+            for (size_t i = p0; i < p0 + np; ++i) {
+                const ShufflePair &P = g.pairs[i];
+                for (uint32_t s = 0; s < per; ++s) {
+                    const uint64_t k = (uint64_t)(i - p0) * per + s;
+                    qo[k] = P.q_off; ql[k] = P.q_len;
+                    to[k] = region + (P.out_off - out_base) + (uint64_t)s * P.t_len;
+                    tl[k] = lens[(uint64_t)i * per + s];
+                }
+            }
+            Chunk &k = plans[j];
+            if ((st = chunk_plan(dev, c, qo.data(), ql.data(), to.data(), tl.data(), 0, m, true, k)) != ALN_OK) return st;
+            // the descriptors are the device's (aln_shuffle_expand_kernel); the host keeps them, and the queue, only for the launches of
+            // copies routed elsewhere (scan_plan does the same)
+            if (k.single_pairs.empty() && k.wg_pairs.empty()) {
+                k.descs.clear(); k.descs.shrink_to_fit();
+                k.order.clear(); k.order.shrink_to_fit();
+            }
+            region_max = std::max(region_max, chunk_region_bytes(g, per, p0, np));
+            seq_need = std::max(seq_need, k.seq_span);
+        }
+    }
+    Slot *sl[1];
+    pool_lease(dev, 1, sl);
+    struct Release { DevCtx *c; Slot **s; ~Release() { pool_release(c, s, 1); } } rel{dev, sl};
+    Slot &s = *sl[0];
+    // every buffer is sized before anything is queued (a buffer that grew later would be freed under a running kernel)
+    if ((st = dev_ensure(s.seqs, std::max(region + region_max, seq_need) + 64, s.pooled)) != ALN_OK) return st;
+    for (const Chunk &k : plans)
+        if ((st = slot_ensure(s, c, k, nullptr, true)) != ALN_OK) return st;
+    const uint64_t f_off = align256(sizeof(ShufflePair) * n_pairs), first_off = align256(f_off + 8 * total);
+    if ((st = dev_ensure(s.shuffle, first_off + 4ull * n_pairs, s.pooled)) != ALN_OK) return st;
+    const ShufflePair *pairs_d = s.shuffle.as<ShufflePair>();
+    double *f_d = reinterpret_cast<double *>(s.shuffle.as<uint8_t>() + f_off);
+    uint32_t *first_d = reinterpret_cast<uint32_t *>(s.shuffle.as<uint8_t>() + first_off);
+    hipStream_t q = s.stream;
+    if ((st = shuffle_upload(s, g, seqs, q)) != ALN_OK) return st;
+    HIPCHK(hipMemsetAsync(first_d, 0xff, 4ull * n_pairs, q));
+    if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) return st;
+    for (size_t j = 0; j < ranges.size(); ++j) {
+        const size_t p0 = ranges[j].first, np = ranges[j].second;
+        const uint64_t m = (uint64_t)np * per, out_base = g.pairs[p0].out_off;
+        const Chunk &k = plans[j];
+        aln_shuffle_launch(s.seqs.as<uint8_t>(), s.seqs.as<uint8_t>() + region, pairs_d, (uint32_t)p0, m, per, spec->seed, spec->pair_base,
+                           spec->max_trim, out_base, shuffle_lds_slot(g, p0, np), q);
+        aln_shuffle_launch_expand(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), pairs_d, (uint32_t)p0, m, per, spec->seed, spec->pair_base,
+                                  spec->max_trim, region, out_base, q);
+        HIPCHK(hipGetLastError());
+        if (k.n_small != k.n && k.n_small)               // some copies take another route: the batch kernel's queue is the plan's
+            HIPCHK(hipMemcpyAsync(s.order.p, k.order.data(), 4 * k.n_small, hipMemcpyHostToDevice, q));
+        if ((st = slot_launch(dev, s, c, k, q, nullptr, nullptr)) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+        aln_shuffle_launch_gather(s.results.as<aln_pair_result>(), f_d + (uint64_t)p0 * per, m, per, first_d + p0, q);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<uint32_t> first(n_pairs);
+    HIPCHK(hipMemcpyAsync(f, f_d, 8 * total, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipMemcpyAsync(first.data(), first_d, 4ull * n_pairs, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    int bad = ALN_OK;
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const int32_t v = first[i] == 0xffffffffu ? ALN_OK : (int32_t)(first[i] & 0xffu);
+        if (status) status[i] = v;
+        if (bad == ALN_OK && v != ALN_OK) bad = v;
+    }
+    if (!status && bad != ALN_OK) { g_err = "a pair failed"; return bad; }
+    return ALN_OK;
+}
+
+extern "C" int aln_shuffle_targets(aln_ctx *ctx, const aln_shuffle_spec *spec, const uint8_t *seqs, const uint64_t *t_off,
+                                   const uint64_t *t_len, size_t n_pairs, uint8_t *out, const uint64_t *out_off)
+{
+    int st = shuffle_check(ctx, spec, seqs, t_off, t_len, n_pairs);
+    if (st != ALN_OK) return st;
+    if (n_pairs && (!out || !out_off)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_pairs == 0) return ALN_OK;
+    const uint32_t per = spec->per_pair;
+    ShuffleStage g;
+    shuffle_stage(seqs, nullptr, nullptr, t_off, t_len, n_pairs, per, g);
+    std::vector<std::pair<size_t, size_t>> ranges;
+    shuffle_chunks(g, per, nullptr, 0.0, ranges);
+    uint64_t region_max = 0;
+    for (const auto &r : ranges) region_max = std::max(region_max, chunk_region_bytes(g, per, r.first, r.second));
+    const uint64_t region = align256(g.bytes);
+    DevCtx *dev = ctx->devs[0];
+    HIPCHK(hipSetDevice(dev->device));
+    Slot *sl[1];
+    pool_lease(dev, 1, sl);
+    struct Release { DevCtx *c; Slot **s; ~Release() { pool_release(c, s, 1); } } rel{dev, sl};
+    Slot &s = *sl[0];
+    if ((st = dev_ensure(s.seqs, region + region_max + 64, s.pooled)) != ALN_OK) return st;
+    if ((st = dev_ensure(s.shuffle, sizeof(ShufflePair) * n_pairs, s.pooled)) != ALN_OK) return st;
+    if ((st = slot_init(s)) != ALN_OK) return st;
+    hipStream_t q = s.stream;
+    if ((st = shuffle_upload(s, g, seqs, q)) != ALN_OK) return st;
+    uint8_t *region_d = s.seqs.as<uint8_t>() + region;
+    for (const auto &r : ranges) {
+        const size_t p0 = r.first, np = r.second;
+        const uint64_t out_base = g.pairs[p0].out_off, bytes = chunk_region_bytes(g, per, p0, np);
+        HIPCHK(hipMemsetAsync(region_d, 0, bytes, q));     // the bytes of a slot beyond its copy's length read 0
+        aln_shuffle_launch(s.seqs.as<uint8_t>(), region_d, s.shuffle.as<ShufflePair>(), (uint32_t)p0, (uint64_t)np * per, per, spec->seed,
+                           spec->pair_base, spec->max_trim, out_base, shuffle_lds_slot(g, p0, np), q);
+        HIPCHK(hipGetLastError());
+        // the caller's layout: one copy when its offsets are this chunk's, one per pair otherwise
+        bool span = true;
+        for (size_t i = p0; i < p0 + np && span; ++i) span = out_off[i] >= out_off[p0] && out_off[i] - out_off[p0] == g.pairs[i].out_off - out_base;
+        if (span) {
+            if (bytes) HIPCHK(hipMemcpyAsync(out + out_off[p0], region_d, bytes, hipMemcpyDeviceToHost, q));
+        } else {
+            for (size_t i = p0; i < p0 + np; ++i)
+                if (g.pairs[i].t_len)
+                    HIPCHK(hipMemcpyAsync(out + out_off[i], region_d + (g.pairs[i].out_off - out_base), (uint64_t)per * g.pairs[i].t_len,
+                                          hipMemcpyDeviceToHost, q));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(q));
     return ALN_OK;
 }

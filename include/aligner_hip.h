@@ -194,6 +194,31 @@ int aln_scan_select(aln_scan *scan, const aln_params *params, const aln_scan_geo
 uint64_t aln_scan_string_stride(const aln_scan *scan, uint32_t cols, const aln_scan_geometry *geometry);
 int aln_scan_stats(const aln_scan *scan, double *ms, uint64_t *bytes);
 
+/* ---- shuffled copies (calculate_p_value, aligner-core/src/statistics/mod.rs:240-320): every pair's target is copied per_pair
+ * times, each copy losing `trim` tail residues (uniform in 0..max_trim) and then shuffled, and the query is aligned against every
+ * copy, score only.  The copies are drawn on the device (one device: the context's first) from SplitMix64 streams specified bit for
+ * bit in aligner_amd/csrc/aln_shuffle_rules.h: copy s of pair i depends on (seed, pair_base + i, s) only, so a job split across
+ * calls with matching pair_base gives the same copies.  The queries and the original targets are uploaded once.
+ * scores: f[i * per_pair + s] is the f of copy s of pair i; lengths (optional) its length L - trim; status (optional) per pair: the
+ * status of the first copy that failed (ALN_ERR_CODE_OUT_OF_RANGE, ALN_ERR_EMPTY_SEQUENCE, ALN_ERR_NO_POSITIVE_CELL ...), ALN_OK
+ * if none did; the other pairs are unaffected.  Without a status array a failed pair is the call's return value.  Any non-PWM
+ * semantics and every scheme aln_align_batch accepts, on the routes it would pick for the copies; ALN_PWM_LOCAL:
+ * ALN_ERR_UNSUPPORTED.  Any t_len[i] < max_trim, per_pair outside 1 .. 2^20: ALN_ERR_INVALID_ARGUMENT for the whole call.
+ * targets: the copies themselves, copy s of pair i at out[out_off[i] + s * t_len[i]], its first L - trim bytes (the rest of the
+ * t_len[i] bytes are 0). ---- */
+typedef struct aln_shuffle_spec {
+    uint64_t seed;
+    uint64_t pair_base;   /* stream index of pair 0 (reproducible sharding) */
+    uint32_t per_pair;    /* shuffled copies per pair: 4999 in calculate_p_value; 1 .. 2^20 */
+    uint32_t max_trim;    /* tail residues dropped, uniform in 0..max_trim: 6 in the reference */
+} aln_shuffle_spec;       /* 24 bytes */
+
+int aln_shuffle_scores(aln_ctx *ctx, const aln_params *params, const aln_shuffle_spec *spec, const uint8_t *seqs,
+                       const uint64_t *q_off, const uint64_t *q_len, const uint64_t *t_off, const uint64_t *t_len,
+                       size_t n_pairs, double *f, uint32_t *lengths, int32_t *status);
+int aln_shuffle_targets(aln_ctx *ctx, const aln_shuffle_spec *spec, const uint8_t *seqs, const uint64_t *t_off,
+                        const uint64_t *t_len, size_t n_pairs, uint8_t *out, const uint64_t *out_off);
+
 #ifdef __cplusplus
 }
 #endif
