@@ -253,6 +253,18 @@ __host__ __device__ inline uint32_t aln_wg_lds_bytes(uint32_t rows, uint32_t col
     return ((rows * cols * sc_size + 15u) & ~15u) + ns * ALN_WG_RING * sc_size + 3u * ((N + 66u + 15u) & ~15u) + 64u * 4u + ns * 32u +
            (N <= 2048u ? (((N + 66u) * sc_size + 15u) & ~15u) : 0u);      // row 1 of the pass: in LDS for short queries, else in the scratch
 }
+// LDS of the fast batch kernels (aln_fill_fast_kernel): [S][four waves' profiles][four waves' feed rings: query ring, boundary ring];
+// feed_bytes = 0 gives the offset of the rings.  PWM scoring (prof_stride == 0) has neither profiles nor rings.  C5 (24 x 24,
+// 12 KiB profiles): 51 456 + 1 856 = 53 312 bytes; three workgroups per CU fit up to 53 760 each (42 of the CU's 128 allocation
+// units of 1 280 bytes).
+#define ALN_QRING_BYTES 192u  // per wave: 128 query codes + the first 64 once more (aln_fast.h)
+#define ALN_BRING_BYTES 272u  // per wave: ints 1 .. 64 hold the 64 columns of the row above that the strip takes next
+#define ALN_FEED_BYTES (ALN_QRING_BYTES + ALN_BRING_BYTES)
+__host__ __device__ inline uint32_t aln_fast_lds_bytes(uint32_t rows, uint32_t cols, uint32_t prof_stride, uint32_t feed_bytes)
+{
+    const uint32_t s_bytes = (rows * cols * 4u + 15u) & ~15u;
+    return prof_stride == 0u ? s_bytes : s_bytes + 4u * prof_stride + 4u * feed_bytes;
+}
 
 // Parallel traceback of one large pair (uniform-R layout): per strip and entry column an "exit map", then a short
 // serial chain through the maps, then one walker per strip that writes its segment of the tag string.

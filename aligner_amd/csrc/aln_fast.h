@@ -10,7 +10,9 @@
 // per code: one ds_read of R bytes per step feeds the lane's R cells (SDWA byte adds).  Not conflict-free: at a step the
 // lanes read the rows of up to 24 different codes, 512 B apart (measured SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.39);
 // LDS instructions are 1.4 % of the VALU count, so it does not bind.
-// The query code flows down the lanes with the same DPP wave_shr:1 that carries the boundary cell.
+// Batch kernels: every lane reads its column's query code from a per-wave LDS ring two steps ahead, and lane 0's boundary cell comes
+// from a second ring one step ahead (below: "the query ring"); only PWM scoring still moves its column word down the lanes with the
+// DPP wave_shr:1 that carries the boundary cell.
 // Local end cell: per row one packed register  (T' << 11) | f(step)  updated with one v_lshl_add per cell and one v_max3
 // per two steps, folded every 2048 steps with the exact tie rule (first in row-major order: core; last in column-major
 // order: legacy).
@@ -96,6 +98,26 @@ __device__ __forceinline__ int prof_byte(const typename ProfWord<R>::T &pw, int 
 
 __device__ __forceinline__ int shr1_i(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, 0x138, 0xf, 0xf, false); }
 
+// Batch kernels: the query ring.  Per wave 128 query codes in LDS, column c at byte c & 127 of a block, and the first 64 entries
+// once more behind the block: a lane's read address is set every 64 steps, where the ring is refilled, to the block
+// + ((k + 2 - lane) & 127) and then only counts up -- by SPB per block with a plain add, by the step's number within the block
+// as the read's immediate offset --, so it reaches at most entry 127 + 63.  128 entries are enough: right after a refill at step k
+// the columns in use are k - 61 (lane 63's read of this step) .. k + 65.
+// The boundary ring: the 64 columns k + 1 .. k + 64 of the row above the strip, fetched at step k, at ints 1 .. 64 of a block of
+// its own; step k + d reads int d + 1 (the column of step k + d + 1) with a broadcast read, so nothing wraps.
+// (ALN_QRING_BYTES, ALN_BRING_BYTES and where the rings sit in the workgroup's LDS: aln_device.h)
+typedef __attribute__((address_space(3))) uint8_t aln_lds_u8;
+typedef __attribute__((address_space(3))) int aln_lds_i32;
+__device__ __forceinline__ void qring_put(uint32_t ring, uint32_t c, uint32_t code)
+{
+    const uint32_t i = c & 127u;
+    *(aln_lds_u8 *)(uintptr_t)(ring + i) = (uint8_t)code;
+    if (i < 64u) *(aln_lds_u8 *)(uintptr_t)(ring + 128u + i) = (uint8_t)code;
+}
+__device__ __forceinline__ int qring_get(uint32_t addr) { return (int)*(const aln_lds_u8 *)(uintptr_t)addr; }
+__device__ __forceinline__ void bring_put(uint32_t addr, int v) { *(aln_lds_i32 *)(uintptr_t)addr = v; }
+__device__ __forceinline__ int bring_get(uint32_t addr) { return *(const aln_lds_i32 *)(uintptr_t)addr; }
+
 // Inter-strip hand-off of the single-pair kernel: every boundary cell travels as one naturally aligned 4-byte granule, the
 // T value itself -- T = 4H + 2 is never zero, and the buffer is zeroed before every pass, so "non-zero" means "produced".
 // Written by ONE write-through (sc1) store and polled with sc1 loads: the data is the flag, no fence
@@ -125,6 +147,8 @@ struct FastIn {
     const int *S;             // LDS, [t][q]
     uint32_t cols;
     uint8_t *prof;            // LDS, this wave's profile
+    uint32_t qring;           // batch kernels: LDS address of this wave's query ring (ALN_QRING_BYTES)
+    uint32_t brow_ring;       // batch kernels: LDS address of this wave's boundary ring (ALN_BRING_BYTES)
     int nd4, ne4;             // -4*del, -4*ext
     uint32_t *dirw;
     unsigned long long *brow_in, *brow_out;   // batch kernels: the row above this strip / this strip's bottom row, as 8-byte granules
@@ -203,6 +227,13 @@ struct FastStrip {
     static constexpr uint32_t CHUNK = (2048u / (4u * SPB)) * (4u * SPB);
     static constexpr uint32_t STRIP_ROWS = SINGLE ? 64u * R : (uint32_t)ALN_STRIP_ROWS;
     static constexpr bool LOCAL = (SEM == ALN_CORE_LOCAL || SEM == ALN_LEGACY_LOCAL);
+    // batch kernels, matrix scoring: every lane reads its own column's query code from the wave's LDS ring two steps ahead (qv) and
+    // its profile word one step ahead (pw), as the single-pair kernel does from qo_pad.  PWM scoring keeps the flow down the lanes:
+    // its flowing register is the column's four packed scores, not a code.
+    static constexpr bool QRING = !SINGLE && !PWM;
+    // ... and a strip with a strip above it reads the next step's boundary cell from the wave's boundary ring one step ahead (top0v)
+    static constexpr bool BRING = QRING && !FIRST;
+    static constexpr int QSHIFT = RP == 8 ? 9 : RP == 4 ? 8 : RP == 2 ? 7 : 6;      // a code's profile row: 64 * RP bytes
     using PW = typename ProfWord<R>::T;
     const FastIn in;
     const uint32_t strip;
@@ -218,6 +249,8 @@ struct FastStrip {
     uint32_t advchunk, dw;
     PW pw;
     const uint8_t *prow;       // this lane's column of the profile: prof + lane*R
+    uint32_t qaddr;            // batch kernels (QRING): LDS address of the code this lane reads in the first step of the current block
+    uint32_t baddr;            // batch kernels (BRING): LDS address of the boundary cell read in the first step of the current block
 
     // single-pair kernel: query offsets and the incoming boundary row are staged in LDS
     const uint8_t *qo_lane;    // &qo_pad[63 - lane] (u16 entries: q[x] * 64R, zero padded on both sides)
@@ -299,24 +332,35 @@ struct FastStrip {
         else __builtin_amdgcn_s_setprio(1);
     }
 
+    // kk: the step's number within its block (a constant after unrolling: the immediate offset of the query ring read)
     template <bool MASKED>
-    __device__ __forceinline__ void step(const uint32_t k)
+    __device__ __forceinline__ void step(const uint32_t k, const int kk)
     {
         if ((k & 63u) == 0) {                                   // wave-uniform: refill the 64-column input chunks
             const uint32_t xi = k + (uint32_t)lane;             // 0-based column
             if (!SINGLE && in.fair) fair_prio();
             if (!SINGLE && !LAST && k >= 64u) flush_below(k, 0u);
-            if (!FIRST && !SINGLE) inchunk = fetch_above(xi);
+            if (BRING) {                                         // columns k + 1 .. k + 64: step k reads column k + 1 for step k + 1
+                bring_put(in.brow_ring + 4u + 4u * (uint32_t)lane, fetch_above(xi + 1u));
+                baddr = in.brow_ring + 4u;
+            } else if (!FIRST && !SINGLE) inchunk = fetch_above(xi);
             if (SEM == ALN_CORE_LOCAL && FIRST && in.hazard) advchunk = (xi < N) ? in.advice[xi + 1] : 0u;
-            if (!SINGLE) qchunk = (xi + 1 < N) ? (PWM ? (int)in.pwm_words[xi + 1] : (int)in.q[xi + 1] * (64 * RP)) : 0;
+            if (!SINGLE && PWM) qchunk = (xi + 1 < N) ? (int)in.pwm_words[xi + 1] : 0;
+            // columns k + 2 .. k + 65 of the query ring: lane 0 reads column k + 2 in this very step, lane 63 read column k - 62 (the
+            // oldest entry in use) in the last one; zeros beyond the query, as the flow had them
+            if (QRING) {
+                qring_put(in.qring, xi + 2, (xi + 2 < N) ? (uint32_t)in.q[xi + 2] : 0u);
+                qaddr = in.qring + ((k + 2u - (uint32_t)lane) & 127u);
+            }
         }
         const int sel = (int)(k & 63u);
         int top0;
         if (FIRST) top0 = LOCAL ? 2 : ((k + 1 == N) ? 2 + (int)(N + 1) * in.nd4 : 2 + (int)(k + 1) * in.nd4);
-        else if (SINGLE) top0 = top0v;                          // read from the LDS ring one step ago
+        else if (SINGLE || BRING) top0 = top0v;                 // read from the LDS ring one step ago
         else top0 = __builtin_amdgcn_readlane(inchunk, sel);
         const int topIn = shr1_i(top0, bottom);                 // lane 0 <- row above the strip, lane l <- lane l-1
         if (SINGLE && !FIRST) top0v = bring[(k + 1) & 127u];    // next step's boundary cell (broadcast read)
+        if (BRING) top0v = bring_get(baddr + 4u * (uint32_t)kk);
         // cross-lane reads stay in wave-uniform control flow: inside a divergent branch the compiler may compute
         // their operand for the active lanes only
         const uint32_t adv = (SEM == ALN_CORE_LOCAL && FIRST) ? (uint32_t)__builtin_amdgcn_readlane((int)advchunk, sel) : 0u;
@@ -324,9 +368,12 @@ struct FastStrip {
         if constexpr (SINGLE) {
             pw = *reinterpret_cast<const PW *>(prow + qv);                           // step k+1: column k+1-lane
             qv = *reinterpret_cast<const uint16_t *>(qo_lane + 2 * (k + 2));         // step k+2
+        } else if constexpr (QRING) {
+            pw = *reinterpret_cast<const PW *>(prow + ((uint32_t)qv << QSHIFT));     // step k+1: column k+1-lane (one v_lshl_add)
+            qv = qring_get(qaddr + (uint32_t)kk);                                    // step k+2: column k+2-lane
         } else {
-            qoff = shr1_i(__builtin_amdgcn_readlane(qchunk, sel), qoff);             // next step's query code reaches every lane
-            if constexpr (PWM) pw = pwm_select((uint32_t)qoff); else pw = *reinterpret_cast<const PW *>(prow + qoff);
+            qoff = shr1_i(__builtin_amdgcn_readlane(qchunk, sel), qoff);             // next step's packed scores reach every lane
+            pw = pwm_select((uint32_t)qoff);
         }
         // end-cell tie-break term of this step: earlier steps win (core) / later steps win (legacy)
         static_assert(CHUNK == 2048u, "the tracker's chunks start at multiples of 2048 steps");
@@ -620,7 +667,9 @@ struct FastStrip {
             const uint32_t k0 = (FIRST || !SINGLE) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)((kb + j) * SPB)) : (kb + j) * SPB;
             if (SINGLE && !FIRST && ((k0 + SPB) & 15u) == 0) stage_boundary16((k0 + SPB) >> 4);   // one block ahead
 #pragma unroll
-            for (int kk = 0; kk < SPB; ++kk) step<MASKED>(k0 + kk);
+            for (int kk = 0; kk < SPB; ++kk) step<MASKED>(k0 + kk, kk);
+            if constexpr (QRING) qaddr += (uint32_t)SPB;
+            if constexpr (BRING) baddr += 4u * (uint32_t)SPB;
             if (SINGLE && !LAST && k0 + SPB >= 64u && ((k0 + SPB) & 15u) == 0) publish(k0 + SPB - 1);
             store_zdw(kb + j);
             if (j == 0) v.x = dw;
@@ -761,6 +810,17 @@ struct FastStrip {
             qv = *reinterpret_cast<const uint16_t *>(qo_lane + 2);                    // step 1
         } else {
             qoff = (lane == 0) ? (PWM ? (int)in.pwm_words[0] : (int)in.q[0] * (64 * RP)) : 0;
+            if constexpr (QRING) {
+                // the query ring before step 0: columns -62 .. 1 (lane l: column 1 - l, the one it uses in step 1; step 0 writes columns
+                // 2 .. 65 before anybody reads them); columns that do not exist are code 0 -- their cells run masked
+                const uint32_t c1 = 1u - (uint32_t)lane;
+                qv = (c1 < N) ? (int)in.q[c1] : 0;
+                qring_put(in.qring, c1, (uint32_t)qv);
+                qaddr = in.qring + ((2u - (uint32_t)lane) & 127u);
+                // column 0 of the row above: lane 0 alone fetches (and waits for) it
+                baddr = in.brow_ring + 4u;
+                if constexpr (BRING) top0v = __builtin_amdgcn_readfirstlane(fetch_above(lane == 0 ? 0u : 0xffffffffu));
+            }
         }
         if (!SINGLE && PWM) pw = pwm_select((uint32_t)qoff);
         else pw = *reinterpret_cast<const PW *>(prow + qoff);

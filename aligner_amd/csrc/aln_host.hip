@@ -763,7 +763,7 @@ static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, c
     k.scratch_stride = (uint64_t)k.cascade_rows * brow_bytes + adv_bytes + zrow_bytes + ck_bytes + row1_bytes;
     k.lds_bytes = (uint32_t)(((uint64_t)rows * cols * (c.is_int ? 4 : 8) + 15) & ~15ull);
     k.prof_stride = 0;
-    if (c.fast && !pwm) { k.prof_stride = cols * 64u * ALN_FULL_R; k.lds_bytes += 4u * k.prof_stride; }
+    if (c.fast && !pwm) { k.prof_stride = cols * 64u * ALN_FULL_R; k.lds_bytes = aln_fast_lds_bytes(rows, cols, k.prof_stride, ALN_FEED_BYTES); }
     // Two short pairs per wave (core global, read pairs: aln_fill_duo_kernel): every pair of the queue at most 256 rows and 1024
     // columns, more pairs than resident waves (with fewer, a wave per pair is through sooner), nothing shared, no walk waves beside
     // the fill, and the staged queries fit beside the profiles with three workgroups per CU.  ALN_NO_DUO=1: off.

@@ -1741,6 +1741,9 @@ void aln_fill_fast_kernel(FillArgs a)
     in.S = S;
     in.cols = a.cols;
     in.prof = smem + ((a.rows * a.cols * 4u + 15u) & ~15u) + (threadIdx.x >> 6) * a.prof_stride;
+    // [S][4 profiles][4 x {query ring, boundary ring}] (aln_fast_lds_bytes); PWM scoring has neither profiles nor rings
+    in.qring = PWM ? 0u : (uint32_t)(uintptr_t)smem + aln_fast_lds_bytes(a.rows, a.cols, a.prof_stride, 0u) + (threadIdx.x >> 6) * ALN_FEED_BYTES;
+    in.brow_ring = in.qring + ALN_QRING_BYTES;
     in.nd4 = -4 * (int)a.del;
     in.ne4 = -4 * (int)a.ext;
     in.gin = nullptr; in.gout = nullptr; in.abort_flag = nullptr; in.qo_pad = nullptr; in.bring = nullptr;
@@ -2888,23 +2891,33 @@ extern "C" __global__ void aln_unpack_directions_kernel(const uint8_t *dirs, con
 #endif   // ALN_PART_TB
 
 // ---------------------------------------------------------------- launch helpers used by aln_host.hip
+// (beyond 64 KiB of dynamic LDS -- S, the profiles and the rings of a 30-letter alphabet -- a kernel has to be told once)
+#define ALN_FAST_GO(...)                                                                                                   \
+    do {                                                                                                                   \
+        auto kern = &__VA_ARGS__;                                                                                          \
+        if (lds_bytes > 64u * 1024u)                                                                                       \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
+        hipLaunchKernelGGL(kern, g, b, lds_bytes, s, *a);                                                                  \
+    } while (0)
 #define ALN_FAST_REST_LAUNCH(COOPV)                                                                                        \
     switch (a->semantics) {                                                                                                \
-    case ALN_CORE_GLOBAL: hipLaunchKernelGGL((aln_fill_fast_kernel<ALN_CORE_GLOBAL, false, COOPV>), g, b, lds_bytes, s, *a); break; \
-    case ALN_CORE_LOCAL: hipLaunchKernelGGL((aln_fill_fast_kernel<ALN_CORE_LOCAL, true, COOPV>), g, b, lds_bytes, s, *a); break;   /* PWM scoring */ \
-    case ALN_LEGACY_GLOBAL: hipLaunchKernelGGL((aln_fill_fast_kernel<ALN_LEGACY_GLOBAL, false, COOPV>), g, b, lds_bytes, s, *a); break; \
-    default: hipLaunchKernelGGL((aln_fill_fast_kernel<ALN_LEGACY_LOCAL, false, COOPV>), g, b, lds_bytes, s, *a); break;      \
+    case ALN_CORE_GLOBAL: ALN_FAST_GO(aln_fill_fast_kernel<ALN_CORE_GLOBAL, false, COOPV>); break; \
+    case ALN_CORE_LOCAL: ALN_FAST_GO(aln_fill_fast_kernel<ALN_CORE_LOCAL, true, COOPV>); break;   /* PWM scoring */ \
+    case ALN_LEGACY_GLOBAL: ALN_FAST_GO(aln_fill_fast_kernel<ALN_LEGACY_GLOBAL, false, COOPV>); break; \
+    default: ALN_FAST_GO(aln_fill_fast_kernel<ALN_LEGACY_LOCAL, false, COOPV>); break;      \
     }
 #if ALN_TU & ALN_PART_FAST_CL
 extern "C" void aln_launch_fill_fast_cl(const FillArgs *a, uint32_t grid, uint32_t lds_bytes, hipStream_t s)
 {
-    hipLaunchKernelGGL((aln_fill_fast_kernel<ALN_CORE_LOCAL, false, true>), dim3(grid), dim3(256), lds_bytes, s, *a);
+    const dim3 g(grid), b(256);
+    ALN_FAST_GO(aln_fill_fast_kernel<ALN_CORE_LOCAL, false, true>);
 }
 #endif
 #if ALN_TU & ALN_PART_FAST_CL_SOLO
 extern "C" void aln_launch_fill_fast_cl_solo(const FillArgs *a, uint32_t grid, uint32_t lds_bytes, hipStream_t s)
 {
-    hipLaunchKernelGGL((aln_fill_fast_kernel<ALN_CORE_LOCAL, false, false>), dim3(grid), dim3(256), lds_bytes, s, *a);
+    const dim3 g(grid), b(256);
+    ALN_FAST_GO(aln_fill_fast_kernel<ALN_CORE_LOCAL, false, false>);
 }
 #endif
 #if ALN_TU & ALN_PART_FAST_REST
@@ -3118,6 +3131,7 @@ extern "C" void aln_launch_fill_fast_rest_solo(const FillArgs *a, uint32_t grid,
 }
 #endif
 #undef ALN_FAST_REST_LAUNCH
+#undef ALN_FAST_GO
 // ---------------------------------------------------------------- code-object warm-up (aln_create)
 // Every translation unit is a code object of its own that the HIP runtime loads onto a device when the first kernel out of it is
 // launched (milliseconds each: a first call used to pay for them).  aln_create asks for the attributes of one kernel per unit,
