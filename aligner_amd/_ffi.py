@@ -36,7 +36,7 @@ EXPORTS = [
     "aln_batch_destroy", "aln_batch_cells", "aln_batch_size", "aln_batch_results_device",
     "aln_batch_direction_bytes", "aln_batch_timing", "aln_batch_enable_timing",
     "aln_scan_create", "aln_scan_destroy", "aln_scan_windows", "aln_scan_score", "aln_scan_select", "aln_scan_string_stride",
-    "aln_scan_stats", "aln_shuffle_scores", "aln_shuffle_targets",
+    "aln_scan_stats", "aln_scan_hits", "aln_scan_held_list", "aln_scan_held_frequencies", "aln_scan_held_strings", "aln_shuffle_scores", "aln_shuffle_targets",
 ]
 
 
@@ -144,6 +144,14 @@ def load():
     lib.aln_scan_select.restype = i
     lib.aln_scan_select.argtypes = [vp, C.POINTER(Params), gp, C.c_double, C.c_double, C.c_double, C.c_size_t,
                                     C.POINTER(C.c_uint64), vp, vp, vp]
+    lib.aln_scan_hits.restype = i
+    lib.aln_scan_hits.argtypes = [vp, C.POINTER(Params), gp, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_uint64)]
+    lib.aln_scan_held_list.restype = i
+    lib.aln_scan_held_list.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
+    lib.aln_scan_held_frequencies.restype = i
+    lib.aln_scan_held_frequencies.argtypes = [vp, vp, C.c_uint64, vp]
+    lib.aln_scan_held_strings.restype = i
+    lib.aln_scan_held_strings.argtypes = [vp, vp, C.c_uint64, vp, vp]
     lib.aln_scan_string_stride.restype = C.c_uint64
     lib.aln_scan_string_stride.argtypes = [vp, C.c_uint32, gp]
     lib.aln_scan_stats.restype = i

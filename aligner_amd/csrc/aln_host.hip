@@ -1706,6 +1706,9 @@ extern "C" int aln_align_pair(aln_ctx *ctx, const aln_params *params, const uint
 // batch (slot_launch), planned by the same chunk_plan from the window lengths -- once per geometry and kind of call, then kept.
 // A select pass tests z on the device, compacts the hits in window order and re-fills only those with directions, all on one
 // stream; what comes back is the hit count, the hits' summaries and strings.
+// A held pass (aln_scan_hits) is a select pass that keeps all of that on the device: the count alone comes back, the hit buffers
+// are sized for it (no capacity, no second fill), and the caller then asks for the hit list (window, f), for the sum of the
+// frequency matrices of a list of hits (aln_scan_freq_kernel: u32 counters, exact in any order) or for the strings of a list.
 extern "C" void aln_scan_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t first, uint64_t step, uint64_t width,
                                        uint64_t len, uint64_t base, uint32_t cols, hipStream_t s);
 extern "C" void aln_scan_launch_f(const aln_pair_result *res, double *f, uint64_t n, int32_t *bad, hipStream_t s);
@@ -1716,6 +1719,12 @@ extern "C" void aln_scan_launch_hits(PairDesc *descs, uint32_t *order, uint32_t 
                                      uint32_t cap, uint64_t first, uint64_t step, uint64_t width, uint64_t len, uint64_t base,
                                      uint32_t cols, uint64_t dir_stride, uint64_t tb_stride, uint64_t tag_stride, hipStream_t s);
 extern "C" void aln_scan_launch_reverse(uint8_t *seq, uint64_t len, hipStream_t s);
+extern "C" void aln_scan_launch_held_f(const aln_pair_result *res, double *f, uint32_t n, hipStream_t s);
+extern "C" void aln_scan_launch_freq(const PairDesc *descs, const aln_pair_result *res, const uint8_t *tb, const uint32_t *keep,
+                                     uint32_t n_keep, uint32_t n_held, uint32_t cols, uint32_t blank, uint32_t *counts, double *out,
+                                     hipStream_t s);
+extern "C" void aln_scan_launch_gather(const aln_pair_result *res, const uint8_t *tb, const uint32_t *keep, uint32_t n_keep, uint32_t n_held,
+                                       uint64_t stride, aln_pair_result *out_res, uint8_t *out_tb, hipStream_t s);
 
 // the re-fill of a select pass has room for at least this many hits: a chunk of <= 4 pairs would take the one-workgroup route,
 // whose plan reads the pairs' shapes on the host
@@ -1741,6 +1750,12 @@ struct aln_scan {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double ms[4] = {0, 0, 0, 0};      // last pass: fill, selection, hit re-fill + walk (kernel time), download (wall)
     uint64_t bytes[2] = {0, 0};       // last pass: host -> device, device -> host
+    // held hits (aln_scan_hits): hit h's window in idx[h], its summary in slot->results[h], its descriptor in slot->descs[h], its
+    // strings in slot->tb at h * held_stride -- until the next pass on this scan
+    bool held = false;
+    uint64_t held_count = 0, held_stride = 0;
+    uint32_t held_cols = 0, held_blank = 0;
+    DevBuf held_f, keep, freq, packed;   // f of every hit; an uploaded list; u32 counters | f64 matrix; a list's summaries | strings
 };
 
 static uint64_t scan_windows(uint64_t len, const aln_scan_geometry *g)
@@ -1760,6 +1775,7 @@ extern "C" void aln_scan_destroy(aln_scan *sc)
     (void)hipSetDevice(sc->ctx->device);
     for (hipEvent_t e : sc->ev) if (e) (void)hipEventDestroy(e);
     dev_free(sc->fbuf); dev_free(sc->tiles); dev_free(sc->idx); dev_free(sc->misc);
+    dev_free(sc->held_f); dev_free(sc->keep); dev_free(sc->freq); dev_free(sc->packed);
     slot_destroy(sc->slot);
     delete sc;
 }
@@ -1916,6 +1932,7 @@ extern "C" int aln_scan_score(aln_scan *sc, const aln_params *params, const aln_
     if (st != ALN_OK) return st;
     const uint64_t n = scan_windows(sc->len, g);
     if (n && !f) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    sc->held = false;
     for (double &v : sc->ms) v = 0;
     sc->bytes[0] = sc->bytes[1] = 0;
     if (n == 0) return ALN_OK;
@@ -1955,6 +1972,7 @@ extern "C" int aln_scan_select(aln_scan *sc, const aln_params *params, const aln
     const uint64_t q1 = 0, t1 = std::min<uint64_t>(g->width, sc->len);
     if ((st = call_init(ct, &pt, &q1, &t1, 1, false)) != ALN_OK) return st;
     *count = 0;
+    sc->held = false;
     for (double &v : sc->ms) v = 0;
     sc->bytes[0] = sc->bytes[1] = 0;
     const uint64_t n = scan_windows(sc->len, g);
@@ -2006,6 +2024,177 @@ extern "C" int aln_scan_select(aln_scan *sc, const aln_params *params, const aln
     sc->bytes[1] = 8 + got * (4 + sizeof(aln_pair_result) + (tb_buf ? ph->tb_stride : 0));
     if (hm[1] != ALN_OK) { g_err = "a window failed"; return (int)hm[1]; }
     if (hm[0] > cap) { g_err = "more windows passed than the capacity holds"; return ALN_ERR_CAPACITY; }
+    return ALN_OK;
+}
+
+// ---- held pass: fill, z test and compaction as aln_scan_select; the count is read where the pass waits anyway, the hit buffers are
+// sized for it, and every hit is re-filled with directions and walked.  Nothing but the count comes back.
+extern "C" int aln_scan_hits(aln_scan *sc, const aln_params *params, const aln_scan_geometry *g, double mean, double sd, double z_min,
+                             uint64_t *count)
+{
+    Call c, ct;
+    int st = scan_call(sc, params, g, ALN_OUT_SCORE, c);
+    if (st != ALN_OK) return st;
+    if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    aln_params pt = *params;
+    pt.outputs = ALN_OUT_SCORE | ALN_OUT_TRACEBACK;
+    const uint64_t q1 = 0, t1 = std::min<uint64_t>(g->width, sc->len);
+    if ((st = call_init(ct, &pt, &q1, &t1, 1, false)) != ALN_OK) return st;
+    *count = 0;
+    sc->held = false;
+    for (double &v : sc->ms) v = 0;
+    sc->bytes[0] = sc->bytes[1] = 0;
+    sc->held_count = 0;
+    sc->held_cols = c.cols;
+    sc->held_blank = ct.p.blank_code;
+    sc->held_stride = aln_scan_string_stride(sc, c.cols, g);
+    const uint64_t n = scan_windows(sc->len, g);
+    if (n == 0) { sc->held = true; return ALN_OK; }
+    Slot &s = *sc->slot;
+    std::shared_ptr<ScanPlan> pl, ph;
+    if ((st = scan_plan(sc, c, g, n, 0, pl)) != ALN_OK) return st;
+    if ((st = slot_ensure(s, c, pl->k, nullptr, true)) != ALN_OK) return st;
+    const uint64_t tiles = aln_scan_tiles(n);
+    if ((st = dev_ensure(sc->fbuf, 8 * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(sc->tiles, 8 * tiles, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(sc->idx, 4 * n, false)) != ALN_OK) return st;           // every window may pass: 4 bytes each
+    hipStream_t q = s.stream;
+    HIPCHK(hipEventRecord(sc->ev[0], q));
+    if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) return st;
+    if ((st = scan_fill(sc, c, g, pl.get(), n)) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    HIPCHK(hipEventRecord(sc->ev[1], q));
+    uint32_t *misc = sc->misc.as<uint32_t>();
+    aln_scan_launch_select(s.results.as<aln_pair_result>(), n, mean, sd, z_min, sc->tiles.as<uint32_t>(), sc->tiles.as<uint32_t>() + tiles,
+                           misc, sc->idx.as<uint32_t>(), (uint32_t)n, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(sc->ev[2], q));
+    uint32_t hm[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(hm, misc, 8, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    sc->ms[0] = ev_ms(sc->ev[0], sc->ev[1]);
+    sc->ms[1] = ev_ms(sc->ev[1], sc->ev[2]);
+    sc->bytes[0] = c.md.size() * (c.is_int ? 4 : 8) + (c.pwm && c.fast ? 4ull * c.cols : 0);
+    sc->bytes[1] = 8;
+    if (hm[1] != ALN_OK) { g_err = "a window failed"; return (int)hm[1]; }
+    const uint64_t hits = hm[0];
+    if (hits) {
+        // the stream is idle: the hit buffers may grow now.  The matrix is the fill's; it goes up again if its buffer moved.
+        const uint64_t slots = std::max<uint64_t>(hits, ALN_SCAN_MIN_SLOTS);
+        const void *m0 = s.matrix.p, *w0 = s.pwm_words.p;
+        if ((st = scan_plan(sc, ct, g, n, slots, ph)) != ALN_OK) return st;
+        st = slot_ensure(s, ct, ph->k, nullptr, true);
+        if (st == ALN_OK) st = dev_ensure(sc->held_f, 8 * hits, false);
+        if (st != ALN_OK) return st;                                 // ALN_ERR_OOM if the memory cannot be had; nothing is held
+        if (s.matrix.p != m0 || s.pwm_words.p != w0)
+            if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) return st;
+        HIPCHK(hipEventRecord(sc->ev[2], q));
+        aln_scan_launch_hits(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), (uint32_t)slots, sc->idx.as<uint32_t>(), misc, (uint32_t)slots,
+                             g->first, g->step, g->width, sc->len, g->reverse ? sc->len : 0, c.cols, ph->dir_stride, ph->tb_stride,
+                             ph->tag_stride, q);
+        HIPCHK(hipGetLastError());
+        if ((st = slot_launch(sc->ctx, s, ct, ph->k, q, nullptr, nullptr)) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+        aln_scan_launch_held_f(s.results.as<aln_pair_result>(), sc->held_f.as<double>(), (uint32_t)hits, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(sc->ev[3], q));
+        HIPCHK(hipStreamSynchronize(q));
+        sc->ms[2] = ev_ms(sc->ev[2], sc->ev[3]);
+        sc->held_stride = ph->tb_stride;
+    }
+    sc->held_count = hits;
+    sc->held = true;
+    *count = hits;
+    return ALN_OK;
+}
+
+static int held_check(aln_scan *sc, const void *keep, uint64_t n_keep)
+{
+    if (!sc) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!sc->held) { g_err = "no held hits: aln_scan_hits has not run, or another pass has replaced them"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_keep && !keep) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_keep > 0x7FFFFFF0ull) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint32_t *k = reinterpret_cast<const uint32_t *>(keep);
+    for (uint64_t i = 0; i < n_keep; ++i)
+        if (k[i] >= sc->held_count) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(sc->ctx->device));
+    for (double &v : sc->ms) v = 0;
+    sc->bytes[0] = sc->bytes[1] = 0;
+    return ALN_OK;
+}
+
+static void held_done(aln_scan *sc, const std::chrono::steady_clock::time_point &t0, uint64_t up, uint64_t down)
+{
+    sc->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    sc->bytes[0] = up; sc->bytes[1] = down;
+}
+
+extern "C" int aln_scan_held_list(aln_scan *sc, uint64_t first, uint64_t n, uint32_t *indices, double *f)
+{
+    int st = held_check(sc, nullptr, 0);
+    if (st != ALN_OK) return st;
+    if (first > sc->held_count || n > sc->held_count - first) { g_err = "range beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && (!indices || !f)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n) {
+        hipStream_t q = sc->slot->stream;
+        HIPCHK(hipMemcpyAsync(indices, sc->idx.as<uint32_t>() + first, 4 * n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(f, sc->held_f.as<double>() + first, 8 * n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+    }
+    held_done(sc, t0, 0, 12 * n);
+    return ALN_OK;
+}
+
+extern "C" int aln_scan_held_frequencies(aln_scan *sc, const uint32_t *keep, uint64_t n_keep, double *counts)
+{
+    int st = held_check(sc, keep, n_keep);
+    if (st != ALN_OK) return st;
+    if (!counts) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t cells = 4ull * sc->held_cols;
+    if ((st = dev_ensure(sc->keep, 4 * n_keep, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(sc->freq, 16 * cells, false)) != ALN_OK) return st;     // u32 counters, then (8-byte aligned) the f64 matrix
+    const auto t0 = std::chrono::steady_clock::now();
+    Slot &s = *sc->slot;
+    hipStream_t q = s.stream;
+    double *out = reinterpret_cast<double *>(sc->freq.as<uint8_t>() + 8 * cells);
+    HIPCHK(hipEventRecord(sc->ev[2], q));
+    if (n_keep) HIPCHK(hipMemcpyAsync(sc->keep.p, keep, 4 * n_keep, hipMemcpyHostToDevice, q));
+    aln_scan_launch_freq(s.descs.as<PairDesc>(), s.results.as<aln_pair_result>(), s.tb.as<uint8_t>(), sc->keep.as<uint32_t>(), (uint32_t)n_keep,
+                         (uint32_t)sc->held_count, sc->held_cols, sc->held_blank, sc->freq.as<uint32_t>(), out, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(sc->ev[3], q));
+    HIPCHK(hipMemcpyAsync(counts, out, 8 * cells, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    sc->ms[2] = ev_ms(sc->ev[2], sc->ev[3]);
+    held_done(sc, t0, 4 * n_keep, 8 * cells);
+    return ALN_OK;
+}
+
+extern "C" int aln_scan_held_strings(aln_scan *sc, const uint32_t *keep, uint64_t n_keep, aln_pair_result *results, uint8_t *tb_buf)
+{
+    int st = held_check(sc, keep, n_keep);
+    if (st != ALN_OK) return st;
+    if (n_keep && (!results || !tb_buf)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n_keep) {
+        const uint64_t stride = sc->held_stride, res_bytes = (sizeof(aln_pair_result) * n_keep + 255) & ~255ull;
+        if ((st = dev_ensure(sc->keep, 4 * n_keep, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(sc->packed, res_bytes + stride * n_keep, false)) != ALN_OK) return st;
+        Slot &s = *sc->slot;
+        hipStream_t q = s.stream;
+        aln_pair_result *pres = sc->packed.as<aln_pair_result>();
+        uint8_t *ptb = sc->packed.as<uint8_t>() + res_bytes;
+        HIPCHK(hipEventRecord(sc->ev[2], q));
+        HIPCHK(hipMemcpyAsync(sc->keep.p, keep, 4 * n_keep, hipMemcpyHostToDevice, q));
+        aln_scan_launch_gather(s.results.as<aln_pair_result>(), s.tb.as<uint8_t>(), sc->keep.as<uint32_t>(), (uint32_t)n_keep,
+                               (uint32_t)sc->held_count, stride, pres, ptb, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(sc->ev[3], q));
+        HIPCHK(hipMemcpyAsync(results, pres, sizeof(aln_pair_result) * n_keep, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(tb_buf, ptb, stride * n_keep, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        sc->ms[2] = ev_ms(sc->ev[2], sc->ev[3]);
+    }
+    held_done(sc, t0, 4 * n_keep, n_keep * (sizeof(aln_pair_result) + sc->held_stride));
     return ALN_OK;
 }
 

@@ -8,12 +8,18 @@
 //              (tile counts, one workgroup's scan over the tiles, tile-local scans): the same indices every run
 //   hits       the selected windows -> PairDesc[cap] of the re-fill with directions (unused entries are skipped by the kernels)
 //   reverse    the reversed strand, written once behind the forward one in the scan's own buffer
+//   held       a held pass (aln_scan_hits) leaves every hit's summary and strings in the slot; held_f gathers the hits' f, freq sums
+//              the frequency matrices (alignment.rs:55-65) of a list of held hits in unsigned integers, gather packs the listed
+//              hits' summaries and strings for one download
 //
-// Every store is a plain C++ store of a thread (vector memory instructions).  The z test is a true IEEE division and compare
+// Every store is a plain C++ store or an atomicAdd of a thread (vector memory instructions).  The z test is a true IEEE division and compare
 // (-ffp-contract=off, no reciprocal): NaN fails it, +inf passes it.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "aln_device.h"
+#include "aln_scheme_rules.h"
 
 #define SCAN_THREADS 256u
 #define SCAN_PER_THREAD 8u
@@ -153,6 +159,74 @@ __global__ __launch_bounds__(256) void aln_scan_hits_kernel(PairDesc *descs, uin
     order[h] = h;
 }
 
+// ---- held hits: f of hit h out of its summary (the re-fill's results lie in hit order)
+__global__ __launch_bounds__(256) void aln_scan_held_f_kernel(const aln_pair_result *res, double *f, uint32_t n)
+{
+    const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
+    if (h < n) f[h] = res[h].f;
+}
+
+// ---- held hits: counts[c * cols + col - 1] += 1 for every position of every listed hit whose column number is not 0 and whose
+// residue is not Blank (alignment.rs:55-65, summed over the list).  A workgroup takes a run of `per` listed hits, one wave a hit at a
+// time: lane l reads positions l, l + 64, ... of the expanded strings (u32 column numbers, then the residues at 4 * (N + M + 2)),
+// so both move in whole lines.  Counters are u32: LDS atomics per workgroup (within one hit a column occurs once, conflicts are
+// between the waves' hits only), then one agent-scope atomicAdd per non-zero counter into the zeroed global array.  Integer sums do
+// not depend on the order of arrival: the same matrix every run, and the host's.  The counters always fit: a position-weight
+// matrix has at most ALN_MAX_PWM_ENTRIES = 4 x 2000 entries (aln_scheme_rules.h), 32 000 bytes of u32.
+static_assert(4u * ALN_MAX_PWM_ENTRIES <= 32768u, "the frequency counters of the widest PWM must fit a workgroup's LDS");
+__global__ __launch_bounds__(256) void aln_scan_freq_kernel(const PairDesc *descs, const aln_pair_result *res, const uint8_t *tb,
+                                                            const uint32_t *keep, uint32_t n_keep, uint32_t per, uint32_t n_held,
+                                                            uint32_t cols, uint32_t blank, uint32_t *counts)
+{
+    extern __shared__ uint32_t freq_lds[];
+    const uint32_t cells = 4u * cols;
+    for (uint32_t i = threadIdx.x; i < cells; i += blockDim.x) freq_lds[i] = 0u;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const uint32_t lo = blockIdx.x * per;
+    const uint32_t hi = lo + per < n_keep ? lo + per : n_keep;
+    for (uint32_t k = lo + wave; k < hi; k += waves) {
+        const uint32_t h = keep[k];
+        if (h >= n_held) continue;                                   // checked on the host; never read beyond the held hits
+        const PairDesc &d = descs[h];
+        const aln_pair_result &r = res[h];
+        if (r.status != ALN_OK) continue;
+        const uint32_t cap = d.N + d.M + 2u;
+        const uint32_t len = r.aln_len < cap ? r.aln_len : cap;
+        const uint32_t *__restrict__ numbered = reinterpret_cast<const uint32_t *>(tb + d.tb_off);
+        const uint8_t *__restrict__ residues = tb + d.tb_off + 4ull * cap;
+        for (uint32_t j = lane; j < len; j += 64u) {
+            const uint32_t col = numbered[j], c = residues[j];
+            if (col == 0u || col > cols || c == blank || c >= 4u) continue;
+            atomicAdd(&freq_lds[c * cols + col - 1u], 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < cells; i += blockDim.x) {
+        const uint32_t v = freq_lds[i];
+        if (v) __hip_atomic_fetch_add(&counts[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---- held hits: the u32 sums as the f64 matrix the caller gets
+__global__ __launch_bounds__(256) void aln_scan_freq_f64_kernel(const uint32_t *counts, double *out, uint32_t cells)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cells) out[i] = (double)counts[i];
+}
+
+// ---- held hits: entry k of the packed output = summary and strings (one stride, as u32 words) of held hit keep[k]
+__global__ __launch_bounds__(256) void aln_scan_gather_kernel(const aln_pair_result *res, const uint8_t *tb, const uint32_t *keep,
+                                                              uint32_t n_held, uint64_t stride, aln_pair_result *out_res, uint8_t *out_tb)
+{
+    const uint32_t k = blockIdx.x, h = keep[k];
+    if (h >= n_held) return;
+    if (threadIdx.x == 0) out_res[k] = res[h];
+    const uint32_t *__restrict__ src = reinterpret_cast<const uint32_t *>(tb + (uint64_t)h * stride);
+    uint32_t *__restrict__ dst = reinterpret_cast<uint32_t *>(out_tb + (uint64_t)k * stride);
+    for (uint64_t i = threadIdx.x; i < stride / 4u; i += blockDim.x) dst[i] = src[i];
+}
+
 // ---- the reversed strand: seq[len + i] = seq[len - 1 - i]
 __global__ __launch_bounds__(256) void aln_scan_reverse_kernel(uint8_t *seq, uint64_t len)
 {
@@ -192,6 +266,34 @@ extern "C" void aln_scan_launch_hits(PairDesc *descs, uint32_t *order, uint32_t 
 {
     if (n_slots) hipLaunchKernelGGL(aln_scan_hits_kernel, dim3(blocks_of(n_slots, 256)), dim3(256), 0, s, descs, order, n_slots, idx, count,
                                     cap, first, step, width, len, base, cols, dir_stride, tb_stride, tag_stride);
+}
+
+extern "C" void aln_scan_launch_held_f(const aln_pair_result *res, double *f, uint32_t n, hipStream_t s)
+{
+    if (n) hipLaunchKernelGGL(aln_scan_held_f_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, res, f, n);
+}
+
+// counts: 4 * cols u32, zeroed here; out: 4 * cols f64
+extern "C" void aln_scan_launch_freq(const PairDesc *descs, const aln_pair_result *res, const uint8_t *tb, const uint32_t *keep,
+                                     uint32_t n_keep, uint32_t n_held, uint32_t cols, uint32_t blank, uint32_t *counts, double *out,
+                                     hipStream_t s)
+{
+    const uint32_t cells = 4u * cols;
+    (void)hipMemsetAsync(counts, 0, 4ull * cells, s);
+    if (n_keep) {
+        // a run of >= 16 hits per workgroup (4 per wave) pays for zeroing and flushing its counters; at most 1024 workgroups
+        const uint32_t grid = std::min<uint32_t>(blocks_of(n_keep, 16), 1024u);
+        const uint32_t per = blocks_of(n_keep, grid);
+        hipLaunchKernelGGL(aln_scan_freq_kernel, dim3(blocks_of(n_keep, per)), dim3(256), 4u * cells, s, descs, res, tb, keep, n_keep, per,
+                           n_held, cols, blank, counts);
+    }
+    hipLaunchKernelGGL(aln_scan_freq_f64_kernel, dim3(blocks_of(cells, 256)), dim3(256), 0, s, counts, out, cells);
+}
+
+extern "C" void aln_scan_launch_gather(const aln_pair_result *res, const uint8_t *tb, const uint32_t *keep, uint32_t n_keep, uint32_t n_held,
+                                       uint64_t stride, aln_pair_result *out_res, uint8_t *out_tb, hipStream_t s)
+{
+    if (n_keep) hipLaunchKernelGGL(aln_scan_gather_kernel, dim3(n_keep), dim3(256), 0, s, res, tb, keep, n_held, stride, out_res, out_tb);
 }
 
 extern "C" void aln_scan_launch_reverse(uint8_t *seq, uint64_t len, hipStream_t s)

@@ -13,7 +13,9 @@ cmd/{testing,exploring,csv}.rs).  Per FASTA record:
 
 The windows are aligned by a scoring backend with two passes over a resident chromosome: `score` (f of every window of a
 geometry) and `select` (the windows with z >= z_min, with their alignments).  ScanBackend is the GPU one (aln_scan_*: the
-chromosome is uploaded once, windows are expanded on the device, only the hits come back).  Randomness comes from a
+chromosome is uploaded once, windows are expanded on the device, only the hits come back).  A scan that also offers `hits` (the
+GPU one by default) keeps a cycle's hits on the device: window numbers and f come back, the overlap filter runs on arrays
+(filter_hits), the kept hits' frequency matrices are summed on the device, and alignment strings are fetched for kept hits only.  Randomness comes from a
 numpy.random.Generator; sums run left to right in ascending window order (the reference's order with its default of one thread).
 `python -m aligner_amd.repeats` is the program.
 """
@@ -140,6 +142,39 @@ def filter_tasks(tasks):
     return result
 
 
+def filter_hits(left, right, z):
+    """filter_tasks on plain arrays: -> the positions (in the input) of the hits it keeps, in its order.  The same stable sort by
+    left_coord, clusters, last of equal maxima, resume-at-the-last-looked-at and ReferencePanic on a NaN comparison."""
+    left = np.asarray(left, dtype=np.int64)
+    n = len(left)
+    if n <= 1:
+        return np.arange(n, dtype=np.int64)
+    order = np.argsort(left, kind="stable")
+    L = left[order].tolist()
+    Rt = np.asarray(right, dtype=np.int64)[order].tolist()
+    Zs = np.asarray(z, dtype=np.float64)[order].tolist()
+    result, seen = [], set()                     # positions in sorted order; the left_coords in `result` (Task equality)
+    lo = 0
+    while lo < n:
+        if n - lo == 1:
+            if L[lo] not in seen:
+                result.append(lo)
+            break
+        cur = (L[lo], Rt[lo])
+        best, index = lo, 0
+        for i in range(n - lo - 1):
+            p = lo + 1 + i
+            index = i
+            if not check_intersection(cur, (L[p], Rt[p])):
+                break
+            if _partial_cmp(Zs[p], Zs[best]) >= 0:       # Iterator::max_by: the LAST of equal maxima
+                best = p
+        result.append(best)
+        seen.add(L[best])
+        lo += index + 1
+    return order[np.asarray(result, dtype=np.int64)]
+
+
 def _partial_cmp(a, b):
     if a != a or b != b:
         raise ReferencePanic(-1, "called `Option::unwrap()` on a `None` value (partial_cmp of NaN, engine/mod.rs:92)")
@@ -247,6 +282,8 @@ def calculate_cycle(query, matrix, indices, mean, std, opts, backend, reverse=Fa
     own = scan is None
     sc = backend.scan(query) if own else scan
     try:
+        if hasattr(sc, "hits"):
+            return _HeldCycle(sc, query, matrix, indices, mean, std, opts, reverse).tasks()
         idx, alns = sc.select(matrix, opts.deletions, opts.extension, 0, step, opts.width, mean, std, Z, reverse=reverse)
     finally:
         if own:
@@ -258,6 +295,54 @@ def calculate_cycle(query, matrix, indices, mean, std, opts, backend, reverse=Fa
         z = _div(np.float64(aln.f) - np.float64(mean), std)
         tasks.append(Task(aln, index_coord(j, indices), index_coord(border, indices), float(z)))
     return tasks
+
+
+class _HeldCycle:
+    """One cycle on a scan that holds its hits (`hits`): window numbers and f as arrays, z and coordinates from them; alignment
+    strings are fetched (`fetch`, raw bytes) for the positions asked for, and Task / PWMAlignment objects are built by `tasks`
+    only.  The held state lasts until the scan's next pass: `fetch` what is to outlive it before that."""
+
+    def __init__(self, sc, query, matrix, indices, mean, std, opts, reverse=False):
+        length, step = len(query), cycle_step(opts)
+        self.held = sc.hits(matrix, opts.deletions, opts.extension, 0, step, opts.width, mean, std, Z, reverse=reverse)
+        self.f = self.held.f
+        j = self.held.idx * step
+        border = np.minimum(j + opts.width, length)
+        if indices:
+            self.left = np.array([index_coord(int(v), indices) for v in j], dtype=np.int64)
+            self.right = np.array([index_coord(int(v), indices) for v in border], dtype=np.int64)
+        else:
+            self.left, self.right = j.astype(np.int64), border.astype(np.int64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.z = (self.f - np.float64(mean)) / np.float64(std)
+        self.kept = np.arange(len(self.f), dtype=np.int64)
+        self._alns = None
+
+    def __len__(self):
+        return len(self.f)
+
+    def keep(self, positions):
+        self.kept = np.asarray(positions, dtype=np.int64)
+        self._alns = None
+
+    def fetch(self):
+        """The kept hits' summaries and strings off the device (no objects yet)."""
+        if self._alns is None:
+            strings = getattr(self.held, "strings", None)     # a scan without `strings` hands over the objects at once
+            self._alns = strings(self.kept) if strings else _Ready(self.held.alignments(self.kept))
+
+    def tasks(self):
+        self.fetch()
+        alns = self._alns.alignments()
+        return [Task(a, self.left[k], self.right[k], float(self.z[k])) for a, k in zip(alns, self.kept)]
+
+
+class _Ready:
+    def __init__(self, alns):
+        self._alns = alns
+
+    def alignments(self):
+        return self._alns
 
 
 def _transform(matrix, opts, freqs):
@@ -275,6 +360,8 @@ def perform_calculation_per_sequence(opts, raw_seq, head, rng, backend):
     result = {}
     tasks = []
     with backend.scan(query) as sc:
+        if hasattr(sc, "hits"):
+            return _held_calculation(opts, query, freqs, indices, matrix, mean, std, sc)
         for i in range(opts.repeats):
             new_tasks = calculate_cycle(query, matrix, indices, mean, std, opts, backend, scan=sc)
             if not new_tasks:
@@ -291,6 +378,39 @@ def perform_calculation_per_sequence(opts, raw_seq, head, rng, backend):
             rotated = rotate_indices(indices, len(query))
             inv = calculate_cycle(query, matrix, rotated, mean, std, opts, backend, reverse=True, scan=sc)
             result["inverse"] = (filter_tasks(inv), matrix)
+    return result
+
+
+def _held_calculation(opts, query, freqs, indices, matrix, mean, std, sc):
+    """The loop of perform_calculation_per_sequence on a scan that holds its hits.  Per cycle: hits -> filter_hits -> mean and
+    variance of the kept f -> the kept hits' frequency sum from the device -> the next PWM.  The kept hits' strings are fetched
+    before the next pass replaces the held state (also when that pass then finds nothing and these are the tasks returned);
+    Task and PWMAlignment objects are built for the cycle that is returned only."""
+    def cycle(indices, reverse=False):
+        if cycle_step(opts) is None or len(query) == 0:          # calculate_cycle's empty cases
+            return None
+        return _HeldCycle(sc, query, matrix, indices, mean, std, opts, reverse)
+
+    result = {}
+    last = None
+    for i in range(opts.repeats):
+        cyc = cycle(indices)
+        if cyc is None or not len(cyc):
+            break
+        cyc.keep(filter_hits(cyc.left, cyc.right, cyc.z))
+        if i < opts.repeats - 1:
+            mean, std = mean_and_variance(cyc.f[cyc.kept])                  # std is the variance here (calc.rs:198-203)
+            matrix = _transform(cyc.held.frequencies(cyc.kept), opts, freqs)
+        cyc.fetch()
+        last = cyc
+    result["direct"] = (last.tasks() if last is not None else [], matrix.copy())
+    if opts.reverse:
+        cyc = cycle(rotate_indices(indices, len(query)), reverse=True)
+        inv = []
+        if cyc is not None:
+            cyc.keep(filter_hits(cyc.left, cyc.right, cyc.z))
+            inv = cyc.tasks()
+        result["inverse"] = (inv, matrix)
     return result
 
 
@@ -408,11 +528,11 @@ class ScanBackend:
     """Scores windows on the GPU through aln_scan_*: `scan(seq)` uploads a chromosome once; its passes send the PWM and a
     geometry and get back f of every window (score) or the hits only (select)."""
 
-    def __init__(self, device=None, cap=4096):
-        self.device, self.cap = device, int(cap)
+    def __init__(self, device=None, cap=4096, held=True):
+        self.device, self.cap, self.held = device, int(cap), bool(held)
 
     def scan(self, seq):
-        return GpuScan(seq, self.device, self.cap)
+        return (HeldGpuScan if self.held else GpuScan)(seq, self.device, self.cap)
 
 
 class GpuScan:
@@ -470,18 +590,9 @@ class GpuScan:
                 break
             cap = count                                    # more hits than room: again, with room for all of them,
             self.cap = max(self.cap, count)                # and that room from now on (the next cycles keep about as many)
-        W = m.shape[1]
-        alns = []
-        for h in range(count):
-            r = res[h]
-            j = first + int(idx[h]) * step
-            M = min(width, self.len - j)
-            L, o, c = int(r["aln_len"]), h * stride, W + M + 2
-            numbered = tb[o:o + 4 * L].view(np.uint32).copy()
-            qal = tb[o + 4 * c:o + 4 * c + L].copy()
-            coords = ((int(r["start_x"]) + 1, int(r["end_x"]) + 1), (int(r["start_y"]) + 1, int(r["end_y"]) + 1))
-            alns.append(PWMAlignment(DNA, numbered, qal, W, coords, float(r["f"])))
-        return idx[:count].astype(np.int64), alns
+        idx = idx[:count].astype(np.int64)
+        lengths = np.minimum(width, self.len - (first + idx * step))
+        return idx, self._alignments(res[:count], tb, stride, lengths, m.shape[1])
 
     def select_raw(self, matrix, del_, ext, first, step, width, mean, sd, z_min, reverse=False, cap=1024):
         """One select pass as the C ABI returns it: (indices, results, strings, true count, string stride, status)."""
@@ -503,12 +614,107 @@ class GpuScan:
             runtime.raise_for_status(st, "aln_scan_select")
         return idx, res, tb, int(count.value), stride
 
+    @staticmethod
+    def _alignments(res, tb, stride, lengths, W):
+        """PWMAlignment objects out of summaries and strings in the layout of aln_scan_select (entry h at h * stride; its residues
+        at 4 * (W + that window's length + 2))."""
+        alns = []
+        for h in range(len(res)):
+            r = res[h]
+            L, o, c = int(r["aln_len"]), h * stride, W + int(lengths[h]) + 2
+            numbered = tb[o:o + 4 * L].view(np.uint32).copy()
+            qal = tb[o + 4 * c:o + 4 * c + L].copy()
+            coords = ((int(r["start_x"]) + 1, int(r["end_x"]) + 1), (int(r["start_y"]) + 1, int(r["end_y"]) + 1))
+            alns.append(PWMAlignment(DNA, numbered, qal, W, coords, float(r["f"])))
+        return alns
+
     def stats(self):
         """The last pass: kernel ms (fill, selection, hit re-fill + walk), download wall ms, bytes host->device, device->host."""
         ms = (C.c_double * 4)()
         by = (C.c_uint64 * 2)()
         self.lib.aln_scan_stats(self.h, ms, by)
         return dict(fill_ms=ms[0], select_ms=ms[1], refill_ms=ms[2], download_ms=ms[3], h2d_bytes=by[0], d2h_bytes=by[1])
+
+
+class HeldGpuScan(GpuScan):
+    """A GpuScan that also offers `hits`: a select pass whose hits stay on the device (aln_scan_hits)."""
+
+    generation = 0                                   # counts the passes: held hits are those of the last one only
+
+    def score(self, *a, **kw):
+        self.generation += 1
+        return GpuScan.score(self, *a, **kw)
+
+    def _select_raw(self, *a, **kw):
+        self.generation += 1
+        return GpuScan._select_raw(self, *a, **kw)
+
+    def hits(self, matrix, del_, ext, first, step, width, mean, sd, z_min, reverse=False):
+        """-> HeldHits: the windows with (f - mean) / sd >= z_min, held on the device until this scan's next pass."""
+        m = np.asarray(matrix, dtype=np.float64)
+        p, keep = runtime.make_params(_ffi.PWM_LOCAL, del_, ext, m)
+        g = self._geometry(first, step, width, reverse)
+        self.generation += 1
+        count = C.c_uint64(0)
+        st = self.lib.aln_scan_hits(self.h, C.byref(p), C.byref(g), float(mean), float(sd), float(z_min), C.byref(count))
+        runtime.raise_for_status(st, "aln_scan_hits")
+        n = int(count.value)
+        idx = np.zeros(n, dtype=np.uint32)
+        f = np.zeros(n, dtype=np.float64)
+        st = self.lib.aln_scan_held_list(self.h, 0, n, idx.ctypes.data, f.ctypes.data)
+        runtime.raise_for_status(st, "aln_scan_held_list")
+        stride = int(self.lib.aln_scan_string_stride(self.h, m.shape[1], C.byref(g)))
+        idx = idx.astype(np.int64)
+        lengths = np.minimum(int(width), self.len - (int(first) + idx * int(step)))
+        return HeldHits(self, idx, f, m.shape[1], stride, lengths)
+
+
+class HeldHits:
+    """The hits of one held pass: `idx` (window numbers, ascending) and `f`; `frequencies(keep)`, `strings(keep)` and
+    `alignments(keep)` take positions in this list and work on what the device holds, until the scan's next pass."""
+
+    def __init__(self, scan, idx, f, W, stride, lengths):
+        self.scan, self.idx, self.f, self.W, self.stride, self.lengths = scan, idx, f, int(W), int(stride), lengths
+        self.generation = scan.generation
+
+    def __len__(self):
+        return len(self.idx)
+
+    def _keep(self, keep):
+        if self.generation != self.scan.generation or not self.scan.h:
+            raise RuntimeError("the held hits have been replaced by a later pass on this scan")
+        keep = np.asarray(keep, dtype=np.int64).ravel()
+        if len(keep) and (keep.min() < 0 or keep.max() >= len(self.idx)):
+            raise IndexError("position outside the held hits")
+        return np.ascontiguousarray(keep, dtype=np.uint32)
+
+    def frequencies(self, keep):
+        """The sum of the listed hits' frequency matrices (PWMAlignment.get_frequency_matrix), float64 (4, W)."""
+        k = self._keep(keep)
+        out = np.zeros((4, self.W), dtype=np.float64)
+        st = self.scan.lib.aln_scan_held_frequencies(self.scan.h, k.ctypes.data, len(k), out.ctypes.data)
+        runtime.raise_for_status(st, "aln_scan_held_frequencies")
+        return out
+
+    def strings(self, keep):
+        """The listed hits' summaries and strings as they come off the device -> HeldStrings."""
+        k = self._keep(keep)
+        res = np.zeros(len(k), dtype=RESULT_DTYPE)
+        tb = np.zeros(self.stride * len(k) + 8, dtype=np.uint8)
+        st = self.scan.lib.aln_scan_held_strings(self.scan.h, k.ctypes.data, len(k), res.ctypes.data, tb.ctypes.data)
+        runtime.raise_for_status(st, "aln_scan_held_strings")
+        return HeldStrings(res, tb, self.stride, self.lengths[k.astype(np.int64)], self.W)
+
+    def alignments(self, keep):
+        return self.strings(keep).alignments()
+
+
+class HeldStrings:
+    def __init__(self, res, tb, stride, lengths, W):
+        self.res, self.tb, self.stride, self.lengths, self.W = res, tb, stride, lengths, W
+
+    def alignments(self):
+        return GpuScan._alignments(self.res, self.tb, self.stride, self.lengths, self.W)
 
 
 # ---------------------------------------------------------------- CLI (args.rs, main.rs)

@@ -176,8 +176,24 @@ void aln_batch_enable_timing(aln_batch *b, int on);
  * number of hits in *count and the first min(count, cap) of them: window indices, summaries and (tb_buf optional) strings, hit h's
  * at h * aln_scan_string_stride(...) in the ALN_PWM_LOCAL layout of aln_align_batch (u32 column numbers, then the residues at
  * 4 * (cols + that window's length + 2)).  count > cap: ALN_ERR_CAPACITY.  params->outputs is ignored.
+ * hits: a HELD select pass.  Fill, z test and compaction exactly as select; the count is read where the pass waits anyway, the
+ * hit buffers are sized for it (no capacity, no second fill; ALN_ERR_OOM and nothing held if that memory cannot be had) and ALL
+ * hits are filled again with directions and walked.  Summaries, strings and the hit list stay on the device; only *count comes
+ * back (8 bytes device -> host).  The hit set, its order, every summary and every string are select's for the same arguments with
+ * enough capacity.  A failed window fails the call with its status, as in select, and nothing is held.  Held state belongs to
+ * the scan and lasts until the next score / select / hits on it or destroy.
+ * held_list: window index and f of held hits first .. first + n - 1 (ascending window order); 12 * n bytes come back.
+ * held_frequencies: counts[c * cols + (col - 1)] = the number of listed hits whose alignment puts residue c on PWM column col
+ * (1-based), over positions whose column number is not 0 and whose residue is not Blank: the sum of the hits' frequency matrices
+ * (alignment.rs:55-65), accumulated on the device in unsigned integers, so exact and the same in any order.  keep[] are positions
+ * in the held list in any order; a position listed twice counts twice; n_keep == 0 gives zeros.  4 * n_keep bytes go up,
+ * 32 * cols come back.
+ * held_strings: summaries and strings of the listed held hits, entry k's strings at k * aln_scan_string_stride(...), layout of
+ * select; 4 * n_keep bytes go up, n_keep * (48 + stride) come back.
+ * held_* without held state, first + n > count, a keep[k] >= count, a null pointer with a non-zero length:
+ * ALN_ERR_INVALID_ARGUMENT, nothing written.
  * stats: the last pass's kernel times in ms (fill, selection, hit re-fill + walk) + its download's wall time, and the bytes it
- * moved (host -> device, device -> host). ---- */
+ * moved (host -> device, device -> host).  After a held_* call: ms[2] its kernels, ms[3] the call's wall time, and its bytes. ---- */
 typedef struct aln_scan aln_scan;
 typedef struct aln_scan_geometry {
     uint64_t first, step, width;
@@ -191,6 +207,11 @@ size_t aln_scan_windows(const aln_scan *scan, const aln_scan_geometry *geometry)
 int aln_scan_score(aln_scan *scan, const aln_params *params, const aln_scan_geometry *geometry, double *f);
 int aln_scan_select(aln_scan *scan, const aln_params *params, const aln_scan_geometry *geometry, double mean, double sd,
                     double z_min, size_t cap, uint64_t *count, uint32_t *indices, aln_pair_result *results, uint8_t *tb_buf);
+int aln_scan_hits(aln_scan *scan, const aln_params *params, const aln_scan_geometry *geometry, double mean, double sd, double z_min,
+                  uint64_t *count);
+int aln_scan_held_list(aln_scan *scan, uint64_t first, uint64_t n, uint32_t *indices, double *f);
+int aln_scan_held_frequencies(aln_scan *scan, const uint32_t *keep, uint64_t n_keep, double *counts /* 4 * cols */);
+int aln_scan_held_strings(aln_scan *scan, const uint32_t *keep, uint64_t n_keep, aln_pair_result *results, uint8_t *tb_buf);
 uint64_t aln_scan_string_stride(const aln_scan *scan, uint32_t cols, const aln_scan_geometry *geometry);
 int aln_scan_stats(const aln_scan *scan, double *ms, uint64_t *bytes);
 

@@ -59,6 +59,41 @@ extern "C" {
                        t_len: *const u64, n_pairs: usize, results: *mut AlnPairResult, tb_buf: *mut u8, tb_off: *const u64) -> c_int;
 }
 
+/// The window scan of `latent-repeat-search` (include/aligner_hip.h, "window scan"): a chromosome resident on the GPU, passes described
+/// by a geometry.  `aln_scan_hits` is the held form of `aln_scan_select`: every hit's summary and strings stay on the device, the count
+/// alone comes back (no capacity, no second fill); `aln_scan_held_list` gives window number and f per hit, `aln_scan_held_frequencies`
+/// the sum of the listed hits' `get_frequency_matrix()` (counted in unsigned integers on the device: exact, any order), and
+/// `aln_scan_held_strings` the summaries and strings of the listed hits only -- what `calculate_cycle` + `filter` + the PWM update of
+/// engine/calc.rs:187-216 need.  Held state lasts until the next score / select / hits on the scan.
+pub mod scan {
+    use super::{AlnCtx, AlnPairResult, AlnParams};
+    use std::os::raw::c_int;
+
+    #[repr(C)]
+    pub struct AlnScan { _private: [u8; 0] }
+
+    #[repr(C)]
+    #[derive(Clone, Copy)]
+    pub struct AlnScanGeometry { pub first: u64, pub step: u64, pub width: u64, pub reverse: u32, pub reserved: u32 }
+
+    extern "C" {
+        pub fn aln_scan_create(ctx: *mut AlnCtx, seq: *const u8, len: usize, status: *mut c_int) -> *mut AlnScan;
+        pub fn aln_scan_destroy(scan: *mut AlnScan);
+        pub fn aln_scan_windows(scan: *const AlnScan, g: *const AlnScanGeometry) -> usize;
+        pub fn aln_scan_score(scan: *mut AlnScan, p: *const AlnParams, g: *const AlnScanGeometry, f: *mut f64) -> c_int;
+        pub fn aln_scan_select(scan: *mut AlnScan, p: *const AlnParams, g: *const AlnScanGeometry, mean: f64, sd: f64, z_min: f64, cap: usize,
+                               count: *mut u64, indices: *mut u32, results: *mut AlnPairResult, tb_buf: *mut u8) -> c_int;
+        pub fn aln_scan_hits(scan: *mut AlnScan, p: *const AlnParams, g: *const AlnScanGeometry, mean: f64, sd: f64, z_min: f64,
+                             count: *mut u64) -> c_int;
+        pub fn aln_scan_held_list(scan: *mut AlnScan, first: u64, n: u64, indices: *mut u32, f: *mut f64) -> c_int;
+        /// counts: 4 * cols doubles, counts[c * cols + (col - 1)]
+        pub fn aln_scan_held_frequencies(scan: *mut AlnScan, keep: *const u32, n_keep: u64, counts: *mut f64) -> c_int;
+        pub fn aln_scan_held_strings(scan: *mut AlnScan, keep: *const u32, n_keep: u64, results: *mut AlnPairResult, tb_buf: *mut u8) -> c_int;
+        pub fn aln_scan_string_stride(scan: *const AlnScan, cols: u32, g: *const AlnScanGeometry) -> u64;
+        pub fn aln_scan_stats(scan: *const AlnScan, ms: *mut f64, bytes: *mut u64) -> c_int;
+    }
+}
+
 pub const CORE_GLOBAL: i32 = 0;
 pub const CORE_LOCAL: i32 = 1;
 pub const PWM_LOCAL: i32 = 4;

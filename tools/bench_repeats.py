@@ -2,9 +2,12 @@
 
 A seeded synthetic 10 Mb chromosome with planted repeats, a real-valued PWM, the default geometry (windows of 330 rows every 30:
 333 334 windows x 300 columns).  Prints the scan's score pass (ms, GCUPS), one select pass split into fill / selection / hit
-re-fill + walk / download, the bytes each pass moves, the same windows through align_window_offsets(want_traceback=False), and
-the whole engine (3 cycles + reverse) in wall time.  `python tools/bench_repeats.py [--mb 10] [--reps 5]`."""
+re-fill + walk / download, the bytes each pass moves, one held pass (aln_scan_hits, then the hit list, the overlap filter on
+arrays, the kept hits' frequency sum and their strings, each with its bytes), the same windows through
+align_window_offsets(want_traceback=False), and the whole engine (3 cycles + reverse) in wall time on the select path and on the
+held path.  `python tools/bench_repeats.py [--mb 10] [--reps 5]`."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -13,7 +16,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from aligner_amd import repeats as R                     # noqa: E402
+from aligner_amd import _ffi, runtime, repeats as R      # noqa: E402
 from aligner_amd.pwm import align_window_offsets         # noqa: E402
 
 
@@ -66,6 +69,53 @@ def main():
         out["select_split_ms"] = {"fill": st["fill_ms"], "selection": st["select_ms"], "hit_refill_walk": st["refill_ms"],
                                   "download": st["download_ms"]}
         out["select_bytes"] = {"h2d": st["h2d_bytes"], "d2h": st["d2h_bytes"]}
+        # one held pass, call by call (the second of two: buffers and plans are warm)
+        p, keepalive = runtime.make_params(_ffi.PWM_LOCAL, d, e, m)
+        g = sc._geometry(0, step, width, False)
+        count = C.c_uint64(0)
+        held, calls = {}, {}
+
+        def timed(name, fn):
+            t0 = time.perf_counter()
+            r = fn()
+            st = sc.stats()
+            calls[name] = {"ms": (time.perf_counter() - t0) * 1e3, "kernel_ms": st["refill_ms"], "h2d": st["h2d_bytes"], "d2h": st["d2h_bytes"]}
+            return r
+
+        for rep in range(2):
+            t_all = time.perf_counter()
+            st = timed("hits", lambda: sc.lib.aln_scan_hits(sc.h, C.byref(p), C.byref(g), mean, sd, 3.0, C.byref(count)))
+            runtime.raise_for_status(st, "aln_scan_hits")
+            s0 = sc.stats()
+            held["split_ms"] = {"fill": s0["fill_ms"], "selection": s0["select_ms"], "hit_refill_walk": s0["refill_ms"]}
+            nh = int(count.value)
+            hidx, hf = np.zeros(nh, dtype=np.uint32), np.zeros(nh)
+            timed("held_list", lambda: sc.lib.aln_scan_held_list(sc.h, 0, nh, hidx.ctypes.data, hf.ctypes.data))
+            t0 = time.perf_counter()
+            j = hidx.astype(np.int64) * step
+            kept = R.filter_hits(j, np.minimum(j + width, n), (hf - mean) / sd)
+            calls["filter_hits"] = {"ms": (time.perf_counter() - t0) * 1e3}
+            k32 = np.ascontiguousarray(kept, dtype=np.uint32)
+            fm = np.zeros((4, W))
+            timed("held_frequencies", lambda: sc.lib.aln_scan_held_frequencies(sc.h, k32.ctypes.data, len(k32), fm.ctypes.data))
+            held["pass_ms"] = (time.perf_counter() - t_all) * 1e3          # hits + list + filter + frequencies: what a cycle needs
+            stride = int(sc.lib.aln_scan_string_stride(sc.h, W, C.byref(g)))
+            res, tb = np.zeros(len(k32), dtype=R.RESULT_DTYPE), np.zeros(stride * len(k32) + 8, dtype=np.uint8)
+            timed("held_strings", lambda: sc.lib.aln_scan_held_strings(sc.h, k32.ctypes.data, len(k32), res.ctypes.data, tb.ctypes.data))
+        out["held_pass_ms"] = held["pass_ms"]
+        out["held_hits"] = nh
+        out["held_kept"] = int(len(kept))
+        out["held_split_ms"] = held["split_ms"]
+        out["held_calls"] = calls
+        # the select path's share of the same work on the host: filter_tasks and the frequency sum of the kept tasks
+        t0 = time.perf_counter()
+        tasks = R.filter_tasks([R.Task(a, int(k) * step, min(int(k) * step + width, n), (a.f - mean) / sd) for k, a in zip(idx, alns)])
+        ms = np.zeros((4, W))
+        for t in tasks:
+            ms = ms + t.alignment.get_frequency_matrix()
+        out["select_host_filter_and_sum_ms"] = (time.perf_counter() - t0) * 1e3
+        out["held_equals_select"] = bool(hidx.tolist() == idx.tolist() and np.array_equal(fm, ms) and
+                                         [t.left_coord for t in tasks] == j[kept].tolist())
     reuse = {}
     align_window_offsets(seq, starts, lens, d, e, m, want_traceback=False, want_alignments=False, reuse=reuse)
     ts = []
@@ -80,9 +130,16 @@ def main():
     raw = bytes(b"ATCG"[c] for c in seq)
     opts = R.Options(repeats=3, reverse=True)
     t0 = time.perf_counter()
-    r = R.perform_calculation_per_sequence(opts, raw, "synthetic", np.random.default_rng(3), R.ScanBackend())
+    r = R.perform_calculation_per_sequence(opts, raw, "synthetic", np.random.default_rng(3), R.ScanBackend(held=False))
     out["engine_3_cycles_reverse_s"] = time.perf_counter() - t0
     out["engine_tasks"] = {k: len(v[0]) for k, v in r.items()}
+    t0 = time.perf_counter()
+    rh = R.perform_calculation_per_sequence(opts, raw, "synthetic", np.random.default_rng(3), R.ScanBackend(held=True))
+    out["engine_held_3_cycles_reverse_s"] = time.perf_counter() - t0
+    out["engine_held_tasks"] = {k: len(v[0]) for k, v in rh.items()}
+    out["engine_held_equals_select"] = bool(list(r) == list(rh) and all(
+        np.array_equal(r[k][1], rh[k][1]) and [(t.left_coord, t.right_coord, t.z) for t in r[k][0]] ==
+        [(t.left_coord, t.right_coord, t.z) for t in rh[k][0]] for k in r))
     print(json.dumps(out, indent=1))
 
 
