@@ -142,7 +142,7 @@ struct FillArgs {
 // tag is the one it expects, so neither the order in which stores become visible nor a copy of an older pass in some cache can be
 // taken for the data (cdna_hip_programming.md, Guideline 16, form R2).  Tag of strip s of a pass: aln_coop_tag(salt, seq) | s --
 // salt: a per-launch number of the slot that owns the scratch rows (10 bits; the host clears the rows when it wraps), seq: the
-// owner wave's count of multi-strip passes in this launch (12 bits; the wave clears its rows when it wraps).  Bit 31 set and
+// owner wave's count of multi-strip passes in this launch (12 bits; the wave clears its rows and its record when it wraps).  Bit 31 set and
 // bit 30 clear: no T value (|T| < 2^28) looks like a tag, whatever else a row was used for.
 struct CoopRec {
     unsigned long long pairg;                      // {pair, tag | 127}

@@ -1403,11 +1403,15 @@ __device__ __forceinline__ bool fast_work(FastIn in, const FastScratch &fs, cons
             ns = (M + srows - 1u) / srows;
             own = (passes == 0 && can_repair) ? 1u : 0u;
             // the tag of this pass's granules (rows, bottom-row record, candidates); when the 12 bits of the count wrap, tags of
-            // this launch could come back: the rows are cleared first
+            // this launch could come back: the rows are cleared first, and this wave's record with them -- its pair granule and
+            // its candidates still carry the tags of seq 1 .., and the owner of an open pass takes a strip's candidate by its tag
+            // alone (nobody else writes the record now: the owner has seen every candidate of the passes it opened)
             ++epoch;
             if ((epoch & 0xfffu) == 0u) {
                 for (uint32_t x = lane; x < fs.nrows * fs.row_elems; x += 64) fs.rows[x] = 0ull;
                 for (uint32_t x = lane; x < a.zrow_bytes / 8u; x += 64) reinterpret_cast<unsigned long long *>(fs.zrow)[x] = 0ull;
+                if (COOP && rec)
+                    for (uint32_t x = lane; x < (uint32_t)(sizeof(CoopRec) / sizeof(gran_t)); x += 64) gran_st(reinterpret_cast<gran_t *>(rec) + x, 0u, 0u);
                 __threadfence();
                 ++epoch;
             }
