@@ -37,7 +37,11 @@ EXPORTS = [
     "aln_batch_direction_bytes", "aln_batch_timing", "aln_batch_enable_timing",
     "aln_scan_create", "aln_scan_destroy", "aln_scan_windows", "aln_scan_score", "aln_scan_select", "aln_scan_string_stride",
     "aln_scan_stats", "aln_scan_hits", "aln_scan_held_list", "aln_scan_held_frequencies", "aln_scan_held_strings", "aln_shuffle_scores", "aln_shuffle_targets",
+    "aln_pairset_create", "aln_pairset_run", "aln_pairset_frequencies", "aln_pairset_strings", "aln_pairset_stats", "aln_pairset_destroy",
+    "aln_transform_matrices",
 ]
+PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
+TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
 
 
 class Params(C.Structure):
@@ -161,6 +165,20 @@ def load():
     lib.aln_shuffle_scores.argtypes = [vp, C.POINTER(Params), sp, vp, u64p, u64p, u64p, u64p, C.c_size_t, vp, vp, vp]
     lib.aln_shuffle_targets.restype = i
     lib.aln_shuffle_targets.argtypes = [vp, sp, vp, u64p, u64p, C.c_size_t, vp, u64p]
+    lib.aln_pairset_create.restype = vp
+    lib.aln_pairset_create.argtypes = [vp, vp, u64p, u64p, u64p, u64p, C.c_size_t, C.POINTER(C.c_int)]
+    lib.aln_pairset_run.restype = i
+    lib.aln_pairset_run.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, vp]
+    lib.aln_pairset_frequencies.restype = i
+    lib.aln_pairset_frequencies.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.aln_pairset_strings.restype = i
+    lib.aln_pairset_strings.argtypes = [vp, vp, C.c_size_t, vp, vp, u64p]
+    lib.aln_pairset_stats.restype = i
+    lib.aln_pairset_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.aln_pairset_destroy.restype = None
+    lib.aln_pairset_destroy.argtypes = [vp]
+    lib.aln_transform_matrices.restype = i
+    lib.aln_transform_matrices.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -60,6 +60,11 @@ struct ShufflePair {
     uint64_t out_off;        // copy 0 in the call's shuffled region; copy s at out_off + s * t_len (L - trim bytes of it written)
     uint32_t q_len, t_len;
 };
+// one held entry of a pair set (aln_pairset_*, aln_pairset.hip): where its strings lie in the held string buffer
+struct PairsetHeld {
+    uint64_t tb_off;         // aligned query here, aligned target N + M + 2 bytes later
+    uint32_t N, M;
+};
 // copies of at most this many residues are shuffled in LDS: 64 threads x 2 KiB = 128 KiB of a CU's 160
 #define ALN_SHUFFLE_LDS_MAX 2048u
 #define ALN_SHUFFLE_THREADS 64u
@@ -115,7 +120,10 @@ struct FillArgs {
                                      // wait for each other (C3: 14 of the 47 us a wave spends per pair lay between two pairs)
     uint32_t fair;                   // fast kernels: 0, or log2 of the time slice (10 ns ticks) in which the waves of a SIMD take turns at stepping down (FastStrip::fair_prio)
     uint32_t f64_old;                // generic f64 kernels: 1 = run_strip's all-options loop instead of the lean f64 strip (ALN_F64_OLD, testing)
+    uint32_t pair_matrices;          // lean f64 kernel (aln_pairset_run): 1 = `matrix` holds one rows x cols f64 matrix per descriptor, staged per wave
 };
+// aln_pairset_run: four waves' matrices of at most ALN_PAIRSET_MAX_ENTRIES doubles each
+__host__ __device__ inline uint32_t aln_pairset_lds_bytes(uint32_t rows, uint32_t cols) { return 4u * 8u * ((rows * cols + 1u) & ~1u); }
 
 // ---- cooperative passes of the fast batch kernel
 // One wave per pair leaves the tail of a small batch to whoever got the last large pair -- or a pair whose row-1 advice did not

@@ -349,6 +349,7 @@ struct Call {
     bool is_int = true, fast = false; // decided from the whole batch (the longest pair), the same for every chunk
     double unscale = 1.0;             // dyadic schemes on the integer kernels: scores come back multiplied by this (2^-k), see call_init
     int semantics = 0;                // what the kernels run (PWM runs as CORE_LOCAL with position-specific scoring)
+    const double *pair_matrices = nullptr;   // aln_pairset_run: DEVICE array, one rows x cols matrix per pair of the call (lean f64 kernel only)
 };
 
 // bytes of the single-pair kernel's advice array and of its bottom-row record (one direction dword per block of the last
@@ -581,7 +582,7 @@ static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, c
         // Generic kernels (real-valued matrix, or an integer one outside the fast path's limits): a chunk of at most four pairs (their launches run one
         // after the other; a larger chunk is better off with one wave per pair, all at once) gives each pair a whole workgroup, one wave per 64 R-row strip (<= 16 strips), instead of one wave -- the call HeuristicAligner makes
         // once per iteration (heuristic/mod.rs:58-77).  Also with the H dump (AlignmentResult.alignment_matrix) and for PWM scoring (HeuristicPWMAligner).
-        if (!single && (!c.fast || c.want_h) && !c.p.force_serial && !getenv("ALN_NO_WGPIPE") && n <= 4 && pc >= (1ull << 14) &&
+        if (!single && (!c.fast || c.want_h) && !c.pair_matrices && !c.p.force_serial && !getenv("ALN_NO_WGPIPE") && n <= 4 && pc >= (1ull << 14) &&
             d.N >= 16 && d.N <= 8192 && d.M >= 65 && d.M <= 2048) {
             // rows per lane: about eight strips = two waves per SIMD of the one CU (measured, 1000 x 1000 f64: R = 1 1.42 ms,
             // R = 2 1.26, R = 4 1.28; 330 x 300: 0.43 / 0.43 / 0.50)
@@ -761,7 +762,7 @@ static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, c
     // generic kernels: row 1 as the pass computed it (values + direction tags), for adopt_advice_checked
     const uint64_t row1_bytes = c.fast ? 0 : brow_bytes + adv_bytes;
     k.scratch_stride = (uint64_t)k.cascade_rows * brow_bytes + adv_bytes + zrow_bytes + ck_bytes + row1_bytes;
-    k.lds_bytes = (uint32_t)(((uint64_t)rows * cols * (c.is_int ? 4 : 8) + 15) & ~15ull);
+    k.lds_bytes = c.pair_matrices ? aln_pairset_lds_bytes(rows, cols) : (uint32_t)(((uint64_t)rows * cols * (c.is_int ? 4 : 8) + 15) & ~15ull);
     k.prof_stride = 0;
     if (c.fast && !pwm) { k.prof_stride = cols * 64u * ALN_FULL_R; k.lds_bytes = aln_fast_lds_bytes(rows, cols, k.prof_stride, ALN_FEED_BYTES); }
     // Two short pairs per wave (core global, read pairs: aln_fill_duo_kernel): every pair of the queue at most 256 rows and 1024
@@ -947,6 +948,7 @@ static int slot_launch(DevCtx *ctx, Slot &s, const Call &c, const Chunk &k, hipS
     fa.max_passes = c.p.max_passes; fa.force_serial = c.p.force_serial;
     fa.no_repair = getenv("ALN_NO_REPAIR") ? 1u : 0u;
     fa.f64_old = getenv("ALN_F64_OLD") ? 1u : 0u;
+    if (c.pair_matrices) { fa.matrix = c.pair_matrices + k.first * ((size_t)c.rows * c.cols); fa.pair_matrices = 1u; fa.f64_old = 0u; }
     fa.max_cells = k.max_cells;
     fa.store_dirs = c.store_dirs ? 1u : 0u;
     fa.pwm = c.pwm ? 1u : 0u;
@@ -2505,5 +2507,308 @@ extern "C" int aln_shuffle_targets(aln_ctx *ctx, const aln_shuffle_spec *spec, c
         }
     }
     HIPCHK(hipStreamSynchronize(q));
+    return ALN_OK;
+}
+
+// ---------------------------------------------------------------- resident pair set (aln_pairset_*, include/aligner_hip.h)
+// The loop of HeuristicAligner (heuristic/mod.rs:36-78) for many pairs in lock step: the residues stay in HBM, every run aligns the
+// listed pairs under a matrix of their own (aln_fill_f64_kernel<SEM, true>: the lean f64 strip, the matrix staged per wave), and the
+// walked strings stay on the device, where the frequency matrices the next iteration needs are counted.
+extern "C" void aln_pairset_launch_freq(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
+                                        uint32_t n_list, uint32_t n_held, uint32_t rows, uint32_t cols, uint32_t blank, uint32_t *counts,
+                                        hipStream_t s);
+extern "C" void aln_pairset_launch_gather(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
+                                          const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
+                                          hipStream_t s);
+
+struct aln_pairset {
+    DevCtx *ctx = nullptr;            // one device: the context's first (as a staged batch)
+    Slot *slot = nullptr;             // private slot; slot->seqs holds every pair's residues, packed in pair order
+    size_t n = 0;
+    std::vector<uint64_t> q_off, q_len, t_off, t_len;      // offsets into slot->seqs
+    // held state of the last run: entry k = pair active[k]
+    bool held = false;
+    size_t n_held = 0;
+    uint32_t rows = 0, cols = 0, blank = 0;
+    std::vector<int64_t> entry_of;    // pair -> held entry, -1: not in the last run
+    std::vector<PairsetHeld> info;    // host copy of the held table
+    DevBuf matrices, held_res, held_tb, held_info, list, out_off, counts, packed_res, packed_tb;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double ms[4] = {0, 0, 0, 0};      // last run: fill kernels, traceback kernels; last fetch: its kernels; last call: wall time of its copies
+    uint64_t bytes[2] = {0, 0};       // last call: host -> device, device -> host
+};
+
+extern "C" void aln_pairset_destroy(aln_pairset *ps)
+{
+    if (!ps) return;
+    (void)hipSetDevice(ps->ctx->device);
+    if (ps->slot && ps->slot->stream) (void)hipStreamSynchronize(ps->slot->stream);
+    for (hipEvent_t e : ps->ev) if (e) (void)hipEventDestroy(e);
+    DevBuf *d[] = {&ps->matrices, &ps->held_res, &ps->held_tb, &ps->held_info, &ps->list, &ps->out_off, &ps->counts, &ps->packed_res, &ps->packed_tb};
+    for (DevBuf *b : d) dev_free(*b);
+    slot_destroy(ps->slot);
+    delete ps;
+}
+
+extern "C" aln_pairset *aln_pairset_create(aln_ctx *ctx, const uint8_t *seqs, const uint64_t *q_off, const uint64_t *q_len,
+                                           const uint64_t *t_off, const uint64_t *t_len, size_t n_pairs, int *status)
+{
+    int st = ALN_OK;
+    aln_pairset *ps = nullptr;
+    uint64_t total = 0;
+    if (!ctx || (n_pairs && (!q_off || !q_len || !t_off || !t_len))) { g_err = "null argument"; st = ALN_ERR_INVALID_ARGUMENT; }
+    else if (n_pairs > 0xFFFFFFF0ull) { g_err = "too many pairs"; st = ALN_ERR_UNSUPPORTED; }
+    else {
+        for (size_t i = 0; i < n_pairs && st == ALN_OK; ++i) {
+            if (q_len[i] > 0x7FFFFFF0ull || t_len[i] > 0x7FFFFFF0ull) { g_err = "sequence too long"; st = ALN_ERR_UNSUPPORTED; }
+            total += q_len[i] + t_len[i];
+        }
+        if (st == ALN_OK && total && !seqs) { g_err = "null argument"; st = ALN_ERR_INVALID_ARGUMENT; }
+    }
+    if (st == ALN_OK) {
+        ps = new aln_pairset();
+        ps->ctx = ctx->devs[0];
+        ps->n = n_pairs;
+        ps->slot = new Slot();
+        ps->slot->pooled = false;
+        ps->q_off.resize(n_pairs); ps->t_off.resize(n_pairs);
+        ps->q_len.assign(q_len, q_len + n_pairs); ps->t_len.assign(t_len, t_len + n_pairs);
+        ps->entry_of.assign(n_pairs, -1);
+        // the residues, packed in pair order (query, then target): the buffer never moves afterwards
+        std::vector<uint8_t> packed(total);
+        uint64_t pos = 0;
+        for (size_t i = 0; i < n_pairs; ++i) {
+            ps->q_off[i] = pos; if (q_len[i]) memcpy(packed.data() + pos, seqs + q_off[i], q_len[i]); pos += q_len[i];
+            ps->t_off[i] = pos; if (t_len[i]) memcpy(packed.data() + pos, seqs + t_off[i], t_len[i]); pos += t_len[i];
+        }
+        hipError_t e = hipSetDevice(ps->ctx->device);
+        if (e != hipSuccess) st = fail(e, "hipSetDevice");
+        if (st == ALN_OK) st = dev_ensure(ps->slot->seqs, total + 256, false);
+        if (st == ALN_OK) st = slot_init(*ps->slot);
+        for (int i = 0; i < 4 && st == ALN_OK; ++i) { e = hipEventCreate(&ps->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
+        if (st == ALN_OK && total) {
+            e = hipMemcpyAsync(ps->slot->seqs.p, packed.data(), total, hipMemcpyHostToDevice, ps->slot->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ps->slot->stream);
+            if (e != hipSuccess) st = fail(e, "upload");
+        }
+        ps->bytes[0] = total;
+        if (st != ALN_OK) { aln_pairset_destroy(ps); ps = nullptr; }
+    }
+    if (status) *status = st;
+    return ps;
+}
+
+// the checks of a run that need no device
+static int pairset_check_run(const aln_pairset *ps, const aln_params *p, const double *matrices, const uint32_t *active, size_t n_active,
+                             const aln_pair_result *results)
+{
+    if (!p) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (p->semantics < ALN_CORE_GLOBAL || p->semantics > ALN_PWM_LOCAL) { g_err = "bad semantics"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (p->semantics != ALN_CORE_GLOBAL && p->semantics != ALN_CORE_LOCAL) { g_err = "a pair set runs the core semantics only"; return ALN_ERR_UNSUPPORTED; }
+    if (p->heuristics_present) return ALN_ERR_UNNECESSARY_ARGUMENT;
+    if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (p->matrix) { g_err = "a pair set takes its matrices per pair: params->matrix must be null"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (p->rows == 0 || p->cols == 0 || (uint64_t)p->rows * p->cols > ALN_PAIRSET_MAX_ENTRIES) {
+        g_err = "per-pair matrices hold 1 .. 1024 entries";
+        return ALN_ERR_INVALID_ARGUMENT;
+    }
+    if (n_active && (!matrices || !active || !results)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_active > ps->n) { g_err = "more active entries than pairs"; return ALN_ERR_INVALID_ARGUMENT; }
+    std::vector<char> seen(ps->n, 0);
+    for (size_t k = 0; k < n_active; ++k) {
+        if (active[k] >= ps->n || seen[active[k]]) { g_err = "active: an entry is out of range or listed twice"; return ALN_ERR_INVALID_ARGUMENT; }
+        seen[active[k]] = 1;
+    }
+    return ALN_OK;
+}
+
+extern "C" int aln_pairset_run(aln_pairset *ps, const aln_params *params, const double *matrices, const uint32_t *active, size_t n_active,
+                               aln_pair_result *results)
+{
+    int st = pairset_check_run(ps, params, matrices, active, n_active, results);
+    if (st != ALN_OK) return st;
+    HIPCHK(hipSetDevice(ps->ctx->device));
+    Slot &s = *ps->slot;
+    hipStream_t q = s.stream;
+    HIPCHK(hipStreamSynchronize(q));
+    ps->held = false;
+    ps->n_held = 0;
+    std::fill(ps->entry_of.begin(), ps->entry_of.end(), (int64_t)-1);
+    for (double &v : ps->ms) v = 0;
+    ps->bytes[0] = ps->bytes[1] = 0;
+    if (n_active == 0) { ps->held = true; ps->rows = params->rows; ps->cols = params->cols; ps->blank = params->blank_code; ps->info.clear(); return ALN_OK; }
+
+    Call c;
+    c.p = *params;
+    c.p.outputs = ALN_OUT_SCORE | ALN_OUT_TRACEBACK;
+    c.core = true;
+    c.semantics = params->semantics;
+    c.rows = params->rows; c.cols = params->cols;
+    c.outs = c.p.outputs;
+    c.is_int = false; c.fast = false; c.all_int = false;
+    const size_t e = (size_t)c.rows * c.cols;
+
+    std::vector<uint64_t> qo(n_active), ql(n_active), to(n_active), tl(n_active);
+    ps->info.assign(n_active, PairsetHeld{});
+    uint64_t tb_total = 0;
+    for (size_t k = 0; k < n_active; ++k) {
+        const uint32_t i = active[k];
+        qo[k] = ps->q_off[i]; ql[k] = ps->q_len[i]; to[k] = ps->t_off[i]; tl[k] = ps->t_len[i];
+        ps->info[k].N = (uint32_t)ql[k]; ps->info[k].M = (uint32_t)tl[k]; ps->info[k].tb_off = tb_total;
+        tb_total += 2ull * (ql[k] + tl[k] + 2);      // the chunks' own layout (chunk_plan), chunk after chunk
+    }
+    std::vector<std::pair<size_t, size_t>> ranges;
+    make_chunks(c, ql.data(), tl.data(), n_active, 1, ranges);
+
+    // every buffer of the run that does not depend on a chunk's plan
+    if ((st = dev_ensure(ps->matrices, 8ull * e * n_active, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->held_res, sizeof(aln_pair_result) * n_active, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->held_tb, tb_total, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->held_info, sizeof(PairsetHeld) * n_active, false)) != ALN_OK) return st;
+    c.pair_matrices = ps->matrices.as<double>();
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemcpyAsync(ps->matrices.p, matrices, 8ull * e * n_active, hipMemcpyHostToDevice, q));
+    HIPCHK(hipMemcpyAsync(ps->held_info.p, ps->info.data(), sizeof(PairsetHeld) * n_active, hipMemcpyHostToDevice, q));
+    ps->bytes[0] = 8ull * e * n_active + sizeof(PairsetHeld) * n_active;
+
+    // chunk after chunk on the one slot: the plan of chunk j + 1 is made while chunk j runs; its tables go through the slot's pinned
+    // staging, so they wait for chunk j
+    Chunk k;
+    bool timed = false;
+    auto collect = [&]() {
+        if (timed) { ps->ms[0] += ev_ms(ps->ev[0], ps->ev[1]); ps->ms[1] += ev_ms(ps->ev[1], ps->ev[2]); timed = false; }
+    };
+    for (size_t j = 0; j < ranges.size(); ++j) {
+        const size_t first = ranges[j].first, n = ranges[j].second;
+        k.reset();
+        if ((st = chunk_plan(ps->ctx, c, qo.data(), ql.data(), to.data(), tl.data(), first, n, ranges.size() == 1, k, ranges.size() > 4)) != ALN_OK) break;
+        for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[first + i]; k.descs[i].t_off = to[first + i]; }      // resident residues
+        k.seq_direct = true;
+        HIPCHK(hipStreamSynchronize(q));
+        collect();
+        if ((st = slot_ensure(s, c, k)) != ALN_OK) break;
+        uint8_t *m = s.h_meta.as<uint8_t>();
+        memcpy(m, k.descs.data(), n * sizeof(PairDesc));
+        HIPCHK(hipMemcpyAsync(s.descs.p, m, n * sizeof(PairDesc), hipMemcpyHostToDevice, q));
+        if (!k.order.empty()) {
+            memcpy(m + n * sizeof(PairDesc), k.order.data(), k.order.size() * 4);
+            HIPCHK(hipMemcpyAsync(s.order.p, m + n * sizeof(PairDesc), k.order.size() * 4, hipMemcpyHostToDevice, q));
+        }
+        ps->bytes[0] += n * (sizeof(PairDesc) + 4);
+        if ((st = slot_launch(ps->ctx, s, c, k, q, ps->ev, nullptr)) != ALN_OK) break;
+        timed = true;
+        HIPCHK(hipMemcpyAsync(ps->held_res.as<aln_pair_result>() + first, s.results.p, n * sizeof(aln_pair_result), hipMemcpyDeviceToDevice, q));
+        if (k.tb_bytes) HIPCHK(hipMemcpyAsync(ps->held_tb.as<uint8_t>() + ps->info[first].tb_off, s.tb.p, k.tb_bytes, hipMemcpyDeviceToDevice, q));
+    }
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    HIPCHK(hipMemcpyAsync(results, ps->held_res.p, sizeof(aln_pair_result) * n_active, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    collect();
+    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->bytes[1] = sizeof(aln_pair_result) * n_active;
+    for (size_t kk = 0; kk < n_active; ++kk) ps->entry_of[active[kk]] = (int64_t)kk;
+    ps->n_held = n_active;
+    ps->rows = c.rows; ps->cols = c.cols; ps->blank = params->blank_code;
+    ps->held = true;
+    return ALN_OK;
+}
+
+// `which` -> held entries (uploaded into ps->list); INVALID_ARGUMENT for a pair that was not in the last run
+static int pairset_list(aln_pairset *ps, const uint32_t *which, size_t n, std::vector<uint32_t> &entries)
+{
+    if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ps->held) { g_err = "no held run"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && !which) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    entries.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+        if (which[k] >= ps->n || ps->entry_of[which[k]] < 0) { g_err = "a listed pair was not in the last run"; return ALN_ERR_INVALID_ARGUMENT; }
+        entries[k] = (uint32_t)ps->entry_of[which[k]];
+    }
+    return ALN_OK;
+}
+
+extern "C" int aln_pairset_frequencies(aln_pairset *ps, const uint32_t *which, size_t n, uint32_t *counts)
+{
+    std::vector<uint32_t> entries;
+    int st = pairset_list(ps, which, n, entries);
+    if (st != ALN_OK) return st;
+    if (n && !counts) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return ALN_OK;
+    HIPCHK(hipSetDevice(ps->ctx->device));
+    hipStream_t q = ps->slot->stream;
+    const uint64_t cells = (uint64_t)ps->rows * ps->cols;
+    if ((st = dev_ensure(ps->list, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->counts, 4ull * cells * n, false)) != ALN_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemcpyAsync(ps->list.p, entries.data(), 4ull * n, hipMemcpyHostToDevice, q));
+    HIPCHK(hipEventRecord(ps->ev[0], q));
+    aln_pairset_launch_freq(ps->held_info.as<PairsetHeld>(), ps->held_res.as<aln_pair_result>(), ps->held_tb.as<uint8_t>(), ps->list.as<uint32_t>(),
+                            (uint32_t)n, (uint32_t)ps->n_held, ps->rows, ps->cols, ps->blank, ps->counts.as<uint32_t>(), q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ps->ev[1], q));
+    HIPCHK(hipMemcpyAsync(counts, ps->counts.p, 4ull * cells * n, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    ps->ms[2] = ev_ms(ps->ev[0], ps->ev[1]);
+    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->bytes[0] = 4ull * n; ps->bytes[1] = 4ull * cells * n;
+    return ALN_OK;
+}
+
+extern "C" int aln_pairset_strings(aln_pairset *ps, const uint32_t *which, size_t n, aln_pair_result *results, uint8_t *tb_buf,
+                                   const uint64_t *tb_off)
+{
+    std::vector<uint32_t> entries;
+    int st = pairset_list(ps, which, n, entries);
+    if (st != ALN_OK) return st;
+    if (n && (!results || (tb_buf && !tb_off))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return ALN_OK;
+    HIPCHK(hipSetDevice(ps->ctx->device));
+    hipStream_t q = ps->slot->stream;
+    // packed for the download in the documented cumulative layout; the caller's own offsets are served from it
+    std::vector<uint64_t> off(n);
+    uint64_t total = 0;
+    for (size_t k = 0; k < n; ++k) { off[k] = total; total += 2ull * ((uint64_t)ps->info[entries[k]].N + ps->info[entries[k]].M + 2); }
+    const bool want = tb_buf != nullptr;
+    bool direct = want;
+    for (size_t k = 0; k < n && direct; ++k) direct = tb_off[k] >= tb_off[0] && tb_off[k] - tb_off[0] == off[k];
+    if ((st = dev_ensure(ps->list, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->out_off, 8ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->packed_res, sizeof(aln_pair_result) * n, false)) != ALN_OK) return st;
+    if (want && (st = dev_ensure(ps->packed_tb, total, false)) != ALN_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemcpyAsync(ps->list.p, entries.data(), 4ull * n, hipMemcpyHostToDevice, q));
+    HIPCHK(hipMemcpyAsync(ps->out_off.p, off.data(), 8ull * n, hipMemcpyHostToDevice, q));
+    HIPCHK(hipEventRecord(ps->ev[0], q));
+    aln_pairset_launch_gather(ps->held_info.as<PairsetHeld>(), ps->held_res.as<aln_pair_result>(), ps->held_tb.as<uint8_t>(), ps->list.as<uint32_t>(),
+                              ps->out_off.as<uint64_t>(), (uint32_t)n, (uint32_t)ps->n_held, ps->packed_res.as<aln_pair_result>(),
+                              want ? ps->packed_tb.as<uint8_t>() : nullptr, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ps->ev[1], q));
+    HIPCHK(hipMemcpyAsync(results, ps->packed_res.p, sizeof(aln_pair_result) * n, hipMemcpyDeviceToHost, q));
+    std::vector<uint8_t> bounce;
+    if (want) {
+        if (direct) HIPCHK(hipMemcpyAsync(tb_buf + tb_off[0], ps->packed_tb.p, total, hipMemcpyDeviceToHost, q));
+        else { bounce.resize(total); HIPCHK(hipMemcpyAsync(bounce.data(), ps->packed_tb.p, total, hipMemcpyDeviceToHost, q)); }
+    }
+    HIPCHK(hipStreamSynchronize(q));
+    if (want && !direct)
+        for (size_t k = 0; k < n; ++k) {
+            if (results[k].status != ALN_OK) continue;
+            const uint64_t cap = (uint64_t)ps->info[entries[k]].N + ps->info[entries[k]].M + 2;
+            const uint64_t len = std::min<uint64_t>(results[k].aln_len, cap);
+            memcpy(tb_buf + tb_off[k], bounce.data() + off[k], len);
+            memcpy(tb_buf + tb_off[k] + cap, bounce.data() + off[k] + cap, len);
+        }
+    ps->ms[2] = ev_ms(ps->ev[0], ps->ev[1]);
+    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->bytes[0] = 12ull * n; ps->bytes[1] = sizeof(aln_pair_result) * n + (want ? total : 0);
+    return ALN_OK;
+}
+
+extern "C" int aln_pairset_stats(const aln_pairset *ps, double *ms, uint64_t *bytes)
+{
+    if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ms) for (int i = 0; i < 4; ++i) ms[i] = ps->ms[i];
+    if (bytes) { bytes[0] = ps->bytes[0]; bytes[1] = ps->bytes[1]; }
     return ALN_OK;
 }

@@ -1683,15 +1683,22 @@ __global__ __launch_bounds__(256, 3) void aln_fill_kernel(FillArgs a)
 
 // The real-valued batch (core semantics, no H dump): the same kernel around the lean f64 strip alone -- without run_strip's all-options
 // loop in it the kernel fits 128 registers, four waves per SIMD instead of three (the f64 cell chain is latency-bound per wave).
-template <int SEM>
+// PERPAIR (aln_pairset_run): every pair of the queue has a matrix of its own, pair p's at a.matrix + p * rows * cols.  Each of the four
+// waves owns rows * cols doubles of LDS (at most ALN_PAIRSET_MAX_ENTRIES: 32 KiB per workgroup, four workgroups per CU) and its 64
+// lanes reload them when the wave takes a pair; the region is private to the wave, so nothing is shared and nothing waits.
+template <int SEM, bool PERPAIR = false>
 __global__ __launch_bounds__(256, 4) void aln_fill_f64_kernel(FillArgs a)
 {
     using SC = double;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     SC *S = reinterpret_cast<SC *>(smem);
     const SC *gm = reinterpret_cast<const SC *>(a.matrix);
-    for (uint32_t i = threadIdx.x; i < a.rows * a.cols; i += blockDim.x) S[i] = gm[i];
-    __syncthreads();
+    const uint32_t entries = a.rows * a.cols;
+    if constexpr (PERPAIR) S += (threadIdx.x >> 6) * ((entries + 1u) & ~1u);
+    else {
+        for (uint32_t i = threadIdx.x; i < entries; i += blockDim.x) S[i] = gm[i];
+        __syncthreads();
+    }
 
     Wave<SC> w;
     w.lane = threadIdx.x & 63;
@@ -1714,7 +1721,16 @@ __global__ __launch_bounds__(256, 4) void aln_fill_f64_kernel(FillArgs a)
         aln_pair_result &res = a.results[pair];
         if (desc.status != ALN_OK) skip_invalid(res, desc.status, w.lane);
         else if (!pair_codes_ok(a.seqs, desc, a.rows, a.cols, a.pwm != 0, w.lane)) skip_invalid(res, ALN_ERR_CODE_OUT_OF_RANGE, w.lane);
-        else do_pair<SC, SEM, true>(w, a, desc, res);
+        else {
+            if constexpr (PERPAIR) {
+                // the wave's own matrix: lanes of one wave only, so the stores are in place once the wave has passed the fence
+                const SC *pm = gm + (size_t)pair * entries;
+                for (uint32_t i = (uint32_t)w.lane; i < entries; i += 64u) S[i] = pm[i];
+                __threadfence_block();
+                __builtin_amdgcn_wave_barrier();
+            }
+            do_pair<SC, SEM, true>(w, a, desc, res);
+        }
         pair_done(a, w.lane, pair, true);
     }
 }
@@ -3192,7 +3208,9 @@ extern "C" void aln_launch_fill(const FillArgs *a, int is_int, int fast, uint32_
         }
     } else {
         const bool lean = a->hmat == nullptr && !a->f64_old;
-        if (lean && a->semantics == ALN_CORE_GLOBAL) hipLaunchKernelGGL((aln_fill_f64_kernel<ALN_CORE_GLOBAL>), g, b, lds_bytes, s, *a);
+        if (lean && a->pair_matrices && a->semantics == ALN_CORE_GLOBAL) hipLaunchKernelGGL((aln_fill_f64_kernel<ALN_CORE_GLOBAL, true>), g, b, lds_bytes, s, *a);
+        else if (lean && a->pair_matrices) hipLaunchKernelGGL((aln_fill_f64_kernel<ALN_CORE_LOCAL, true>), g, b, lds_bytes, s, *a);
+        else if (lean && a->semantics == ALN_CORE_GLOBAL) hipLaunchKernelGGL((aln_fill_f64_kernel<ALN_CORE_GLOBAL>), g, b, lds_bytes, s, *a);
         else if (lean) hipLaunchKernelGGL((aln_fill_f64_kernel<ALN_CORE_LOCAL>), g, b, lds_bytes, s, *a);
         else if (a->semantics == ALN_CORE_GLOBAL) ALN_LAUNCH(double, ALN_CORE_GLOBAL);
         else ALN_LAUNCH(double, ALN_CORE_LOCAL);

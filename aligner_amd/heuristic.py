@@ -125,6 +125,136 @@ class HeuristicAligner(_HeuristicLoop):
                           params, device)
 
 
+def _wrong_matrix_panic():
+    return ReferencePanic(-1, "called `Result::unwrap()` on an `Err` value: WrongMatrixSpecified")
+
+
+def _transform_batch(how, matrices, params_list):
+    """transform_matrix for a list of (matrix, Heuristics): a list of matrices, a ReferencePanic in the place of a matrix the
+    reference would panic on."""
+    if how == "numpy":
+        out = []
+        for m, h in zip(matrices, params_list):
+            try:
+                out.append(_transform_or_panic(m, h))
+            except ReferencePanic as e:
+                out.append(e)
+        return out
+    if how != "native":
+        raise ValueError("transform: 'numpy' or 'native'")
+    if not len(matrices):
+        return []
+    from . import _ffi
+    from .pairset import transform_matrices
+    res, status = transform_matrices(np.asarray(matrices, dtype=np.float64),
+                                     np.asarray([np.asarray(h.frequencies, dtype=np.float64) for h in params_list]),
+                                     np.asarray([h.kd for h in params_list], dtype=np.float64),
+                                     np.asarray([h.r_squared for h in params_list], dtype=np.float64))
+    return [res[k] if status[k] == 0 else _wrong_matrix_panic() for k in range(len(status))]
+
+
+def align_many(pairs, del_, ext, matrix, heuristics, alphabet=None, transform="numpy", device=None, errors="raise", backend=None):
+    """HeuristicAligner.from_seqs(q, t, alphabet).perform_alignment(del_, ext, matrix, heuristics) for every (q, t) of `pairs`, in
+    lock step on one resident pair set (aligner_amd.pairset.PairSet): every iteration is ONE run over the pairs that are still
+    going, each under its own matrix; the pairs whose f did not grow finish and have their strings fetched, the others have their
+    frequency matrices counted on the device and transformed on the host.
+
+    heuristics: one Heuristics, or one per pair.  transform: "numpy" (transform_matrix per pair: the single-pair class's bits by
+    construction) or "native" (aln_transform_matrices, the same order of operations in the library's host code).  Returns the
+    AlignmentResults in input order, `matrix` being the matrix of the pair's last run.  A pair on which the reference panics
+    (empty sequence, code outside the matrix, no positive cell, WrongMatrixSpecified) gives the same ReferencePanic: raised for the
+    first such pair (errors="raise") or returned in its place (errors="return").  The matrix must be volume x volume of the
+    alphabet (the shape of the frequency matrices) and hold at most 1024 entries.
+    backend: a factory (pairs, device) -> object with run / frequencies / strings / close (tests)."""
+    from . import _ffi
+    from . import runtime
+    from .alignment import Alignment, AlignmentResult
+    from .enums import Protein
+    if alphabet is None:
+        alphabet = Protein
+    if heuristics is None:
+        raise AlignerError(ErrorKind.MissingArgument)                           # heuristic/mod.rs:42-45
+    if errors not in ("raise", "return"):
+        raise ValueError("errors: 'raise' or 'return'")
+    if transform not in ("numpy", "native"):
+        raise ValueError("transform: 'numpy' or 'native'")
+    pairs = [(np.array(q, dtype=np.uint8), np.array(t, dtype=np.uint8)) for q, t in pairs]
+    n = len(pairs)
+    m = np.asarray(matrix, dtype=np.float64)
+    v = alphabet.volume()
+    if m.shape != (v, v):
+        raise ValueError("align_many: the matrix must be %d x %d (the alphabet's frequency matrix)" % (v, v))
+    hs = list(heuristics) if isinstance(heuristics, (list, tuple)) else [heuristics] * n
+    if len(hs) != n:
+        raise ValueError("heuristics: one, or one per pair")
+    if any(h is None for h in hs):
+        raise AlignerError(ErrorKind.MissingArgument)
+    params = []
+    for h in hs:
+        r2 = h.r_squared
+        if abs(r2 - 0.0) < np.finfo(np.float64).eps:                            # :47-49
+            r2 = float(m.shape[0] * m.shape[1])
+        params.append(Heuristics(h.kd, r2, h.frequencies))
+    out = [None] * n
+    if n == 0:
+        return out
+    if backend is None:
+        from .pairset import PairSet
+        backend = PairSet
+    blank = alphabet.blank()
+    active = list(range(n))
+    max_f = np.zeros(n, dtype=np.float64)
+    current = dict(zip(active, _transform_batch(transform, [m] * n, params)))
+    ps = backend(pairs, device)
+    try:
+        while active:
+            going = []
+            for i in active:                                                    # `.unwrap()` at heuristic/mod.rs:53, :71
+                if isinstance(current[i], ReferencePanic):
+                    out[i] = current.pop(i)
+                else:
+                    going.append(i)
+            active = going
+            if not active:
+                break
+            res = ps.run(_ffi.CORE_LOCAL, del_, ext, np.asarray([current[i] for i in active], dtype=np.float64), active, blank=blank)
+            done, more = [], []
+            for k, i in enumerate(active):
+                st = int(res["status"][k])
+                if st != _ffi.OK:
+                    try:
+                        runtime.raise_for_status(st, "aln_pairset_run")
+                    except ReferencePanic as e:
+                        out[i] = e
+                    current.pop(i)
+                elif res["f"][k] > max_f[i]:                                    # :64-72
+                    max_f[i] = res["f"][k]
+                    more.append(i)
+                else:
+                    done.append(i)
+            if done:
+                summ, strs = ps.strings(done)
+                for k, i in enumerate(done):
+                    r = summ[k]
+                    coords = ((int(r["start_x"]) + 1, int(r["end_x"]) + 1), (int(r["start_y"]) + 1, int(r["end_y"]) + 1))
+                    aln = Alignment(alphabet, strs[k][0], strs[k][1], coords, float(r["f"]))
+                    out[i] = AlignmentResult(aln, matrix=current.pop(i), score=float(r["score"]),      # :73-75
+                                             summary={name: r[name].item() for name in r.dtype.names})
+            if more:
+                counts = ps.frequencies(more)
+                new = _transform_batch(transform, [counts[k].astype(np.float64) for k in range(len(more))], [params[i] for i in more])
+                for i, mat in zip(more, new):
+                    current[i] = mat
+            active = more
+    finally:
+        ps.close()
+    if errors == "raise":
+        for r in out:
+            if isinstance(r, ReferencePanic):
+                raise r
+    return out
+
+
 class HeuristicPWMAligner(_HeuristicLoop):
     """heuristic/mod.rs:80-140."""
 

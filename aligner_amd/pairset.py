@@ -1,0 +1,119 @@
+"""A set of pairs resident in HBM, aligned again and again under per-pair matrices (aln_pairset_*, include/aligner_hip.h).
+
+The device-resident form of the loop of HeuristicAligner (aligner-core/src/heuristic/mod.rs:36-78) for many pairs at once:
+`run` aligns the listed pairs, each under a real-valued matrix of its own, and leaves the walked strings on the device;
+`frequencies` counts Alignment::get_frequency_matrix (alignment.rs:13-23) there for the pairs that go on, `strings` fetches
+the pairs that are done.  heuristic.align_many drives it.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi
+from . import runtime
+from .batch import RESULT_DTYPE, PairBatch
+
+
+class PairSet:
+    def __init__(self, pairs, device=None):
+        self.lib = _ffi.load()
+        self.batch = pairs if isinstance(pairs, PairBatch) else PairBatch.from_pairs(pairs)
+        b = self.batch
+        st = C.c_int(0)
+        self.handle = self.lib.aln_pairset_create(runtime.context(device), b.seqs.ctypes.data, b.q_off.ctypes.data, b.q_len.ctypes.data,
+                                                  b.t_off.ctypes.data, b.t_len.ctypes.data, len(b), C.byref(st))
+        if not self.handle:
+            runtime.raise_for_status(st.value, "aln_pairset_create")
+            raise RuntimeError("aln_pairset_create returned NULL")
+        self.shape = None
+
+    def __len__(self):
+        return len(self.batch)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.handle:
+            self.lib.aln_pairset_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, semantics, del_, ext, matrices, active, blank=98, force_serial=False, max_passes=0):
+        """matrices: (len(active), rows, cols) f64, entry k scores pair active[k].  Returns the summaries (RESULT_DTYPE), entry k
+        pair active[k]'s; a failed pair carries its status and leaves the others untouched."""
+        m = np.ascontiguousarray(matrices, dtype=np.float64)
+        act = np.ascontiguousarray(active, dtype=np.uint32)
+        if m.ndim != 3 or m.shape[0] != len(act):
+            raise ValueError("matrices: one (rows, cols) matrix per active pair")
+        p = _ffi.Params(int(semantics), 0, float(del_), float(ext), None, m.shape[1], m.shape[2], m.shape[2], 0, int(blank), 0,
+                        int(bool(force_serial)), 0, int(max_passes))
+        res = np.zeros(len(act), dtype=RESULT_DTYPE)
+        st = self.lib.aln_pairset_run(self.handle, C.byref(p), m.ctypes.data, act.ctypes.data, len(act), res.ctypes.data)
+        runtime.raise_for_status(st, "aln_pairset_run")
+        self.shape = (m.shape[1], m.shape[2])
+        return res
+
+    def frequencies(self, which):
+        """uint32 (len(which), rows, cols): the frequency matrix of every listed pair of the last run."""
+        w = np.ascontiguousarray(which, dtype=np.uint32)
+        rows, cols = self.shape if self.shape else (0, 0)
+        out = np.zeros((len(w), rows, cols), dtype=np.uint32)
+        st = self.lib.aln_pairset_frequencies(self.handle, w.ctypes.data, len(w), out.ctypes.data)
+        runtime.raise_for_status(st, "aln_pairset_frequencies")
+        return out
+
+    def strings(self, which):
+        """(summaries, [(aligned query, aligned target)]) of the listed pairs of the last run (empty strings for a failed pair)."""
+        w = np.ascontiguousarray(which, dtype=np.uint32)
+        b = self.batch
+        cap = (b.q_len[w] + b.t_len[w] + np.uint64(2)).astype(np.uint64) if len(w) else np.zeros(0, dtype=np.uint64)
+        off = np.zeros(len(w), dtype=np.uint64)
+        if len(w) > 1:
+            off[1:] = np.cumsum(2 * cap)[:-1]
+        tb = np.zeros(int((2 * cap).sum()), dtype=np.uint8)
+        res = np.zeros(len(w), dtype=RESULT_DTYPE)
+        st = self.lib.aln_pairset_strings(self.handle, w.ctypes.data, len(w), res.ctypes.data, tb.ctypes.data, off.ctypes.data)
+        runtime.raise_for_status(st, "aln_pairset_strings")
+        out = []
+        for k in range(len(w)):
+            n = int(res["aln_len"][k]) if res["status"][k] == _ffi.OK else 0
+            o, c = int(off[k]), int(cap[k])
+            out.append((tb[o:o + n].copy(), tb[o + c:o + c + n].copy()))
+        return res, out
+
+    def stats(self):
+        ms, by = (C.c_double * 4)(), (C.c_uint64 * 2)()
+        runtime.raise_for_status(self.lib.aln_pairset_stats(self.handle, ms, by), "aln_pairset_stats")
+        return dict(fill_ms=ms[0], traceback_ms=ms[1], fetch_kernel_ms=ms[2], wall_ms=ms[3], bytes_up=int(by[0]), bytes_down=int(by[1]))
+
+
+def transform_matrices(matrices, frequencies, kd, r_squared):
+    """aln_transform_matrices: transform_matrix (heuristic.py) for n matrices at once, in the library's host code -- the same bits as
+    the numpy mirror (aligner_amd/csrc/aln_transform_rules.h).  matrices (n, rows, cols), frequencies (n, rows), kd and r_squared
+    scalars or (n,).  Returns (out (n, rows, cols), status (n,) int32: 0, or _ffi.TRANSFORM_NO_ROOT = WrongMatrixSpecified)."""
+    lib = _ffi.load()
+    m = np.ascontiguousarray(matrices, dtype=np.float64)
+    if m.ndim != 3:
+        raise ValueError("matrices: (n, rows, cols)")
+    n, rows, cols = m.shape
+    fr = np.ascontiguousarray(frequencies, dtype=np.float64)
+    if fr.shape != (n, rows):
+        raise ValueError("frequencies: (n, rows)")
+    kd = np.ascontiguousarray(np.broadcast_to(np.asarray(kd, dtype=np.float64), (n,)))
+    r2 = np.ascontiguousarray(np.broadcast_to(np.asarray(r_squared, dtype=np.float64), (n,)))
+    out = np.zeros_like(m)
+    status = np.zeros(n, dtype=np.int32)
+    st = lib.aln_transform_matrices(n, rows, cols, m.ctypes.data, fr.ctypes.data, kd.ctypes.data, r2.ctypes.data, out.ctypes.data,
+                                    status.ctypes.data)
+    if st != _ffi.OK:
+        raise ValueError("aln_transform_matrices: %s" % _ffi.STATUS_NAMES.get(st, st))
+    return out, status

@@ -240,6 +240,50 @@ int aln_shuffle_scores(aln_ctx *ctx, const aln_params *params, const aln_shuffle
 int aln_shuffle_targets(aln_ctx *ctx, const aln_shuffle_spec *spec, const uint8_t *seqs, const uint64_t *t_off,
                         const uint64_t *t_len, size_t n_pairs, uint8_t *out, const uint64_t *out_off);
 
+/* ---- resident pair set (the loop of HeuristicAligner, aligner-core/src/heuristic/mod.rs:36-78, for many pairs in lock step): the
+ * residues of n_pairs pairs are uploaded once (one device: the context's first; layout of aln_align_batch), and every run aligns a
+ * list of them, each under a real-valued matrix of its own, on the f64 kernels.
+ * run: params->rows / cols give the shape shared by all matrices, at most ALN_PAIRSET_MAX_ENTRIES entries (each wave of the fill
+ * kernel keeps its pair's matrix in LDS: 4 x 8 KiB per workgroup, four workgroups per CU); params->matrix must be NULL; del, ext,
+ * max_passes, blank_code and force_serial as elsewhere; outputs is ignored (scores and strings are always produced and held).
+ * ALN_CORE_LOCAL and ALN_CORE_GLOBAL; the legacy and PWM semantics: ALN_ERR_UNSUPPORTED.  matrices: n_active compact row-major
+ * matrices, entry k scores pair active[k]; results[k] is that pair's summary.  Per-pair failures (ALN_ERR_CODE_OUT_OF_RANGE,
+ * ALN_ERR_EMPTY_SEQUENCE, ALN_ERR_NO_POSITIVE_CELL) are that pair's status and leave the others untouched; the call returns ALN_OK.
+ * A run is cut into chunks by the cell bounds of aln_align_batch (ALN_CHUNK_CELLS overrides); a pair's bytes do not depend on the
+ * chunking, the order of `active` or the other pairs' matrices.  Summaries and walked strings of all active pairs stay on the
+ * device until the next run or destroy.  ALN_ERR_INVALID_ARGUMENT, nothing written: rows * cols outside 1 .. ALN_PAIRSET_MAX_ENTRIES,
+ * a matrix in params, an active[k] >= n_pairs or listed twice, a null pointer with a non-zero length.
+ * frequencies: counts[k * rows * cols + t * cols + q] = the columns of listed pair which[k]'s held strings that put target residue t
+ * on query residue q, neither being blank (Alignment::get_frequency_matrix, alignment.rs:13-23, the duplicated seed pair included),
+ * counted on the device in unsigned integers: exact, the same in any order.  A failed pair's counts are zero.  4 * n bytes go up,
+ * 4 * rows * cols * n come back.
+ * strings: summaries and strings of the listed pairs in the layout of aln_align_batch (pair which[k]: aligned query at tb_off[k],
+ * aligned target q_len + t_len + 2 bytes later; tb_buf optional).
+ * A which[k] that was not in the last run, a fetch without a run: ALN_ERR_INVALID_ARGUMENT, nothing written.
+ * stats: ms[0] fill kernels and ms[1] traceback kernels of the last run, ms[2] kernels of the last fetch, ms[3] wall time of the
+ * last call; bytes moved by the last call (host -> device, device -> host). ---- */
+#define ALN_PAIRSET_MAX_ENTRIES 1024u
+typedef struct aln_pairset aln_pairset;
+aln_pairset *aln_pairset_create(aln_ctx *ctx, const uint8_t *seqs, const uint64_t *q_off, const uint64_t *q_len, const uint64_t *t_off,
+                                const uint64_t *t_len, size_t n_pairs, int *status);
+int aln_pairset_run(aln_pairset *ps, const aln_params *params, const double *matrices, const uint32_t *active, size_t n_active,
+                    aln_pair_result *results);
+int aln_pairset_frequencies(aln_pairset *ps, const uint32_t *which, size_t n, uint32_t *counts);
+int aln_pairset_strings(aln_pairset *ps, const uint32_t *which, size_t n, aln_pair_result *results, uint8_t *tb_buf,
+                        const uint64_t *tb_off);
+int aln_pairset_stats(const aln_pairset *ps, double *ms /* 4 */, uint64_t *bytes /* 2 */);
+void aln_pairset_destroy(aln_pairset *ps);
+
+/* ---- transform_matrix (aligner-helpers/src/matrices/mod.rs:19-68) for n matrices at once, on the HOST (no GPU is touched): matrix i
+ * (rows x cols, compact row-major) is rescaled under frequencies[i * rows .. + rows), kd[i], r_squared[i] into matrices_out (which may
+ * be matrices_in); status[i] = 0, or ALN_TRANSFORM_NO_ROOT where the reference returns Err(WrongMatrixSpecified) (matrix i of the
+ * output is then left as it was).  Plain f64 arithmetic in the order aligner_amd/csrc/aln_transform_rules.h specifies, which is the
+ * order of the numpy mirror (aligner_amd/heuristic.py): the same bits.  rows * cols above 8192, a null pointer with n != 0:
+ * ALN_ERR_INVALID_ARGUMENT. ---- */
+#define ALN_TRANSFORM_NO_ROOT 1
+int aln_transform_matrices(size_t n, uint32_t rows, uint32_t cols, const double *matrices_in, const double *frequencies,
+                           const double *kd, const double *r_squared, double *matrices_out, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif
