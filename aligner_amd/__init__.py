@@ -14,11 +14,12 @@ from .heuristic import HeuristicAligner, HeuristicPWMAligner, get_threshold, tra
 from .legacy import SimpleAligner
 from .matrices import get_blosum62, nucleotide_matrix
 from .pwm import PWMAligner, PWMAlignment, align_windows
+from .seqset import SeqSet, all_pairs
 from .simple import Heuristics, SimpleGlobalAligner, SimpleLocalAligner
 
 __all__ = [
     "Alignment", "AlignmentResult", "BatchResult", "PairBatch", "StagedBatch", "align_batch", "DNA", "Direction",
     "Protein", "AlignerError", "DeviceError", "ErrorKind", "ReferencePanic", "SimpleAligner", "get_blosum62",
     "nucleotide_matrix", "PWMAligner", "PWMAlignment", "align_windows", "Heuristics", "SimpleGlobalAligner", "SimpleLocalAligner",
-    "HeuristicAligner", "HeuristicPWMAligner", "get_threshold", "transform_matrix",
+    "HeuristicAligner", "HeuristicPWMAligner", "get_threshold", "transform_matrix", "SeqSet", "all_pairs",
 ]

@@ -39,6 +39,8 @@ EXPORTS = [
     "aln_scan_stats", "aln_scan_hits", "aln_scan_held_list", "aln_scan_held_frequencies", "aln_scan_held_strings", "aln_shuffle_scores", "aln_shuffle_targets",
     "aln_pairset_create", "aln_pairset_run", "aln_pairset_frequencies", "aln_pairset_strings", "aln_pairset_stats", "aln_pairset_destroy",
     "aln_transform_matrices",
+    "aln_seqset_create", "aln_seqset_destroy", "aln_seqset_pairs", "aln_seqset_score", "aln_seqset_hits", "aln_seqset_held_list",
+    "aln_seqset_held_strings", "aln_seqset_stats",
 ]
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
 TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
@@ -78,6 +80,14 @@ class ShuffleSpec(C.Structure):
 
 
 assert C.sizeof(ShuffleSpec) == 24
+
+
+class SeqsetBlock(C.Structure):
+    _fields_ = [("q_first", C.c_uint64), ("q_count", C.c_uint64), ("t_first", C.c_uint64), ("t_count", C.c_uint64),
+                ("upper", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(SeqsetBlock) == 40
 
 _lib = None
 
@@ -179,6 +189,23 @@ def load():
     lib.aln_pairset_destroy.argtypes = [vp]
     lib.aln_transform_matrices.restype = i
     lib.aln_transform_matrices.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    bp = C.POINTER(SeqsetBlock)
+    lib.aln_seqset_create.restype = vp
+    lib.aln_seqset_create.argtypes = [vp, vp, u64p, u64p, C.c_size_t, C.POINTER(C.c_int)]
+    lib.aln_seqset_destroy.restype = None
+    lib.aln_seqset_destroy.argtypes = [vp]
+    lib.aln_seqset_pairs.restype = C.c_uint64
+    lib.aln_seqset_pairs.argtypes = [vp, bp]
+    lib.aln_seqset_score.restype = i
+    lib.aln_seqset_score.argtypes = [vp, C.POINTER(Params), bp, vp, vp]
+    lib.aln_seqset_hits.restype = i
+    lib.aln_seqset_hits.argtypes = [vp, C.POINTER(Params), bp, C.c_double, C.POINTER(C.c_uint64)]
+    lib.aln_seqset_held_list.restype = i
+    lib.aln_seqset_held_list.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
+    lib.aln_seqset_held_strings.restype = i
+    lib.aln_seqset_held_strings.argtypes = [vp, vp, C.c_uint64, vp, vp, u64p]
+    lib.aln_seqset_stats.restype = i
+    lib.aln_seqset_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 

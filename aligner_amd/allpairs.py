@@ -1,0 +1,51 @@
+"""python -m aligner_amd.allpairs -i x.fasta [--f-min F]: every pair i < j of a FASTA, scored on the device.
+
+The request path of the reference (aligner-web dispatcher: generate_pairs, handlers.rs:253-264) as a command: prints
+`q_head,t_head,f` per pair in generate_pairs order -- all pairs, or with --f-min only those with f >= F.  Local alignment, BLOSUM62,
+gap opening 11, extension 2 unless told otherwise.
+"""
+import argparse
+import sys
+
+from . import _ffi
+from .enums import DNA, Protein
+from .fasta import encode_records, read_fasta
+from .matrices import get_blosum62, nucleotide_matrix
+from .seqset import SeqSet
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m aligner_amd.allpairs", description=__doc__.split("\n\n")[0])
+    ap.add_argument("-i", "--input", required=True, help="FASTA with two or more records")
+    ap.add_argument("--f-min", type=float, default=None, help="print only the pairs with f >= F")
+    ap.add_argument("--del", dest="del_", type=float, default=11.0)
+    ap.add_argument("--ext", type=float, default=2.0)
+    ap.add_argument("--global", dest="global_", action="store_true", help="global instead of local alignment")
+    ap.add_argument("--dna", action="store_true", help="nucleotide records (match 5, mismatch -4)")
+    ap.add_argument("--device", type=int, default=None)
+    a = ap.parse_args(argv)
+    records = read_fasta(a.input)
+    if len(records) < 2:
+        ap.error("%s: an all-against-all run needs two or more records" % a.input)
+    alphabet = DNA if a.dna else Protein
+    matrix = nucleotide_matrix() if a.dna else get_blosum62()
+    sem = _ffi.CORE_GLOBAL if a.global_ else _ffi.CORE_LOCAL
+    heads = [r.head.decode("utf-8", "replace") for r in records]
+    out = sys.stdout
+    with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
+        if a.f_min is None:
+            f, status = ss.score(matrix, a.del_, a.ext, None, semantics=sem)
+            k = 0
+            for i in range(len(heads)):
+                for j in range(i + 1, len(heads)):
+                    out.write("%s,%s,%s\n" % (heads[i], heads[j], repr(float(f[k])) if status[k] == _ffi.OK else _ffi.STATUS_NAMES[int(status[k])]))
+                    k += 1
+        else:
+            held = ss.hits(matrix, a.del_, a.ext, a.f_min, None, semantics=sem)
+            for q, t, f in zip(held.q, held.t, held.f):
+                out.write("%s,%s,%r\n" % (heads[int(q)], heads[int(t)], float(f)))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

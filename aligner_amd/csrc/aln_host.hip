@@ -41,6 +41,7 @@
 #include "aln_device.h"
 #include "aln_plan_rules.h"
 #include "aln_scheme_rules.h"
+#include "aln_seqset_rules.h"
 #include "aln_shuffle_rules.h"
 
 #define ALN_TIMING_SLOTS 256u
@@ -2810,5 +2811,484 @@ extern "C" int aln_pairset_stats(const aln_pairset *ps, double *ms, uint64_t *by
     if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if (ms) for (int i = 0; i < 4; ++i) ms[i] = ps->ms[i];
     if (bytes) { bytes[0] = ps->bytes[0]; bytes[1] = ps->bytes[1]; }
+    return ALN_OK;
+}
+
+// ---------------------------------------------------------------- resident sequence set (aln_seqset_*, include/aligner_hip.h)
+// The request path of the reference (generate_pairs, dispatcher/handlers.rs:253-264: every pair i < j of a FASTA; blast_p_value_cmp
+// and calc: rows of one sequence table): S sequences stay in HBM and a call names a block of the S x S grid.  A call is cut into chunks
+// of consecutive pair numbers by the cell bounds of aln_align_batch (and 2^22 pairs).  The host derives a chunk's lengths from
+// aln_seqset_rules.h for chunk_plan -- routing, grid and scratch are the batch's -- while the chunk before it runs; the descriptors
+// themselves are expanded on the device (aln_seqset.hip), the staged batch's launches (slot_launch) fill them, and what a chunk leaves
+// is gathered there: f and status (score), or the pairs at or above a threshold, compacted in pair order (hits).  A held pass then
+// plans the re-fill of the hits from their list (the routes and the direction layout depend on every hit's shape, so this plan is the
+// host's, as in aln_pairset_run), runs it chunk by chunk and keeps summaries and strings on the device.
+extern "C" void aln_seqset_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t k0, const aln_seqset_block *block,
+                                         const uint64_t *seq_off, const uint32_t *seq_len, hipStream_t s);
+extern "C" void aln_seqset_launch_gather(const aln_pair_result *res, double *f, int32_t *status, uint64_t n, unsigned long long *bad,
+                                         hipStream_t s);
+extern "C" uint64_t aln_seqset_tiles(uint64_t n);
+extern "C" void aln_seqset_launch_select(const aln_pair_result *res, uint64_t n, uint64_t k0, double f_min, uint32_t *tile_count,
+                                         uint32_t *tile_off, uint32_t *count, uint64_t *hit_k, double *hit_f, hipStream_t s);
+extern "C" void aln_seqset_launch_held(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
+                                       const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
+                                       hipStream_t s);
+
+#define ALN_SEQSET_CHUNK_PAIRS (1ull << 22)        // per chunk: the pair limit of a chunk of aln_align_batch
+
+struct aln_seqset {
+    DevCtx *ctx = nullptr;            // one device: the context's first (as a staged batch)
+    Slot *slot = nullptr;             // private slot; slot->seqs holds every sequence once, packed in set order
+    size_t n = 0;
+    uint64_t total = 0;               // residues
+    std::vector<uint64_t> off;        // into slot->seqs
+    std::vector<uint32_t> len;
+    DevBuf d_off, d_len;              // the same tables on the device (the expansion reads them)
+    // a chunk's gathered output: f | status; tile counts | offsets; the chunk's hits (pair number, f); [0] hit count, [2..3] first failure
+    DevBuf fbuf, stbuf, tiles, hit_k, hit_f, misc;
+    PinBuf h_out;                     // a chunk's f | status | misc on their way to the caller
+    // held hits (aln_seqset_hits): the list lives on the host (it is what the re-fill was planned from); hit h's summary in
+    // held_res[h], its strings in held_tb at info[h].tb_off -- until the next pass on this set
+    bool held = false;
+    std::vector<uint64_t> hit_pair;
+    std::vector<double> hit_score;
+    std::vector<uint32_t> hit_q, hit_t;
+    std::vector<PairsetHeld> info;
+    DevBuf held_res, held_tb, held_info, list, out_off, packed_res, packed_tb;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double ms[4] = {0, 0, 0, 0};
+    uint64_t bytes[2] = {0, 0};
+};
+
+extern "C" void aln_seqset_destroy(aln_seqset *ss)
+{
+    if (!ss) return;
+    (void)hipSetDevice(ss->ctx->device);
+    if (ss->slot && ss->slot->stream) (void)hipStreamSynchronize(ss->slot->stream);
+    for (hipEvent_t e : ss->ev) if (e) (void)hipEventDestroy(e);
+    DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->held_res, &ss->held_tb,
+                   &ss->held_info, &ss->list, &ss->out_off, &ss->packed_res, &ss->packed_tb};
+    for (DevBuf *b : d) dev_free(*b);
+    pin_free(ss->h_out);
+    slot_destroy(ss->slot);
+    delete ss;
+}
+
+extern "C" aln_seqset *aln_seqset_create(aln_ctx *ctx, const uint8_t *seqs, const uint64_t *off, const uint64_t *len, size_t n_seqs, int *status)
+{
+    int st = ALN_OK;
+    aln_seqset *ss = nullptr;
+    uint64_t total = 0;
+    if (!ctx || (n_seqs && (!off || !len))) { g_err = "null argument"; st = ALN_ERR_INVALID_ARGUMENT; }
+    else if ((uint64_t)n_seqs >= (1ull << 32)) { g_err = "a sequence set holds fewer than 2^32 sequences"; st = ALN_ERR_INVALID_ARGUMENT; }
+    else {
+        for (size_t i = 0; i < n_seqs && st == ALN_OK; ++i) {
+            if (len[i] > 0x7FFFFFF0ull) { g_err = "sequence too long"; st = ALN_ERR_UNSUPPORTED; }
+            total += len[i];
+        }
+        if (st == ALN_OK && total && !seqs) { g_err = "null argument"; st = ALN_ERR_INVALID_ARGUMENT; }
+    }
+    if (st == ALN_OK) {
+        ss = new aln_seqset();
+        ss->ctx = ctx->devs[0];
+        ss->n = n_seqs;
+        ss->total = total;
+        ss->slot = new Slot();
+        ss->slot->pooled = false;
+        ss->off.resize(n_seqs); ss->len.resize(n_seqs);
+        // every sequence once, packed in set order: the buffer never moves afterwards
+        std::vector<uint8_t> packed(total);
+        uint64_t pos = 0;
+        for (size_t i = 0; i < n_seqs; ++i) {
+            ss->off[i] = pos; ss->len[i] = (uint32_t)len[i];
+            if (len[i]) memcpy(packed.data() + pos, seqs + off[i], len[i]);
+            pos += len[i];
+        }
+        hipError_t e = hipSetDevice(ss->ctx->device);
+        if (e != hipSuccess) st = fail(e, "hipSetDevice");
+        if (st == ALN_OK) st = dev_ensure(ss->slot->seqs, total + 256, false);
+        if (st == ALN_OK) st = dev_ensure(ss->d_off, 8ull * n_seqs, false);
+        if (st == ALN_OK) st = dev_ensure(ss->d_len, 4ull * n_seqs, false);
+        if (st == ALN_OK) st = dev_ensure(ss->misc, 256, false);
+        if (st == ALN_OK) st = slot_init(*ss->slot);
+        for (int i = 0; i < 4 && st == ALN_OK; ++i) { e = hipEventCreate(&ss->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
+        if (st == ALN_OK) {
+            hipStream_t q = ss->slot->stream;
+            e = hipSuccess;
+            if (total) e = hipMemcpyAsync(ss->slot->seqs.p, packed.data(), total, hipMemcpyHostToDevice, q);
+            if (e == hipSuccess && n_seqs) e = hipMemcpyAsync(ss->d_off.p, ss->off.data(), 8ull * n_seqs, hipMemcpyHostToDevice, q);
+            if (e == hipSuccess && n_seqs) e = hipMemcpyAsync(ss->d_len.p, ss->len.data(), 4ull * n_seqs, hipMemcpyHostToDevice, q);
+            if (e == hipSuccess) e = hipStreamSynchronize(q);
+            if (e != hipSuccess) st = fail(e, "upload");
+        }
+        ss->bytes[0] = total + 12ull * n_seqs;
+        if (st != ALN_OK) { aln_seqset_destroy(ss); ss = nullptr; }
+    }
+    if (status) *status = st;
+    return ss;
+}
+
+extern "C" uint64_t aln_seqset_pairs(const aln_seqset *ss, const aln_seqset_block *b)
+{
+    if (!ss || !b) return 0;
+    return aln_seqset_block_pairs(ss->n, *b);
+}
+
+// the checks of a pass that need no device, and the call's analysis: the longest pair of the block decides the kernels, as the longest
+// pair of a batch does (call_init)
+static int seqset_call(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, uint32_t outputs, Call &c)
+{
+    if (!ss || !params || !b) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (params->semantics == ALN_PWM_LOCAL) { g_err = "a sequence set aligns with the substitution-matrix semantics only"; return ALN_ERR_UNSUPPORTED; }
+    if (aln_seqset_block_pairs(ss->n, *b) == 0) { g_err = "block: a range beyond the set, unequal ranges of an upper block, a reserved word, or no pairs"; return ALN_ERR_INVALID_ARGUMENT; }
+    uint64_t q1 = 0, t1 = 0;
+    if (b->upper) {                                   // i < j: the two longest sequences of the square
+        for (uint64_t i = b->q_first; i < b->q_first + b->q_count; ++i) {
+            const uint64_t L = ss->len[i];
+            if (L > q1) { t1 = q1; q1 = L; } else if (L > t1) t1 = L;
+        }
+    } else {
+        for (uint64_t i = b->q_first; i < b->q_first + b->q_count; ++i) q1 = std::max<uint64_t>(q1, ss->len[i]);
+        for (uint64_t i = b->t_first; i < b->t_first + b->t_count; ++i) t1 = std::max<uint64_t>(t1, ss->len[i]);
+    }
+    aln_params p = *params;
+    p.outputs = outputs;
+    return call_init(c, &p, &q1, &t1, 1, false);
+}
+
+// cells of a block (as a double, like make_chunks) out of the length sums
+static double seqset_cells(const aln_seqset *ss, const aln_seqset_block &b)
+{
+    double sq = 0, st = 0, s2 = 0;
+    for (uint64_t i = b.q_first; i < b.q_first + b.q_count; ++i) { sq += (double)ss->len[i]; s2 += (double)ss->len[i] * (double)ss->len[i]; }
+    if (b.upper) return (sq * sq - s2) / 2.0;
+    for (uint64_t i = b.t_first; i < b.t_first + b.t_count; ++i) st += (double)ss->len[i];
+    return sq * st;
+}
+
+// the chunks of a pass: pair counts of consecutive ranges of the block's order, by the bounds of make_chunks (the pair limit holds for
+// every chunk: the queue entries are 32-bit and chunk-local).  One walk over the block, nothing kept per pair.
+static void seqset_chunks(const aln_seqset *ss, const Call &c, const aln_seqset_block &b, uint64_t pairs, std::vector<uint64_t> &counts)
+{
+    counts.clear();
+    const double total = seqset_cells(ss, b);
+    double target = std::min(1.6e10, std::max(5.0e9, total / 4.0));
+    if (!c.fast) target *= 3.0;
+    if (total / (double)pairs >= 3.0e6) target = std::max(target, std::min(6.4e10, 2.0 * 3072.0 * (total / (double)pairs)));
+    bool forced = false;
+    if (const char *e = getenv("ALN_CHUNK_CELLS")) { target = std::max(1.0, atof(e)); forced = true; }
+    if (pairs <= ALN_SEQSET_CHUNK_PAIRS && (total <= 1.5 * target || (!forced && total <= 2.0e10))) { counts.push_back(pairs); return; }
+    uint64_t q, t, n = 0;
+    aln_seqset_unrank(b, 0, &q, &t);
+    double acc = 0, done = 0;
+    for (uint64_t k = 0; k < pairs; ++k) {
+        acc += (double)ss->len[q] * (double)ss->len[t];
+        ++n;
+        aln_seqset_next(b, &q, &t);
+        // (a short tail joins the chunk before it, unless that chunk is full)
+        if (n >= ALN_SEQSET_CHUNK_PAIRS || (acc >= target && (total - done - acc >= 0.25 * target || k + 1 == pairs))) {
+            counts.push_back(n);
+            done += acc; acc = 0; n = 0;
+        }
+    }
+    if (n) counts.push_back(n);
+}
+
+// One pass over a block: every chunk expanded, filled and gathered on the set's stream.  f / status (optional): the caller's arrays.
+// select: the chunk's pairs with status ALN_OK and f >= f_min are appended to ss->hit_pair / hit_score.  *first_bad: the status of
+// the first failed pair, ALN_OK if none failed.
+static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_block &b, uint64_t pairs, double *f, int32_t *status, bool select,
+                              double f_min, int *first_bad, Chunk *plans)
+{
+    Slot &s = *ss->slot;
+    hipStream_t q = s.stream;
+    std::vector<uint64_t> counts;
+    seqset_chunks(ss, c, b, pairs, counts);
+    const bool want_out = f != nullptr || status != nullptr;
+    std::vector<uint64_t> qo, ql, to, tl;
+    uint64_t cq, ct;
+    aln_seqset_unrank(b, 0, &cq, &ct);
+    // what the chunk in flight leaves behind, collected where the pass waits for it anyway
+    uint64_t prev_k0 = 0, prev_n = 0;
+    bool timed = false;
+    int st = ALN_OK;
+    auto collect = [&]() -> int {
+        if (timed) { ss->ms[0] += ev_ms(ss->ev[0], ss->ev[1]); timed = false; }
+        if (!prev_n) return ALN_OK;
+        const uint8_t *h = ss->h_out.as<uint8_t>();
+        const uint64_t *misc = reinterpret_cast<const uint64_t *>(h);
+        if (f) memcpy(f + prev_k0, h + 256, 8 * prev_n);
+        if (status) memcpy(status + prev_k0, h + 256 + 8 * prev_n, 4 * prev_n);
+        if (*first_bad == ALN_OK && misc[1] != 0) *first_bad = (int)(misc[1] & 0xffu);
+        const uint64_t got = (uint32_t)misc[0];
+        if (select && got) {
+            const size_t at = ss->hit_pair.size();
+            ss->hit_pair.resize(at + got); ss->hit_score.resize(at + got);
+            HIPCHK(hipMemcpy(ss->hit_pair.data() + at, ss->hit_k.p, 8 * got, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(ss->hit_score.data() + at, ss->hit_f.p, 8 * got, hipMemcpyDeviceToHost));
+            ss->bytes[1] += 16 * got;
+        }
+        prev_n = 0;
+        return ALN_OK;
+    };
+    uint64_t k0 = 0;
+    for (size_t j = 0; j < counts.size(); ++j) {
+        const uint64_t n = counts[j];
+        Chunk &k = plans[j & 1];
+        qo.resize(n); ql.resize(n); to.resize(n); tl.resize(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            qo[i] = ss->off[cq]; ql[i] = ss->len[cq]; to[i] = ss->off[ct]; tl[i] = ss->len[ct];
+            aln_seqset_next(b, &cq, &ct);
+        }
+        k.reset();
+        if ((st = chunk_plan(ss->ctx, c, qo.data(), ql.data(), to.data(), tl.data(), 0, n, counts.size() == 1, k, counts.size() > 4)) != ALN_OK) break;
+        // the residues are resident: the descriptors (the device's, and the host's copy that the launches of pairs routed off the batch
+        // kernel read) carry offsets into the set's own buffer, which must not grow
+        for (uint64_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[i]; k.descs[i].t_off = to[i]; }
+        k.seq_direct = true; k.seq_lo = 0; k.seq_span = ss->total;
+        bool identity = k.n_small == n;
+        for (uint64_t i = 0; i < n && identity; ++i) identity = k.order[i] == (uint32_t)i;
+        HIPCHK(hipStreamSynchronize(q));
+        if ((st = collect()) != ALN_OK) break;
+        // the stream is idle: buffers may grow now
+        if ((st = slot_ensure(s, c, k, nullptr, true)) != ALN_OK) break;
+        if ((st = dev_ensure(ss->fbuf, 8 * n, false)) != ALN_OK) break;
+        if ((st = dev_ensure(ss->stbuf, 4 * n, false)) != ALN_OK) break;
+        if ((st = pin_ensure(ss->h_out, 256 + (want_out ? 12 * n : 0))) != ALN_OK) break;
+        const uint64_t tiles = aln_seqset_tiles(n);
+        if (select) {
+            if ((st = dev_ensure(ss->tiles, 8 * tiles, false)) != ALN_OK) break;
+            if ((st = dev_ensure(ss->hit_k, 8 * n, false)) != ALN_OK) break;
+            if ((st = dev_ensure(ss->hit_f, 8 * n, false)) != ALN_OK) break;
+        }
+        if (j == 0) {
+            if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) break;
+            ss->bytes[0] += c.md.size() * (c.is_int ? 4 : 8);
+        }
+        HIPCHK(hipMemsetAsync(ss->misc.p, 0, 16, q));
+        aln_seqset_launch_expand(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), n, k0, &b, ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), q);
+        HIPCHK(hipGetLastError());
+        if (!identity && k.n_small) {                  // the plan's queue: longest pairs first, without the pairs routed elsewhere
+            HIPCHK(hipMemcpyAsync(s.order.p, k.order.data(), 4 * k.n_small, hipMemcpyHostToDevice, q));
+            ss->bytes[0] += 4 * k.n_small;
+        }
+        if ((st = slot_launch(ss->ctx, s, c, k, q, ss->ev, nullptr)) != ALN_OK) break;
+        timed = true;
+        aln_seqset_launch_gather(s.results.as<aln_pair_result>(), ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), n,
+                                 reinterpret_cast<unsigned long long *>(ss->misc.as<uint8_t>() + 8), q);
+        HIPCHK(hipGetLastError());
+        if (select) {
+            aln_seqset_launch_select(s.results.as<aln_pair_result>(), n, k0, f_min, ss->tiles.as<uint32_t>(), ss->tiles.as<uint32_t>() + tiles,
+                                     ss->misc.as<uint32_t>(), ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
+            HIPCHK(hipGetLastError());
+        }
+        uint8_t *h = ss->h_out.as<uint8_t>();
+        HIPCHK(hipMemcpyAsync(h, ss->misc.p, 16, hipMemcpyDeviceToHost, q));
+        ss->bytes[1] += 16;
+        if (f) { HIPCHK(hipMemcpyAsync(h + 256, ss->fbuf.p, 8 * n, hipMemcpyDeviceToHost, q)); ss->bytes[1] += 8 * n; }
+        if (status) { HIPCHK(hipMemcpyAsync(h + 256 + 8 * n, ss->stbuf.p, 4 * n, hipMemcpyDeviceToHost, q)); ss->bytes[1] += 4 * n; }
+        prev_k0 = k0; prev_n = n;
+        k0 += n;
+    }
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    HIPCHK(hipStreamSynchronize(q));
+    return collect();
+}
+
+// (every way out of a failed pass waits for the stream: queued work reads the plans' queues and writes the pinned staging)
+static int seqset_pass(aln_seqset *ss, const Call &c, const aln_seqset_block &b, uint64_t pairs, double *f, int32_t *status, bool select,
+                       double f_min, int *first_bad)
+{
+    Chunk plans[2];                    // chunk j's queue may still be on its way while chunk j + 1 is planned
+    const int st = seqset_pass_chunks(ss, c, b, pairs, f, status, select, f_min, first_bad, plans);
+    if (st != ALN_OK) (void)hipStreamSynchronize(ss->slot->stream);
+    return st;
+}
+
+static void seqset_begin(aln_seqset *ss)
+{
+    ss->held = false;
+    ss->hit_pair.clear(); ss->hit_score.clear(); ss->hit_q.clear(); ss->hit_t.clear(); ss->info.clear();
+    for (double &v : ss->ms) v = 0;
+    ss->bytes[0] = ss->bytes[1] = 0;
+}
+
+extern "C" int aln_seqset_score(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double *f, int32_t *status)
+{
+    Call c;
+    int st = seqset_call(ss, params, b, ALN_OUT_SCORE, c);
+    if (st != ALN_OK) return st;
+    if (!f) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    HIPCHK(hipStreamSynchronize(ss->slot->stream));
+    seqset_begin(ss);
+    const auto t0 = std::chrono::steady_clock::now();
+    int bad = ALN_OK;
+    st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), f, status, false, 0.0, &bad);
+    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (st != ALN_OK) return st;
+    if (!status && bad != ALN_OK) { g_err = "a pair failed"; return bad; }
+    return ALN_OK;
+}
+
+extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double f_min, uint64_t *count)
+{
+    Call c, ct;
+    int st = seqset_call(ss, params, b, ALN_OUT_SCORE, c);
+    if (st != ALN_OK) return st;
+    if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE | ALN_OUT_TRACEBACK, ct)) != ALN_OK) return st;
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    Slot &s = *ss->slot;
+    hipStream_t q = s.stream;
+    HIPCHK(hipStreamSynchronize(q));
+    seqset_begin(ss);
+    *count = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    int bad = ALN_OK;
+    if ((st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), nullptr, nullptr, true, f_min, &bad)) != ALN_OK) { seqset_begin(ss); return st; }
+    const size_t hits = ss->hit_pair.size();
+    if (hits > 0xFFFFFFF0ull) { seqset_begin(ss); g_err = "too many hits"; return ALN_ERR_UNSUPPORTED; }
+    if (hits) {
+        // the re-fill with directions: the hits as a batch of their own over the resident residues
+        std::vector<uint64_t> qo(hits), ql(hits), to(hits), tl(hits);
+        ss->hit_q.resize(hits); ss->hit_t.resize(hits);
+        ss->info.assign(hits, PairsetHeld{});
+        uint64_t tb_total = 0;
+        for (size_t h = 0; h < hits; ++h) {
+            uint64_t sq, tq;
+            aln_seqset_unrank(*b, ss->hit_pair[h], &sq, &tq);
+            ss->hit_q[h] = (uint32_t)sq; ss->hit_t[h] = (uint32_t)tq;
+            qo[h] = ss->off[sq]; ql[h] = ss->len[sq]; to[h] = ss->off[tq]; tl[h] = ss->len[tq];
+            ss->info[h].N = (uint32_t)ql[h]; ss->info[h].M = (uint32_t)tl[h]; ss->info[h].tb_off = tb_total;
+            tb_total += 2ull * (ql[h] + tl[h] + 2);      // the chunks' own layout (chunk_plan), chunk after chunk
+        }
+        std::vector<std::pair<size_t, size_t>> ranges;
+        make_chunks(ct, ql.data(), tl.data(), hits, 1, ranges);
+        // the held buffers, sized for exactly this count; nothing is held if the memory cannot be had
+        st = dev_ensure(ss->held_res, sizeof(aln_pair_result) * hits, false);
+        if (st == ALN_OK) st = dev_ensure(ss->held_tb, tb_total, false);
+        if (st == ALN_OK) st = dev_ensure(ss->held_info, sizeof(PairsetHeld) * hits, false);
+        if (st != ALN_OK) { seqset_begin(ss); return st; }
+        HIPCHK(hipMemcpyAsync(ss->held_info.p, ss->info.data(), sizeof(PairsetHeld) * hits, hipMemcpyHostToDevice, q));
+        ss->bytes[0] += sizeof(PairsetHeld) * hits;
+        Chunk k;
+        bool timed = false;
+        auto collect = [&]() {
+            if (timed) { ss->ms[1] += ev_ms(ss->ev[0], ss->ev[2]); timed = false; }
+        };
+        auto refill = [&]() -> int {      // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+            for (size_t j = 0; j < ranges.size(); ++j) {
+                const size_t first = ranges[j].first, n = ranges[j].second;
+                k.reset();
+                if ((st = chunk_plan(ss->ctx, ct, qo.data(), ql.data(), to.data(), tl.data(), first, n, ranges.size() == 1, k, ranges.size() > 4)) != ALN_OK) break;
+                for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[first + i]; k.descs[i].t_off = to[first + i]; }
+                k.seq_direct = true; k.seq_lo = 0; k.seq_span = ss->total;
+                HIPCHK(hipStreamSynchronize(q));             // the tables go through the slot's pinned staging
+                collect();
+                if ((st = slot_ensure(s, ct, k)) != ALN_OK) break;
+                if ((st = slot_upload(s, ct, k, nullptr, qo.data(), ql.data(), to.data(), tl.data(), q, false, true)) != ALN_OK) break;
+                ss->bytes[0] += n * (sizeof(PairDesc) + 4);
+                if ((st = slot_launch(ss->ctx, s, ct, k, q, ss->ev, nullptr)) != ALN_OK) break;
+                timed = true;
+                HIPCHK(hipMemcpyAsync(ss->held_res.as<aln_pair_result>() + first, s.results.p, n * sizeof(aln_pair_result), hipMemcpyDeviceToDevice, q));
+                if (k.tb_bytes) HIPCHK(hipMemcpyAsync(ss->held_tb.as<uint8_t>() + ss->info[first].tb_off, s.tb.p, k.tb_bytes, hipMemcpyDeviceToDevice, q));
+            }
+            return st;
+        };
+        st = refill();
+        if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_begin(ss); return st; }
+        HIPCHK(hipStreamSynchronize(q));
+        collect();
+    }
+    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->held = true;
+    *count = hits;
+    return ALN_OK;
+}
+
+static int seqset_held_check(aln_seqset *ss)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ss->held) { g_err = "no held hits: aln_seqset_hits has not run, or another pass has replaced them"; return ALN_ERR_INVALID_ARGUMENT; }
+    return ALN_OK;
+}
+
+extern "C" int aln_seqset_held_list(aln_seqset *ss, uint64_t first, uint64_t n, uint64_t *pair_index, uint32_t *q_seq, uint32_t *t_seq, double *f)
+{
+    int st = seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    const uint64_t held = ss->hit_pair.size();
+    if (first > held || n > held - first) { g_err = "range beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && (!pair_index || !q_seq || !t_seq || !f)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    // (the list is the host's: the re-fill was planned from it)
+    for (uint64_t i = 0; i < n; ++i) {
+        pair_index[i] = ss->hit_pair[first + i]; q_seq[i] = ss->hit_q[first + i]; t_seq[i] = ss->hit_t[first + i]; f[i] = ss->hit_score[first + i];
+    }
+    return ALN_OK;                       // (no byte moves and no kernel runs: the stats of the pass stay as they are)
+}
+
+extern "C" int aln_seqset_held_strings(aln_seqset *ss, const uint32_t *keep, uint64_t n, aln_pair_result *results, uint8_t *tb_buf,
+                                       const uint64_t *tb_off)
+{
+    int st = seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    if (n && (!keep || !results || (tb_buf && !tb_off))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n > 0x7FFFFFF0ull) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t held = ss->hit_pair.size();
+    for (uint64_t k = 0; k < n; ++k)
+        if (keep[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return ALN_OK;
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    // packed for the download in the documented cumulative layout; the caller's own offsets are served from it
+    std::vector<uint64_t> off(n);
+    uint64_t total = 0;
+    for (uint64_t k = 0; k < n; ++k) { off[k] = total; total += 2ull * ((uint64_t)ss->info[keep[k]].N + ss->info[keep[k]].M + 2); }
+    const bool want = tb_buf != nullptr;
+    bool direct = want;
+    for (uint64_t k = 0; k < n && direct; ++k) direct = tb_off[k] >= tb_off[0] && tb_off[k] - tb_off[0] == off[k];
+    if ((st = dev_ensure(ss->list, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->out_off, 8ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->packed_res, sizeof(aln_pair_result) * n, false)) != ALN_OK) return st;
+    if (want && (st = dev_ensure(ss->packed_tb, total, false)) != ALN_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemcpyAsync(ss->list.p, keep, 4ull * n, hipMemcpyHostToDevice, q));
+    HIPCHK(hipMemcpyAsync(ss->out_off.p, off.data(), 8ull * n, hipMemcpyHostToDevice, q));
+    HIPCHK(hipEventRecord(ss->ev[0], q));
+    // (the kernel writes aln_len bytes per string: whatever else the packed span holds goes to the caller as zeros, not as what an
+    // earlier fetch left there)
+    if (want) HIPCHK(hipMemsetAsync(ss->packed_tb.p, 0, total, q));
+    aln_seqset_launch_held(ss->held_info.as<PairsetHeld>(), ss->held_res.as<aln_pair_result>(), ss->held_tb.as<uint8_t>(), ss->list.as<uint32_t>(),
+                           ss->out_off.as<uint64_t>(), (uint32_t)n, (uint32_t)held, ss->packed_res.as<aln_pair_result>(),
+                           want ? ss->packed_tb.as<uint8_t>() : nullptr, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ss->ev[1], q));
+    // (the summaries land in a buffer of the call's own first: an error on the way leaves the caller's arrays as they were)
+    std::vector<aln_pair_result> res(n);
+    HIPCHK(hipMemcpyAsync(res.data(), ss->packed_res.p, sizeof(aln_pair_result) * n, hipMemcpyDeviceToHost, q));
+    std::vector<uint8_t> bounce;
+    if (want) {
+        if (direct) HIPCHK(hipMemcpyAsync(tb_buf + tb_off[0], ss->packed_tb.p, total, hipMemcpyDeviceToHost, q));
+        else { bounce.resize(total); HIPCHK(hipMemcpyAsync(bounce.data(), ss->packed_tb.p, total, hipMemcpyDeviceToHost, q)); }
+    }
+    HIPCHK(hipStreamSynchronize(q));
+    memcpy(results, res.data(), sizeof(aln_pair_result) * n);
+    if (want && !direct)                             // an entry's whole capacity, as the direct copy: zeros beyond aln_len
+        for (uint64_t k = 0; k < n; ++k) {
+            const uint64_t cap = (uint64_t)ss->info[keep[k]].N + ss->info[keep[k]].M + 2;
+            memcpy(tb_buf + tb_off[k], bounce.data() + off[k], 2 * cap);
+        }
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->bytes[0] = 12ull * n; ss->bytes[1] = sizeof(aln_pair_result) * n + (want ? total : 0);
+    return ALN_OK;
+}
+
+extern "C" int aln_seqset_stats(const aln_seqset *ss, double *ms, uint64_t *bytes)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ms) for (int i = 0; i < 4; ++i) ms[i] = ss->ms[i];
+    if (bytes) { bytes[0] = ss->bytes[0]; bytes[1] = ss->bytes[1]; }
     return ALN_OK;
 }

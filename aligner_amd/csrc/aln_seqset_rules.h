@@ -1,0 +1,78 @@
+// aln_seqset_rules.h -- the pair order of a block of the S x S grid of a resident sequence set (aln_seqset_*, include/aligner_hip.h):
+// plain integer arithmetic, no HIP, so that the host plan, the expansion kernel (aln_seqset.hip) and a CPU test driver number the
+// pairs the same way.
+//
+//   rectangle  pair k = (q_first + k / t_count, t_first + k % t_count): the queries are the slow index
+//   upper      the pairs i < j of the square first .. first + n - 1 in the order of generate_pairs (aligner-web
+//              dispatcher/handlers.rs:253-264): (0,1) (0,2) .. (0,n-1) (1,2) ..; row r holds n - 1 - r pairs and starts at
+//              r (2n - r - 1) / 2.  The row of a k is found by binary search on that closed form in uint64_t: a floating-point square
+//              root rounds wrongly near row boundaries once n approaches 2^32.
+//   sizes      n_seqs < 2^32, so a rectangle has fewer than 2^64 pairs and a triangle fewer than 2^63: every product below fits
+#pragma once
+#include <stdint.h>
+
+#include "../../include/aligner_hip.h"
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define ALN_HD __host__ __device__
+#else
+#define ALN_HD
+#endif
+
+// pairs of a block over a set of n_seqs sequences; 0 for an invalid block (a range past the set, upper with unequal ranges, a
+// reserved word that is not 0, no pairs)
+ALN_HD inline uint64_t aln_seqset_block_pairs(uint64_t n_seqs, const aln_seqset_block &b)
+{
+    if (b.reserved != 0u || b.upper > 1u) return 0;
+    if (b.q_first > n_seqs || b.q_count > n_seqs - b.q_first) return 0;
+    if (b.t_first > n_seqs || b.t_count > n_seqs - b.t_first) return 0;
+    if (b.upper) {
+        if (b.q_first != b.t_first || b.q_count != b.t_count) return 0;
+        const uint64_t n = b.q_count;
+        return (n & 1u) ? n * ((n - 1u) / 2u) : (n / 2u) * (n - 1u);
+    }
+    return b.q_count * b.t_count;
+}
+
+// first pair of row r of the upper triangle of an n-square, r <= n - 1 < 2^32: r (2n - r - 1) / 2 without leaving uint64_t
+// (r even: r / 2 is exact; r odd: 2n - r - 1 is even)
+ALN_HD inline uint64_t aln_seqset_row_start(uint64_t n, uint64_t r)
+{
+    const uint64_t w = 2u * n - r - 1u;
+    return (r & 1u) ? r * (w / 2u) : (r / 2u) * w;
+}
+
+// pair k of a valid block, k < aln_seqset_block_pairs: absolute sequence numbers (query, target)
+ALN_HD inline void aln_seqset_unrank(const aln_seqset_block &b, uint64_t k, uint64_t *q, uint64_t *t)
+{
+    if (!b.upper) {
+        *q = b.q_first + k / b.t_count;
+        *t = b.t_first + k % b.t_count;
+        return;
+    }
+    const uint64_t n = b.q_count;
+    uint64_t lo = 0, hi = n - 2u;                    // the largest row whose start is <= k
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1u) / 2u;
+        if (aln_seqset_row_start(n, mid) <= k) lo = mid;
+        else hi = mid - 1u;
+    }
+    *q = b.q_first + lo;
+    *t = b.q_first + lo + 1u + (k - aln_seqset_row_start(n, lo));
+}
+
+// the inverse: the number of pair (q, t) of a valid block that holds it
+ALN_HD inline uint64_t aln_seqset_rank(const aln_seqset_block &b, uint64_t q, uint64_t t)
+{
+    if (!b.upper) return (q - b.q_first) * b.t_count + (t - b.t_first);
+    return aln_seqset_row_start(b.q_count, q - b.q_first) + (t - q - 1u);
+}
+
+// the pair after (q, t) in the block's order (the host walks a chunk's pairs with it instead of unranking each)
+ALN_HD inline void aln_seqset_next(const aln_seqset_block &b, uint64_t *q, uint64_t *t)
+{
+    ++*t;
+    if (b.upper) {
+        if (*t == b.q_first + b.q_count) { ++*q; *t = *q + 1u; }
+    } else if (*t == b.t_first + b.t_count) { ++*q; *t = b.t_first; }
+}

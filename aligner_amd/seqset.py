@@ -1,0 +1,185 @@
+"""A set of sequences resident in HBM, scored all against all (aln_seqset_*, include/aligner_hip.h).
+
+The device-resident form of the reference's request path (generate_pairs, aligner-web/src/bin/dispatcher/handlers.rs:253-264:
+every pair i < j of a FASTA): the residues go up once, a call names a block of the S x S pair grid, and either every pair's f or
+the held hits -- the pairs at or above a threshold, filled again with directions and walked -- come back.  Sequence q of a pair is
+the query (columns), sequence t the target (rows); pair k of a block is what align_batch computes for (q, t).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi
+from . import runtime
+from .alignment import Alignment
+from .batch import RESULT_DTYPE
+from .enums import Protein
+
+
+def _block(block, n):
+    """A block as the C struct: a SeqsetBlock, None (the upper triangle of the whole set), or a dict / tuple
+    (q_first, q_count, t_first, t_count[, upper])."""
+    if isinstance(block, _ffi.SeqsetBlock):
+        return block
+    if block is None:
+        return _ffi.SeqsetBlock(0, n, 0, n, 1, 0)
+    if isinstance(block, dict):
+        return _ffi.SeqsetBlock(int(block["q_first"]), int(block["q_count"]), int(block["t_first"]), int(block["t_count"]),
+                                int(block.get("upper", 0)), int(block.get("reserved", 0)))
+    b = tuple(block)
+    return _ffi.SeqsetBlock(int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(b[4]) if len(b) > 4 else 0, 0)
+
+
+def upper(first, count):
+    """The pairs i < j of sequences first .. first + count - 1, in generate_pairs order."""
+    return _ffi.SeqsetBlock(int(first), int(count), int(first), int(count), 1, 0)
+
+
+def rectangle(q_first, q_count, t_first, t_count):
+    """Every (q, t) with q in the first range and t in the second; the queries are the slow index."""
+    return _ffi.SeqsetBlock(int(q_first), int(q_count), int(t_first), int(t_count), 0, 0)
+
+
+class SeqSet:
+    def __init__(self, seqs, alphabet=Protein, device=None):
+        """seqs: residue code arrays (or strings, encoded with alphabet.str_to_vec)."""
+        self.lib = _ffi.load()
+        self.alphabet = alphabet
+        codes = [np.asarray(alphabet.str_to_vec(s) if isinstance(s, str) else s, dtype=np.uint8) for s in seqs]
+        self.len = np.array([len(c) for c in codes], dtype=np.uint64)
+        self.off = np.zeros(len(codes), dtype=np.uint64)
+        if len(codes) > 1:
+            self.off[1:] = np.cumsum(self.len)[:-1]
+        self.seqs = np.concatenate(codes) if codes else np.zeros(0, dtype=np.uint8)
+        st = C.c_int(0)
+        self.handle = self.lib.aln_seqset_create(runtime.context(device), self.seqs.ctypes.data, self.off.ctypes.data, self.len.ctypes.data,
+                                                 len(codes), C.byref(st))
+        if not self.handle:
+            runtime.raise_for_status(st.value, "aln_seqset_create")
+            raise RuntimeError("aln_seqset_create returned NULL")
+
+    def __len__(self):
+        return len(self.len)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.handle:
+            self.lib.aln_seqset_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def pairs(self, block=None):
+        """Pairs of a block; 0 for an invalid one."""
+        b = _block(block, len(self))
+        return int(self.lib.aln_seqset_pairs(self.handle, C.byref(b)))
+
+    def _checked(self, block):
+        b = _block(block, len(self))
+        n = int(self.lib.aln_seqset_pairs(self.handle, C.byref(b)))
+        if n == 0:
+            raise ValueError("aln_seqset: invalid block (a range beyond the set, unequal ranges of an upper block, or no pairs)")
+        return b, n
+
+    def score(self, matrix, del_, ext, block=None, semantics=_ffi.CORE_LOCAL, blank=98, **kw):
+        """(f, status) of every pair of the block: f64 and int32 arrays in the block's pair order.  A failed pair carries its status
+        (its f is 0) and leaves the others untouched."""
+        b, n = self._checked(block)
+        p, keep = runtime.make_params(semantics, del_, ext, matrix, outputs=_ffi.OUT_SCORE, blank=blank, **kw)
+        f = np.zeros(n, dtype=np.float64)
+        status = np.zeros(n, dtype=np.int32)
+        st = self.lib.aln_seqset_score(self.handle, C.byref(p), C.byref(b), f.ctypes.data, status.ctypes.data)
+        runtime.raise_for_status(st, "aln_seqset_score")
+        return f, status
+
+    def hits(self, matrix, del_, ext, f_min, block=None, semantics=_ffi.CORE_LOCAL, blank=98, **kw):
+        """A held pass: the pairs with f >= f_min, aligned.  Returns a HeldHits (valid until the next score / hits on this set)."""
+        b, n = self._checked(block)
+        p, keep = runtime.make_params(semantics, del_, ext, matrix, blank=blank, **kw)
+        count = C.c_uint64(0)
+        st = self.lib.aln_seqset_hits(self.handle, C.byref(p), C.byref(b), float(f_min), C.byref(count))
+        runtime.raise_for_status(st, "aln_seqset_hits")
+        return HeldHits(self, int(count.value), semantics)
+
+    def stats(self):
+        ms, by = (C.c_double * 4)(), (C.c_uint64 * 2)()
+        runtime.raise_for_status(self.lib.aln_seqset_stats(self.handle, ms, by), "aln_seqset_stats")
+        return dict(fill_ms=ms[0], refill_ms=ms[1], fetch_kernel_ms=ms[2], wall_ms=ms[3], bytes_up=int(by[0]), bytes_down=int(by[1]))
+
+
+class HeldHits:
+    """The hits of SeqSet.hits: .index (pair numbers in the block), .q, .t (sequence numbers) and .f in ascending pair order;
+    .alignments(keep) fetches Alignment objects of the listed positions."""
+
+    def __init__(self, owner, count, semantics):
+        self.owner, self.count, self.semantics = owner, count, semantics
+        self.index = np.zeros(count, dtype=np.uint64)
+        self.q = np.zeros(count, dtype=np.uint32)
+        self.t = np.zeros(count, dtype=np.uint32)
+        self.f = np.zeros(count, dtype=np.float64)
+        if count:
+            st = owner.lib.aln_seqset_held_list(owner.handle, 0, count, self.index.ctypes.data, self.q.ctypes.data, self.t.ctypes.data,
+                                                self.f.ctypes.data)
+            runtime.raise_for_status(st, "aln_seqset_held_list")
+
+    def __len__(self):
+        return self.count
+
+    def strings(self, keep=None):
+        """(summaries, [(aligned query, aligned target)]) of the listed positions of the held list (default: all)."""
+        o = self.owner
+        w = np.arange(self.count, dtype=np.uint32) if keep is None else np.ascontiguousarray(keep, dtype=np.uint32)
+        if len(w) and int(w.max()) >= self.count:
+            raise ValueError("aln_seqset_held_strings: a listed position is beyond the held hits")
+        cap = (o.len[self.q[w]] + o.len[self.t[w]] + np.uint64(2)).astype(np.uint64) if len(w) else np.zeros(0, dtype=np.uint64)
+        off = np.zeros(len(w), dtype=np.uint64)
+        if len(w) > 1:
+            off[1:] = np.cumsum(2 * cap)[:-1]
+        tb = np.zeros(max(int((2 * cap).sum()), 1), dtype=np.uint8)
+        res = np.zeros(len(w), dtype=RESULT_DTYPE)
+        st = o.lib.aln_seqset_held_strings(o.handle, w.ctypes.data, len(w), res.ctypes.data, tb.ctypes.data, off.ctypes.data)
+        runtime.raise_for_status(st, "aln_seqset_held_strings")
+        out = []
+        for k in range(len(w)):
+            n = int(res["aln_len"][k]) if res["status"][k] == _ffi.OK else 0
+            a, c = int(off[k]), int(cap[k])
+            out.append((tb[a:a + n].copy(), tb[a + c:a + c + n].copy()))
+        return res, out
+
+    def alignments(self, keep=None):
+        """Alignment objects of the listed positions (default: all), coordinates as SimpleLocalAligner / SimpleGlobalAligner give them."""
+        o = self.owner
+        w = np.arange(self.count, dtype=np.uint32) if keep is None else np.ascontiguousarray(keep, dtype=np.uint32)
+        res, strs = self.strings(w)
+        out = []
+        for k in range(len(w)):
+            r = res[k]
+            runtime.raise_for_status(int(r["status"]), "aln_seqset_held_strings")
+            if self.semantics == _ffi.CORE_GLOBAL:
+                coords = ((1, int(o.len[self.q[w[k]]])), (1, int(o.len[self.t[w[k]]])))
+            else:
+                coords = ((int(r["start_x"]) + 1, int(r["end_x"]) + 1), (int(r["start_y"]) + 1, int(r["end_y"]) + 1))
+            out.append(Alignment(o.alphabet, strs[k][0], strs[k][1], coords, float(r["f"])))
+        return out
+
+
+def all_pairs(records, matrix, del_, ext, f_min=None, alphabet=Protein, semantics=_ffi.CORE_LOCAL, device=None, **kw):
+    """Every pair i < j of `records` (code arrays or strings) in generate_pairs order.  Without f_min: (q, t, f, status) arrays over
+    all pairs.  With f_min: (q, t, f, alignments) of the pairs with f >= f_min."""
+    with SeqSet(records, alphabet, device=device) as ss:
+        n = len(ss)
+        if f_min is None:
+            f, status = ss.score(matrix, del_, ext, None, semantics=semantics, **kw)
+            q, t = np.triu_indices(n, 1)
+            return q.astype(np.uint32), t.astype(np.uint32), f, status
+        held = ss.hits(matrix, del_, ext, f_min, None, semantics=semantics, **kw)
+        return held.q, held.t, held.f, held.alignments()

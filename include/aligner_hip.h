@@ -274,6 +274,57 @@ int aln_pairset_strings(aln_pairset *ps, const uint32_t *which, size_t n, aln_pa
 int aln_pairset_stats(const aln_pairset *ps, double *ms /* 4 */, uint64_t *bytes /* 2 */);
 void aln_pairset_destroy(aln_pairset *ps);
 
+/* ---- resident sequence set (the request path, aligner-web dispatcher/handlers.rs:104,253-264 generate_pairs: every pair i < j of
+ * a FASTA; blast_p_value_cmp.rs and calc: rows of (query, target) drawn from one table): S sequences are uploaded once (one device:
+ * the context's first) and a call names a BLOCK of the S x S pair grid.  The descriptors are expanded on the device, every pair is
+ * scored by the kernels aln_align_batch would take for it, and either the scores or the held hits come back.
+ * block: upper = 0: every (q, t) of the rectangle, pair k = (q_first + k / t_count, t_first + k % t_count); upper = 1 (q_first ==
+ * t_first and q_count == t_count required): the pairs i < j of that square in generate_pairs order, row-major (0,1) (0,2) .. (0,n-1)
+ * (1,2) .., n (n - 1) / 2 pairs (aligner_amd/csrc/aln_seqset_rules.h has the numbering).  Sequence q is the query (columns),
+ * sequence t the target (rows).
+ * Pair k is exactly what aln_align_batch computes for (query = sequence q, target = sequence t), for every scheme and every non-PWM
+ * semantics it accepts (ALN_PWM_LOCAL: ALN_ERR_UNSUPPORTED); a pair's bytes do not depend on the block it was named through, on the
+ * chunking (the cell bounds of aln_align_batch and 2^22 pairs per chunk; ALN_CHUNK_CELLS overrides) or on the other pairs.
+ * score: f[k] = the batch's results[k].f.  Per-pair failures (ALN_ERR_EMPTY_SEQUENCE, ALN_ERR_CODE_OUT_OF_RANGE,
+ * ALN_ERR_NO_POSITIVE_CELL) go into status[k] and the call returns ALN_OK; without a status array the first failed pair's status is
+ * the return value (as aln_shuffle_scores).  8 bytes per pair come back, 4 more with status.  params->outputs is ignored.
+ * hits: a HELD pass (as aln_scan_hits).  The same fill; on the device the pairs with status ALN_OK and f >= f_min (plain IEEE
+ * compare: a NaN f_min selects nothing) are compacted per chunk in ascending pair order by an ordered prefix sum (no atomic appends).
+ * A chunk's hits (pair number and f, 16 bytes each) are read where the pass waits for that chunk anyway and appended to one ascending
+ * list, which is kept on the HOST: the re-fill of the hits is planned from it like a batch of its own (routes and direction layout
+ * depend on every hit's shape), so its descriptors and queue are uploaded (60 bytes per hit).  The held buffers are sized for exactly
+ * the count (ALN_ERR_OOM and nothing held if that memory cannot be had), and ALL hits are filled again with directions and walked.
+ * Their summaries and strings stay on the device; the call itself returns *count.  Failed pairs are never hits and do not fail the
+ * call.  Held state lasts until the set's next score / hits or destroy.
+ * held_list: pair index (in the block of the hits call), query and target sequence numbers and f of held hits first .. first + n - 1,
+ * ascending pair order; served from the host's list (no device traffic, the stats of the pass stay).
+ * held_strings: summaries and strings of the listed positions of the held list (any order; a position may be listed twice) in the
+ * layout of aln_align_batch: entry k's aligned query at tb_off[k], aligned target q_len + t_len + 2 bytes later; tb_buf optional.
+ * Bytes of a string's capacity beyond aln_len, and both strings of a failed entry, are zero.
+ * held_* without held state, first + n > count, a keep[k] >= count, a null pointer with a non-zero length:
+ * ALN_ERR_INVALID_ARGUMENT, nothing written.
+ * ALN_ERR_INVALID_ARGUMENT for the whole call, nothing written: an invalid block (a range past n_seqs, upper with unequal ranges,
+ * reserved != 0, no pairs), a null matrix, a null output; create with n_seqs >= 2^32.
+ * stats: ms[0] fill kernels of the last score / hits pass, ms[1] its hit re-fill and walk, ms[2] kernels of the last held fetch,
+ * ms[3] wall time of the last call; bytes moved by the last call (host -> device, device -> host). ---- */
+typedef struct aln_seqset aln_seqset;
+typedef struct aln_seqset_block {
+    uint64_t q_first, q_count;   /* sequences used as query (columns) */
+    uint64_t t_first, t_count;   /* sequences used as target (rows)   */
+    uint32_t upper;              /* 0: the rectangle; 1: the pairs i < j of the square (ranges must be equal) */
+    uint32_t reserved;           /* 0 */
+} aln_seqset_block;              /* 40 bytes */
+
+aln_seqset *aln_seqset_create(aln_ctx *ctx, const uint8_t *seqs, const uint64_t *off, const uint64_t *len, size_t n_seqs, int *status);
+void aln_seqset_destroy(aln_seqset *set);
+uint64_t aln_seqset_pairs(const aln_seqset *set, const aln_seqset_block *block);          /* 0 for an invalid block */
+int aln_seqset_score(aln_seqset *set, const aln_params *params, const aln_seqset_block *block, double *f, int32_t *status /* optional, per pair */);
+int aln_seqset_hits(aln_seqset *set, const aln_params *params, const aln_seqset_block *block, double f_min, uint64_t *count);
+int aln_seqset_held_list(aln_seqset *set, uint64_t first, uint64_t n, uint64_t *pair_index, uint32_t *q_seq, uint32_t *t_seq, double *f);
+int aln_seqset_held_strings(aln_seqset *set, const uint32_t *keep, uint64_t n_keep, aln_pair_result *results, uint8_t *tb_buf,
+                            const uint64_t *tb_off);
+int aln_seqset_stats(const aln_seqset *set, double *ms /* 4 */, uint64_t *bytes /* 2 */);
+
 /* ---- transform_matrix (aligner-helpers/src/matrices/mod.rs:19-68) for n matrices at once, on the HOST (no GPU is touched): matrix i
  * (rows x cols, compact row-major) is rescaled under frequencies[i * rows .. + rows), kd[i], r_squared[i] into matrices_out (which may
  * be matrices_in); status[i] = 0, or ALN_TRANSFORM_NO_ROOT where the reference returns Err(WrongMatrixSpecified) (matrix i of the

@@ -228,6 +228,35 @@ impl<T: BioData + Into<usize> + From<usize> + Copy + Eq> AlignerTrait<T, PWMAlig
     }
 }
 
+/// Resident sequence set (`aln_seqset_*`, include/aligner_hip.h): the request path of aligner-web (`generate_pairs`,
+/// dispatcher/handlers.rs:253-264) with the residues uploaded once.  A call names a block of the S x S pair grid; `aln_seqset_score`
+/// brings back f (and the status) of every pair, `aln_seqset_hits` holds the pairs with f >= f_min -- filled again with directions and
+/// walked -- on the device, `aln_seqset_held_list` / `aln_seqset_held_strings` fetch what the caller keeps.
+pub mod seqset {
+    use super::{AlnCtx, AlnPairResult, AlnParams};
+    use std::os::raw::c_int;
+    #[repr(C)]
+    pub struct AlnSeqset { _private: [u8; 0] }
+    #[repr(C)]
+    #[derive(Clone, Copy, Default)]
+    pub struct AlnSeqsetBlock { pub q_first: u64, pub q_count: u64, pub t_first: u64, pub t_count: u64, pub upper: u32, pub reserved: u32 } // 40 bytes
+    impl AlnSeqsetBlock {
+        /// every pair i < j of sequences first .. first + n - 1, in generate_pairs order
+        pub fn upper(first: u64, n: u64) -> Self { AlnSeqsetBlock { q_first: first, q_count: n, t_first: first, t_count: n, upper: 1, reserved: 0 } }
+    }
+    extern "C" {
+        pub fn aln_seqset_create(ctx: *mut AlnCtx, seqs: *const u8, off: *const u64, len: *const u64, n_seqs: usize, status: *mut c_int) -> *mut AlnSeqset;
+        pub fn aln_seqset_destroy(set: *mut AlnSeqset);
+        pub fn aln_seqset_pairs(set: *const AlnSeqset, block: *const AlnSeqsetBlock) -> u64;
+        pub fn aln_seqset_score(set: *mut AlnSeqset, p: *const AlnParams, block: *const AlnSeqsetBlock, f: *mut f64, status: *mut i32) -> c_int;
+        pub fn aln_seqset_hits(set: *mut AlnSeqset, p: *const AlnParams, block: *const AlnSeqsetBlock, f_min: f64, count: *mut u64) -> c_int;
+        pub fn aln_seqset_held_list(set: *mut AlnSeqset, first: u64, n: u64, pair_index: *mut u64, q_seq: *mut u32, t_seq: *mut u32, f: *mut f64) -> c_int;
+        pub fn aln_seqset_held_strings(set: *mut AlnSeqset, keep: *const u32, n_keep: u64, results: *mut AlnPairResult, tb_buf: *mut u8,
+                                       tb_off: *const u64) -> c_int;
+        pub fn aln_seqset_stats(set: *const AlnSeqset, ms: *mut f64, bytes: *mut u64) -> c_int;
+    }
+}
+
 /// The batch site of the reference, `calculate_p_value` (statistics/mod.rs:255-286): one query against `targets.len()` shuffled
 /// targets, only `alignment.f` is kept.  One call instead of ten threads x 500 aligners; `del` / `ins` / `matrix` as there.
 pub fn local_scores<T: BioData + Into<usize> + Copy + Eq>(query: &[T], targets: &[Vec<T>], del: f64, ins: f64, matrix: &Array2<f64>) -> Vec<f64> {
