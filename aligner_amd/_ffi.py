@@ -39,6 +39,7 @@ EXPORTS = [
     "aln_scan_stats", "aln_scan_hits", "aln_scan_held_list", "aln_scan_held_frequencies", "aln_scan_held_strings", "aln_shuffle_scores", "aln_shuffle_targets",
     "aln_pairset_create", "aln_pairset_run", "aln_pairset_frequencies", "aln_pairset_strings", "aln_pairset_stats", "aln_pairset_destroy",
     "aln_transform_matrices",
+    "aln_pairset_heuristics", "aln_pairset_reestimate", "aln_pairset_run_stored", "aln_pairset_matrices", "aln_transform_matrices_device",
     "aln_seqset_create", "aln_seqset_destroy", "aln_seqset_pairs", "aln_seqset_score", "aln_seqset_hits", "aln_seqset_held_list",
     "aln_seqset_held_strings", "aln_seqset_stats",
 ]
@@ -189,6 +190,16 @@ def load():
     lib.aln_pairset_destroy.argtypes = [vp]
     lib.aln_transform_matrices.restype = i
     lib.aln_transform_matrices.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    lib.aln_pairset_heuristics.restype = i
+    lib.aln_pairset_heuristics.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+    lib.aln_pairset_reestimate.restype = i
+    lib.aln_pairset_reestimate.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    lib.aln_pairset_run_stored.restype = i
+    lib.aln_pairset_run_stored.argtypes = [vp, C.POINTER(Params), vp, C.c_size_t, vp]
+    lib.aln_pairset_matrices.restype = i
+    lib.aln_pairset_matrices.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.aln_transform_matrices_device.restype = i
+    lib.aln_transform_matrices_device.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     bp = C.POINTER(SeqsetBlock)
     lib.aln_seqset_create.restype = vp
     lib.aln_seqset_create.argtypes = [vp, vp, u64p, u64p, C.c_size_t, C.POINTER(C.c_int)]

@@ -65,6 +65,18 @@ struct PairsetHeld {
     uint64_t tb_off;         // aligned query here, aligned target N + M + 2 bytes later
     uint32_t N, M;
 };
+// aln_pairset_transform_kernel (aln_pairset.hip): transform_matrix for n_list matrices, one wave each.  Listed entry k takes its source
+// from `shared` (one matrix for all), else from own[k], else from the counts of held entry entry[k]; its parameters are those of
+// index par[k] (k without a table) and its result goes to dst[dst_index[k]] (dst[k] without a table) unless it has no root.
+struct PairsetTransformArgs {
+    const double *shared, *own;
+    const PairsetHeld *held; const aln_pair_result *res; const uint8_t *tb; const uint32_t *entry;
+    const uint32_t *par, *dst_index;
+    const double *freq, *kd, *r2;
+    double *dst;
+    int32_t *status;
+    uint32_t n_list, n_held, rows, cols, blank;
+};
 // copies of at most this many residues are shuffled in LDS: 64 threads x 2 KiB = 128 KiB of a CU's 160
 #define ALN_SHUFFLE_LDS_MAX 2048u
 #define ALN_SHUFFLE_THREADS 64u

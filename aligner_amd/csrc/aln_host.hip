@@ -2521,6 +2521,8 @@ extern "C" void aln_pairset_launch_freq(const PairsetHeld *held, const aln_pair_
 extern "C" void aln_pairset_launch_gather(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
                                           const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
                                           hipStream_t s);
+extern "C" int aln_pairset_launch_transform(const PairsetTransformArgs *a, hipStream_t s);
+extern "C" void aln_pairset_launch_pick(const double *store, const uint32_t *list, uint32_t n_list, uint32_t e, double *out, hipStream_t s);
 
 struct aln_pairset {
     DevCtx *ctx = nullptr;            // one device: the context's first (as a staged batch)
@@ -2534,9 +2536,14 @@ struct aln_pairset {
     std::vector<int64_t> entry_of;    // pair -> held entry, -1: not in the last run
     std::vector<PairsetHeld> info;    // host copy of the held table
     DevBuf matrices, held_res, held_tb, held_info, list, out_off, counts, packed_res, packed_tb;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a run's launches; 4, 5: transform / pick kernels
     double ms[4] = {0, 0, 0, 0};      // last run: fill kernels, traceback kernels; last fetch: its kernels; last call: wall time of its copies
     uint64_t bytes[2] = {0, 0};       // last call: host -> device, device -> host
+    // the heuristic loop's resident state (aln_pairset_heuristics): every pair's parameters and one matrix per pair
+    bool heur = false;
+    uint32_t h_rows = 0, h_cols = 0;
+    DevBuf h_freq, h_kd, h_r2, store, shared, h_list, h_entry, h_status, picked;
+    std::vector<char> written;        // pair -> its store entry holds a matrix
 };
 
 extern "C" void aln_pairset_destroy(aln_pairset *ps)
@@ -2545,7 +2552,8 @@ extern "C" void aln_pairset_destroy(aln_pairset *ps)
     (void)hipSetDevice(ps->ctx->device);
     if (ps->slot && ps->slot->stream) (void)hipStreamSynchronize(ps->slot->stream);
     for (hipEvent_t e : ps->ev) if (e) (void)hipEventDestroy(e);
-    DevBuf *d[] = {&ps->matrices, &ps->held_res, &ps->held_tb, &ps->held_info, &ps->list, &ps->out_off, &ps->counts, &ps->packed_res, &ps->packed_tb};
+    DevBuf *d[] = {&ps->matrices, &ps->held_res, &ps->held_tb, &ps->held_info, &ps->list, &ps->out_off, &ps->counts, &ps->packed_res, &ps->packed_tb,
+                   &ps->h_freq, &ps->h_kd, &ps->h_r2, &ps->store, &ps->shared, &ps->h_list, &ps->h_entry, &ps->h_status, &ps->picked};
     for (DevBuf *b : d) dev_free(*b);
     slot_destroy(ps->slot);
     delete ps;
@@ -2586,7 +2594,7 @@ extern "C" aln_pairset *aln_pairset_create(aln_ctx *ctx, const uint8_t *seqs, co
         if (e != hipSuccess) st = fail(e, "hipSetDevice");
         if (st == ALN_OK) st = dev_ensure(ps->slot->seqs, total + 256, false);
         if (st == ALN_OK) st = slot_init(*ps->slot);
-        for (int i = 0; i < 4 && st == ALN_OK; ++i) { e = hipEventCreate(&ps->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
+        for (int i = 0; i < 6 && st == ALN_OK; ++i) { e = hipEventCreate(&ps->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
         if (st == ALN_OK && total) {
             e = hipMemcpyAsync(ps->slot->seqs.p, packed.data(), total, hipMemcpyHostToDevice, ps->slot->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ps->slot->stream);
@@ -2601,7 +2609,7 @@ extern "C" aln_pairset *aln_pairset_create(aln_ctx *ctx, const uint8_t *seqs, co
 
 // the checks of a run that need no device
 static int pairset_check_run(const aln_pairset *ps, const aln_params *p, const double *matrices, const uint32_t *active, size_t n_active,
-                             const aln_pair_result *results)
+                             const aln_pair_result *results, bool stored = false)
 {
     if (!p) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if (p->semantics < ALN_CORE_GLOBAL || p->semantics > ALN_PWM_LOCAL) { g_err = "bad semantics"; return ALN_ERR_INVALID_ARGUMENT; }
@@ -2613,20 +2621,24 @@ static int pairset_check_run(const aln_pairset *ps, const aln_params *p, const d
         g_err = "per-pair matrices hold 1 .. 1024 entries";
         return ALN_ERR_INVALID_ARGUMENT;
     }
-    if (n_active && (!matrices || !active || !results)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_active && ((!stored && !matrices) || !active || !results)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (stored && !ps->heur) { g_err = "no heuristics set"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (stored && (p->rows != ps->h_rows || p->cols != ps->h_cols)) { g_err = "the shape differs from the store's"; return ALN_ERR_INVALID_ARGUMENT; }
     if (n_active > ps->n) { g_err = "more active entries than pairs"; return ALN_ERR_INVALID_ARGUMENT; }
     std::vector<char> seen(ps->n, 0);
     for (size_t k = 0; k < n_active; ++k) {
         if (active[k] >= ps->n || seen[active[k]]) { g_err = "active: an entry is out of range or listed twice"; return ALN_ERR_INVALID_ARGUMENT; }
+        if (stored && !ps->written[active[k]]) { g_err = "active: a pair's store entry was never written"; return ALN_ERR_INVALID_ARGUMENT; }
         seen[active[k]] = 1;
     }
     return ALN_OK;
 }
 
-extern "C" int aln_pairset_run(aln_pairset *ps, const aln_params *params, const double *matrices, const uint32_t *active, size_t n_active,
-                               aln_pair_result *results)
+// aln_pairset_run (matrices from the host) and aln_pairset_run_stored (matrices == nullptr: entry k scored by store[active[k]])
+static int pairset_run(aln_pairset *ps, const aln_params *params, const double *matrices, const uint32_t *active, size_t n_active,
+                       aln_pair_result *results, bool stored)
 {
-    int st = pairset_check_run(ps, params, matrices, active, n_active, results);
+    int st = pairset_check_run(ps, params, matrices, active, n_active, results, stored);
     if (st != ALN_OK) return st;
     HIPCHK(hipSetDevice(ps->ctx->device));
     Slot &s = *ps->slot;
@@ -2668,9 +2680,21 @@ extern "C" int aln_pairset_run(aln_pairset *ps, const aln_params *params, const 
     if ((st = dev_ensure(ps->held_info, sizeof(PairsetHeld) * n_active, false)) != ALN_OK) return st;
     c.pair_matrices = ps->matrices.as<double>();
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemcpyAsync(ps->matrices.p, matrices, 8ull * e * n_active, hipMemcpyHostToDevice, q));
+    if (stored) {
+        // the listed store entries, gathered on the device into the compact array the fill reads
+        if ((st = dev_ensure(ps->h_list, 4ull * n_active, false)) != ALN_OK) return st;
+        HIPCHK(hipMemcpyAsync(ps->h_list.p, active, 4ull * n_active, hipMemcpyHostToDevice, q));
+        HIPCHK(hipEventRecord(ps->ev[4], q));
+        aln_pairset_launch_pick(ps->store.as<double>(), ps->h_list.as<uint32_t>(), (uint32_t)n_active, (uint32_t)e, ps->matrices.as<double>(), q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ps->ev[5], q));
+        ps->bytes[0] = 4ull * n_active;
+    } else {
+        HIPCHK(hipMemcpyAsync(ps->matrices.p, matrices, 8ull * e * n_active, hipMemcpyHostToDevice, q));
+        ps->bytes[0] = 8ull * e * n_active;
+    }
     HIPCHK(hipMemcpyAsync(ps->held_info.p, ps->info.data(), sizeof(PairsetHeld) * n_active, hipMemcpyHostToDevice, q));
-    ps->bytes[0] = 8ull * e * n_active + sizeof(PairsetHeld) * n_active;
+    ps->bytes[0] += sizeof(PairsetHeld) * n_active;
 
     // chunk after chunk on the one slot: the plan of chunk j + 1 is made while chunk j runs; its tables go through the slot's pinned
     // staging, so they wait for chunk j
@@ -2705,6 +2729,7 @@ extern "C" int aln_pairset_run(aln_pairset *ps, const aln_params *params, const 
     HIPCHK(hipMemcpyAsync(results, ps->held_res.p, sizeof(aln_pair_result) * n_active, hipMemcpyDeviceToHost, q));
     HIPCHK(hipStreamSynchronize(q));
     collect();
+    if (stored) ps->ms[2] = ev_ms(ps->ev[4], ps->ev[5]);
     ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ps->bytes[1] = sizeof(aln_pair_result) * n_active;
     for (size_t kk = 0; kk < n_active; ++kk) ps->entry_of[active[kk]] = (int64_t)kk;
@@ -2712,6 +2737,200 @@ extern "C" int aln_pairset_run(aln_pairset *ps, const aln_params *params, const 
     ps->rows = c.rows; ps->cols = c.cols; ps->blank = params->blank_code;
     ps->held = true;
     return ALN_OK;
+}
+
+extern "C" int aln_pairset_run(aln_pairset *ps, const aln_params *params, const double *matrices, const uint32_t *active, size_t n_active,
+                               aln_pair_result *results)
+{
+    return pairset_run(ps, params, matrices, active, n_active, results, false);
+}
+
+extern "C" int aln_pairset_run_stored(aln_pairset *ps, const aln_params *params, const uint32_t *active, size_t n_active,
+                                      aln_pair_result *results)
+{
+    return pairset_run(ps, params, nullptr, active, n_active, results, true);
+}
+
+// ---- the heuristic loop's matrices, re-estimated and kept on the device
+extern "C" int aln_pairset_heuristics(aln_pairset *ps, uint32_t rows, uint32_t cols, const double *frequencies, const double *kd,
+                                      const double *r_squared)
+{
+    if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (rows == 0 || cols == 0 || (uint64_t)rows * cols > ALN_PAIRSET_MAX_ENTRIES) {
+        g_err = "per-pair matrices hold 1 .. 1024 entries";
+        return ALN_ERR_INVALID_ARGUMENT;
+    }
+    if (ps->n && (!frequencies || !kd || !r_squared)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ps->ctx->device));
+    hipStream_t q = ps->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const uint64_t e = (uint64_t)rows * cols;
+    // new buffers first: a failure leaves the old parameters and the old store as they were
+    DevBuf nb[4];
+    const size_t want[4] = {8ull * rows * ps->n, 8ull * ps->n, 8ull * ps->n, 8ull * e * ps->n};
+    for (int i = 0; i < 4; ++i) {
+        const int st = dev_ensure(nb[i], want[i], false);
+        if (st != ALN_OK) {
+            for (DevBuf &b : nb) dev_free(b);
+            (void)hipGetLastError();
+            return st == ALN_ERR_OOM ? ALN_ERR_OOM : st;
+        }
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    hipError_t err = hipSuccess;
+    if (ps->n) {
+        err = hipMemcpyAsync(nb[0].p, frequencies, want[0], hipMemcpyHostToDevice, q);
+        if (err == hipSuccess) err = hipMemcpyAsync(nb[1].p, kd, want[1], hipMemcpyHostToDevice, q);
+        if (err == hipSuccess) err = hipMemcpyAsync(nb[2].p, r_squared, want[2], hipMemcpyHostToDevice, q);
+        if (err == hipSuccess) err = hipMemsetAsync(nb[3].p, 0, want[3], q);
+        if (err == hipSuccess) err = hipStreamSynchronize(q);
+    }
+    if (err != hipSuccess) { for (DevBuf &b : nb) dev_free(b); return fail(err, "upload"); }
+    DevBuf *old[4] = {&ps->h_freq, &ps->h_kd, &ps->h_r2, &ps->store};
+    for (int i = 0; i < 4; ++i) { dev_free(*old[i]); *old[i] = nb[i]; }
+    ps->written.assign(ps->n, 0);
+    ps->h_rows = rows; ps->h_cols = cols;
+    ps->heur = true;
+    ps->ms[2] = 0;
+    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->bytes[0] = want[0] + want[1] + want[2]; ps->bytes[1] = 0;
+    return ALN_OK;
+}
+
+extern "C" int aln_pairset_reestimate(aln_pairset *ps, const double *shared_matrix, const uint32_t *which, size_t n, int32_t *status)
+{
+    if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ps->heur) { g_err = "no heuristics set"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && (!which || !status)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n > ps->n) { g_err = "more listed entries than pairs"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!shared_matrix) {
+        if (!ps->held) { g_err = "no held run"; return ALN_ERR_INVALID_ARGUMENT; }
+        if (n && (ps->rows != ps->h_rows || ps->cols != ps->h_cols)) { g_err = "the held run's shape differs from the store's"; return ALN_ERR_INVALID_ARGUMENT; }
+    }
+    std::vector<char> seen(ps->n, 0);
+    std::vector<uint32_t> entries(shared_matrix ? 0 : n);
+    for (size_t k = 0; k < n; ++k) {
+        if (which[k] >= ps->n || seen[which[k]]) { g_err = "which: an entry is out of range or listed twice"; return ALN_ERR_INVALID_ARGUMENT; }
+        seen[which[k]] = 1;
+        if (!shared_matrix) {
+            if (ps->entry_of[which[k]] < 0) { g_err = "a listed pair was not in the last run"; return ALN_ERR_INVALID_ARGUMENT; }
+            entries[k] = (uint32_t)ps->entry_of[which[k]];
+        }
+    }
+    if (n == 0) return ALN_OK;
+    HIPCHK(hipSetDevice(ps->ctx->device));
+    hipStream_t q = ps->slot->stream;
+    const uint64_t e = (uint64_t)ps->h_rows * ps->h_cols;
+    int st;
+    if ((st = dev_ensure(ps->h_list, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->h_status, 4ull * n, false)) != ALN_OK) return st;
+    if (shared_matrix) { if ((st = dev_ensure(ps->shared, 8ull * e, false)) != ALN_OK) return st; }
+    else if ((st = dev_ensure(ps->h_entry, 4ull * n, false)) != ALN_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemcpyAsync(ps->h_list.p, which, 4ull * n, hipMemcpyHostToDevice, q));
+    if (shared_matrix) HIPCHK(hipMemcpyAsync(ps->shared.p, shared_matrix, 8ull * e, hipMemcpyHostToDevice, q));
+    else HIPCHK(hipMemcpyAsync(ps->h_entry.p, entries.data(), 4ull * n, hipMemcpyHostToDevice, q));
+    PairsetTransformArgs a{};
+    a.shared = shared_matrix ? ps->shared.as<double>() : nullptr;
+    a.own = nullptr;
+    a.held = ps->held_info.as<PairsetHeld>(); a.res = ps->held_res.as<aln_pair_result>(); a.tb = ps->held_tb.as<uint8_t>();
+    a.entry = ps->h_entry.as<uint32_t>();
+    a.par = a.dst_index = ps->h_list.as<uint32_t>();
+    a.freq = ps->h_freq.as<double>(); a.kd = ps->h_kd.as<double>(); a.r2 = ps->h_r2.as<double>();
+    a.dst = ps->store.as<double>();
+    a.status = ps->h_status.as<int32_t>();
+    a.n_list = (uint32_t)n; a.n_held = (uint32_t)ps->n_held; a.rows = ps->h_rows; a.cols = ps->h_cols; a.blank = ps->blank;
+    HIPCHK(hipEventRecord(ps->ev[4], q));
+    if (aln_pairset_launch_transform(&a, q) != 0) { g_err = "per-pair matrices hold 1 .. 1024 entries"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ps->ev[5], q));
+    HIPCHK(hipMemcpyAsync(status, ps->h_status.p, 4ull * n, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    for (size_t k = 0; k < n; ++k) if (status[k] == 0) ps->written[which[k]] = 1;
+    ps->ms[2] = ev_ms(ps->ev[4], ps->ev[5]);
+    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->bytes[0] = (shared_matrix ? 4ull * n + 8ull * e : 8ull * n); ps->bytes[1] = 4ull * n;
+    return ALN_OK;
+}
+
+extern "C" int aln_pairset_matrices(aln_pairset *ps, const uint32_t *which, size_t n, double *out)
+{
+    if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ps->heur) { g_err = "no heuristics set"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && (!which || !out)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    for (size_t k = 0; k < n; ++k)
+        if (which[k] >= ps->n || !ps->written[which[k]]) { g_err = "which: a pair is out of range or its store entry was never written"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return ALN_OK;
+    if (n > 0xFFFFFFF0ull) { g_err = "too many entries"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ps->ctx->device));
+    hipStream_t q = ps->slot->stream;
+    const uint64_t e = (uint64_t)ps->h_rows * ps->h_cols;
+    int st;
+    if ((st = dev_ensure(ps->h_list, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->picked, 8ull * e * n, false)) != ALN_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemcpyAsync(ps->h_list.p, which, 4ull * n, hipMemcpyHostToDevice, q));
+    HIPCHK(hipEventRecord(ps->ev[4], q));
+    aln_pairset_launch_pick(ps->store.as<double>(), ps->h_list.as<uint32_t>(), (uint32_t)n, (uint32_t)e, ps->picked.as<double>(), q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ps->ev[5], q));
+    HIPCHK(hipMemcpyAsync(out, ps->picked.p, 8ull * e * n, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    ps->ms[2] = ev_ms(ps->ev[4], ps->ev[5]);
+    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->bytes[0] = 4ull * n; ps->bytes[1] = 8ull * e * n;
+    return ALN_OK;
+}
+
+// transform_matrix for n matrices on the device (the context's first): aln_transform_matrices with aln_pairset_transform_kernel
+extern "C" int aln_transform_matrices_device(aln_ctx *ctx, size_t n, uint32_t rows, uint32_t cols, const double *matrices_in,
+                                             const double *frequencies, const double *kd, const double *r_squared, double *matrices_out,
+                                             int32_t *status)
+{
+    if (!ctx) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return ALN_OK;
+    if (!matrices_in || !frequencies || !kd || !r_squared || !matrices_out || !status || rows == 0 || cols == 0 ||
+        (uint64_t)rows * cols > ALN_PAIRSET_MAX_ENTRIES) {
+        g_err = "null argument, or a matrix outside 1 .. 1024 entries";
+        return ALN_ERR_INVALID_ARGUMENT;
+    }
+    HIPCHK(hipSetDevice(ctx->devs[0]->device));
+    const size_t e = (size_t)rows * cols;
+    const size_t step = std::max<size_t>(1, std::min<size_t>(n, (256ull << 20) / (8 * e)));      // at most 256 MiB of matrices at a time
+    DevBuf m, fr, k, r, stt;
+    std::vector<double> back(step * e);
+    int st = ALN_OK;
+    auto body = [&]() -> int {
+        int s2;
+        if ((s2 = dev_ensure(m, 8 * e * step, false)) != ALN_OK || (s2 = dev_ensure(fr, 8ull * rows * step, false)) != ALN_OK ||
+            (s2 = dev_ensure(k, 8 * step, false)) != ALN_OK || (s2 = dev_ensure(r, 8 * step, false)) != ALN_OK ||
+            (s2 = dev_ensure(stt, 4 * step, false)) != ALN_OK)
+            return s2;
+        for (size_t first = 0; first < n; first += step) {
+            const size_t c = std::min(step, n - first);
+            HIPCHK(hipMemcpy(m.p, matrices_in + first * e, 8 * e * c, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(fr.p, frequencies + first * rows, 8ull * rows * c, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(k.p, kd + first, 8 * c, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(r.p, r_squared + first, 8 * c, hipMemcpyHostToDevice));
+            PairsetTransformArgs a{};
+            a.own = m.as<double>();
+            a.freq = fr.as<double>(); a.kd = k.as<double>(); a.r2 = r.as<double>();
+            a.dst = m.as<double>();                                  // in place: a wave holds its source in LDS before it writes
+            a.status = stt.as<int32_t>();
+            a.n_list = (uint32_t)c; a.rows = rows; a.cols = cols;
+            if (aln_pairset_launch_transform(&a, nullptr) != 0) { g_err = "a matrix outside 1 .. 1024 entries"; return ALN_ERR_INVALID_ARGUMENT; }
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpy(status + first, stt.p, 4 * c, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(back.data(), m.p, 8 * e * c, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < c; ++i)                           // a matrix without a root is left as it was
+                if (status[first + i] == 0) memcpy(matrices_out + (first + i) * e, back.data() + i * e, 8 * e);
+        }
+        return ALN_OK;
+    };
+    st = body();
+    DevBuf *d[] = {&m, &fr, &k, &r, &stt};
+    for (DevBuf *b : d) dev_free(*b);
+    return st;
 }
 
 // `which` -> held entries (uploaded into ps->list); INVALID_ARGUMENT for a pair that was not in the last run

@@ -160,12 +160,15 @@ def align_many(pairs, del_, ext, matrix, heuristics, alphabet=None, transform="n
     frequency matrices counted on the device and transformed on the host.
 
     heuristics: one Heuristics, or one per pair.  transform: "numpy" (transform_matrix per pair: the single-pair class's bits by
-    construction) or "native" (aln_transform_matrices, the same order of operations in the library's host code).  Returns the
+    construction), "native" (aln_transform_matrices, the same order of operations in the library's host code) or "resident" (the
+    same order again in a kernel: the parameters go up once, PairSet.reestimate rebuilds the matrices on the device from the held
+    strings, run_stored aligns under them, and only the matrices of finished pairs come back).  Returns the
     AlignmentResults in input order, `matrix` being the matrix of the pair's last run.  A pair on which the reference panics
     (empty sequence, code outside the matrix, no positive cell, WrongMatrixSpecified) gives the same ReferencePanic: raised for the
     first such pair (errors="raise") or returned in its place (errors="return").  The matrix must be volume x volume of the
     alphabet (the shape of the frequency matrices) and hold at most 1024 entries.
-    backend: a factory (pairs, device) -> object with run / frequencies / strings / close (tests)."""
+    backend: a factory (pairs, device) -> object with run / frequencies / strings / close (tests); in "resident" mode with
+    set_heuristics / reestimate / run_stored / matrices / strings / close."""
     from . import _ffi
     from . import runtime
     from .alignment import Alignment, AlignmentResult
@@ -176,8 +179,9 @@ def align_many(pairs, del_, ext, matrix, heuristics, alphabet=None, transform="n
         raise AlignerError(ErrorKind.MissingArgument)                           # heuristic/mod.rs:42-45
     if errors not in ("raise", "return"):
         raise ValueError("errors: 'raise' or 'return'")
-    if transform not in ("numpy", "native"):
-        raise ValueError("transform: 'numpy' or 'native'")
+    if transform not in ("numpy", "native", "resident"):
+        raise ValueError("transform: 'numpy', 'native' or 'resident'")
+    resident = transform == "resident"
     pairs = [(np.array(q, dtype=np.uint8), np.array(t, dtype=np.uint8)) for q, t in pairs]
     n = len(pairs)
     m = np.asarray(matrix, dtype=np.float64)
@@ -204,9 +208,16 @@ def align_many(pairs, del_, ext, matrix, heuristics, alphabet=None, transform="n
     blank = alphabet.blank()
     active = list(range(n))
     max_f = np.zeros(n, dtype=np.float64)
-    current = dict(zip(active, _transform_batch(transform, [m] * n, params)))
+    if not resident:
+        current = dict(zip(active, _transform_batch(transform, [m] * n, params)))
     ps = backend(pairs, device)
     try:
+        if resident:                                                            # current[i]: True, the matrix being store entry i
+            ps.set_heuristics(m.shape[0], m.shape[1], np.asarray([np.asarray(h.frequencies, dtype=np.float64) for h in params]),
+                              np.asarray([h.kd for h in params], dtype=np.float64),
+                              np.asarray([h.r_squared for h in params], dtype=np.float64))
+            status = ps.reestimate(active, matrix=m)
+            current = {i: True if status[k] == 0 else _wrong_matrix_panic() for k, i in enumerate(active)}
         while active:
             going = []
             for i in active:                                                    # `.unwrap()` at heuristic/mod.rs:53, :71
@@ -217,7 +228,10 @@ def align_many(pairs, del_, ext, matrix, heuristics, alphabet=None, transform="n
             active = going
             if not active:
                 break
-            res = ps.run(_ffi.CORE_LOCAL, del_, ext, np.asarray([current[i] for i in active], dtype=np.float64), active, blank=blank)
+            if resident:
+                res = ps.run_stored(_ffi.CORE_LOCAL, del_, ext, active, blank=blank)
+            else:
+                res = ps.run(_ffi.CORE_LOCAL, del_, ext, np.asarray([current[i] for i in active], dtype=np.float64), active, blank=blank)
             done, more = [], []
             for k, i in enumerate(active):
                 st = int(res["status"][k])
@@ -234,13 +248,21 @@ def align_many(pairs, del_, ext, matrix, heuristics, alphabet=None, transform="n
                     done.append(i)
             if done:
                 summ, strs = ps.strings(done)
+                if resident:
+                    for i, mat in zip(done, ps.matrices(done)):
+                        current[i] = mat.copy()
                 for k, i in enumerate(done):
                     r = summ[k]
                     coords = ((int(r["start_x"]) + 1, int(r["end_x"]) + 1), (int(r["start_y"]) + 1, int(r["end_y"]) + 1))
                     aln = Alignment(alphabet, strs[k][0], strs[k][1], coords, float(r["f"]))
                     out[i] = AlignmentResult(aln, matrix=current.pop(i), score=float(r["score"]),      # :73-75
                                              summary={name: r[name].item() for name in r.dtype.names})
-            if more:
+            if more and resident:
+                status = ps.reestimate(more)
+                for k, i in enumerate(more):
+                    if status[k] != 0:
+                        current[i] = _wrong_matrix_panic()
+            elif more:
                 counts = ps.frequencies(more)
                 new = _transform_batch(transform, [counts[k].astype(np.float64) for k in range(len(more))], [params[i] for i in more])
                 for i, mat in zip(more, new):

@@ -4,6 +4,10 @@ The device-resident form of the loop of HeuristicAligner (aligner-core/src/heuri
 `run` aligns the listed pairs, each under a real-valued matrix of its own, and leaves the walked strings on the device;
 `frequencies` counts Alignment::get_frequency_matrix (alignment.rs:13-23) there for the pairs that go on, `strings` fetches
 the pairs that are done.  heuristic.align_many drives it.
+
+The matrices can stay in HBM as well: `set_heuristics` uploads every pair's transform parameters once, `reestimate` rebuilds the
+listed pairs' matrices on the device (from one shared matrix, or from the counts of their held strings) into a resident store,
+`run_stored` aligns under the store's entries and `matrices` downloads the entries of the pairs that are done.
 """
 import ctypes as C
 
@@ -90,16 +94,62 @@ class PairSet:
             out.append((tb[o:o + n].copy(), tb[o + c:o + c + n].copy()))
         return res, out
 
+    def set_heuristics(self, rows, cols, frequencies, kd, r_squared):
+        """Every pair's transform parameters (frequencies (n, rows), kd and r_squared scalars or (n,)), uploaded once; reserves the
+        store of one rows x cols matrix per pair and clears it."""
+        n = len(self)
+        fr = np.ascontiguousarray(frequencies, dtype=np.float64)
+        if fr.shape != (n, rows):
+            raise ValueError("frequencies: (n_pairs, rows)")
+        kd = np.ascontiguousarray(np.broadcast_to(np.asarray(kd, dtype=np.float64), (n,)))
+        r2 = np.ascontiguousarray(np.broadcast_to(np.asarray(r_squared, dtype=np.float64), (n,)))
+        st = self.lib.aln_pairset_heuristics(self.handle, int(rows), int(cols), fr.ctypes.data, kd.ctypes.data, r2.ctypes.data)
+        runtime.raise_for_status(st, "aln_pairset_heuristics")
+        self.store_shape = (int(rows), int(cols))
+
+    def reestimate(self, which, matrix=None):
+        """store[which[k]] = transform_matrix(source, pair which[k]'s parameters) on the device; the source is `matrix` for every
+        listed pair, or (None) the frequency counts of the pair's held strings.  Returns status (len(which),) int32: 0, or
+        _ffi.TRANSFORM_NO_ROOT (the store entry is then unchanged)."""
+        w = np.ascontiguousarray(which, dtype=np.uint32)
+        m = None
+        if matrix is not None:
+            m = np.ascontiguousarray(matrix, dtype=np.float64)
+            if m.shape != getattr(self, "store_shape", None):
+                raise ValueError("matrix: the shape given to set_heuristics")
+        status = np.zeros(len(w), dtype=np.int32)
+        st = self.lib.aln_pairset_reestimate(self.handle, m.ctypes.data if m is not None else None, w.ctypes.data, len(w), status.ctypes.data)
+        runtime.raise_for_status(st, "aln_pairset_reestimate")
+        return status
+
+    def run_stored(self, semantics, del_, ext, active, blank=98, force_serial=False, max_passes=0):
+        """`run` with entry k scored by the store entry of pair active[k]."""
+        act = np.ascontiguousarray(active, dtype=np.uint32)
+        rows, cols = getattr(self, "store_shape", None) or (0, 0)
+        p = _ffi.Params(int(semantics), 0, float(del_), float(ext), None, rows, cols, cols, 0, int(blank), 0, int(bool(force_serial)), 0,
+                        int(max_passes))
+        res = np.zeros(len(act), dtype=RESULT_DTYPE)
+        st = self.lib.aln_pairset_run_stored(self.handle, C.byref(p), act.ctypes.data, len(act), res.ctypes.data)
+        runtime.raise_for_status(st, "aln_pairset_run_stored")
+        self.shape = (rows, cols)
+        return res
+
+    def matrices(self, which):
+        """f64 (len(which), rows, cols): the store entries of the listed pairs."""
+        w = np.ascontiguousarray(which, dtype=np.uint32)
+        rows, cols = getattr(self, "store_shape", None) or (0, 0)
+        out = np.zeros((len(w), rows, cols), dtype=np.float64)
+        st = self.lib.aln_pairset_matrices(self.handle, w.ctypes.data, len(w), out.ctypes.data)
+        runtime.raise_for_status(st, "aln_pairset_matrices")
+        return out
+
     def stats(self):
         ms, by = (C.c_double * 4)(), (C.c_uint64 * 2)()
         runtime.raise_for_status(self.lib.aln_pairset_stats(self.handle, ms, by), "aln_pairset_stats")
         return dict(fill_ms=ms[0], traceback_ms=ms[1], fetch_kernel_ms=ms[2], wall_ms=ms[3], bytes_up=int(by[0]), bytes_down=int(by[1]))
 
 
-def transform_matrices(matrices, frequencies, kd, r_squared):
-    """aln_transform_matrices: transform_matrix (heuristic.py) for n matrices at once, in the library's host code -- the same bits as
-    the numpy mirror (aligner_amd/csrc/aln_transform_rules.h).  matrices (n, rows, cols), frequencies (n, rows), kd and r_squared
-    scalars or (n,).  Returns (out (n, rows, cols), status (n,) int32: 0, or _ffi.TRANSFORM_NO_ROOT = WrongMatrixSpecified)."""
+def _transform(context, matrices, frequencies, kd, r_squared):
     lib = _ffi.load()
     m = np.ascontiguousarray(matrices, dtype=np.float64)
     if m.ndim != 3:
@@ -112,8 +162,22 @@ def transform_matrices(matrices, frequencies, kd, r_squared):
     r2 = np.ascontiguousarray(np.broadcast_to(np.asarray(r_squared, dtype=np.float64), (n,)))
     out = np.zeros_like(m)
     status = np.zeros(n, dtype=np.int32)
-    st = lib.aln_transform_matrices(n, rows, cols, m.ctypes.data, fr.ctypes.data, kd.ctypes.data, r2.ctypes.data, out.ctypes.data,
-                                    status.ctypes.data)
+    args = (n, rows, cols, m.ctypes.data, fr.ctypes.data, kd.ctypes.data, r2.ctypes.data, out.ctypes.data, status.ctypes.data)
+    name = "aln_transform_matrices" if context is None else "aln_transform_matrices_device"
+    st = lib.aln_transform_matrices(*args) if context is None else lib.aln_transform_matrices_device(context, *args)
     if st != _ffi.OK:
-        raise ValueError("aln_transform_matrices: %s" % _ffi.STATUS_NAMES.get(st, st))
+        raise ValueError("%s: %s" % (name, _ffi.STATUS_NAMES.get(st, st)))
     return out, status
+
+
+def transform_matrices(matrices, frequencies, kd, r_squared):
+    """aln_transform_matrices: transform_matrix (heuristic.py) for n matrices at once, in the library's host code -- the same bits as
+    the numpy mirror (aligner_amd/csrc/aln_transform_rules.h).  matrices (n, rows, cols), frequencies (n, rows), kd and r_squared
+    scalars or (n,).  Returns (out (n, rows, cols), status (n,) int32: 0, or _ffi.TRANSFORM_NO_ROOT = WrongMatrixSpecified)."""
+    return _transform(None, matrices, frequencies, kd, r_squared)
+
+
+def transform_matrices_device(matrices, frequencies, kd, r_squared, device=None):
+    """aln_transform_matrices_device: transform_matrices computed on the GPU by the kernel of PairSet.reestimate (at most 1024 entries
+    per matrix): the same arguments, the same results bit for bit."""
+    return _transform(runtime.context(device), matrices, frequencies, kd, r_squared)

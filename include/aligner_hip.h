@@ -261,7 +261,26 @@ int aln_shuffle_targets(aln_ctx *ctx, const aln_shuffle_spec *spec, const uint8_
  * aligned target q_len + t_len + 2 bytes later; tb_buf optional).
  * A which[k] that was not in the last run, a fetch without a run: ALN_ERR_INVALID_ARGUMENT, nothing written.
  * stats: ms[0] fill kernels and ms[1] traceback kernels of the last run, ms[2] kernels of the last fetch, ms[3] wall time of the
- * last call; bytes moved by the last call (host -> device, device -> host). ---- */
+ * last call; bytes moved by the last call (host -> device, device -> host).
+ *
+ * The loop's matrices can stay on the device as well (additions of the same ABI version; run, frequencies and strings are unchanged):
+ * heuristics: uploads every pair's transform parameters once (frequencies[i * rows .. + rows), kd[i], r_squared[i] of pair i) and
+ * reserves the STORE, one rows x cols f64 matrix per pair, rows * cols in 1 .. ALN_PAIRSET_MAX_ENTRIES.  If the memory cannot be had:
+ * ALN_ERR_OOM, parameters and store as before.  A later call replaces the parameters and clears the store.
+ * reestimate: for listed pair which[k], store[which[k]] = transform_matrix(source, that pair's parameters), computed by one wave per
+ * pair (aligner_amd/csrc/aln_pairset.hip) in the operation order of aligner_amd/csrc/aln_transform_rules.h: the bits of
+ * aln_transform_matrices.  The source is shared_matrix (rows * cols doubles) if given, otherwise the frequency counts of the pair's
+ * held strings of the last run, counted as `frequencies` counts them.  status[k] = 0, or ALN_TRANSFORM_NO_ROOT, and then the store
+ * entry is left as it was.  ALN_ERR_INVALID_ARGUMENT, nothing written: no parameters set; a pair listed twice or out of range;
+ * without a shared matrix a pair that was not in the last run, no held run, or a held run of another shape than the store's.
+ * 4 bytes per listed pair go up (8 without a shared matrix: the pair and its held entry; rows * cols * 8 once with one), 4 come back.
+ * run_stored: `run` with entry k scored by store[active[k]]; the listed entries are gathered on the device, so the call's uploads
+ * are those of `run` less its 8 * rows * cols * n_active bytes of matrices, plus 4 bytes per pair for the list.  Checks, chunking,
+ * held state and per-pair failures as `run`; in addition ALN_ERR_INVALID_ARGUMENT for no parameters set, params->rows / cols other
+ * than the store's, and a listed pair whose store entry was never written.
+ * matrices: downloads the listed store entries (8 * rows * cols bytes each) in the order listed; an entry that was never written or
+ * out of range: ALN_ERR_INVALID_ARGUMENT, nothing written.
+ * stats after these calls: ms[2] = the transform kernel (reestimate) or the gather kernel (run_stored, matrices), bytes[] as above. ---- */
 #define ALN_PAIRSET_MAX_ENTRIES 1024u
 typedef struct aln_pairset aln_pairset;
 aln_pairset *aln_pairset_create(aln_ctx *ctx, const uint8_t *seqs, const uint64_t *q_off, const uint64_t *q_len, const uint64_t *t_off,
@@ -273,6 +292,12 @@ int aln_pairset_strings(aln_pairset *ps, const uint32_t *which, size_t n, aln_pa
                         const uint64_t *tb_off);
 int aln_pairset_stats(const aln_pairset *ps, double *ms /* 4 */, uint64_t *bytes /* 2 */);
 void aln_pairset_destroy(aln_pairset *ps);
+int aln_pairset_heuristics(aln_pairset *ps, uint32_t rows, uint32_t cols, const double *frequencies /* n_pairs * rows */,
+                           const double *kd /* n_pairs */, const double *r_squared /* n_pairs */);
+int aln_pairset_reestimate(aln_pairset *ps, const double *shared_matrix /* rows * cols, or NULL */, const uint32_t *which, size_t n,
+                           int32_t *status);
+int aln_pairset_run_stored(aln_pairset *ps, const aln_params *params, const uint32_t *active, size_t n_active, aln_pair_result *results);
+int aln_pairset_matrices(aln_pairset *ps, const uint32_t *which, size_t n, double *out);
 
 /* ---- resident sequence set (the request path, aligner-web dispatcher/handlers.rs:104,253-264 generate_pairs: every pair i < j of
  * a FASTA; blast_p_value_cmp.rs and calc: rows of (query, target) drawn from one table): S sequences are uploaded once (one device:
@@ -334,6 +359,12 @@ int aln_seqset_stats(const aln_seqset *set, double *ms /* 4 */, uint64_t *bytes 
 #define ALN_TRANSFORM_NO_ROOT 1
 int aln_transform_matrices(size_t n, uint32_t rows, uint32_t cols, const double *matrices_in, const double *frequencies,
                            const double *kd, const double *r_squared, double *matrices_out, int32_t *status);
+/* The same contract, status codes and bits, computed on the context's first device by the kernel of aln_pairset_reestimate (host
+ * buffers in and out; in place allowed).  rows * cols in 1 .. ALN_PAIRSET_MAX_ENTRIES; beyond that, a null context, a null pointer
+ * with n != 0: ALN_ERR_INVALID_ARGUMENT. */
+int aln_transform_matrices_device(aln_ctx *ctx, size_t n, uint32_t rows, uint32_t cols, const double *matrices_in,
+                                  const double *frequencies, const double *kd, const double *r_squared, double *matrices_out,
+                                  int32_t *status);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
-"""The heuristic loop for many pairs at once: heuristic.align_many (one resident pair set, per-pair matrices) with each transform,
-split into kernels, transfers and host transform; a loop of single HeuristicAligner calls on a sample of the same pairs; and one
+"""The heuristic loop for many pairs at once: heuristic.align_many (one resident pair set, per-pair matrices) with each transform
+(numpy and native on the host, resident on the device), split into fill, transform kernel, transfers and host transform; a loop of single HeuristicAligner calls on a sample of the same pairs; and one
 aln_pairset_run against aln_align_batch (f64 kernels forced) on the same pairs with one shared matrix.
 usage: python tools/bench_heuristic.py [n=2000] [sample=200]"""
 import sys, time
@@ -39,16 +39,26 @@ class Timed(PairSet):
         t0 = time.perf_counter(); r = fn(*a, **kw); dt = time.perf_counter() - t0
         st = self.stats()
         acc[name] = acc.get(name, 0.0) + dt
-        acc["kernels"] = acc.get("kernels", 0.0) + (st["fill_ms"] + st["traceback_ms"] if name == "run" else st["fetch_kernel_ms"]) * 1e-3
+        run = name in ("run", "run_stored")
+        acc["kernels"] = acc.get("kernels", 0.0) + ((st["fill_ms"] + st["traceback_ms"] if run else 0.0) + st["fetch_kernel_ms"]) * 1e-3
+        if name == "reestimate":
+            acc["transform_kernel"] = acc.get("transform_kernel", 0.0) + st["fetch_kernel_ms"] * 1e-3
         acc["bytes"] = acc.get("bytes", 0) + st["bytes_up"] + st["bytes_down"]
-        if name == "run":
+        acc["up"] = acc.get("up", 0) + st["bytes_up"]
+        acc["down"] = acc.get("down", 0) + st["bytes_down"]
+        if run:
+            acc["run"] = acc.get("run", 0.0) + (dt if name != "run" else 0.0)
             acc["runs"] = acc.get("runs", 0) + 1
-            acc["pair_runs"] = acc.get("pair_runs", 0) + len(a[5])
+            acc["pair_runs"] = acc.get("pair_runs", 0) + len(a[5] if name == "run" else a[4])
         return r
 
     def run(self, *a, **kw): return self._t("run", PairSet.run, self, *a, **kw)
     def frequencies(self, *a): return self._t("frequencies", PairSet.frequencies, self, *a)
     def strings(self, *a): return self._t("strings", PairSet.strings, self, *a)
+    def set_heuristics(self, *a): return self._t("set_heuristics", PairSet.set_heuristics, self, *a)
+    def reestimate(self, *a, **kw): return self._t("reestimate", PairSet.reestimate, self, *a, **kw)
+    def run_stored(self, *a, **kw): return self._t("run_stored", PairSet.run_stored, self, *a, **kw)
+    def matrices(self, *a): return self._t("matrices", PairSet.matrices, self, *a)
 
 
 inner = heuristic._transform_batch
@@ -58,19 +68,23 @@ def timed_transform(*a):
 heuristic._transform_batch = timed_transform
 
 results = {}
-for how in ("numpy", "native"):
+for how in ("numpy", "native", "resident"):
     for rep in range(2):                      # the second run is reported (buffers and code objects warm)
         acc.clear()
         t0 = time.perf_counter()
         results[how] = heuristic.align_many(pairs, 11.0, 2.0, S, hs, Protein, transform=how, backend=Timed)
         wall = time.perf_counter() - t0
-    calls = acc["run"] + acc.get("frequencies", 0) + acc.get("strings", 0)
-    print("align_many %-6s: %8.1f ms wall = %7.1f kernels + %7.1f transfers and call overhead + %7.1f host transform + %7.1f driver; "
-          "%d runs, %d pair-runs, %.1f MB moved" % (how, wall * 1e3, acc["kernels"] * 1e3, (calls - acc["kernels"]) * 1e3,
-                                                   acc["transform"] * 1e3, (wall - calls - acc["transform"]) * 1e3, acc["runs"],
-                                                   acc["pair_runs"], acc["bytes"] / 1e6))
-same = all(a.alignment.f == b.alignment.f and a.matrix.tobytes() == b.matrix.tobytes() for a, b in zip(results["numpy"], results["native"]))
-print("numpy and native transforms give the same results: %s" % same)
+    calls = sum(acc.get(k, 0) for k in ("run", "frequencies", "strings", "set_heuristics", "reestimate", "matrices"))
+    host = acc.get("transform", 0.0)
+    print("align_many %-8s: %8.1f ms wall = %7.1f kernels (of them %6.2f transform kernel) + %7.1f transfers and call overhead + %7.1f host "
+          "transform + %7.1f driver; %d runs, %d pair-runs, %.1f ms per run, %.1f MB moved, per pair-run %.0f bytes up, %.0f down"
+          % (how, wall * 1e3, acc["kernels"] * 1e3, acc.get("transform_kernel", 0.0) * 1e3, (calls - acc["kernels"]) * 1e3, host * 1e3,
+             (wall - calls - host) * 1e3, acc["runs"], acc["pair_runs"], wall * 1e3 / acc["runs"], acc["bytes"] / 1e6,
+             acc["up"] / acc["pair_runs"], acc["down"] / acc["pair_runs"]))
+same = all(a.alignment.f == b.alignment.f and a.matrix.tobytes() == b.matrix.tobytes() and a.matrix.tobytes() == c.matrix.tobytes()
+           and a.alignment.query.tobytes() == c.alignment.query.tobytes()
+           for a, b, c in zip(results["numpy"], results["native"], results["resident"]))
+print("numpy, native and resident transforms give the same results: %s" % same)
 
 idx = rng.choice(n, min(sample, n), replace=False)
 t0 = time.perf_counter()
