@@ -18,6 +18,8 @@
 // order: legacy).
 // Per cell (core local): v_cmp, v_cndmask (penalty), v_add, v_add3, v_add_sdwa, v_max3, v_and_or, v_max_u32 (tag 3),
 // v_alignbit, v_lshl_add, half a v_max3 = 10.5 VALU instructions; core global / legacy global: 6.
+// A step runs its cells in two phases: first every row's diagonal key (the v_add_sdwa, from the lane state as the last step
+// left it), then the chain down the rows, which overwrites each row's carried cell in place (v_diag_keys, v_cell_chain).
 // Two kernels use this file: the batch kernel (one wave per pair, strips in sequence, C++ step below) and the single-pair
 // kernel (one wave per strip; its steady state is the generated asm of aln_single_unit.inc, see steady_run).
 #pragma once
@@ -49,8 +51,8 @@ __device__ __forceinline__ int v_pack11(int t, int kterm)      // (t << 11) + kt
     asm("v_lshl_add_u32 %0, %1, 11, %2" : "=v"(d) : "v"(t), "s"(kterm));
     return d;
 }
-// The heart of a cell as ONE statement (hipcc pads every asm statement with a wait state, so one statement per cell,
-// not one per instruction).  pw holds four int8 profile scores; B selects this row's byte:
+// The cell as ONE statement, diagonal key included: the two-pairs-per-wave kernel (duo_fill, aln_kernels.hip).  pw holds four int8
+// profile scores; B selects this row's byte:
 //   c = diag + sext(pw.byte[B]);  key = max3(top + negp, left + negp - 1, c);  nt = (key & ~3) | 2
 #define ALN_CELL_ASM(BYTE)                                                                                    \
     asm("v_add_u32_sdwa %0, %8, sext(%9) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:" BYTE "\n\t" \
@@ -70,6 +72,43 @@ __device__ __forceinline__ void v_cell(int top, int left, int negp, int diag, ui
     else ALN_CELL_ASM("BYTE_3");
 }
 #undef ALN_CELL_ASM
+// FastStrip::step: the heart of a cell in TWO phases (hipcc pads every asm statement with a wait state, so one statement per group of
+// instructions, not one per instruction).
+// Phase A, before the serial chain: the diagonal keys of up to four rows, one statement per profile word.  pw holds four
+// int8 profile scores, row j of the word takes byte j:  c[j] = d[j] + sext(pw.byte[j]),  d[j] = the OLD value of the cell
+// to the left of the row above (hdiag for row 0, Tl[r - 1] otherwise) -- none of them depends on this step's chain.
+#define ALN_DIAG_LINE(OUT, IN, PW, BYTE)                                                                       \
+    "v_add_u32_sdwa %" OUT ", %" IN ", sext(%" PW ") dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_" BYTE
+template <int NB>
+__device__ __forceinline__ void v_diag_keys(const int *d, uint32_t pw, int *c)
+{
+    if constexpr (NB == 1)
+        asm(ALN_DIAG_LINE("0", "1", "2", "0") : "=v"(c[0]) : "v"(d[0]), "v"(pw));
+    else if constexpr (NB == 2)
+        asm(ALN_DIAG_LINE("0", "2", "4", "0") "\n\t" ALN_DIAG_LINE("1", "3", "4", "1")
+            : "=&v"(c[0]), "=&v"(c[1]) : "v"(d[0]), "v"(d[1]), "v"(pw));
+    else if constexpr (NB == 3)
+        asm(ALN_DIAG_LINE("0", "3", "6", "0") "\n\t" ALN_DIAG_LINE("1", "4", "6", "1") "\n\t" ALN_DIAG_LINE("2", "5", "6", "2")
+            : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]) : "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(pw));
+    else
+        asm(ALN_DIAG_LINE("0", "4", "8", "0") "\n\t" ALN_DIAG_LINE("1", "5", "8", "1") "\n\t" ALN_DIAG_LINE("2", "6", "8", "2") "\n\t"
+            ALN_DIAG_LINE("3", "7", "8", "3")
+            : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3]) : "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(pw));
+}
+#undef ALN_DIAG_LINE
+// Phase B, the chain, one statement per cell:  key = max3(top + negp, left + negp - 1, c);  nt = (key & ~3) | 2.  `tl` is the
+// row's carried cell: read as Left and overwritten with nt in the same register -- its old value has no reader left, the row
+// below took its diagonal key in phase A -- so a step under an exec mask needs no copy to put the new state back.
+__device__ __forceinline__ void v_cell_chain(int top, int &tl, int negp, int c, int &key)
+{
+    int b;
+    asm("v_add_u32 %0, %3, %4\n\t"
+        "v_add3_u32 %1, %2, %4, -1\n\t"
+        "v_max3_i32 %0, %0, %1, %5\n\t"
+        "v_and_or_b32 %2, %0, -4, 2"
+        : "=&v"(key), "=&v"(b), "+v"(tl)
+        : "v"(top), "v"(negp), "v"(c));
+}
 
 // a lane's R profile bytes are read as one LDS word of RP = 1, 2, 4 or 8 bytes (R rounded up), RP-aligned
 template <int RP> struct ProfWordP;
@@ -233,6 +272,8 @@ struct FastStrip {
     static constexpr bool QRING = !SINGLE && !PWM;
     // ... and a strip with a strip above it reads the next step's boundary cell from the wave's boundary ring one step ahead (top0v)
     static constexpr bool BRING = QRING && !FIRST;
+    // strip 0 of a local batch fill: the row above is the constant border (see topIn in step)
+    static constexpr bool BORDER2 = !SINGLE && FIRST && LOCAL;
     static constexpr int QSHIFT = RP == 8 ? 9 : RP == 4 ? 8 : RP == 2 ? 7 : 6;      // a code's profile row: 64 * RP bytes
     using PW = typename ProfWord<R>::T;
     const FastIn in;
@@ -245,10 +286,14 @@ struct FastStrip {
     uint32_t cchg;             // repair: a column of this lane's whose bottom-row cell changed (0: none)
     bool zsel_on, brow_bad, aborted;
     int Tl[R], rbv[R];
-    int hdiag, bottom, qoff, inchunk, qchunk, outq;
+    // hdiag: the cell above-left of row 0 (topIn of the last step).  BORDER2 relies on lane 0 of it being 2 for the whole strip -- set so in
+    // run(), and wave_shr:1 never writes lane 0 --: whatever re-initialises it or restores it from a checkpoint must keep that, and
+    // likewise lanes 1 .. 63 of cmp2 (below) stay 2.
+    int hdiag, qoff, inchunk, qchunk, outq;
     uint32_t advchunk, dw;
     PW pw;
     const uint8_t *prow;       // this lane's column of the profile: prof + lane*R
+    int cmp2;                  // batch kernels, core local strip 0: 2, but for lane 0, which every step rewrites (row 1's penalty select)
     uint32_t qaddr;            // batch kernels (QRING): LDS address of the code this lane reads in the first step of the current block
     uint32_t baddr;            // batch kernels (BRING): LDS address of the boundary cell read in the first step of the current block
 
@@ -358,13 +403,27 @@ struct FastStrip {
         if (FIRST) top0 = LOCAL ? 2 : ((k + 1 == N) ? 2 + (int)(N + 1) * in.nd4 : 2 + (int)(k + 1) * in.nd4);
         else if (SINGLE || BRING) top0 = top0v;                 // read from the LDS ring one step ago
         else top0 = __builtin_amdgcn_readlane(inchunk, sel);
-        const int topIn = shr1_i(top0, bottom);                 // lane 0 <- row above the strip, lane l <- lane l-1
+        // phase A: every row's diagonal key from the untouched Tl[] and hdiag (for every lane, whether its column exists or not)
+        const PW pwc = pw;                                      // profile bytes of THIS step (loaded one step ago)
+        int dsrc[R], c[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) dsrc[r] = r == 0 ? hdiag : Tl[r - 1];
+        if (SEM == ALN_LEGACY_LOCAL) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) c[r] = dsrc[r] + prof_byte<R>(pwc, r);
+        } else {
+            v_diag_keys<(R < 4 ? R : 4)>(dsrc, prof_word<R>(pwc, 0), c);
+            if constexpr (R > 4) v_diag_keys<R - 4>(dsrc + 4, prof_word<R>(pwc, 4), c + 4);
+        }
+        // lane 0 <- row above the strip, lane l <- lane l-1.  Strip 0 of a local batch fill: the row above is the border, T = 2 in
+        // every column, and so is lane 0 of hdiag, which wave_shr:1 never writes: hdiag, whose last reader was phase A, is the DPP's
+        // `old` operand and becomes topIn in place, instead of a constant moved into a fresh register every step.
+        const int topIn = BORDER2 ? shr1_i(hdiag, Tl[R - 1]) : shr1_i(top0, Tl[R - 1]);
         if (SINGLE && !FIRST) top0v = bring[(k + 1) & 127u];    // next step's boundary cell (broadcast read)
         if (BRING) top0v = bring_get(baddr + 4u * (uint32_t)kk);
         // cross-lane reads stay in wave-uniform control flow: inside a divergent branch the compiler may compute
         // their operand for the active lanes only
         const uint32_t adv = (SEM == ALN_CORE_LOCAL && FIRST) ? (uint32_t)__builtin_amdgcn_readlane((int)advchunk, sel) : 0u;
-        const PW pwc = pw;                                      // profile bytes of THIS step (loaded one step ago)
         if constexpr (SINGLE) {
             pw = *reinterpret_cast<const PW *>(prow + qv);                           // step k+1: column k+1-lane
             qv = *reinterpret_cast<const uint16_t *>(qo_lane + 2 * (k + 2));         // step k+2
@@ -381,37 +440,32 @@ struct FastStrip {
         const int kterm = (SEM == ALN_CORE_LOCAL) ? (int)(2047u - kc) : (int)kc;
         const uint32_t xm1 = k - (uint32_t)lane;
         if (!MASKED || xm1 < N) {
-            int top = topIn, diag = hdiag;
             // "cell above is Beginning" -> penalty del.  Row 1 (lane 0 of strip 0) sits under the border, T = 2 always:
             // its carried penalty comes from the bottom cell of the previous column instead (the advice), so lane 0
             // compares against 2 when the advice says "zero" and against a value no T takes when it does not -- one
-            // v_writelane instead of a select chain
+            // v_writelane instead of a select chain (batch kernels: into cmp2, whose other lanes hold 2 for the whole strip)
             int cmpv = 2;
             if (SEM == ALN_CORE_LOCAL && FIRST) {
                 const int l0 = __builtin_amdgcn_readfirstlane(((k == 0) || (adv != 0)) ? 2 : 1);   // wave-uniform, in an SGPR
-                asm("v_writelane_b32 %0, %1, 0" : "+v"(cmpv) : "s"(l0));
+                if constexpr (SINGLE) asm("v_writelane_b32 %0, %1, 0" : "+v"(cmpv) : "s"(l0));
+                else { asm("v_writelane_b32 %0, %1, 0" : "+v"(cmp2) : "s"(l0)); cmpv = cmp2; }
             }
             bool zr = (topIn == cmpv);
+            // phase B: the chain down the rows; Tl[r] is Left going in and the new cell coming out
+            int top = topIn;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 int negp;
                 if (SEM == ALN_CORE_LOCAL) negp = zr ? in.nd4 : in.ne4;
                 else if (SEM == ALN_CORE_GLOBAL) negp = (r == 0 && FIRST && lane == 0 && k == 0) ? in.nd4 : in.ne4;
                 else negp = in.nd4;
-                int key, nt;
+                int key;
                 if (SEM == ALN_LEGACY_LOCAL) {
-                    const int c = diag + prof_byte<R>(pwc, r);
-                    key = max(v_max3(top + negp, v_add3_m1(Tl[r], negp), c), 3);
-                    nt = v_tform(key);
-                } else {
-                    const uint32_t w32 = prof_word<R>(pwc, r);
-                    switch (r & 3) {                       // constant after unrolling: picks the SDWA byte select
-                    case 0: v_cell<0>(top, Tl[r], negp, diag, w32, key, nt); break;
-                    case 1: v_cell<1>(top, Tl[r], negp, diag, w32, key, nt); break;
-                    case 2: v_cell<2>(top, Tl[r], negp, diag, w32, key, nt); break;
-                    default: v_cell<3>(top, Tl[r], negp, diag, w32, key, nt); break;
-                    }
-                }
+                    key = max(v_max3(top + negp, v_add3_m1(Tl[r], negp), c[r]), 3);
+                    Tl[r] = v_tform(key);
+                } else
+                    v_cell_chain(top, Tl[r], negp, c[r], key);
+                const int nt = Tl[r];
                 uint32_t stored = (uint32_t)key;
                 if (SEM == ALN_CORE_LOCAL) {
                     zr = (nt == 2);
@@ -421,15 +475,12 @@ struct FastStrip {
                 }
                 dw = __builtin_amdgcn_alignbit(stored, dw, 2);
                 if (LOCAL) rbv[r] = max(rbv[r], v_pack11(nt, kterm));
-                diag = Tl[r];
-                Tl[r] = nt;
                 top = nt;
             }
             hdiag = topIn;
-            bottom = Tl[R - 1];
         }
         // bottom row to the strip below: lane 63's newest cell enters a 64-deep lane shift register (DPP wave_shl:1)
-        if (!LAST) outq = __builtin_amdgcn_update_dpp(bottom, outq, 0x130, 0xf, 0xf, false);
+        if (!LAST) outq = __builtin_amdgcn_update_dpp(Tl[R - 1], outq, 0x130, 0xf, 0xf, false);
     }
 
     // single-pair kernel: after step k lanes 48..63 hold the bottom-row cells of columns c-15..c, c = k - 63; one
@@ -630,7 +681,6 @@ struct FastStrip {
 #undef ALN_PICK
 #undef ALN_STEADY_OPERANDS
         pw = (PW)P0; pw1 = (PW)P1; qv2 = Q2; qv3 = Q3;
-        bottom = Tl[R - 1];
         if (st != 0) {                                        // the producer never arrived: poison the run
             if (lane == 0) __hip_atomic_store(in.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             aborted = true;
@@ -749,8 +799,9 @@ struct FastStrip {
                 }
             }
         }
-        if (save) { base[16 * 64] = hdiag; base[17 * 64] = bottom; }
-        else same = same && base[16 * 64] == hdiag && base[17 * 64] == bottom;
+        // (word 17 held `bottom`, which always equalled Tl[R - 1]: the same cell as word 2 (R - 1); kept so that the 18-word layout stands)
+        if (save) { base[16 * 64] = hdiag; base[17 * 64] = Tl[R - 1]; }
+        else same = same && base[16 * 64] == hdiag && base[17 * 64] == Tl[R - 1];
         return same;
     }
 
@@ -797,8 +848,8 @@ struct FastStrip {
             else *dst = (uint8_t)lo;
         }
         hdiag = LOCAL || yb == 0 ? 2 : 2 + (int)yb * in.nd4;            // H[yb][0]; yb < M always for valid lanes
-        bottom = Tl[R - 1];
         inchunk = 2; qchunk = 0; advchunk = 0; dw = 0; outq = 0; qv = 0; top0v = 2;
+        cmp2 = 2;
         twov = (FIRST && lane == 0) ? 1 : 2;                 // T is always 2 (mod 4)
         pw1 = PW{}; qv2 = 0; qv3 = 0; gA = 0; gB = 0; insteady = false; ring_staged = false;
         if constexpr (SINGLE) {
