@@ -42,9 +42,12 @@ EXPORTS = [
     "aln_pairset_heuristics", "aln_pairset_reestimate", "aln_pairset_run_stored", "aln_pairset_matrices", "aln_transform_matrices_device",
     "aln_seqset_create", "aln_seqset_destroy", "aln_seqset_pairs", "aln_seqset_score", "aln_seqset_hits", "aln_seqset_held_list",
     "aln_seqset_held_strings", "aln_seqset_stats",
+    "aln_pairset_create_from_set", "aln_pairset_loop_begin", "aln_pairset_loop_step",
 ]
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
 TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
+# aln_pairset_loop_step's causes (aligner_amd/csrc/aln_loop_rules.h)
+LOOP_CAUSE_DONE, LOOP_CAUSE_FAILED, LOOP_CAUSE_NO_ROOT = 0, 1, 2
 
 
 class Params(C.Structure):
@@ -217,6 +220,12 @@ def load():
     lib.aln_seqset_held_strings.argtypes = [vp, vp, C.c_uint64, vp, vp, u64p]
     lib.aln_seqset_stats.restype = i
     lib.aln_seqset_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.aln_pairset_create_from_set.restype = vp
+    lib.aln_pairset_create_from_set.argtypes = [vp, bp, C.c_uint64, C.c_uint64, C.POINTER(C.c_int)]
+    lib.aln_pairset_loop_begin.restype = i
+    lib.aln_pairset_loop_begin.argtypes = [vp, vp, vp]
+    lib.aln_pairset_loop_step.restype = i
+    lib.aln_pairset_loop_step.argtypes = [vp, C.POINTER(Params), vp, vp, vp, vp]
     _lib = lib
     return lib
 

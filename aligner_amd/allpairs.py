@@ -3,6 +3,10 @@
 The request path of the reference (aligner-web dispatcher: generate_pairs, handlers.rs:253-264) as a command: prints
 `q_head,t_head,f` per pair in generate_pairs order -- all pairs, or with --f-min only those with f >= F.  Local alignment, BLOSUM62,
 gap opening 11, extension 2 unless told otherwise.
+
+With --heuristic every pair runs the loop of HeuristicAligner instead (heuristic.align_set: local alignment under a matrix re-estimated
+from the pair's own alignment until f stops growing), --kd K and --r-squared R being its parameters and --frequencies a,b,... the
+residue frequencies (default: those of the FASTA over the alphabet's volume); a pair the reference panics on prints the panic.
 """
 import argparse
 import sys
@@ -23,6 +27,10 @@ def main(argv=None):
     ap.add_argument("--global", dest="global_", action="store_true", help="global instead of local alignment")
     ap.add_argument("--dna", action="store_true", help="nucleotide records (match 5, mismatch -4)")
     ap.add_argument("--device", type=int, default=None)
+    ap.add_argument("--heuristic", action="store_true", help="the matrix re-estimation loop per pair (needs --kd and --r-squared)")
+    ap.add_argument("--kd", type=float, default=None)
+    ap.add_argument("--r-squared", type=float, default=None)
+    ap.add_argument("--frequencies", default=None, help="comma-separated residue frequencies, one per code of the alphabet")
     a = ap.parse_args(argv)
     records = read_fasta(a.input)
     if len(records) < 2:
@@ -32,6 +40,28 @@ def main(argv=None):
     sem = _ffi.CORE_GLOBAL if a.global_ else _ffi.CORE_LOCAL
     heads = [r.head.decode("utf-8", "replace") for r in records]
     out = sys.stdout
+    if a.heuristic:
+        if a.kd is None or a.r_squared is None:
+            ap.error("--heuristic needs --kd and --r-squared")
+        if a.global_ or a.f_min is not None:
+            ap.error("--heuristic is the local loop over all pairs: no --global, no --f-min")
+        import numpy as np
+        from .heuristic import align_set
+        from .simple import Heuristics
+        codes = encode_records(records, alphabet)
+        v = alphabet.volume()
+        if a.frequencies is not None:
+            freq = np.array([float(x) for x in a.frequencies.split(",")], dtype=np.float64)
+            if len(freq) != v:
+                ap.error("--frequencies: %d values, one per code of the alphabet" % v)
+        else:
+            every = np.concatenate([np.asarray(c, dtype=np.uint8) for c in codes])
+            every = every[every < v]
+            freq = np.bincount(every, minlength=v).astype(np.float64) / max(len(every), 1)
+        with SeqSet(codes, alphabet, device=a.device) as ss:
+            for _, q, t, r in align_set(ss, a.del_, a.ext, matrix, Heuristics(kd=a.kd, r_squared=a.r_squared, frequencies=freq)):
+                out.write("%s,%s,%s\n" % (heads[q], heads[t], repr(float(r.alignment.f)) if not isinstance(r, Exception) else "panic: %s" % r))
+        return 0
     with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
         if a.f_min is None:
             f, status = ss.score(matrix, a.del_, a.ext, None, semantics=sem)

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "aln_device.h"
+#include "aln_loop_rules.h"
 #include "aln_plan_rules.h"
 #include "aln_scheme_rules.h"
 #include "aln_seqset_rules.h"
@@ -2523,10 +2524,24 @@ extern "C" void aln_pairset_launch_gather(const PairsetHeld *held, const aln_pai
                                           hipStream_t s);
 extern "C" int aln_pairset_launch_transform(const PairsetTransformArgs *a, hipStream_t s);
 extern "C" void aln_pairset_launch_pick(const double *store, const uint32_t *list, uint32_t n_list, uint32_t e, double *out, hipStream_t s);
+// the loop's step (aln_loop.hip)
+extern "C" void aln_loop_launch_classify(const aln_pair_result *res, const uint32_t *going, uint32_t n, double *best, uint32_t *cls, hipStream_t s);
+extern "C" void aln_loop_launch_settle(const uint32_t *entry, const int32_t *transform_status, uint32_t n, uint32_t *cls, hipStream_t s);
+extern "C" uint32_t aln_loop_tiles(uint32_t n);
+extern "C" void aln_loop_launch_select(const uint32_t *cls, uint32_t n, uint32_t kind, const uint32_t *going, const aln_pair_result *res,
+                                       uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint32_t *out_pair, uint32_t *out_word,
+                                       aln_pair_result *out_res, hipStream_t s);
+
+struct aln_seqset;
+static void seqset_derived_gone(aln_seqset *ss);
 
 struct aln_pairset {
     DevCtx *ctx = nullptr;            // one device: the context's first (as a staged batch)
     Slot *slot = nullptr;             // private slot; slot->seqs holds every pair's residues, packed in pair order
+    // a pair set over a block of a sequence set (aln_pairset_create_from_set): slot->seqs is the set's residue buffer, borrowed -- never
+    // grown and never freed here; residues = its size
+    aln_seqset *owner = nullptr;
+    uint64_t residues = 0;
     size_t n = 0;
     std::vector<uint64_t> q_off, q_len, t_off, t_len;      // offsets into slot->seqs
     // held state of the last run: entry k = pair active[k]
@@ -2544,6 +2559,12 @@ struct aln_pairset {
     uint32_t h_rows = 0, h_cols = 0;
     DevBuf h_freq, h_kd, h_r2, store, shared, h_list, h_entry, h_status, picked;
     std::vector<char> written;        // pair -> its store entry holds a matrix
+    // the loop's own state (aln_pairset_loop_begin / loop_step): best f per pair and the going list on the device -- going[cur] is the
+    // list, going[cur ^ 1] where the next one is compacted -- and the host's copy of the list, from which the chunks are planned
+    bool loop = false;
+    int cur = 0;
+    DevBuf best, going[2], cls, l_tiles, l_count, cand_pair, cand_entry, fin_pair, fin_cause, fin_res;
+    std::vector<uint32_t> going_h;
 };
 
 extern "C" void aln_pairset_destroy(aln_pairset *ps)
@@ -2553,9 +2574,13 @@ extern "C" void aln_pairset_destroy(aln_pairset *ps)
     if (ps->slot && ps->slot->stream) (void)hipStreamSynchronize(ps->slot->stream);
     for (hipEvent_t e : ps->ev) if (e) (void)hipEventDestroy(e);
     DevBuf *d[] = {&ps->matrices, &ps->held_res, &ps->held_tb, &ps->held_info, &ps->list, &ps->out_off, &ps->counts, &ps->packed_res, &ps->packed_tb,
-                   &ps->h_freq, &ps->h_kd, &ps->h_r2, &ps->store, &ps->shared, &ps->h_list, &ps->h_entry, &ps->h_status, &ps->picked};
+                   &ps->h_freq, &ps->h_kd, &ps->h_r2, &ps->store, &ps->shared, &ps->h_list, &ps->h_entry, &ps->h_status, &ps->picked,
+                   &ps->best, &ps->going[0], &ps->going[1], &ps->cls, &ps->l_tiles, &ps->l_count, &ps->cand_pair, &ps->cand_entry, &ps->fin_pair,
+                   &ps->fin_cause, &ps->fin_res};
     for (DevBuf *b : d) dev_free(*b);
+    if (ps->owner && ps->slot) ps->slot->seqs = DevBuf{};           // borrowed: the set's to free
     slot_destroy(ps->slot);
+    if (ps->owner) seqset_derived_gone(ps->owner);
     delete ps;
 }
 
@@ -2609,7 +2634,7 @@ extern "C" aln_pairset *aln_pairset_create(aln_ctx *ctx, const uint8_t *seqs, co
 
 // the checks of a run that need no device
 static int pairset_check_run(const aln_pairset *ps, const aln_params *p, const double *matrices, const uint32_t *active, size_t n_active,
-                             const aln_pair_result *results, bool stored = false)
+                             const aln_pair_result *results, bool stored = false, bool loop = false)
 {
     if (!p) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if (p->semantics < ALN_CORE_GLOBAL || p->semantics > ALN_PWM_LOCAL) { g_err = "bad semantics"; return ALN_ERR_INVALID_ARGUMENT; }
@@ -2621,7 +2646,7 @@ static int pairset_check_run(const aln_pairset *ps, const aln_params *p, const d
         g_err = "per-pair matrices hold 1 .. 1024 entries";
         return ALN_ERR_INVALID_ARGUMENT;
     }
-    if (n_active && ((!stored && !matrices) || !active || !results)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_active && ((!stored && !matrices) || !active || (!results && !loop))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if (stored && !ps->heur) { g_err = "no heuristics set"; return ALN_ERR_INVALID_ARGUMENT; }
     if (stored && (p->rows != ps->h_rows || p->cols != ps->h_cols)) { g_err = "the shape differs from the store's"; return ALN_ERR_INVALID_ARGUMENT; }
     if (n_active > ps->n) { g_err = "more active entries than pairs"; return ALN_ERR_INVALID_ARGUMENT; }
@@ -2634,11 +2659,12 @@ static int pairset_check_run(const aln_pairset *ps, const aln_params *p, const d
     return ALN_OK;
 }
 
-// aln_pairset_run (matrices from the host) and aln_pairset_run_stored (matrices == nullptr: entry k scored by store[active[k]])
+// aln_pairset_run (matrices from the host) and aln_pairset_run_stored (matrices == nullptr: entry k scored by store[active[k]]).
+// dev_list (aln_pairset_loop_step): `active` as it already lies on the device -- the list is not uploaded, and the summaries stay there
 static int pairset_run(aln_pairset *ps, const aln_params *params, const double *matrices, const uint32_t *active, size_t n_active,
-                       aln_pair_result *results, bool stored)
+                       aln_pair_result *results, bool stored, const uint32_t *dev_list = nullptr)
 {
-    int st = pairset_check_run(ps, params, matrices, active, n_active, results, stored);
+    int st = pairset_check_run(ps, params, matrices, active, n_active, results, stored, dev_list != nullptr);
     if (st != ALN_OK) return st;
     HIPCHK(hipSetDevice(ps->ctx->device));
     Slot &s = *ps->slot;
@@ -2682,13 +2708,16 @@ static int pairset_run(aln_pairset *ps, const aln_params *params, const double *
     const auto t0 = std::chrono::steady_clock::now();
     if (stored) {
         // the listed store entries, gathered on the device into the compact array the fill reads
-        if ((st = dev_ensure(ps->h_list, 4ull * n_active, false)) != ALN_OK) return st;
-        HIPCHK(hipMemcpyAsync(ps->h_list.p, active, 4ull * n_active, hipMemcpyHostToDevice, q));
+        if (!dev_list) {
+            if ((st = dev_ensure(ps->h_list, 4ull * n_active, false)) != ALN_OK) return st;
+            HIPCHK(hipMemcpyAsync(ps->h_list.p, active, 4ull * n_active, hipMemcpyHostToDevice, q));
+        }
         HIPCHK(hipEventRecord(ps->ev[4], q));
-        aln_pairset_launch_pick(ps->store.as<double>(), ps->h_list.as<uint32_t>(), (uint32_t)n_active, (uint32_t)e, ps->matrices.as<double>(), q);
+        aln_pairset_launch_pick(ps->store.as<double>(), dev_list ? dev_list : ps->h_list.as<uint32_t>(), (uint32_t)n_active, (uint32_t)e,
+                                ps->matrices.as<double>(), q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ps->ev[5], q));
-        ps->bytes[0] = 4ull * n_active;
+        ps->bytes[0] = dev_list ? 0 : 4ull * n_active;
     } else {
         HIPCHK(hipMemcpyAsync(ps->matrices.p, matrices, 8ull * e * n_active, hipMemcpyHostToDevice, q));
         ps->bytes[0] = 8ull * e * n_active;
@@ -2709,6 +2738,7 @@ static int pairset_run(aln_pairset *ps, const aln_params *params, const double *
         if ((st = chunk_plan(ps->ctx, c, qo.data(), ql.data(), to.data(), tl.data(), first, n, ranges.size() == 1, k, ranges.size() > 4)) != ALN_OK) break;
         for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[first + i]; k.descs[i].t_off = to[first + i]; }      // resident residues
         k.seq_direct = true;
+        if (ps->owner) { k.seq_lo = 0; k.seq_span = ps->residues; }      // the set's buffer: pairs share sequences, and it must not grow
         HIPCHK(hipStreamSynchronize(q));
         collect();
         if ((st = slot_ensure(s, c, k)) != ALN_OK) break;
@@ -2726,12 +2756,12 @@ static int pairset_run(aln_pairset *ps, const aln_params *params, const double *
         if (k.tb_bytes) HIPCHK(hipMemcpyAsync(ps->held_tb.as<uint8_t>() + ps->info[first].tb_off, s.tb.p, k.tb_bytes, hipMemcpyDeviceToDevice, q));
     }
     if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
-    HIPCHK(hipMemcpyAsync(results, ps->held_res.p, sizeof(aln_pair_result) * n_active, hipMemcpyDeviceToHost, q));
+    if (results) HIPCHK(hipMemcpyAsync(results, ps->held_res.p, sizeof(aln_pair_result) * n_active, hipMemcpyDeviceToHost, q));
     HIPCHK(hipStreamSynchronize(q));
     collect();
     if (stored) ps->ms[2] = ev_ms(ps->ev[4], ps->ev[5]);
     ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ps->bytes[1] = sizeof(aln_pair_result) * n_active;
+    ps->bytes[1] = results ? sizeof(aln_pair_result) * n_active : 0;
     for (size_t kk = 0; kk < n_active; ++kk) ps->entry_of[active[kk]] = (int64_t)kk;
     ps->n_held = n_active;
     ps->rows = c.rows; ps->cols = c.cols; ps->blank = params->blank_code;
@@ -2791,6 +2821,8 @@ extern "C" int aln_pairset_heuristics(aln_pairset *ps, uint32_t rows, uint32_t c
     ps->written.assign(ps->n, 0);
     ps->h_rows = rows; ps->h_cols = cols;
     ps->heur = true;
+    ps->loop = false;                    // the store is new: a loop begins again with aln_pairset_loop_begin
+    ps->going_h.clear();
     ps->ms[2] = 0;
     ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ps->bytes[0] = want[0] + want[1] + want[2]; ps->bytes[1] = 0;
@@ -3077,19 +3109,38 @@ struct aln_seqset {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double ms[4] = {0, 0, 0, 0};
     uint64_t bytes[2] = {0, 0};
+    // pair sets made by aln_pairset_create_from_set read the residue buffer: a destroy with some of them alive releases everything
+    // else, moves the buffer here and leaves the rest to the last of them
+    size_t derived = 0;
+    bool destroyed = false;
+    DevBuf residues;
 };
+
+// a derived pair set is gone (aln_pairset_destroy)
+static void seqset_derived_gone(aln_seqset *ss)
+{
+    if (ss->derived) --ss->derived;
+    if (ss->destroyed && ss->derived == 0) {
+        (void)hipSetDevice(ss->ctx->device);
+        dev_free(ss->residues);
+        delete ss;
+    }
+}
 
 extern "C" void aln_seqset_destroy(aln_seqset *ss)
 {
-    if (!ss) return;
+    if (!ss || ss->destroyed) return;
     (void)hipSetDevice(ss->ctx->device);
     if (ss->slot && ss->slot->stream) (void)hipStreamSynchronize(ss->slot->stream);
-    for (hipEvent_t e : ss->ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t &e : ss->ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->held_res, &ss->held_tb,
                    &ss->held_info, &ss->list, &ss->out_off, &ss->packed_res, &ss->packed_tb};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
+    if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
     slot_destroy(ss->slot);
+    ss->slot = nullptr;
+    if (ss->derived) { ss->destroyed = true; ss->held = false; return; }      // the residues go with the last derived pair set
     delete ss;
 }
 
@@ -3509,5 +3560,198 @@ extern "C" int aln_seqset_stats(const aln_seqset *ss, double *ms, uint64_t *byte
     if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if (ms) for (int i = 0; i < 4; ++i) ms[i] = ss->ms[i];
     if (bytes) { bytes[0] = ss->bytes[0]; bytes[1] = ss->bytes[1]; }
+    return ALN_OK;
+}
+
+// ---------------------------------------------------------------- a pair set over a block of a sequence set, and the loop's step
+// Pairs first .. first + n_pairs - 1 of the block as a pair set that reads the set's own residue buffer: the host tables come from one
+// walk over the block (aln_seqset_window), nothing is uploaded.
+extern "C" aln_pairset *aln_pairset_create_from_set(aln_seqset *ss, const aln_seqset_block *b, uint64_t first, uint64_t n_pairs, int *status)
+{
+    int st = ALN_OK;
+    aln_pairset *ps = nullptr;
+    uint64_t pairs = 0;
+    if (!ss || !b) { g_err = "null argument"; st = ALN_ERR_INVALID_ARGUMENT; }
+    else if (ss->destroyed) { g_err = "the set was destroyed"; st = ALN_ERR_INVALID_ARGUMENT; }
+    else if ((pairs = aln_seqset_block_pairs(ss->n, *b)) == 0) {
+        g_err = "block: a range beyond the set, unequal ranges of an upper block, a reserved word, or no pairs";
+        st = ALN_ERR_INVALID_ARGUMENT;
+    }
+    else if (first > pairs || n_pairs > pairs - first) { g_err = "first + n_pairs is beyond the block's pairs"; st = ALN_ERR_INVALID_ARGUMENT; }
+    else if (n_pairs > 0xFFFFFFF0ull) { g_err = "too many pairs"; st = ALN_ERR_UNSUPPORTED; }
+    if (st == ALN_OK) {
+        ps = new aln_pairset();
+        ps->ctx = ss->ctx;
+        ps->n = (size_t)n_pairs;
+        ps->slot = new Slot();
+        ps->slot->pooled = false;
+        ps->q_off.resize(n_pairs); ps->t_off.resize(n_pairs); ps->q_len.resize(n_pairs); ps->t_len.resize(n_pairs);
+        ps->entry_of.assign(n_pairs, -1);
+        std::vector<uint64_t> sq(n_pairs), tq(n_pairs);
+        aln_seqset_window(*b, first, n_pairs, sq.data(), tq.data());
+        for (uint64_t i = 0; i < n_pairs; ++i) {
+            ps->q_off[i] = ss->off[sq[i]]; ps->q_len[i] = ss->len[sq[i]];
+            ps->t_off[i] = ss->off[tq[i]]; ps->t_len[i] = ss->len[tq[i]];
+        }
+        hipError_t e = hipSetDevice(ps->ctx->device);
+        if (e != hipSuccess) st = fail(e, "hipSetDevice");
+        if (st == ALN_OK) st = slot_init(*ps->slot);
+        for (int i = 0; i < 6 && st == ALN_OK; ++i) { e = hipEventCreate(&ps->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
+        if (st != ALN_OK) { aln_pairset_destroy(ps); ps = nullptr; }      // (no owner yet: the set's count is untouched)
+        else {
+            ps->slot->seqs = ss->slot->seqs;       // borrowed: uploaded and waited for by aln_seqset_create, read-only since
+            ps->residues = ss->total;
+            ps->owner = ss;
+            ++ss->derived;
+        }
+    }
+    if (status) *status = st;
+    return ps;
+}
+
+// best = 0, store[i] = transform(shared_matrix, pair i's parameters), the going list = the pairs with a root, ascending
+extern "C" int aln_pairset_loop_begin(aln_pairset *ps, const double *shared_matrix, int32_t *status)
+{
+    if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ps->heur) { g_err = "no heuristics set"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!shared_matrix || (ps->n && !status)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ps->ctx->device));
+    hipStream_t q = ps->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const uint32_t n = (uint32_t)ps->n;
+    const uint64_t e = (uint64_t)ps->h_rows * ps->h_cols;
+    const uint32_t tiles = aln_loop_tiles(n);
+    int st;
+    if ((st = dev_ensure(ps->best, 8ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->going[0], 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->going[1], 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->cls, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->l_tiles, 8ull * tiles, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->l_count, 256, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->h_status, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->shared, 8ull * e, false)) != ALN_OK) return st;
+    ps->loop = false;
+    ps->going_h.clear();
+    ps->cur = 0;
+    ps->ms[2] = 0;
+    ps->bytes[0] = ps->bytes[1] = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n) {
+        HIPCHK(hipMemsetAsync(ps->best.p, 0, 8ull * n, q));                     // +0.0
+        HIPCHK(hipMemcpyAsync(ps->shared.p, shared_matrix, 8ull * e, hipMemcpyHostToDevice, q));
+        PairsetTransformArgs a{};
+        a.shared = ps->shared.as<double>();
+        a.freq = ps->h_freq.as<double>(); a.kd = ps->h_kd.as<double>(); a.r2 = ps->h_r2.as<double>();
+        a.dst = ps->store.as<double>();                                        // listed entry k is pair k: no tables
+        a.status = ps->h_status.as<int32_t>();
+        a.n_list = n; a.rows = ps->h_rows; a.cols = ps->h_cols;       // (no held strings are read: blank stays 0)
+        HIPCHK(hipEventRecord(ps->ev[4], q));
+        if (aln_pairset_launch_transform(&a, q) != 0) { g_err = "per-pair matrices hold 1 .. 1024 entries"; return ALN_ERR_INVALID_ARGUMENT; }
+        HIPCHK(hipGetLastError());
+        aln_loop_launch_settle(nullptr, ps->h_status.as<int32_t>(), n, ps->cls.as<uint32_t>(), q);
+        aln_loop_launch_select(ps->cls.as<uint32_t>(), n, 1u, nullptr, nullptr, ps->l_tiles.as<uint32_t>(), ps->l_tiles.as<uint32_t>() + tiles,
+                               ps->l_count.as<uint32_t>(), ps->going[0].as<uint32_t>(), nullptr, nullptr, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ps->ev[5], q));
+        HIPCHK(hipMemcpyAsync(status, ps->h_status.p, 4ull * n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        for (uint32_t i = 0; i < n; ++i)
+            if (status[i] == 0) { ps->written[i] = 1; ps->going_h.push_back(i); }
+        ps->ms[2] = ev_ms(ps->ev[4], ps->ev[5]);
+        ps->bytes[0] = 8ull * e; ps->bytes[1] = 4ull * n;
+    }
+    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->loop = true;
+    return ALN_OK;
+}
+
+// One iteration for every going pair: aln_pairset_run_stored on the going list as it lies on the device, then classification,
+// re-estimation and the two ordered compactions there; the finished pairs' numbers, causes and summaries come back.
+extern "C" int aln_pairset_loop_step(aln_pairset *ps, const aln_params *params, uint32_t *finished, uint32_t *cause,
+                                     aln_pair_result *finished_results, uint32_t *counts)
+{
+    if (!params) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const size_t n = ps ? ps->going_h.size() : 0;
+    // the run's own checks (nothing is touched if one fails); the list is the library's own
+    int st = pairset_check_run(ps, params, nullptr, ps ? ps->going_h.data() : nullptr, n, nullptr, true, true);
+    if (st != ALN_OK) return st;
+    if (!ps->loop) { g_err = "no loop: aln_pairset_loop_begin has not run, or aln_pairset_heuristics has replaced the store"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && (!finished || !cause || !finished_results || !counts)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n == 0) {
+        if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;
+        return ALN_OK;
+    }
+    HIPCHK(hipSetDevice(ps->ctx->device));
+    hipStream_t q = ps->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const uint32_t n32 = (uint32_t)n;
+    const uint32_t tiles = aln_loop_tiles(n32);
+    // every buffer of the step before the run: a failure leaves the loop's state as it was
+    if ((st = dev_ensure(ps->cand_pair, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->cand_entry, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->fin_pair, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->fin_cause, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->fin_res, sizeof(aln_pair_result) * n, false)) != ALN_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t *going = ps->going[ps->cur].as<uint32_t>(), *next = ps->going[ps->cur ^ 1].as<uint32_t>();
+    if ((st = pairset_run(ps, params, nullptr, ps->going_h.data(), n, nullptr, true, going)) != ALN_OK) return st;
+    const double pick_ms = ps->ms[2];
+    uint32_t *cls = ps->cls.as<uint32_t>(), *tile_count = ps->l_tiles.as<uint32_t>(), *tile_off = tile_count + tiles;
+    uint32_t *cnt = ps->l_count.as<uint32_t>();
+    const aln_pair_result *res = ps->held_res.as<aln_pair_result>();
+    HIPCHK(hipEventRecord(ps->ev[4], q));
+    aln_loop_launch_classify(res, going, n32, ps->best.as<double>(), cls, q);
+    aln_loop_launch_select(cls, n32, 0u, going, nullptr, tile_count, tile_off, cnt, ps->cand_pair.as<uint32_t>(), ps->cand_entry.as<uint32_t>(),
+                           nullptr, q);
+    HIPCHK(hipGetLastError());
+    uint32_t improved = 0;
+    HIPCHK(hipMemcpyAsync(&improved, cnt, 4, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));                                          // the transform's grid is its count
+    if (improved > n32) { g_err = "loop: the device's count is out of range"; return ALN_ERR_DEVICE; }
+    if (improved) {
+        PairsetTransformArgs a{};
+        a.held = ps->held_info.as<PairsetHeld>(); a.res = res; a.tb = ps->held_tb.as<uint8_t>();
+        a.entry = ps->cand_entry.as<uint32_t>();
+        a.par = a.dst_index = ps->cand_pair.as<uint32_t>();
+        a.freq = ps->h_freq.as<double>(); a.kd = ps->h_kd.as<double>(); a.r2 = ps->h_r2.as<double>();
+        a.dst = ps->store.as<double>();
+        a.status = ps->h_status.as<int32_t>();
+        a.n_list = improved; a.n_held = n32; a.rows = ps->h_rows; a.cols = ps->h_cols; a.blank = ps->blank;
+        if (aln_pairset_launch_transform(&a, q) != 0) { g_err = "per-pair matrices hold 1 .. 1024 entries"; return ALN_ERR_INVALID_ARGUMENT; }
+        aln_loop_launch_settle(ps->cand_entry.as<uint32_t>(), ps->h_status.as<int32_t>(), improved, cls, q);
+        HIPCHK(hipGetLastError());
+    }
+    aln_loop_launch_select(cls, n32, 1u, going, nullptr, tile_count, tile_off, cnt + 1, next, nullptr, nullptr, q);
+    aln_loop_launch_select(cls, n32, 2u, going, res, tile_count, tile_off, cnt + 2, ps->fin_pair.as<uint32_t>(), ps->fin_cause.as<uint32_t>(),
+                           ps->fin_res.as<aln_pair_result>(), q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ps->ev[5], q));
+    uint32_t got[2] = {0, 0};                                                 // going on, finished
+    HIPCHK(hipMemcpyAsync(got, cnt + 1, 8, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    const uint32_t more = got[0], fin = got[1];
+    if ((uint64_t)more + fin != n) { g_err = "loop: the device's lists do not add up to the going list"; return ALN_ERR_DEVICE; }
+    if (fin) {
+        HIPCHK(hipMemcpyAsync(finished, ps->fin_pair.p, 4ull * fin, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(cause, ps->fin_cause.p, 4ull * fin, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(finished_results, ps->fin_res.p, sizeof(aln_pair_result) * fin, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+    }
+    // the host's copy of the next list: the going list less the finished pairs (both ascending in going order)
+    uint32_t done = 0;
+    {
+        size_t w = 0, f = 0;
+        for (size_t k = 0; k < n; ++k) {
+            if (f < fin && finished[f] == ps->going_h[k]) { if (cause[f] == ALN_LOOP_CAUSE_DONE) ++done; ++f; }
+            else ps->going_h[w++] = ps->going_h[k];
+        }
+        if (f != fin || w != more) { ps->loop = false; g_err = "loop: the finished list is not a sublist of the going list"; return ALN_ERR_DEVICE; }
+        ps->going_h.resize(w);
+    }
+    ps->cur ^= 1;
+    counts[0] = n32; counts[1] = done; counts[2] = fin - done; counts[3] = more;
+    ps->ms[2] = pick_ms + ev_ms(ps->ev[4], ps->ev[5]);
+    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->bytes[1] += 12ull + (4ull + 4ull + sizeof(aln_pair_result)) * fin;
     return ALN_OK;
 }

@@ -76,3 +76,15 @@ ALN_HD inline void aln_seqset_next(const aln_seqset_block &b, uint64_t *q, uint6
         if (*t == b.q_first + b.q_count) { ++*q; *t = *q + 1u; }
     } else if (*t == b.t_first + b.t_count) { ++*q; *t = b.t_first; }
 }
+
+// pairs first .. first + n - 1 of a valid block (first + n <= aln_seqset_block_pairs) by one unrank and n - 1 steps: q[i], t[i]
+inline void aln_seqset_window(const aln_seqset_block &b, uint64_t first, uint64_t n, uint64_t *q, uint64_t *t)
+{
+    if (n == 0) return;
+    uint64_t cq, ct;
+    aln_seqset_unrank(b, first, &cq, &ct);
+    for (uint64_t i = 0; i < n; ++i) {
+        q[i] = cq; t[i] = ct;
+        if (i + 1 < n) aln_seqset_next(b, &cq, &ct);
+    }
+}

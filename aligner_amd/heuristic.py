@@ -277,6 +277,101 @@ def align_many(pairs, del_, ext, matrix, heuristics, alphabet=None, transform="n
     return out
 
 
+def align_set(seqset, del_, ext, matrix, heuristics, block=None, max_pairs=1 << 18, errors="return", backend=None):
+    """HeuristicAligner for every pair of a block of a resident SeqSet (default: every pair i < j, the request path of the reference):
+    a generator of (pair_index, q, t, AlignmentResult | ReferencePanic) in pair order, q and t being sequence numbers of the set
+    (sequence q the query), `result.matrix` the matrix of the pair's last run -- what align_many(..., transform="resident") gives for
+    the same pairs, bit for bit.
+
+    The block is taken in slices of at most max_pairs consecutive pairs.  A slice is one pair set derived from the set
+    (PairSet.from_seqset: the residues are the set's, nothing is uploaded) and driven by PairSet.loop_step: the decision, the
+    re-estimation and the going list stay on the device, and per step only the finished pairs come back.  What bounds a slice is its
+    per-pair device memory: the store entry and the compact run matrix (8 * v * v bytes each, v the alphabet's volume), the held
+    strings (2 * (N + M + 2)), the summary (2 * 48) and the loop's words (36) -- about 10 KiB per pair of 300-residue proteins under a
+    24 x 24 matrix, 2.5 GiB for the default slice.
+
+    heuristics: one Heuristics for every pair, or a callable (q, t) -> Heuristics.  r_squared == 0 stands for rows * cols
+    (heuristic/mod.rs:47-49), as in align_many.  errors: "return" yields a ReferencePanic in the place of a pair the reference panics
+    on; "raise" raises the first one in pair order.  All per-pair work of the host is numpy on arrays.
+    backend: a factory (seqset, block, first, n) -> object with q / t / set_heuristics / loop_begin / loop_step / strings / matrices /
+    close (tests)."""
+    from . import _ffi
+    from . import runtime
+    from . import seqset as seqset_module
+    from .alignment import Alignment, AlignmentResult
+    if heuristics is None:
+        raise AlignerError(ErrorKind.MissingArgument)                           # heuristic/mod.rs:42-45
+    if errors not in ("raise", "return"):
+        raise ValueError("errors: 'raise' or 'return'")
+    if int(max_pairs) < 1:
+        raise ValueError("max_pairs: at least 1")
+    alphabet = seqset.alphabet
+    m = np.asarray(matrix, dtype=np.float64)
+    v = alphabet.volume()
+    if m.shape != (v, v):
+        raise ValueError("align_set: the matrix must be %d x %d (the alphabet's frequency matrix)" % (v, v))
+    b = seqset_module._block(block, len(seqset))
+    total = seqset.pairs(b)
+    if total == 0:
+        raise ValueError("align_set: invalid block (a range beyond the set, unequal ranges of an upper block, or no pairs)")
+    if backend is None:
+        from .pairset import PairSet
+        backend = PairSet.from_seqset
+    eps = np.finfo(np.float64).eps
+    blank = alphabet.blank()
+    for first in range(0, total, int(max_pairs)):
+        n = min(int(max_pairs), total - first)
+        ps = backend(seqset, b, first, n)
+        try:
+            sq, st_ = np.asarray(ps.q), np.asarray(ps.t)
+            if callable(heuristics):
+                hs = [heuristics(int(a), int(c)) for a, c in zip(sq, st_)]
+                if any(h is None for h in hs):
+                    raise AlignerError(ErrorKind.MissingArgument)
+                freq = np.asarray([np.asarray(h.frequencies, dtype=np.float64) for h in hs])
+                kd = np.asarray([h.kd for h in hs], dtype=np.float64)
+                r2 = np.asarray([h.r_squared for h in hs], dtype=np.float64)
+            else:
+                freq = np.broadcast_to(np.asarray(heuristics.frequencies, dtype=np.float64), (n, v))
+                kd = np.full(n, heuristics.kd, dtype=np.float64)
+                r2 = np.full(n, heuristics.r_squared, dtype=np.float64)
+            r2 = np.where(np.abs(r2 - 0.0) < eps, float(m.shape[0] * m.shape[1]), r2)      # :47-49
+            ps.set_heuristics(v, v, freq, kd, r2)
+            out = np.empty(n, dtype=object)
+            status = np.asarray(ps.loop_begin(m))
+            for i in np.flatnonzero(status != 0):                               # `.unwrap()` at heuristic/mod.rs:53
+                out[i] = _wrong_matrix_panic()
+            more = int((status == 0).sum())
+            while more:
+                fin, cause, res, counts = ps.loop_step(_ffi.CORE_LOCAL, del_, ext, blank=blank)
+                if counts[0] != more or counts[1] + counts[2] + counts[3] != counts[0] or len(fin) != counts[1] + counts[2]:
+                    raise RuntimeError("align_set: a step's counters do not add up")
+                more = counts[3]
+                done = fin[cause == _ffi.LOOP_CAUSE_DONE]
+                for i, r in zip(fin[cause == _ffi.LOOP_CAUSE_FAILED], res[cause == _ffi.LOOP_CAUSE_FAILED]):
+                    try:
+                        runtime.raise_for_status(int(r["status"]), "aln_pairset_loop_step")
+                    except ReferencePanic as e:
+                        out[i] = e
+                for i in fin[cause == _ffi.LOOP_CAUSE_NO_ROOT]:                  # `.unwrap()` at :71
+                    out[i] = _wrong_matrix_panic()
+                if len(done):
+                    summ, strs = ps.strings(done)
+                    mats = ps.matrices(done)
+                    for k, i in enumerate(done):
+                        r = summ[k]
+                        coords = ((int(r["start_x"]) + 1, int(r["end_x"]) + 1), (int(r["start_y"]) + 1, int(r["end_y"]) + 1))
+                        aln = Alignment(alphabet, strs[k][0], strs[k][1], coords, float(r["f"]))
+                        out[i] = AlignmentResult(aln, matrix=mats[k].copy(), score=float(r["score"]),      # :73-75
+                                                 summary={name: r[name].item() for name in r.dtype.names})
+        finally:
+            ps.close()
+        for i in range(n):
+            if errors == "raise" and isinstance(out[i], ReferencePanic):
+                raise out[i]
+            yield first + i, int(sq[i]), int(st_[i]), out[i]
+
+
 class HeuristicPWMAligner(_HeuristicLoop):
     """heuristic/mod.rs:80-140."""
 

@@ -31,6 +31,28 @@ class PairSet:
             raise RuntimeError("aln_pairset_create returned NULL")
         self.shape = None
 
+    @classmethod
+    def from_seqset(cls, seqset, block=None, first=0, n=None):
+        """Pairs first .. first + n - 1 (default: to the end) of a block of a resident SeqSet as a pair set that reads the set's own
+        residues on the device (aln_pairset_create_from_set): nothing is uploaded.  .q / .t are the pairs' sequence numbers."""
+        from . import seqset as seqset_module
+        self = cls.__new__(cls)
+        self.lib = _ffi.load()
+        self.handle = None
+        self.shape = None
+        b = seqset_module._block(block, len(seqset))
+        total = int(self.lib.aln_seqset_pairs(seqset.handle, C.byref(b)))
+        if n is None:
+            n = max(total - int(first), 0)
+        st = C.c_int(0)
+        self.handle = self.lib.aln_pairset_create_from_set(seqset.handle, C.byref(b), int(first), int(n), C.byref(st))
+        if not self.handle:
+            runtime.raise_for_status(st.value, "aln_pairset_create_from_set")
+            raise RuntimeError("aln_pairset_create_from_set returned NULL")
+        self.q, self.t = seqset_module.window(b, first, n)
+        self.batch = _Lengths(seqset.len[self.q.astype(np.int64)], seqset.len[self.t.astype(np.int64)])
+        return self
+
     def __len__(self):
         return len(self.batch)
 
@@ -143,10 +165,52 @@ class PairSet:
         runtime.raise_for_status(st, "aln_pairset_matrices")
         return out
 
+    def loop_begin(self, matrix):
+        """The loop's start (aln_pairset_loop_begin, after set_heuristics): best f = 0 and store entry i = transform(matrix, pair i's
+        parameters) for every pair; the pairs with a root form the going list on the device.  Returns status (n,) int32: 0, or
+        _ffi.TRANSFORM_NO_ROOT."""
+        m = np.ascontiguousarray(matrix, dtype=np.float64)
+        if m.shape != getattr(self, "store_shape", None):
+            raise ValueError("matrix: the shape given to set_heuristics")
+        status = np.zeros(len(self), dtype=np.int32)
+        st = self.lib.aln_pairset_loop_begin(self.handle, m.ctypes.data, status.ctypes.data)
+        runtime.raise_for_status(st, "aln_pairset_loop_begin")
+        self._going = int((status == 0).sum())
+        return status
+
+    def loop_step(self, semantics, del_, ext, blank=98):
+        """One iteration for every going pair (aln_pairset_loop_step): the run, the decision, the re-estimation and both lists on the
+        device.  Returns (finished pair numbers uint32, causes uint32 -- _ffi.LOOP_CAUSE_*, summaries RESULT_DTYPE, counts (run, done,
+        failed, more)); strings / matrices of the finished pairs can be fetched until the next step."""
+        rows, cols = getattr(self, "store_shape", None) or (0, 0)
+        p = _ffi.Params(int(semantics), 0, float(del_), float(ext), None, rows, cols, cols, 0, int(blank), 0, 0, 0, 0)
+        room = max(int(getattr(self, "_going", len(self))), 1)
+        fin = np.zeros(room, dtype=np.uint32)
+        cause = np.zeros(room, dtype=np.uint32)
+        res = np.zeros(room, dtype=RESULT_DTYPE)
+        counts = np.zeros(4, dtype=np.uint32)
+        st = self.lib.aln_pairset_loop_step(self.handle, C.byref(p), fin.ctypes.data, cause.ctypes.data, res.ctypes.data, counts.ctypes.data)
+        runtime.raise_for_status(st, "aln_pairset_loop_step")
+        self.shape = (rows, cols)
+        self._going = int(counts[3])
+        k = int(counts[1]) + int(counts[2])
+        return fin[:k], cause[:k], res[:k], tuple(int(c) for c in counts)
+
     def stats(self):
         ms, by = (C.c_double * 4)(), (C.c_uint64 * 2)()
         runtime.raise_for_status(self.lib.aln_pairset_stats(self.handle, ms, by), "aln_pairset_stats")
         return dict(fill_ms=ms[0], traceback_ms=ms[1], fetch_kernel_ms=ms[2], wall_ms=ms[3], bytes_up=int(by[0]), bytes_down=int(by[1]))
+
+
+class _Lengths:
+    """What PairSet needs of a PairBatch when the residues are a sequence set's: the pairs' lengths."""
+
+    def __init__(self, q_len, t_len):
+        self.q_len = np.ascontiguousarray(q_len, dtype=np.uint64)
+        self.t_len = np.ascontiguousarray(t_len, dtype=np.uint64)
+
+    def __len__(self):
+        return len(self.q_len)
 
 
 def _transform(context, matrices, frequencies, kd, r_squared):

@@ -40,6 +40,19 @@ def rectangle(q_first, q_count, t_first, t_count):
     return _ffi.SeqsetBlock(int(q_first), int(q_count), int(t_first), int(t_count), 0, 0)
 
 
+def window(block, first, n):
+    """(q, t) uint64 arrays: the sequence numbers of pairs first .. first + n - 1 of a valid block, in the numbering of
+    aligner_amd/csrc/aln_seqset_rules.h, with numpy on whole arrays (exact: integers below 2^63)."""
+    k = np.arange(int(first), int(first) + int(n), dtype=np.int64)
+    if not block.upper:
+        return (block.q_first + k // block.t_count).astype(np.uint64), (block.t_first + k % block.t_count).astype(np.uint64)
+    m = int(block.q_count)
+    r = np.arange(m, dtype=np.int64)
+    start = r * (m - 1) - r * (r - 1) // 2                                      # the pairs in front of row r
+    row = np.searchsorted(start[:max(m - 1, 1)], k, side="right") - 1
+    return (block.q_first + row).astype(np.uint64), (block.q_first + row + 1 + (k - start[row])).astype(np.uint64)
+
+
 class SeqSet:
     def __init__(self, seqs, alphabet=Protein, device=None):
         """seqs: residue code arrays (or strings, encoded with alphabet.str_to_vec)."""

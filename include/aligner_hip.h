@@ -350,6 +350,43 @@ int aln_seqset_held_strings(aln_seqset *set, const uint32_t *keep, uint64_t n_ke
                             const uint64_t *tb_off);
 int aln_seqset_stats(const aln_seqset *set, double *ms /* 4 */, uint64_t *bytes /* 2 */);
 
+/* ---- heuristic alignment of the pairs of a sequence set (additions of the same ABI version): the request path's two halves joined --
+ * every pair of a FASTA (generate_pairs), each run through the loop of HeuristicAligner (heuristic/mod.rs:36-78).
+ * create_from_set: a pair set whose pair i is pair first + i of the block, in the block's numbering (sequence q the query, sequence
+ * t the target).  It BORROWS the set's residue buffer: nothing is uploaded or copied, the host tables come from one walk over the
+ * block.  Every aln_pairset_* call works on it with its contract unchanged.  The set counts its derived pair sets: aln_seqset_destroy
+ * with some alive releases everything but the residues, which go with the last derived pair set; any other call on the destroyed
+ * handle (create_from_set included) is the caller's error.  Passes on the set and runs on a derived pair set may interleave (different
+ * slots and streams, read-only residues).  ALN_ERR_INVALID_ARGUMENT, nothing created: a null set or block, an invalid block,
+ * first + n_pairs beyond the block's pairs.  ALN_ERR_UNSUPPORTED: n_pairs > 0xFFFFFFF0.
+ * The loop's decision lives in the library (on any pair set, after aln_pairset_heuristics).  Its state is resident: best f per pair
+ * (f64) and the GOING LIST, both on the device.
+ * loop_begin: best[i] = 0.0, store[i] = transform(shared_matrix, pair i's parameters) as `reestimate` computes it; status[i] = 0 or
+ * ALN_TRANSFORM_NO_ROOT (heuristic/mod.rs:52-57); the going list becomes the pairs with status 0, ascending.  8 * rows * cols bytes
+ * go up, 4 per pair come back.  Without heuristics, a null matrix or status: ALN_ERR_INVALID_ARGUMENT.
+ * loop_step: one iteration for all going pairs.  The going list is aligned under the store exactly as `run_stored` aligns it (same
+ * checks, chunking, per-pair failures and held state; the descriptors are planned on the host and uploaded), but the list is read
+ * where it lies and no summary comes back for it.  Then, on the device, each held entry (pair i) is classified by
+ * aligner_amd/csrc/aln_loop_rules.h: status != ALN_OK: finished, cause 1 (the status is in its summary); else f > best[i] (plain
+ * IEEE compare: a NaN does not go on): best[i] = f and store[i] is re-estimated from the pair's held strings as `reestimate` does
+ * it -- ALN_TRANSFORM_NO_ROOT: finished, cause 2, store[i] left as it was; otherwise the pair goes on; else: finished, cause 0
+ * (heuristic/mod.rs:64-75), store[i] being the matrix of its last run.  Both lists are compacted in ascending going order by an
+ * ordered prefix sum (no atomic appends; tiles of 2048 entries, 256 tiles a trip), and the next step reads its list there.
+ * Back come finished[k] (pair numbers, ascending going order), cause[k], finished_results[k] (48 bytes each, gathered on the device)
+ * for k < counts[1] + counts[2], and counts = {pairs run, finished with cause 0, finished with cause 1 or 2, going on}; the
+ * arrays must hold as many entries as pairs are going (counts[3] of the step before; the status-0 pairs after loop_begin).  Nothing
+ * comes back for a pair that goes on: 12 bytes per step beside.  The held run lasts until the next step or run: aln_pairset_strings
+ * and aln_pairset_matrices on the finished pairs fetch what HeuristicAligner returns.  With nothing going: counts all 0, ALN_OK.
+ * ALN_ERR_INVALID_ARGUMENT, state untouched: no loop_begin since the last aln_pairset_heuristics, params of another shape than the
+ * store's, a matrix in params, a null output while pairs are going.  ALN_ERR_UNSUPPORTED: semantics other than the two core ones.
+ * aln_pairset_run / run_stored / reestimate between two steps are the caller's business: they replace the held run and may rewrite
+ * store entries, but touch neither best nor the going list.
+ * stats after a step: ms[0], ms[1] as after a run, ms[2] the gather, transform and compaction kernels; bytes as moved. ---- */
+aln_pairset *aln_pairset_create_from_set(aln_seqset *set, const aln_seqset_block *block, uint64_t first, uint64_t n_pairs, int *status);
+int aln_pairset_loop_begin(aln_pairset *ps, const double *shared_matrix, int32_t *status /* n_pairs */);
+int aln_pairset_loop_step(aln_pairset *ps, const aln_params *params, uint32_t *finished, uint32_t *cause,
+                          aln_pair_result *finished_results, uint32_t *counts /* 4: run, done, failed, more */);
+
 /* ---- transform_matrix (aligner-helpers/src/matrices/mod.rs:19-68) for n matrices at once, on the HOST (no GPU is touched): matrix i
  * (rows x cols, compact row-major) is rescaled under frequencies[i * rows .. + rows), kd[i], r_squared[i] into matrices_out (which may
  * be matrices_in); status[i] = 0, or ALN_TRANSFORM_NO_ROOT where the reference returns Err(WrongMatrixSpecified) (matrix i of the

@@ -255,6 +255,18 @@ pub mod seqset {
                                        tb_off: *const u64) -> c_int;
         pub fn aln_seqset_stats(set: *const AlnSeqset, ms: *mut f64, bytes: *mut u64) -> c_int;
     }
+    /// A pair set (`aln_pairset_*`) over pairs first .. first + n_pairs - 1 of a block: it borrows the set's residues.  After
+    /// `aln_pairset_heuristics`, `aln_pairset_loop_begin` and one `aln_pairset_loop_step` per iteration run the loop of
+    /// HeuristicAligner (heuristic/mod.rs:36-78) for all pairs; a step returns the finished pairs, their causes (0 done, 1 failed,
+    /// 2 no root) and summaries, and counts = [run, done, failed, more].
+    #[repr(C)]
+    pub struct AlnPairset { _private: [u8; 0] }
+    extern "C" {
+        pub fn aln_pairset_create_from_set(set: *mut AlnSeqset, block: *const AlnSeqsetBlock, first: u64, n_pairs: u64, status: *mut c_int) -> *mut AlnPairset;
+        pub fn aln_pairset_loop_begin(ps: *mut AlnPairset, shared_matrix: *const f64, status: *mut i32) -> c_int;
+        pub fn aln_pairset_loop_step(ps: *mut AlnPairset, p: *const AlnParams, finished: *mut u32, cause: *mut u32,
+                                     finished_results: *mut AlnPairResult, counts: *mut u32) -> c_int;
+    }
 }
 
 /// The batch site of the reference, `calculate_p_value` (statistics/mod.rs:255-286): one query against `targets.len()` shuffled
