@@ -28,6 +28,9 @@ STATUS_NAMES = {0: "OK", 1: "ERR_UNNECESSARY_ARGUMENT", 2: "ERR_EMPTY_SEQUENCE",
                 8: "ERR_UNSUPPORTED", 9: "ERR_MATRIX_SHAPE", 10: "ERR_CAPACITY"}
 # enum aln_outputs
 OUT_SCORE, OUT_TRACEBACK, OUT_DIRECTIONS, OUT_H_MATRIX = 1, 2, 4, 8
+# aln_seqset_best
+SEQSET_BEST_MAX = 64
+BEST_SKIP_SELF = 1
 
 # every symbol include/aligner_hip.h declares
 EXPORTS = [
@@ -41,7 +44,7 @@ EXPORTS = [
     "aln_transform_matrices",
     "aln_pairset_heuristics", "aln_pairset_reestimate", "aln_pairset_run_stored", "aln_pairset_matrices", "aln_transform_matrices_device",
     "aln_seqset_create", "aln_seqset_destroy", "aln_seqset_pairs", "aln_seqset_score", "aln_seqset_hits", "aln_seqset_held_list",
-    "aln_seqset_held_strings", "aln_seqset_stats",
+    "aln_seqset_held_strings", "aln_seqset_stats", "aln_seqset_best",
     "aln_pairset_create_from_set", "aln_pairset_loop_begin", "aln_pairset_loop_step",
 ]
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
@@ -214,6 +217,8 @@ def load():
     lib.aln_seqset_score.argtypes = [vp, C.POINTER(Params), bp, vp, vp]
     lib.aln_seqset_hits.restype = i
     lib.aln_seqset_hits.argtypes = [vp, C.POINTER(Params), bp, C.c_double, C.POINTER(C.c_uint64)]
+    lib.aln_seqset_best.restype = i
+    lib.aln_seqset_best.argtypes = [vp, C.POINTER(Params), bp, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_uint64)]
     lib.aln_seqset_held_list.restype = i
     lib.aln_seqset_held_list.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
     lib.aln_seqset_held_strings.restype = i

@@ -7,6 +7,10 @@ gap opening 11, extension 2 unless told otherwise.
 With --heuristic every pair runs the loop of HeuristicAligner instead (heuristic.align_set: local alignment under a matrix re-estimated
 from the pair's own alignment until f stops growing), --kd K and --r-squared R being its parameters and --frequencies a,b,... the
 residue frequencies (default: those of the FASTA over the alphabet's volume); a pair the reference panics on prints the panic.
+
+With --best K the question is a database search's: per record, its K best partners among all the others (higher f first, equal f by
+the earlier record), optionally only those with f >= F, selected on the device; prints `q_head,rank,t_head,f`, records in input
+order, ranks from 1.  Not with --heuristic.
 """
 import argparse
 import sys
@@ -31,6 +35,7 @@ def main(argv=None):
     ap.add_argument("--kd", type=float, default=None)
     ap.add_argument("--r-squared", type=float, default=None)
     ap.add_argument("--frequencies", default=None, help="comma-separated residue frequencies, one per code of the alphabet")
+    ap.add_argument("--best", type=int, default=None, metavar="K", help="per record its K best partners (1 .. %d), self pairs skipped" % _ffi.SEQSET_BEST_MAX)
     a = ap.parse_args(argv)
     records = read_fasta(a.input)
     if len(records) < 2:
@@ -40,6 +45,17 @@ def main(argv=None):
     sem = _ffi.CORE_GLOBAL if a.global_ else _ffi.CORE_LOCAL
     heads = [r.head.decode("utf-8", "replace") for r in records]
     out = sys.stdout
+    if a.best is not None:
+        if a.heuristic:
+            ap.error("--best selects by the score of the plain alignment: not with --heuristic")
+        if not 1 <= a.best <= _ffi.SEQSET_BEST_MAX:
+            ap.error("--best: K must lie in 1 .. %d" % _ffi.SEQSET_BEST_MAX)
+        with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
+            held = ss.best(matrix, a.del_, a.ext, a.best, f_min=float("-inf") if a.f_min is None else a.f_min, skip_self=True, semantics=sem)
+            for q, pos in held.by_query():
+                for p in pos:
+                    out.write("%s,%d,%s,%r\n" % (heads[q], int(held.rank[p]) + 1, heads[int(held.t[p])], float(held.f[p])))
+        return 0
     if a.heuristic:
         if a.kd is None or a.r_squared is None:
             ap.error("--heuristic needs --kd and --r-squared")

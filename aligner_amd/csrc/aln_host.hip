@@ -43,6 +43,7 @@
 #include "aln_plan_rules.h"
 #include "aln_scheme_rules.h"
 #include "aln_seqset_rules.h"
+#include "aln_best_rules.h"
 #include "aln_shuffle_rules.h"
 
 #define ALN_TIMING_SLOTS 256u
@@ -241,6 +242,7 @@ extern "C" int aln_warm_fast_rest_solo(void);
 extern "C" int aln_warm_generic(void);
 extern "C" int aln_warm_single(void);
 extern "C" int aln_warm_tb(void);
+extern "C" int aln_warm_best(void);
 static void warm_context(aln_ctx *c)
 {
     if (getenv("ALN_NO_WARMUP")) return;
@@ -263,6 +265,7 @@ static void warm_context(aln_ctx *c)
         if (hipSetDevice(c->devs[d]->device) != hipSuccess) continue;
         (void)aln_warm_single(); (void)aln_warm_tb(); (void)aln_warm_generic();
         (void)aln_warm_fast_cl(); (void)aln_warm_fast_cl_solo(); (void)aln_warm_fast_rest(); (void)aln_warm_fast_rest_solo();
+        (void)aln_warm_best();
         aln_pair_result r;
         (void)aln_align_pair(c, &p, q.data(), L, t.data(), L, &r, qa.data(), ta.data(), nullptr, nullptr);   // devices in turn
     }
@@ -3085,6 +3088,18 @@ extern "C" void aln_seqset_launch_held(const PairsetHeld *held, const aln_pair_r
                                        const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
                                        hipStream_t s);
 
+extern "C" void aln_best_launch_chunk(const double *f, const int32_t *status, uint64_t n, uint64_t k0, const aln_seqset_block *block,
+                                      double f_min, uint32_t flags, uint32_t slots, uint64_t *cand_key, uint32_t *cand_t, uint32_t *cand_n,
+                                      uint64_t *run_key, uint32_t *run_t, uint32_t *run_n, hipStream_t s);
+extern "C" uint64_t aln_best_tiles(uint64_t rows);
+extern "C" void aln_best_launch_count(const uint32_t *run_n, uint64_t rows, uint32_t *tile_count, uint64_t *tile_off, uint64_t *total, hipStream_t s);
+extern "C" void aln_best_launch_emit(const uint64_t *run_key, const uint32_t *run_t, const uint32_t *run_n, uint64_t rows, uint32_t slots,
+                                     const aln_seqset_block *block, const uint64_t *tile_off, uint64_t cap, uint64_t *out_k, double *out_f,
+                                     hipStream_t s);
+
+// the per-row selection of aln_seqset_best, as a pass carries it from chunk to chunk
+struct BestPass { uint32_t slots; uint32_t flags; double f_min; };
+
 #define ALN_SEQSET_CHUNK_PAIRS (1ull << 22)        // per chunk: the pair limit of a chunk of aln_align_batch
 
 struct aln_seqset {
@@ -3106,7 +3121,9 @@ struct aln_seqset {
     std::vector<uint32_t> hit_q, hit_t;
     std::vector<PairsetHeld> info;
     DevBuf held_res, held_tb, held_info, list, out_off, packed_res, packed_tb;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // aln_seqset_best: a chunk's piece lists (key | target | count per piece) and the rows' running lists (aln_best.hip)
+    DevBuf cand_key, cand_t, cand_n, run_key, run_t, run_n;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a chunk's launches; 4, 5: the best selection
     double ms[4] = {0, 0, 0, 0};
     uint64_t bytes[2] = {0, 0};
     // pair sets made by aln_pairset_create_from_set read the residue buffer: a destroy with some of them alive releases everything
@@ -3134,7 +3151,8 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     if (ss->slot && ss->slot->stream) (void)hipStreamSynchronize(ss->slot->stream);
     for (hipEvent_t &e : ss->ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->held_res, &ss->held_tb,
-                   &ss->held_info, &ss->list, &ss->out_off, &ss->packed_res, &ss->packed_tb};
+                   &ss->held_info, &ss->list, &ss->out_off, &ss->packed_res, &ss->packed_tb, &ss->cand_key, &ss->cand_t, &ss->cand_n,
+                   &ss->run_key, &ss->run_t, &ss->run_n};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
@@ -3181,7 +3199,7 @@ extern "C" aln_seqset *aln_seqset_create(aln_ctx *ctx, const uint8_t *seqs, cons
         if (st == ALN_OK) st = dev_ensure(ss->d_len, 4ull * n_seqs, false);
         if (st == ALN_OK) st = dev_ensure(ss->misc, 256, false);
         if (st == ALN_OK) st = slot_init(*ss->slot);
-        for (int i = 0; i < 4 && st == ALN_OK; ++i) { e = hipEventCreate(&ss->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
+        for (int i = 0; i < 6 && st == ALN_OK; ++i) { e = hipEventCreate(&ss->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
         if (st == ALN_OK) {
             hipStream_t q = ss->slot->stream;
             e = hipSuccess;
@@ -3266,9 +3284,10 @@ static void seqset_chunks(const aln_seqset *ss, const Call &c, const aln_seqset_
 
 // One pass over a block: every chunk expanded, filled and gathered on the set's stream.  f / status (optional): the caller's arrays.
 // select: the chunk's pairs with status ALN_OK and f >= f_min are appended to ss->hit_pair / hit_score.  *first_bad: the status of
-// the first failed pair, ALN_OK if none failed.
+// the first failed pair, ALN_OK if none failed.  best: the chunk's f / status go through the piece and merge kernels into the rows'
+// running lists (ss->run_*, zeroed by the caller).
 static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_block &b, uint64_t pairs, double *f, int32_t *status, bool select,
-                              double f_min, int *first_bad, Chunk *plans)
+                              double f_min, int *first_bad, Chunk *plans, const BestPass *best)
 {
     Slot &s = *ss->slot;
     hipStream_t q = s.stream;
@@ -3283,6 +3302,7 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
     bool timed = false;
     int st = ALN_OK;
     auto collect = [&]() -> int {
+        if (timed && best) ss->ms[2] += ev_ms(ss->ev[4], ss->ev[5]);
         if (timed) { ss->ms[0] += ev_ms(ss->ev[0], ss->ev[1]); timed = false; }
         if (!prev_n) return ALN_OK;
         const uint8_t *h = ss->h_out.as<uint8_t>();
@@ -3331,6 +3351,12 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
             if ((st = dev_ensure(ss->hit_k, 8 * n, false)) != ALN_OK) break;
             if ((st = dev_ensure(ss->hit_f, 8 * n, false)) != ALN_OK) break;
         }
+        if (best) {
+            const uint64_t pieces = aln_best_chunk_geometry(k0, n, b.t_count).pieces;
+            if ((st = dev_ensure(ss->cand_key, 8 * pieces * best->slots, false)) != ALN_OK) break;
+            if ((st = dev_ensure(ss->cand_t, 4 * pieces * best->slots, false)) != ALN_OK) break;
+            if ((st = dev_ensure(ss->cand_n, 4 * pieces, false)) != ALN_OK) break;
+        }
         if (j == 0) {
             if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) break;
             ss->bytes[0] += c.md.size() * (c.is_int ? 4 : 8);
@@ -3352,6 +3378,14 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
                                      ss->misc.as<uint32_t>(), ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
             HIPCHK(hipGetLastError());
         }
+        if (best) {
+            HIPCHK(hipEventRecord(ss->ev[4], q));
+            aln_best_launch_chunk(ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), n, k0, &b, best->f_min, best->flags, best->slots,
+                                  ss->cand_key.as<uint64_t>(), ss->cand_t.as<uint32_t>(), ss->cand_n.as<uint32_t>(), ss->run_key.as<uint64_t>(),
+                                  ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), q);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ss->ev[5], q));
+        }
         uint8_t *h = ss->h_out.as<uint8_t>();
         HIPCHK(hipMemcpyAsync(h, ss->misc.p, 16, hipMemcpyDeviceToHost, q));
         ss->bytes[1] += 16;
@@ -3367,10 +3401,10 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
 
 // (every way out of a failed pass waits for the stream: queued work reads the plans' queues and writes the pinned staging)
 static int seqset_pass(aln_seqset *ss, const Call &c, const aln_seqset_block &b, uint64_t pairs, double *f, int32_t *status, bool select,
-                       double f_min, int *first_bad)
+                       double f_min, int *first_bad, const BestPass *best = nullptr)
 {
     Chunk plans[2];                    // chunk j's queue may still be on its way while chunk j + 1 is planned
-    const int st = seqset_pass_chunks(ss, c, b, pairs, f, status, select, f_min, first_bad, plans);
+    const int st = seqset_pass_chunks(ss, c, b, pairs, f, status, select, f_min, first_bad, plans, best);
     if (st != ALN_OK) (void)hipStreamSynchronize(ss->slot->stream);
     return st;
 }
@@ -3401,6 +3435,69 @@ extern "C" int aln_seqset_score(aln_seqset *ss, const aln_params *params, const 
     return ALN_OK;
 }
 
+// Holds the ascending pair list in ss->hit_pair / hit_score (what a selection left there): the re-fill with directions, the listed
+// pairs as a batch of their own over the resident residues, chunk by chunk, summaries and strings kept in held_res / held_tb.  On a
+// failure nothing is held (the caller clears the list).
+static int seqset_hold_list(aln_seqset *ss, const Call &ct, const aln_seqset_block *b)
+{
+    Slot &s = *ss->slot;
+    hipStream_t q = s.stream;
+    int st = ALN_OK;
+    const size_t hits = ss->hit_pair.size();
+    if (hits > 0xFFFFFFF0ull) { g_err = "too many hits"; return ALN_ERR_UNSUPPORTED; }
+    if (!hits) return ALN_OK;
+    std::vector<uint64_t> qo(hits), ql(hits), to(hits), tl(hits);
+    ss->hit_q.resize(hits); ss->hit_t.resize(hits);
+    ss->info.assign(hits, PairsetHeld{});
+    uint64_t tb_total = 0;
+    for (size_t h = 0; h < hits; ++h) {
+        uint64_t sq, tq;
+        aln_seqset_unrank(*b, ss->hit_pair[h], &sq, &tq);
+        ss->hit_q[h] = (uint32_t)sq; ss->hit_t[h] = (uint32_t)tq;
+        qo[h] = ss->off[sq]; ql[h] = ss->len[sq]; to[h] = ss->off[tq]; tl[h] = ss->len[tq];
+        ss->info[h].N = (uint32_t)ql[h]; ss->info[h].M = (uint32_t)tl[h]; ss->info[h].tb_off = tb_total;
+        tb_total += 2ull * (ql[h] + tl[h] + 2);      // the chunks' own layout (chunk_plan), chunk after chunk
+    }
+    std::vector<std::pair<size_t, size_t>> ranges;
+    make_chunks(ct, ql.data(), tl.data(), hits, 1, ranges);
+    // the held buffers, sized for exactly this count; nothing is held if the memory cannot be had
+    st = dev_ensure(ss->held_res, sizeof(aln_pair_result) * hits, false);
+    if (st == ALN_OK) st = dev_ensure(ss->held_tb, tb_total, false);
+    if (st == ALN_OK) st = dev_ensure(ss->held_info, sizeof(PairsetHeld) * hits, false);
+    if (st != ALN_OK) return st;
+    HIPCHK(hipMemcpyAsync(ss->held_info.p, ss->info.data(), sizeof(PairsetHeld) * hits, hipMemcpyHostToDevice, q));
+    ss->bytes[0] += sizeof(PairsetHeld) * hits;
+    Chunk k;
+    bool timed = false;
+    auto collect = [&]() {
+        if (timed) { ss->ms[1] += ev_ms(ss->ev[0], ss->ev[2]); timed = false; }
+    };
+    auto refill = [&]() -> int {      // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        for (size_t j = 0; j < ranges.size(); ++j) {
+            const size_t first = ranges[j].first, n = ranges[j].second;
+            k.reset();
+            if ((st = chunk_plan(ss->ctx, ct, qo.data(), ql.data(), to.data(), tl.data(), first, n, ranges.size() == 1, k, ranges.size() > 4)) != ALN_OK) break;
+            for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[first + i]; k.descs[i].t_off = to[first + i]; }
+            k.seq_direct = true; k.seq_lo = 0; k.seq_span = ss->total;
+            HIPCHK(hipStreamSynchronize(q));             // the tables go through the slot's pinned staging
+            collect();
+            if ((st = slot_ensure(s, ct, k)) != ALN_OK) break;
+            if ((st = slot_upload(s, ct, k, nullptr, qo.data(), ql.data(), to.data(), tl.data(), q, false, true)) != ALN_OK) break;
+            ss->bytes[0] += n * (sizeof(PairDesc) + 4);
+            if ((st = slot_launch(ss->ctx, s, ct, k, q, ss->ev, nullptr)) != ALN_OK) break;
+            timed = true;
+            HIPCHK(hipMemcpyAsync(ss->held_res.as<aln_pair_result>() + first, s.results.p, n * sizeof(aln_pair_result), hipMemcpyDeviceToDevice, q));
+            if (k.tb_bytes) HIPCHK(hipMemcpyAsync(ss->held_tb.as<uint8_t>() + ss->info[first].tb_off, s.tb.p, k.tb_bytes, hipMemcpyDeviceToDevice, q));
+        }
+        return st;
+    };
+    st = refill();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    HIPCHK(hipStreamSynchronize(q));
+    collect();
+    return ALN_OK;
+}
+
 extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double f_min, uint64_t *count)
 {
     Call c, ct;
@@ -3409,71 +3506,92 @@ extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const a
     if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE | ALN_OUT_TRACEBACK, ct)) != ALN_OK) return st;
     HIPCHK(hipSetDevice(ss->ctx->device));
-    Slot &s = *ss->slot;
-    hipStream_t q = s.stream;
-    HIPCHK(hipStreamSynchronize(q));
+    HIPCHK(hipStreamSynchronize(ss->slot->stream));
     seqset_begin(ss);
     *count = 0;
     const auto t0 = std::chrono::steady_clock::now();
     int bad = ALN_OK;
     if ((st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), nullptr, nullptr, true, f_min, &bad)) != ALN_OK) { seqset_begin(ss); return st; }
-    const size_t hits = ss->hit_pair.size();
-    if (hits > 0xFFFFFFF0ull) { seqset_begin(ss); g_err = "too many hits"; return ALN_ERR_UNSUPPORTED; }
-    if (hits) {
-        // the re-fill with directions: the hits as a batch of their own over the resident residues
-        std::vector<uint64_t> qo(hits), ql(hits), to(hits), tl(hits);
-        ss->hit_q.resize(hits); ss->hit_t.resize(hits);
-        ss->info.assign(hits, PairsetHeld{});
-        uint64_t tb_total = 0;
-        for (size_t h = 0; h < hits; ++h) {
-            uint64_t sq, tq;
-            aln_seqset_unrank(*b, ss->hit_pair[h], &sq, &tq);
-            ss->hit_q[h] = (uint32_t)sq; ss->hit_t[h] = (uint32_t)tq;
-            qo[h] = ss->off[sq]; ql[h] = ss->len[sq]; to[h] = ss->off[tq]; tl[h] = ss->len[tq];
-            ss->info[h].N = (uint32_t)ql[h]; ss->info[h].M = (uint32_t)tl[h]; ss->info[h].tb_off = tb_total;
-            tb_total += 2ull * (ql[h] + tl[h] + 2);      // the chunks' own layout (chunk_plan), chunk after chunk
-        }
-        std::vector<std::pair<size_t, size_t>> ranges;
-        make_chunks(ct, ql.data(), tl.data(), hits, 1, ranges);
-        // the held buffers, sized for exactly this count; nothing is held if the memory cannot be had
-        st = dev_ensure(ss->held_res, sizeof(aln_pair_result) * hits, false);
-        if (st == ALN_OK) st = dev_ensure(ss->held_tb, tb_total, false);
-        if (st == ALN_OK) st = dev_ensure(ss->held_info, sizeof(PairsetHeld) * hits, false);
-        if (st != ALN_OK) { seqset_begin(ss); return st; }
-        HIPCHK(hipMemcpyAsync(ss->held_info.p, ss->info.data(), sizeof(PairsetHeld) * hits, hipMemcpyHostToDevice, q));
-        ss->bytes[0] += sizeof(PairsetHeld) * hits;
-        Chunk k;
-        bool timed = false;
-        auto collect = [&]() {
-            if (timed) { ss->ms[1] += ev_ms(ss->ev[0], ss->ev[2]); timed = false; }
-        };
-        auto refill = [&]() -> int {      // (a HIPCHK in here leaves through the exit below, which waits for the stream)
-            for (size_t j = 0; j < ranges.size(); ++j) {
-                const size_t first = ranges[j].first, n = ranges[j].second;
-                k.reset();
-                if ((st = chunk_plan(ss->ctx, ct, qo.data(), ql.data(), to.data(), tl.data(), first, n, ranges.size() == 1, k, ranges.size() > 4)) != ALN_OK) break;
-                for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[first + i]; k.descs[i].t_off = to[first + i]; }
-                k.seq_direct = true; k.seq_lo = 0; k.seq_span = ss->total;
-                HIPCHK(hipStreamSynchronize(q));             // the tables go through the slot's pinned staging
-                collect();
-                if ((st = slot_ensure(s, ct, k)) != ALN_OK) break;
-                if ((st = slot_upload(s, ct, k, nullptr, qo.data(), ql.data(), to.data(), tl.data(), q, false, true)) != ALN_OK) break;
-                ss->bytes[0] += n * (sizeof(PairDesc) + 4);
-                if ((st = slot_launch(ss->ctx, s, ct, k, q, ss->ev, nullptr)) != ALN_OK) break;
-                timed = true;
-                HIPCHK(hipMemcpyAsync(ss->held_res.as<aln_pair_result>() + first, s.results.p, n * sizeof(aln_pair_result), hipMemcpyDeviceToDevice, q));
-                if (k.tb_bytes) HIPCHK(hipMemcpyAsync(ss->held_tb.as<uint8_t>() + ss->info[first].tb_off, s.tb.p, k.tb_bytes, hipMemcpyDeviceToDevice, q));
-            }
-            return st;
-        };
-        st = refill();
-        if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_begin(ss); return st; }
-        HIPCHK(hipStreamSynchronize(q));
-        collect();
-    }
+    if ((st = seqset_hold_list(ss, ct, b)) != ALN_OK) { seqset_begin(ss); return st; }
     ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ss->held = true;
-    *count = hits;
+    *count = ss->hit_pair.size();
+    return ALN_OK;
+}
+
+// The k best targets per query row: the pass of hits with the per-row selection of aln_best.hip in place of the threshold's, then the
+// rows' lists as one ascending pair list, held like the hits.
+extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, uint32_t k, double f_min, uint32_t flags,
+                               uint64_t *count)
+{
+    Call c, ct;
+    int st = seqset_call(ss, params, b, ALN_OUT_SCORE, c);
+    if (st != ALN_OK) return st;
+    if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (k < 1u || k > ALN_SEQSET_BEST_MAX) { g_err = "k must lie in 1 .. ALN_SEQSET_BEST_MAX"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (flags & ~ALN_BEST_SKIP_SELF) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (b->upper) { g_err = "the k best per query are defined on a rectangle: a pair of an upper block belongs to both of its sequences"; return ALN_ERR_UNSUPPORTED; }
+    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE | ALN_OUT_TRACEBACK, ct)) != ALN_OK) return st;
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    seqset_begin(ss);
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t rows = b->q_count;
+    BestPass best;
+    best.slots = aln_best_slots(k, b->t_count); best.flags = flags; best.f_min = f_min;
+    // the rows' running lists, for this call
+    st = dev_ensure(ss->run_key, 8 * rows * best.slots, false);
+    if (st == ALN_OK) st = dev_ensure(ss->run_t, 4 * rows * best.slots, false);
+    if (st == ALN_OK) st = dev_ensure(ss->run_n, 4 * rows, false);
+    const uint64_t tiles = aln_best_tiles(rows);
+    if (st == ALN_OK) st = dev_ensure(ss->tiles, 12 * tiles, false);
+    if (st != ALN_OK) return st;
+    HIPCHK(hipMemsetAsync(ss->run_n.p, 0, 4 * rows, q));
+    int bad = ALN_OK;
+    if ((st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), nullptr, nullptr, false, 0.0, &bad, &best)) != ALN_OK) { seqset_begin(ss); return st; }
+    // finish: the rows' counts -> offsets and the total, then (sized for exactly the total) the ascending list
+    uint64_t *tile_off = reinterpret_cast<uint64_t *>(ss->tiles.as<uint8_t>());
+    uint32_t *tile_count = reinterpret_cast<uint32_t *>(ss->tiles.as<uint8_t>() + 8 * tiles);
+    uint64_t *d_total = reinterpret_cast<uint64_t *>(ss->misc.as<uint8_t>() + 32);
+    uint64_t total = 0;
+    auto finish = [&]() -> int {       // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        HIPCHK(hipEventRecord(ss->ev[4], q));
+        aln_best_launch_count(ss->run_n.as<uint32_t>(), rows, tile_count, tile_off, d_total, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        ss->bytes[1] += 8;
+        if (total > 0xFFFFFFF0ull) { g_err = "too many hits"; return ALN_ERR_UNSUPPORTED; }
+        if (total) {
+            int e = dev_ensure(ss->hit_k, 8 * total, false);
+            if (e == ALN_OK) e = dev_ensure(ss->hit_f, 8 * total, false);
+            if (e != ALN_OK) return e;
+            aln_best_launch_emit(ss->run_key.as<uint64_t>(), ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), rows, best.slots, b, tile_off, total,
+                                 ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(ss->ev[5], q));
+        ss->hit_pair.resize(total); ss->hit_score.resize(total);
+        if (total) {
+            HIPCHK(hipMemcpyAsync(ss->hit_pair.data(), ss->hit_k.p, 8 * total, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipMemcpyAsync(ss->hit_score.data(), ss->hit_f.p, 8 * total, hipMemcpyDeviceToHost, q));
+            ss->bytes[1] += 16 * total;
+        }
+        HIPCHK(hipStreamSynchronize(q));
+        ss->ms[2] += ev_ms(ss->ev[4], ss->ev[5]);
+        // the host indexes its tables with this list: pairs of the block, ascending
+        const uint64_t pairs = aln_seqset_block_pairs(ss->n, *b);
+        for (uint64_t h = 0; h < total; ++h)
+            if (ss->hit_pair[h] >= pairs || (h && ss->hit_pair[h] <= ss->hit_pair[h - 1])) { g_err = "the selection's list is not an ascending list of the block's pairs"; return ALN_ERR_DEVICE; }
+        return ALN_OK;
+    };
+    st = finish();
+    if (st == ALN_OK) st = seqset_hold_list(ss, ct, b);
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_begin(ss); return st; }
+    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->held = true;
+    *count = total;
     return ALN_OK;
 }
 

@@ -123,7 +123,22 @@ class SeqSet:
         runtime.raise_for_status(st, "aln_seqset_hits")
         return HeldHits(self, int(count.value), semantics)
 
+    def best(self, matrix, del_, ext, k, f_min=float("-inf"), block=None, skip_self=False, semantics=_ffi.CORE_LOCAL, blank=98, **kw):
+        """A held pass: of every query of a rectangle (default: the whole set against itself) the k best targets among the pairs that
+        succeeded with f >= f_min -- higher f first, equal f by the lower target number -- selected on the device and aligned.
+        skip_self leaves (i, i) out.  Returns a BestHits (valid until the next score / hits / best on this set)."""
+        if block is None:
+            block = rectangle(0, len(self), 0, len(self))
+        b, n = self._checked(block)
+        p, keep = runtime.make_params(semantics, del_, ext, matrix, blank=blank, **kw)
+        count = C.c_uint64(0)
+        st = self.lib.aln_seqset_best(self.handle, C.byref(p), C.byref(b), int(k), float(f_min), _ffi.BEST_SKIP_SELF if skip_self else 0,
+                                      C.byref(count))
+        runtime.raise_for_status(st, "aln_seqset_best")
+        return BestHits(self, int(count.value), semantics)
+
     def stats(self):
+        """(after best, fetch_kernel_ms is the selection kernels' time until a held fetch overwrites it)"""
         ms, by = (C.c_double * 4)(), (C.c_uint64 * 2)()
         runtime.raise_for_status(self.lib.aln_seqset_stats(self.handle, ms, by), "aln_seqset_stats")
         return dict(fill_ms=ms[0], refill_ms=ms[1], fetch_kernel_ms=ms[2], wall_ms=ms[3], bytes_up=int(by[0]), bytes_down=int(by[1]))
@@ -183,6 +198,37 @@ class HeldHits:
                 coords = ((int(r["start_x"]) + 1, int(r["end_x"]) + 1), (int(r["start_y"]) + 1, int(r["end_y"]) + 1))
             out.append(Alignment(o.alphabet, strs[k][0], strs[k][1], coords, float(r["f"])))
         return out
+
+
+def best_ranks(q, t, f):
+    """Rank of every entry within its query under the rule of aln_best_rules.h: higher f first, equal f (-0.0 == +0.0) by the lower
+    target number."""
+    q, t, f = np.asarray(q), np.asarray(t), np.asarray(f, dtype=np.float64)
+    order = np.lexsort((t, -f, q))
+    rank = np.zeros(len(q), dtype=np.uint32)
+    if len(q):
+        qs = q[order]
+        start = np.flatnonzero(np.concatenate([[True], qs[1:] != qs[:-1]]))
+        first = np.repeat(start, np.diff(np.concatenate([start, [len(q)]])))
+        rank[order] = (np.arange(len(q)) - first).astype(np.uint32)
+    return rank
+
+
+class BestHits(HeldHits):
+    """The held list of SeqSet.best: ascending pair order (query by query, targets ascending) as HeldHits, plus .rank -- 0 for a
+    query's best target -- computed here from f and t by the rule.  by_query() yields (q, positions in rank order)."""
+
+    def __init__(self, owner, count, semantics):
+        super().__init__(owner, count, semantics)
+        self.rank = best_ranks(self.q, self.t, self.f)
+
+    def by_query(self):
+        order = np.lexsort((self.rank, self.q))
+        qs = self.q[order]
+        cuts = np.flatnonzero(qs[1:] != qs[:-1]) + 1 if len(qs) else np.zeros(0, dtype=np.int64)
+        for part in np.split(order, cuts):
+            if len(part):
+                yield int(self.q[part[0]]), part
 
 
 def all_pairs(records, matrix, del_, ext, f_min=None, alphabet=Protein, semantics=_ffi.CORE_LOCAL, device=None, **kw):

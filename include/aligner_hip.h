@@ -350,6 +350,31 @@ int aln_seqset_held_strings(aln_seqset *set, const uint32_t *keep, uint64_t n_ke
                             const uint64_t *tb_off);
 int aln_seqset_stats(const aln_seqset *set, double *ms /* 4 */, uint64_t *bytes /* 2 */);
 
+/* ---- the k best targets per query (an addition of the same ABI version): the question of a database search.  A HELD pass like
+ * aln_seqset_hits -- the same chunking, fill, gather, per-pair failures and re-fill -- whose selection is per query row instead of
+ * one global threshold: of every query q of a rectangle (upper = 1: ALN_ERR_UNSUPPORTED, a pair would belong to both of its
+ * sequences), the min(k, candidates) candidates that come first.
+ * candidate: a pair of the row with status ALN_OK, f == f and f >= f_min (plain IEEE compares: a NaN f_min selects nothing; -inf
+ * admits every pair that succeeded); with ALN_BEST_SKIP_SELF also q != t as sequence numbers.  A failed pair is never a candidate and
+ * does not fail the call.
+ * order: (f, t) before (f', t') iff f > f', or f == f' and t < t' (-0.0 == +0.0): total within a row, so the kept set does not depend
+ * on the launch geometry, the chunking or anything else (aligner_amd/csrc/aln_best_rules.h is the rule as code).
+ * The selection runs on the device (aln_best.hip): per-row running lists of min(k, t_count) slots of 12 bytes, allocated for the
+ * call (ALN_ERR_OOM and nothing held if they cannot be had), and after the last chunk one ascending (pair number, f) list, 16 bytes
+ * per kept pair, comes down -- nothing per pair of the block does.  *count = the sum over the query rows of min(k, candidates).  The list is held as
+ * the hits of aln_seqset_hits are: held_list and held_strings serve it with their contracts unchanged, in ascending pair order
+ * (query by query, targets ascending); the rank within a query follows from f and t by the order.  A kept f of -0.0 is listed as
+ * +0.0 (equal under the order); held_strings' summary carries the fill's own bits.  Held state lasts until the set's next score /
+ * hits / best or destroy.
+ * ALN_ERR_INVALID_ARGUMENT, nothing held and *count untouched: k outside 1 .. ALN_SEQSET_BEST_MAX, a flag bit other than
+ * ALN_BEST_SKIP_SELF, a null count, an invalid block.  ALN_PWM_LOCAL: ALN_ERR_UNSUPPORTED.  A refused call leaves earlier held state
+ * as it was.
+ * stats after a best pass: ms[0] fill, ms[1] re-fill and walk, ms[2] the selection kernels (a later held fetch overwrites it). ---- */
+#define ALN_SEQSET_BEST_MAX 64u
+#define ALN_BEST_SKIP_SELF 1u
+int aln_seqset_best(aln_seqset *set, const aln_params *params, const aln_seqset_block *block, uint32_t k, double f_min, uint32_t flags,
+                    uint64_t *count);
+
 /* ---- heuristic alignment of the pairs of a sequence set (additions of the same ABI version): the request path's two halves joined --
  * every pair of a FASTA (generate_pairs), each run through the loop of HeuristicAligner (heuristic/mod.rs:36-78).
  * create_from_set: a pair set whose pair i is pair first + i of the block, in the block's numbering (sequence q the query, sequence

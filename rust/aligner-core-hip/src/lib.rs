@@ -244,12 +244,17 @@ pub mod seqset {
         /// every pair i < j of sequences first .. first + n - 1, in generate_pairs order
         pub fn upper(first: u64, n: u64) -> Self { AlnSeqsetBlock { q_first: first, q_count: n, t_first: first, t_count: n, upper: 1, reserved: 0 } }
     }
+    pub const ALN_SEQSET_BEST_MAX: u32 = 64;
+    pub const ALN_BEST_SKIP_SELF: u32 = 1;
     extern "C" {
         pub fn aln_seqset_create(ctx: *mut AlnCtx, seqs: *const u8, off: *const u64, len: *const u64, n_seqs: usize, status: *mut c_int) -> *mut AlnSeqset;
         pub fn aln_seqset_destroy(set: *mut AlnSeqset);
         pub fn aln_seqset_pairs(set: *const AlnSeqset, block: *const AlnSeqsetBlock) -> u64;
         pub fn aln_seqset_score(set: *mut AlnSeqset, p: *const AlnParams, block: *const AlnSeqsetBlock, f: *mut f64, status: *mut i32) -> c_int;
         pub fn aln_seqset_hits(set: *mut AlnSeqset, p: *const AlnParams, block: *const AlnSeqsetBlock, f_min: f64, count: *mut u64) -> c_int;
+        /// the k best targets per query of a rectangle (k in 1 ..= ALN_SEQSET_BEST_MAX), selected on the device and held like the hits
+        pub fn aln_seqset_best(set: *mut AlnSeqset, p: *const AlnParams, block: *const AlnSeqsetBlock, k: u32, f_min: f64, flags: u32,
+                               count: *mut u64) -> c_int;
         pub fn aln_seqset_held_list(set: *mut AlnSeqset, first: u64, n: u64, pair_index: *mut u64, q_seq: *mut u32, t_seq: *mut u32, f: *mut f64) -> c_int;
         pub fn aln_seqset_held_strings(set: *mut AlnSeqset, keep: *const u32, n_keep: u64, results: *mut AlnPairResult, tb_buf: *mut u8,
                                        tb_off: *const u64) -> c_int;

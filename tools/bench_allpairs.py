@@ -3,6 +3,10 @@ descriptors built on the host.  2 000 random proteins with C5's length distribut
 local, all 1 999 000 pairs.  Both paths run in one session, alternating, three runs each; the minimum is the figure and the batch
 path's own spread is the noise a difference has to exceed.
 usage: python tools/bench_allpairs.py [--n 2000] [--runs 3] [--out profiles/r08_seqset.txt] [--rocprof DIR]
+       python tools/bench_allpairs.py --best 10 [--out profiles/r11_best.txt]
+--best K: the K best targets per query over the full n x n rectangle instead: SeqSet.best (selection on the device, winners held with
+their strings) against SeqSet.score on the same block + numpy.argpartition and a sort per row on the host + align_batch with traceback
+on the winners.
 --rocprof DIR: afterwards, one `rocprofv3 --kernel-trace --stats` run of its own (one score pass and one hits pass) into DIR."""
 import argparse, csv, glob, os, subprocess, sys, time
 sys.path.insert(0, ".")
@@ -17,6 +21,7 @@ ap.add_argument("--n", type=int, default=2000)
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--out", default="profiles/r08_seqset.txt")
 ap.add_argument("--rocprof", default=None)
+ap.add_argument("--best", type=int, default=None, metavar="K")
 ap.add_argument("--once", action="store_true", help="one score pass and one hits pass, nothing else (the run under the profiler)")
 a = ap.parse_args()
 
@@ -35,6 +40,73 @@ lines = []
 def say(s=""):
     print(s, flush=True)
     lines.append(s)
+
+
+def best_case(K):
+    """SeqSet.best against score + host selection + align_batch on the winners, alternating; minima."""
+    from aligner_amd.seqset import rectangle
+    blk = rectangle(0, n, 0, n)
+    rect_pairs, rect_cells = n * n, int(lens.sum()) ** 2
+
+    def host_select(f, status):
+        g = np.where(status == 0, f, -np.inf).reshape(n, n)
+        part = np.argpartition(-g, K - 1, axis=1)[:, :K]
+        rows = np.repeat(np.arange(n), K).reshape(n, K)
+        order = np.lexsort((part, -g[rows, part]), axis=1)
+        return rows[:, 0:1].repeat(K, 1).ravel(), np.take_along_axis(part, order, axis=1).ravel()
+
+    with SeqSet(seqs) as ss:
+        say("The %d best targets per query on a resident sequence set: SeqSet.best against SeqSet.score + numpy + align_batch" % K)
+        say("%d proteins (C5 lengths, %d residues), the full %d x %d rectangle: %d pairs, %.4g cells; BLOSUM62 11 / 2 core local; %d runs each, alternating"
+            % (n, int(lens.sum()), n, n, rect_pairs, rect_cells, a.runs))
+        ss.best(S, 11.0, 2.0, K, block=blk)                 # warm: code objects, buffers
+        t_best, t_score, t_sel, t_aln, st_best, st_score = [], [], [], [], None, None
+        for r in range(a.runs):
+            t0 = time.perf_counter(); held = ss.best(S, 11.0, 2.0, K, block=blk); t_best.append(time.perf_counter() - t0)
+            if t_best[-1] == min(t_best): st_best = ss.stats()
+            t0 = time.perf_counter(); f, status = ss.score(S, 11.0, 2.0, blk); t_score.append(time.perf_counter() - t0)
+            if t_score[-1] == min(t_score): st_score = ss.stats()
+            t0 = time.perf_counter(); q, t = host_select(f, status); t_sel.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            b = PairBatch(residues, off[q], lens[q].astype(np.uint64), off[t], lens[t].astype(np.uint64))
+            won = align_batch(b, _ffi.CORE_LOCAL, 11.0, 2.0, S, want_traceback=True)
+            t_aln.append(time.perf_counter() - t0)
+        base = [x + y + z for x, y, z in zip(t_score, t_sel, t_aln)]
+        # argpartition keeps any of the targets tied at the cut; the check is the rule itself (a full sort per row, outside the timing)
+        g = np.where(status == 0, f, -np.inf).reshape(n, n)
+        exact = np.sort(np.stack([np.lexsort((np.arange(n), -g[i]))[:K] for i in range(n)]), axis=1)
+        same = bool(len(held) == n * K and np.array_equal(held.t.reshape(n, K), exact) and np.array_equal(held.f, g[held.q, held.t]))
+        same_f = bool(np.array_equal(np.sort(g[q, t].reshape(n, K), axis=1), np.sort(held.f.reshape(n, K), axis=1))) if len(held) == n * K else False
+
+        def row(name, ts):
+            say("%-52s %s  min %.1f  spread %.1f" % (name, " ".join("%.1f" % (1e3 * v) for v in ts), 1e3 * min(ts), 1e3 * (max(ts) - min(ts))))
+
+        say()
+        say("wall time per call [ms]")
+        row("SeqSet.best (k = %d: %d kept)" % (K, len(held)), t_best)
+        row("baseline: score + select + align_batch", base)
+        row("  SeqSet.score", t_score)
+        row("  numpy.argpartition + sort per row", t_sel)
+        row("  align_batch with traceback on the winners", t_aln)
+        say()
+        say("SeqSet.best:  fill kernels %.1f ms, selection kernels %.2f ms (%.2f %% of the fill), re-fill + walk %.1f ms, %.2f MB up, %.2f MB down"
+            % (st_best["fill_ms"], st_best["fetch_kernel_ms"], 100.0 * st_best["fetch_kernel_ms"] / st_best["fill_ms"], st_best["refill_ms"],
+               st_best["bytes_up"] / 1e6, st_best["bytes_down"] / 1e6))
+        say("SeqSet.score: fill kernels %.1f ms, %.2f MB up, %.2f MB down (12 bytes per pair); the winners' batch: %.2f MB up, %.2f MB down"
+            % (st_score["fill_ms"], st_score["bytes_up"] / 1e6, st_score["bytes_down"] / 1e6,
+               (32 * len(q) + len(residues)) / 1e6, (48 * len(q) + 2 * int((lens[q] + lens[t] + 2).sum())) / 1e6))
+        say("the kept pairs equal the rule applied to the scores (full sort per row): %s; their f equal the host selection's, row by row: %s" % (same, same_f))
+        d = min(base) - min(t_best)
+        noise = max(max(base) - min(base), max(t_best) - min(t_best))
+        say("SeqSet.best against the baseline: %.1f ms %s (the larger spread of the two: %.1f ms)" % (1e3 * abs(d), "less" if d > 0 else "MORE", 1e3 * noise))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.best is not None:
+    best_case(a.best)
+    sys.exit(0)
 
 
 def batch_descriptors():
