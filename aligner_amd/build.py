@@ -15,7 +15,7 @@ SOURCES = ["aln_kernels.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip",
 # aln_kernels.hip is compiled as several translation units side by side (-DALN_TU=<mask of its ALN_PART_* families>): the fast
 # core-local batch kernel alone is half of the compile time
 KERNEL_UNITS = [("generic", 1), ("fast_cl", 2), ("fast_rest", 4), ("single", 8), ("tb", 16), ("fast_cl_solo", 32), ("fast_rest_solo", 64)]
-HEADERS = ["aln_best_rules.h", "aln_device.h", "aln_fast.h", "aln_loop_rules.h", "aln_plan_rules.h", "aln_scheme_rules.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_transform_rules.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h")]
+HEADERS = ["aln_best_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_loop_rules.h", "aln_plan_rules.h", "aln_scheme_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_transform_rules.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h")]
 # host-only helper of the synthetic workloads (splitmix64 residues; aligner_amd/workloads.py only LOADS it)
 SYNTH_LIB = os.path.join(LIBDIR, "libaln_synth.so")
 SYNTH_SRC = os.path.join(CSRC, "aln_synth.c")
@@ -78,13 +78,7 @@ def _build_lib(force=False, remarks=False):
     os.makedirs(objdir, exist_ok=True)
     jobs = [(base + ["-DALN_TU=%d" % mask, "-c", os.path.join(CSRC, "aln_kernels.hip"), "-o", os.path.join(objdir, "aln_kernels_%s.o" % name)])
             for name, mask in KERNEL_UNITS]
-    jobs.append(base + ["-c", os.path.join(CSRC, "aln_host.hip"), "-o", os.path.join(objdir, "aln_host.o")])
-    jobs.append(base + ["-c", os.path.join(CSRC, "aln_scan.hip"), "-o", os.path.join(objdir, "aln_scan.o")])
-    jobs.append(base + ["-c", os.path.join(CSRC, "aln_shuffle.hip"), "-o", os.path.join(objdir, "aln_shuffle.o")])
-    jobs.append(base + ["-c", os.path.join(CSRC, "aln_pairset.hip"), "-o", os.path.join(objdir, "aln_pairset.o")])
-    jobs.append(base + ["-c", os.path.join(CSRC, "aln_seqset.hip"), "-o", os.path.join(objdir, "aln_seqset.o")])
-    jobs.append(base + ["-c", os.path.join(CSRC, "aln_loop.hip"), "-o", os.path.join(objdir, "aln_loop.o")])
-    jobs.append(base + ["-c", os.path.join(CSRC, "aln_best.hip"), "-o", os.path.join(objdir, "aln_best.o")])
+    jobs += [base + ["-c", os.path.join(CSRC, src), "-o", os.path.join(objdir, src.replace(".hip", ".o"))] for src in SOURCES[1:]]
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as pool:
         for rc, cmd in zip(pool.map(subprocess.call, jobs), jobs):

@@ -1,6 +1,5 @@
 // aln_best.hip -- device side of aln_seqset_best (include/aligner_hip.h): the k best targets of every query row of a rectangle of a
-// resident sequence set, selected where the scores are.  A sibling of the set's threshold selection (aln_seqset.hip), in a translation
-// unit of its own so that the existing kernels stay as they are.  The rule -- candidate, order, geometry, fold -- is aln_best_rules.h.
+// resident sequence set, selected where the scores are.  The rule -- candidate, order, geometry, fold -- is aln_best_rules.h.
 //
 //   piece      one workgroup per (touched row, piece of <= 2048 pairs) of a chunk: the candidates' (key, target) go into LDS (2048 x 12
 //              bytes), non-candidates as a sentinel that sorts last; a bitonic sort under the rule; the first min(slots, candidates)
@@ -8,16 +7,19 @@
 //   merge      one wave per touched row: the row's piece lists, each sorted, are folded one after the other into the row's running list
 //              (rank by counting over <= 2 x 64 entries per fold).  A row cut by a chunk border meets its running list again in the next
 //              chunk; the launches of one stream keep the order
-//   finish     after the last chunk: rows' counts -> tile sums (256 rows per tile), one workgroup's scan over the tiles, then every tile
-//              writes its rows' entries in ascending target order at their offsets: one ascending (pair number, f) list, no atomics
+//   finish     after the last chunk: rows' counts -> tile sums (256 rows per tile, one row per thread), the shared scan over the tiles
+//              with 64-bit offsets (aln_select.h), then every tile writes its rows' entries in ascending target order at their
+//              offsets: one ascending (pair number, f) list, no atomics
 //
 // Every loop is bounded by the problem size, no kernel waits for another workgroup, every store is a plain C++ store.
 #include <hip/hip_runtime.h>
 
 #include "aln_best_rules.h"
+#include "aln_launch.h"
+#include "aln_select.h"
 
 #define BEST_THREADS 256u
-#define BEST_TILE_ROWS 256u
+#define BEST_TILE_ROWS ALN_SELECT_THREADS            // one row per thread of the block scan
 #define BEST_SENTINEL_T 0xFFFFFFFFu               // with key 0 (no candidate has it): after every candidate
 
 // ---- piece p of the chunk: sorted, its first min(slots, candidates) at cand_*[p * slots ..], their number in cand_n[p]
@@ -107,48 +109,14 @@ __global__ __launch_bounds__(64) void aln_best_merge_kernel(uint64_t n, uint64_t
     if (lane == 0) run_n[row] = na;
 }
 
-// block-wide exclusive prefix sum of one value per thread (256 threads); returns the thread's offset, *total the block's sum
-__device__ __forceinline__ uint32_t best_block_scan(uint32_t v, uint32_t *lds, uint32_t *total)
-{
-    const uint32_t t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (uint32_t o = 1; o < BEST_THREADS; o <<= 1) {
-        const uint32_t add = t >= o ? lds[t - o] : 0u;
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const uint32_t incl = lds[t];
-    *total = lds[BEST_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
 // ---- finish, step 1: kept entries per tile of 256 rows
 __global__ __launch_bounds__(256) void aln_best_count_kernel(const uint32_t *run_n, uint64_t rows, uint32_t *tile_count)
 {
-    __shared__ uint32_t lds[BEST_THREADS];
+    __shared__ uint32_t lds[ALN_SELECT_THREADS];
     const uint64_t row = (uint64_t)blockIdx.x * BEST_TILE_ROWS + threadIdx.x;
     uint32_t total;
-    (void)best_block_scan(row < rows ? run_n[row] : 0u, lds, &total);
+    (void)aln_block_exclusive_scan(row < rows ? run_n[row] : 0u, lds, &total);
     if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
-}
-
-// ---- finish, step 2: one workgroup turns the tile counts into tile offsets (64-bit: 2^32 rows of 64); total[0] = kept entries
-__global__ __launch_bounds__(256) void aln_best_offsets_kernel(const uint32_t *tile_count, uint64_t *tile_off, uint64_t tiles, uint64_t *total_out)
-{
-    __shared__ uint32_t lds[BEST_THREADS];
-    uint64_t carry = 0;
-    for (uint64_t b = 0; b < tiles; b += BEST_THREADS) {
-        const uint64_t i = b + threadIdx.x;
-        const uint32_t v = i < tiles ? tile_count[i] : 0u;        // <= 256 x 64: a trip's sum fits 32 bits
-        uint32_t total;
-        const uint32_t ex = best_block_scan(v, lds, &total);
-        if (i < tiles) tile_off[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) total_out[0] = carry;
 }
 
 // ---- finish, step 3: a tile's rows, each in ascending target order (rank by counting within the row; one wave per row, four rows
@@ -157,12 +125,12 @@ __global__ __launch_bounds__(256) void aln_best_emit_kernel(const uint64_t *run_
                                                             uint32_t slots, uint64_t t_count, uint64_t t_first, const uint64_t *tile_off,
                                                             uint64_t cap, uint64_t *out_k, double *out_f)
 {
-    __shared__ uint32_t lds[BEST_THREADS];
+    __shared__ uint32_t lds[ALN_SELECT_THREADS];
     __shared__ uint32_t row_off[BEST_TILE_ROWS];
     const uint64_t row0 = (uint64_t)blockIdx.x * BEST_TILE_ROWS;
     const uint64_t mine = row0 + threadIdx.x;
     uint32_t total;
-    row_off[threadIdx.x] = best_block_scan(mine < rows ? run_n[mine] : 0u, lds, &total);
+    row_off[threadIdx.x] = aln_block_exclusive_scan(mine < rows ? run_n[mine] : 0u, lds, &total);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t base = tile_off[blockIdx.x];
@@ -203,12 +171,13 @@ extern "C" void aln_best_launch_chunk(const double *f, const int32_t *status, ui
 
 extern "C" uint64_t aln_best_tiles(uint64_t rows) { return (rows + BEST_TILE_ROWS - 1) / BEST_TILE_ROWS; }
 
-// tile_count: aln_best_tiles(rows) words; tile_off: as many uint64_t; total[0]: the kept entries of all rows
+// tile_count: aln_best_tiles(rows) words, each <= 256 x 64; tile_off: as many uint64_t (2^32 rows of 64); total[0]: the kept entries of
+// all rows
 extern "C" void aln_best_launch_count(const uint32_t *run_n, uint64_t rows, uint32_t *tile_count, uint64_t *tile_off, uint64_t *total, hipStream_t s)
 {
     const uint64_t tiles = aln_best_tiles(rows);
     if (tiles) hipLaunchKernelGGL(aln_best_count_kernel, dim3((uint32_t)tiles), dim3(BEST_THREADS), 0, s, run_n, rows, tile_count);
-    hipLaunchKernelGGL(aln_best_offsets_kernel, dim3(1), dim3(BEST_THREADS), 0, s, tile_count, tile_off, tiles, total);
+    hipLaunchKernelGGL(aln_select_offsets_kernel<uint64_t>, dim3(1), dim3(ALN_SELECT_THREADS), 0, s, tile_count, tile_off, tiles, total);
 }
 
 // out_k / out_f: cap entries (the total of aln_best_launch_count)

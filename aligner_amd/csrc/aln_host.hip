@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "aln_device.h"
+#include "aln_launch.h"
 #include "aln_loop_rules.h"
 #include "aln_plan_rules.h"
 #include "aln_scheme_rules.h"
@@ -113,6 +114,15 @@ static void dev_free(DevBuf &b)
 {
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr; b.cap = 0;
+}
+// the tile buffer of an ordered selection (aln_select.h): `tiles` offsets (the wider words first: aligned), then as many counts
+template <class Off> static int tiles_ensure(DevBuf &b, uint64_t tiles, uint32_t **tile_count, Off **tile_off)
+{
+    const int st = dev_ensure(b, (sizeof(Off) + 4) * tiles, false);
+    if (st != ALN_OK) return st;
+    *tile_off = b.as<Off>();
+    *tile_count = reinterpret_cast<uint32_t *>(*tile_off + tiles);
+    return ALN_OK;
 }
 struct PinBuf {
     void *p = nullptr;
@@ -242,7 +252,6 @@ extern "C" int aln_warm_fast_rest_solo(void);
 extern "C" int aln_warm_generic(void);
 extern "C" int aln_warm_single(void);
 extern "C" int aln_warm_tb(void);
-extern "C" int aln_warm_best(void);
 static void warm_context(aln_ctx *c)
 {
     if (getenv("ALN_NO_WARMUP")) return;
@@ -1717,22 +1726,6 @@ extern "C" int aln_align_pair(aln_ctx *ctx, const aln_params *params, const uint
 // A held pass (aln_scan_hits) is a select pass that keeps all of that on the device: the count alone comes back, the hit buffers
 // are sized for it (no capacity, no second fill), and the caller then asks for the hit list (window, f), for the sum of the
 // frequency matrices of a list of hits (aln_scan_freq_kernel: u32 counters, exact in any order) or for the strings of a list.
-extern "C" void aln_scan_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t first, uint64_t step, uint64_t width,
-                                       uint64_t len, uint64_t base, uint32_t cols, hipStream_t s);
-extern "C" void aln_scan_launch_f(const aln_pair_result *res, double *f, uint64_t n, int32_t *bad, hipStream_t s);
-extern "C" uint64_t aln_scan_tiles(uint64_t n);
-extern "C" void aln_scan_launch_select(const aln_pair_result *res, uint64_t n, double mean, double sd, double z_min, uint32_t *tile_count,
-                                       uint32_t *tile_off, uint32_t *count, uint32_t *idx, uint32_t cap, hipStream_t s);
-extern "C" void aln_scan_launch_hits(PairDesc *descs, uint32_t *order, uint32_t n_slots, const uint32_t *idx, const uint32_t *count,
-                                     uint32_t cap, uint64_t first, uint64_t step, uint64_t width, uint64_t len, uint64_t base,
-                                     uint32_t cols, uint64_t dir_stride, uint64_t tb_stride, uint64_t tag_stride, hipStream_t s);
-extern "C" void aln_scan_launch_reverse(uint8_t *seq, uint64_t len, hipStream_t s);
-extern "C" void aln_scan_launch_held_f(const aln_pair_result *res, double *f, uint32_t n, hipStream_t s);
-extern "C" void aln_scan_launch_freq(const PairDesc *descs, const aln_pair_result *res, const uint8_t *tb, const uint32_t *keep,
-                                     uint32_t n_keep, uint32_t n_held, uint32_t cols, uint32_t blank, uint32_t *counts, double *out,
-                                     hipStream_t s);
-extern "C" void aln_scan_launch_gather(const aln_pair_result *res, const uint8_t *tb, const uint32_t *keep, uint32_t n_keep, uint32_t n_held,
-                                       uint64_t stride, aln_pair_result *out_res, uint8_t *out_tb, hipStream_t s);
 
 // the re-fill of a select pass has room for at least this many hits: a chunk of <= 4 pairs would take the one-workgroup route,
 // whose plan reads the pairs' shapes on the host
@@ -1993,9 +1986,9 @@ extern "C" int aln_scan_select(aln_scan *sc, const aln_params *params, const aln
     // every buffer is sized before anything is queued: a buffer that grew later would be freed under a running kernel
     if ((st = slot_ensure(s, c, pl->k, nullptr, true)) != ALN_OK) return st;
     if ((st = slot_ensure(s, ct, ph->k, nullptr, true)) != ALN_OK) return st;
-    const uint64_t tiles = aln_scan_tiles(n);
+    uint32_t *tile_count, *tile_off;
     if ((st = dev_ensure(sc->fbuf, 8 * n, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(sc->tiles, 8 * tiles, false)) != ALN_OK) return st;
+    if ((st = tiles_ensure(sc->tiles, aln_scan_tiles(n), &tile_count, &tile_off)) != ALN_OK) return st;
     if ((st = dev_ensure(sc->idx, 4 * slots, false)) != ALN_OK) return st;
     hipStream_t q = s.stream;
     HIPCHK(hipEventRecord(sc->ev[0], q));
@@ -2003,8 +1996,7 @@ extern "C" int aln_scan_select(aln_scan *sc, const aln_params *params, const aln
     if ((st = scan_fill(sc, c, g, pl.get(), n)) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
     HIPCHK(hipEventRecord(sc->ev[1], q));
     uint32_t *misc = sc->misc.as<uint32_t>();
-    aln_scan_launch_select(s.results.as<aln_pair_result>(), n, mean, sd, z_min, sc->tiles.as<uint32_t>(), sc->tiles.as<uint32_t>() + tiles,
-                           misc, sc->idx.as<uint32_t>(), (uint32_t)slots, q);
+    aln_scan_launch_select(s.results.as<aln_pair_result>(), n, mean, sd, z_min, tile_count, tile_off, misc, sc->idx.as<uint32_t>(), (uint32_t)slots, q);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sc->ev[2], q));
     aln_scan_launch_hits(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), (uint32_t)slots, sc->idx.as<uint32_t>(), misc, (uint32_t)slots,
@@ -2062,9 +2054,9 @@ extern "C" int aln_scan_hits(aln_scan *sc, const aln_params *params, const aln_s
     std::shared_ptr<ScanPlan> pl, ph;
     if ((st = scan_plan(sc, c, g, n, 0, pl)) != ALN_OK) return st;
     if ((st = slot_ensure(s, c, pl->k, nullptr, true)) != ALN_OK) return st;
-    const uint64_t tiles = aln_scan_tiles(n);
+    uint32_t *tile_count, *tile_off;
     if ((st = dev_ensure(sc->fbuf, 8 * n, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(sc->tiles, 8 * tiles, false)) != ALN_OK) return st;
+    if ((st = tiles_ensure(sc->tiles, aln_scan_tiles(n), &tile_count, &tile_off)) != ALN_OK) return st;
     if ((st = dev_ensure(sc->idx, 4 * n, false)) != ALN_OK) return st;           // every window may pass: 4 bytes each
     hipStream_t q = s.stream;
     HIPCHK(hipEventRecord(sc->ev[0], q));
@@ -2072,8 +2064,7 @@ extern "C" int aln_scan_hits(aln_scan *sc, const aln_params *params, const aln_s
     if ((st = scan_fill(sc, c, g, pl.get(), n)) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
     HIPCHK(hipEventRecord(sc->ev[1], q));
     uint32_t *misc = sc->misc.as<uint32_t>();
-    aln_scan_launch_select(s.results.as<aln_pair_result>(), n, mean, sd, z_min, sc->tiles.as<uint32_t>(), sc->tiles.as<uint32_t>() + tiles,
-                           misc, sc->idx.as<uint32_t>(), (uint32_t)n, q);
+    aln_scan_launch_select(s.results.as<aln_pair_result>(), n, mean, sd, z_min, tile_count, tile_off, misc, sc->idx.as<uint32_t>(), (uint32_t)n, q);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sc->ev[2], q));
     uint32_t hm[2] = {0, 0};
@@ -2228,11 +2219,6 @@ extern "C" int aln_scan_stats(const aln_scan *sc, double *ms, uint64_t *bytes)
 // makes (slot_launch, planned by chunk_plan from the copies' lengths, which the host computes with aln_shuffle_rules.h), and
 // their f gathered into one array: 8 bytes per copy and 4 per pair come back.  Every chunk is queued on one stream behind the
 // one before it; the host waits once, at the end.
-extern "C" void aln_shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
-                                   uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t out_base, uint32_t slot, hipStream_t s);
-extern "C" void aln_shuffle_launch_expand(PairDesc *descs, uint32_t *order, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
-                                          uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t region, uint64_t out_base, hipStream_t s);
-extern "C" void aln_shuffle_launch_gather(const aln_pair_result *res, double *f, uint64_t n, uint32_t per_pair, uint32_t *first, hipStream_t s);
 
 #define ALN_SHUFFLE_MAX_COPIES (1u << 20)          // per pair
 #define ALN_SHUFFLE_CHUNK_COPIES (1ull << 22)      // per chunk: the pair limit of a chunk of aln_align_batch
@@ -2519,21 +2505,6 @@ extern "C" int aln_shuffle_targets(aln_ctx *ctx, const aln_shuffle_spec *spec, c
 // The loop of HeuristicAligner (heuristic/mod.rs:36-78) for many pairs in lock step: the residues stay in HBM, every run aligns the
 // listed pairs under a matrix of their own (aln_fill_f64_kernel<SEM, true>: the lean f64 strip, the matrix staged per wave), and the
 // walked strings stay on the device, where the frequency matrices the next iteration needs are counted.
-extern "C" void aln_pairset_launch_freq(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
-                                        uint32_t n_list, uint32_t n_held, uint32_t rows, uint32_t cols, uint32_t blank, uint32_t *counts,
-                                        hipStream_t s);
-extern "C" void aln_pairset_launch_gather(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
-                                          const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
-                                          hipStream_t s);
-extern "C" int aln_pairset_launch_transform(const PairsetTransformArgs *a, hipStream_t s);
-extern "C" void aln_pairset_launch_pick(const double *store, const uint32_t *list, uint32_t n_list, uint32_t e, double *out, hipStream_t s);
-// the loop's step (aln_loop.hip)
-extern "C" void aln_loop_launch_classify(const aln_pair_result *res, const uint32_t *going, uint32_t n, double *best, uint32_t *cls, hipStream_t s);
-extern "C" void aln_loop_launch_settle(const uint32_t *entry, const int32_t *transform_status, uint32_t n, uint32_t *cls, hipStream_t s);
-extern "C" uint32_t aln_loop_tiles(uint32_t n);
-extern "C" void aln_loop_launch_select(const uint32_t *cls, uint32_t n, uint32_t kind, const uint32_t *going, const aln_pair_result *res,
-                                       uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint32_t *out_pair, uint32_t *out_word,
-                                       aln_pair_result *out_res, hipStream_t s);
 
 struct aln_seqset;
 static void seqset_derived_gone(aln_seqset *ss);
@@ -3077,26 +3048,6 @@ extern "C" int aln_pairset_stats(const aln_pairset *ps, double *ms, uint64_t *by
 // is gathered there: f and status (score), or the pairs at or above a threshold, compacted in pair order (hits).  A held pass then
 // plans the re-fill of the hits from their list (the routes and the direction layout depend on every hit's shape, so this plan is the
 // host's, as in aln_pairset_run), runs it chunk by chunk and keeps summaries and strings on the device.
-extern "C" void aln_seqset_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t k0, const aln_seqset_block *block,
-                                         const uint64_t *seq_off, const uint32_t *seq_len, hipStream_t s);
-extern "C" void aln_seqset_launch_gather(const aln_pair_result *res, double *f, int32_t *status, uint64_t n, unsigned long long *bad,
-                                         hipStream_t s);
-extern "C" uint64_t aln_seqset_tiles(uint64_t n);
-extern "C" void aln_seqset_launch_select(const aln_pair_result *res, uint64_t n, uint64_t k0, double f_min, uint32_t *tile_count,
-                                         uint32_t *tile_off, uint32_t *count, uint64_t *hit_k, double *hit_f, hipStream_t s);
-extern "C" void aln_seqset_launch_held(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
-                                       const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
-                                       hipStream_t s);
-
-extern "C" void aln_best_launch_chunk(const double *f, const int32_t *status, uint64_t n, uint64_t k0, const aln_seqset_block *block,
-                                      double f_min, uint32_t flags, uint32_t slots, uint64_t *cand_key, uint32_t *cand_t, uint32_t *cand_n,
-                                      uint64_t *run_key, uint32_t *run_t, uint32_t *run_n, hipStream_t s);
-extern "C" uint64_t aln_best_tiles(uint64_t rows);
-extern "C" void aln_best_launch_count(const uint32_t *run_n, uint64_t rows, uint32_t *tile_count, uint64_t *tile_off, uint64_t *total, hipStream_t s);
-extern "C" void aln_best_launch_emit(const uint64_t *run_key, const uint32_t *run_t, const uint32_t *run_n, uint64_t rows, uint32_t slots,
-                                     const aln_seqset_block *block, const uint64_t *tile_off, uint64_t cap, uint64_t *out_k, double *out_f,
-                                     hipStream_t s);
-
 // the per-row selection of aln_seqset_best, as a pass carries it from chunk to chunk
 struct BestPass { uint32_t slots; uint32_t flags; double f_min; };
 
@@ -3345,9 +3296,9 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
         if ((st = dev_ensure(ss->fbuf, 8 * n, false)) != ALN_OK) break;
         if ((st = dev_ensure(ss->stbuf, 4 * n, false)) != ALN_OK) break;
         if ((st = pin_ensure(ss->h_out, 256 + (want_out ? 12 * n : 0))) != ALN_OK) break;
-        const uint64_t tiles = aln_seqset_tiles(n);
+        uint32_t *tile_count = nullptr, *tile_off = nullptr;
         if (select) {
-            if ((st = dev_ensure(ss->tiles, 8 * tiles, false)) != ALN_OK) break;
+            if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(n), &tile_count, &tile_off)) != ALN_OK) break;
             if ((st = dev_ensure(ss->hit_k, 8 * n, false)) != ALN_OK) break;
             if ((st = dev_ensure(ss->hit_f, 8 * n, false)) != ALN_OK) break;
         }
@@ -3374,8 +3325,7 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
                                  reinterpret_cast<unsigned long long *>(ss->misc.as<uint8_t>() + 8), q);
         HIPCHK(hipGetLastError());
         if (select) {
-            aln_seqset_launch_select(s.results.as<aln_pair_result>(), n, k0, f_min, ss->tiles.as<uint32_t>(), ss->tiles.as<uint32_t>() + tiles,
-                                     ss->misc.as<uint32_t>(), ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
+            aln_seqset_launch_select(s.results.as<aln_pair_result>(), n, k0, f_min, tile_count, tile_off, ss->misc.as<uint32_t>(), ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
             HIPCHK(hipGetLastError());
         }
         if (best) {
@@ -3544,15 +3494,14 @@ extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const a
     st = dev_ensure(ss->run_key, 8 * rows * best.slots, false);
     if (st == ALN_OK) st = dev_ensure(ss->run_t, 4 * rows * best.slots, false);
     if (st == ALN_OK) st = dev_ensure(ss->run_n, 4 * rows, false);
-    const uint64_t tiles = aln_best_tiles(rows);
-    if (st == ALN_OK) st = dev_ensure(ss->tiles, 12 * tiles, false);
+    uint32_t *tile_count;
+    uint64_t *tile_off;
+    if (st == ALN_OK) st = tiles_ensure(ss->tiles, aln_best_tiles(rows), &tile_count, &tile_off);
     if (st != ALN_OK) return st;
     HIPCHK(hipMemsetAsync(ss->run_n.p, 0, 4 * rows, q));
     int bad = ALN_OK;
     if ((st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), nullptr, nullptr, false, 0.0, &bad, &best)) != ALN_OK) { seqset_begin(ss); return st; }
     // finish: the rows' counts -> offsets and the total, then (sized for exactly the total) the ascending list
-    uint64_t *tile_off = reinterpret_cast<uint64_t *>(ss->tiles.as<uint8_t>());
-    uint32_t *tile_count = reinterpret_cast<uint32_t *>(ss->tiles.as<uint8_t>() + 8 * tiles);
     uint64_t *d_total = reinterpret_cast<uint64_t *>(ss->misc.as<uint8_t>() + 32);
     uint64_t total = 0;
     auto finish = [&]() -> int {       // (a HIPCHK in here leaves through the exit below, which waits for the stream)
@@ -3738,13 +3687,13 @@ extern "C" int aln_pairset_loop_begin(aln_pairset *ps, const double *shared_matr
     HIPCHK(hipStreamSynchronize(q));
     const uint32_t n = (uint32_t)ps->n;
     const uint64_t e = (uint64_t)ps->h_rows * ps->h_cols;
-    const uint32_t tiles = aln_loop_tiles(n);
+    uint32_t *tile_count, *tile_off;
     int st;
     if ((st = dev_ensure(ps->best, 8ull * n, false)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->going[0], 4ull * n, false)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->going[1], 4ull * n, false)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->cls, 4ull * n, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ps->l_tiles, 8ull * tiles, false)) != ALN_OK) return st;
+    if ((st = tiles_ensure(ps->l_tiles, aln_loop_tiles(n), &tile_count, &tile_off)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->l_count, 256, false)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->h_status, 4ull * n, false)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->shared, 8ull * e, false)) != ALN_OK) return st;
@@ -3767,8 +3716,7 @@ extern "C" int aln_pairset_loop_begin(aln_pairset *ps, const double *shared_matr
         if (aln_pairset_launch_transform(&a, q) != 0) { g_err = "per-pair matrices hold 1 .. 1024 entries"; return ALN_ERR_INVALID_ARGUMENT; }
         HIPCHK(hipGetLastError());
         aln_loop_launch_settle(nullptr, ps->h_status.as<int32_t>(), n, ps->cls.as<uint32_t>(), q);
-        aln_loop_launch_select(ps->cls.as<uint32_t>(), n, 1u, nullptr, nullptr, ps->l_tiles.as<uint32_t>(), ps->l_tiles.as<uint32_t>() + tiles,
-                               ps->l_count.as<uint32_t>(), ps->going[0].as<uint32_t>(), nullptr, nullptr, q);
+        aln_loop_launch_select(ps->cls.as<uint32_t>(), n, 1u, nullptr, nullptr, tile_count, tile_off, ps->l_count.as<uint32_t>(), ps->going[0].as<uint32_t>(), nullptr, nullptr, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ps->ev[5], q));
         HIPCHK(hipMemcpyAsync(status, ps->h_status.p, 4ull * n, hipMemcpyDeviceToHost, q));
@@ -3803,8 +3751,9 @@ extern "C" int aln_pairset_loop_step(aln_pairset *ps, const aln_params *params, 
     hipStream_t q = ps->slot->stream;
     HIPCHK(hipStreamSynchronize(q));
     const uint32_t n32 = (uint32_t)n;
-    const uint32_t tiles = aln_loop_tiles(n32);
+    uint32_t *tile_count, *tile_off;
     // every buffer of the step before the run: a failure leaves the loop's state as it was
+    if ((st = tiles_ensure(ps->l_tiles, aln_loop_tiles(n32), &tile_count, &tile_off)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->cand_pair, 4ull * n, false)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->cand_entry, 4ull * n, false)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->fin_pair, 4ull * n, false)) != ALN_OK) return st;
@@ -3814,7 +3763,7 @@ extern "C" int aln_pairset_loop_step(aln_pairset *ps, const aln_params *params, 
     uint32_t *going = ps->going[ps->cur].as<uint32_t>(), *next = ps->going[ps->cur ^ 1].as<uint32_t>();
     if ((st = pairset_run(ps, params, nullptr, ps->going_h.data(), n, nullptr, true, going)) != ALN_OK) return st;
     const double pick_ms = ps->ms[2];
-    uint32_t *cls = ps->cls.as<uint32_t>(), *tile_count = ps->l_tiles.as<uint32_t>(), *tile_off = tile_count + tiles;
+    uint32_t *cls = ps->cls.as<uint32_t>();
     uint32_t *cnt = ps->l_count.as<uint32_t>();
     const aln_pair_result *res = ps->held_res.as<aln_pair_result>();
     HIPCHK(hipEventRecord(ps->ev[4], q));

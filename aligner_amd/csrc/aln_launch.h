@@ -1,0 +1,75 @@
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip and aln_best.hip define
+// and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
+// declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "aln_device.h"
+
+static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+
+extern "C" {
+
+// ---- aln_scan.hip: the window scan
+void aln_scan_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t first, uint64_t step, uint64_t width, uint64_t len,
+                            uint64_t base, uint32_t cols, hipStream_t s);
+void aln_scan_launch_f(const aln_pair_result *res, double *f, uint64_t n, int32_t *bad, hipStream_t s);
+uint64_t aln_scan_tiles(uint64_t n);
+void aln_scan_launch_select(const aln_pair_result *res, uint64_t n, double mean, double sd, double z_min, uint32_t *tile_count,
+                            uint32_t *tile_off, uint32_t *count, uint32_t *idx, uint32_t cap, hipStream_t s);
+void aln_scan_launch_hits(PairDesc *descs, uint32_t *order, uint32_t n_slots, const uint32_t *idx, const uint32_t *count, uint32_t cap,
+                          uint64_t first, uint64_t step, uint64_t width, uint64_t len, uint64_t base, uint32_t cols, uint64_t dir_stride,
+                          uint64_t tb_stride, uint64_t tag_stride, hipStream_t s);
+void aln_scan_launch_held_f(const aln_pair_result *res, double *f, uint32_t n, hipStream_t s);
+void aln_scan_launch_freq(const PairDesc *descs, const aln_pair_result *res, const uint8_t *tb, const uint32_t *keep, uint32_t n_keep,
+                          uint32_t n_held, uint32_t cols, uint32_t blank, uint32_t *counts, double *out, hipStream_t s);
+void aln_scan_launch_gather(const aln_pair_result *res, const uint8_t *tb, const uint32_t *keep, uint32_t n_keep, uint32_t n_held,
+                            uint64_t stride, aln_pair_result *out_res, uint8_t *out_tb, hipStream_t s);
+void aln_scan_launch_reverse(uint8_t *seq, uint64_t len, hipStream_t s);
+
+// ---- aln_shuffle.hip: shuffled copies
+void aln_shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair, uint64_t seed,
+                        uint64_t pair_base, uint32_t max_trim, uint64_t out_base, uint32_t slot, hipStream_t s);
+void aln_shuffle_launch_expand(PairDesc *descs, uint32_t *order, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
+                               uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t region, uint64_t out_base, hipStream_t s);
+void aln_shuffle_launch_gather(const aln_pair_result *res, double *f, uint64_t n, uint32_t per_pair, uint32_t *first, hipStream_t s);
+
+// ---- aln_pairset.hip: the held strings of a pair set, per-pair matrices
+void aln_pairset_launch_freq(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list, uint32_t n_list,
+                             uint32_t n_held, uint32_t rows, uint32_t cols, uint32_t blank, uint32_t *counts, hipStream_t s);
+void aln_pairset_launch_gather(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
+                               const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
+                               hipStream_t s);
+int aln_pairset_launch_transform(const PairsetTransformArgs *a, hipStream_t s);
+void aln_pairset_launch_pick(const double *store, const uint32_t *list, uint32_t n_list, uint32_t e, double *out, hipStream_t s);
+
+// ---- aln_loop.hip: the heuristic loop's step
+void aln_loop_launch_classify(const aln_pair_result *res, const uint32_t *going, uint32_t n, double *best, uint32_t *cls, hipStream_t s);
+void aln_loop_launch_settle(const uint32_t *entry, const int32_t *transform_status, uint32_t n, uint32_t *cls, hipStream_t s);
+uint32_t aln_loop_tiles(uint32_t n);
+// kind: 0 improved, 1 going, 2 finished
+void aln_loop_launch_select(const uint32_t *cls, uint32_t n, uint32_t kind, const uint32_t *going, const aln_pair_result *res,
+                            uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint32_t *out_pair, uint32_t *out_word,
+                            aln_pair_result *out_res, hipStream_t s);
+
+// ---- aln_seqset.hip: the resident sequence set
+void aln_seqset_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t k0, const aln_seqset_block *block, const uint64_t *seq_off,
+                              const uint32_t *seq_len, hipStream_t s);
+void aln_seqset_launch_gather(const aln_pair_result *res, double *f, int32_t *status, uint64_t n, unsigned long long *bad, hipStream_t s);
+uint64_t aln_seqset_tiles(uint64_t n);
+void aln_seqset_launch_select(const aln_pair_result *res, uint64_t n, uint64_t k0, double f_min, uint32_t *tile_count, uint32_t *tile_off,
+                              uint32_t *count, uint64_t *hit_k, double *hit_f, hipStream_t s);
+void aln_seqset_launch_held(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
+                            const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb, hipStream_t s);
+
+// ---- aln_best.hip: the k best targets per query
+int aln_warm_best(void);
+void aln_best_launch_chunk(const double *f, const int32_t *status, uint64_t n, uint64_t k0, const aln_seqset_block *block, double f_min,
+                           uint32_t flags, uint32_t slots, uint64_t *cand_key, uint32_t *cand_t, uint32_t *cand_n, uint64_t *run_key,
+                           uint32_t *run_t, uint32_t *run_n, hipStream_t s);
+uint64_t aln_best_tiles(uint64_t rows);
+void aln_best_launch_count(const uint32_t *run_n, uint64_t rows, uint32_t *tile_count, uint64_t *tile_off, uint64_t *total, hipStream_t s);
+void aln_best_launch_emit(const uint64_t *run_key, const uint32_t *run_t, const uint32_t *run_n, uint64_t rows, uint32_t slots,
+                          const aln_seqset_block *block, const uint64_t *tile_off, uint64_t cap, uint64_t *out_k, double *out_f, hipStream_t s);
+
+}

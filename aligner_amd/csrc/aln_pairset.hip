@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "aln_device.h"
+#include "aln_launch.h"
 #include "aln_transform_rules.h"
 
 // ---- counts[k][t * cols + q] for listed entry k = held entry list[k]

@@ -4,8 +4,8 @@
 //   expand     window k of a geometry (first, step, width, reverse) -> PairDesc k (+ queue entry k): the descriptors the batch
 //              fill kernels read, built where they are used instead of on the host
 //   f          the f of every window out of the 48-byte summaries (8 bytes per window go back instead of 48)
-//   select     z = (f - mean) / sd >= z_min per window, compacted in ascending window order by a two-level prefix sum
-//              (tile counts, one workgroup's scan over the tiles, tile-local scans): the same indices every run
+//   select     z = (f - mean) / sd >= z_min per window, compacted in ascending window order by the shared two-level prefix sum
+//              (aln_select.h; a predicate and an emitter here): the same indices every run
 //   hits       the selected windows -> PairDesc[cap] of the re-fill with directions (unused entries are skipped by the kernels)
 //   reverse    the reversed strand, written once behind the forward one in the scan's own buffer
 //   held       a held pass (aln_scan_hits) leaves every hit's summary and strings in the slot; held_f gathers the hits' f, freq sums
@@ -19,11 +19,9 @@
 #include <algorithm>
 
 #include "aln_device.h"
+#include "aln_launch.h"
 #include "aln_scheme_rules.h"
-
-#define SCAN_THREADS 256u
-#define SCAN_PER_THREAD 8u
-#define SCAN_TILE (SCAN_THREADS * SCAN_PER_THREAD)
+#include "aln_select.h"
 
 // ---- window expansion: descriptor k = window j = first + k * step, rows seq[j .. min(j + width, len)) of the strand at `base`
 __global__ __launch_bounds__(256) void aln_scan_expand_kernel(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t first,
@@ -62,72 +60,17 @@ __device__ __forceinline__ bool scan_keep(double f, double mean, double sd, doub
     return z >= z_min;
 }
 
-// block-wide exclusive prefix sum of one value per thread (256 threads); returns the thread's offset, *total the block's sum
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *lds, uint32_t *total)
-{
-    const uint32_t t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (uint32_t o = 1; o < SCAN_THREADS; o <<= 1) {
-        const uint32_t add = t >= o ? lds[t - o] : 0u;
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const uint32_t incl = lds[t];
-    *total = lds[SCAN_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-// ---- selection, step 1: kept windows per tile of SCAN_TILE windows (thread t looks at windows t*8 .. t*8+7 of the tile)
-__global__ __launch_bounds__(256) void aln_scan_count_kernel(const aln_pair_result *res, uint64_t n, double mean, double sd,
-                                                             double z_min, uint32_t *tile_count)
-{
-    __shared__ uint32_t lds[SCAN_THREADS];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_PER_THREAD;
-    uint32_t c = 0;
-    for (uint32_t i = 0; i < SCAN_PER_THREAD; ++i)
-        if (base + i < n && scan_keep(res[base + i].f, mean, sd, z_min)) ++c;
-    uint32_t total;
-    (void)block_exclusive_scan(c, lds, &total);
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
-}
-
-// ---- selection, step 2: one workgroup turns the tile counts into tile offsets; count[0] = kept windows in all
-__global__ __launch_bounds__(256) void aln_scan_offsets_kernel(const uint32_t *tile_count, uint32_t *tile_off, uint64_t tiles,
-                                                               uint32_t *count)
-{
-    __shared__ uint32_t lds[SCAN_THREADS];
-    uint32_t carry = 0;
-    for (uint64_t b = 0; b < tiles; b += SCAN_THREADS) {
-        const uint64_t i = b + threadIdx.x;
-        const uint32_t v = i < tiles ? tile_count[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_exclusive_scan(v, lds, &total);
-        if (i < tiles) tile_off[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) count[0] = carry;
-}
-
-// ---- selection, step 3: every tile writes its kept window indices at its offset, in ascending order (the first `cap` of all)
-__global__ __launch_bounds__(256) void aln_scan_compact_kernel(const aln_pair_result *res, uint64_t n, double mean, double sd,
-                                                               double z_min, const uint32_t *tile_off, uint32_t *idx, uint32_t cap)
-{
-    __shared__ uint32_t lds[SCAN_THREADS];
-    const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_PER_THREAD;
-    uint32_t keep = 0, c = 0;
-    for (uint32_t i = 0; i < SCAN_PER_THREAD; ++i)
-        if (base + i < n && scan_keep(res[base + i].f, mean, sd, z_min)) { keep |= 1u << i; ++c; }
-    uint32_t total;
-    uint32_t o = tile_off[blockIdx.x] + block_exclusive_scan(c, lds, &total);
-    for (uint32_t i = 0; i < SCAN_PER_THREAD; ++i)
-        if (keep & (1u << i)) {
-            if (o < cap) idx[o] = (uint32_t)(base + i);
-            ++o;
-        }
-}
+// ---- selection (aln_select.h): window k is kept by its z; kept window k goes to idx[o], the first `cap` of all
+struct ScanKeep {
+    const aln_pair_result *res;
+    double mean, sd, z_min;
+    __device__ bool operator()(uint64_t k) const { return scan_keep(res[k].f, mean, sd, z_min); }
+};
+struct ScanEmit {
+    uint32_t *idx;
+    uint32_t cap;
+    __device__ void operator()(uint32_t o, uint64_t k) const { if (o < cap) idx[o] = (uint32_t)k; }
+};
 
 // ---- the re-fill's descriptors: entry h < min(count, cap) is window idx[h], laid out at h * stride in dirs / strings / tags;
 // the others are skipped by every kernel (ALN_PRE_EMPTY_OK: nothing to align)
@@ -234,8 +177,6 @@ __global__ __launch_bounds__(256) void aln_scan_reverse_kernel(uint8_t *seq, uin
     if (i < len) seq[len + i] = seq[len - 1 - i];
 }
 
-static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
 extern "C" void aln_scan_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t first, uint64_t step, uint64_t width,
                                        uint64_t len, uint64_t base, uint32_t cols, hipStream_t s)
 {
@@ -248,16 +189,12 @@ extern "C" void aln_scan_launch_f(const aln_pair_result *res, double *f, uint64_
     if (n) hipLaunchKernelGGL(aln_scan_f_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, res, f, n, bad);
 }
 
-extern "C" uint64_t aln_scan_tiles(uint64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
+extern "C" uint64_t aln_scan_tiles(uint64_t n) { return aln_select_tiles(n); }
 
 extern "C" void aln_scan_launch_select(const aln_pair_result *res, uint64_t n, double mean, double sd, double z_min, uint32_t *tile_count,
                                        uint32_t *tile_off, uint32_t *count, uint32_t *idx, uint32_t cap, hipStream_t s)
 {
-    const uint64_t tiles = aln_scan_tiles(n);
-    if (tiles) hipLaunchKernelGGL(aln_scan_count_kernel, dim3((uint32_t)tiles), dim3(SCAN_THREADS), 0, s, res, n, mean, sd, z_min, tile_count);
-    hipLaunchKernelGGL(aln_scan_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, tile_count, tile_off, tiles, count);
-    if (tiles) hipLaunchKernelGGL(aln_scan_compact_kernel, dim3((uint32_t)tiles), dim3(SCAN_THREADS), 0, s, res, n, mean, sd, z_min, tile_off,
-                                  idx, cap);
+    aln_select_launch(ScanKeep{res, mean, sd, z_min}, ScanEmit{idx, cap}, n, tile_count, tile_off, count, s);
 }
 
 extern "C" void aln_scan_launch_hits(PairDesc *descs, uint32_t *order, uint32_t n_slots, const uint32_t *idx, const uint32_t *count,

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "aln_device.h"
+#include "aln_launch.h"
 #include "aln_shuffle_rules.h"
 
 // ---- the copies of pairs p0 .. of a chunk: copy k of the chunk is copy k % per_pair of pair p0 + k / per_pair, written at
@@ -81,8 +82,6 @@ __global__ __launch_bounds__(256) void aln_shuffle_gather_kernel(const aln_pair_
     f[k] = r.f;
     if (r.status != ALN_OK) atomicMin(first + k / per_pair, ((uint32_t)(k % per_pair) << 8) | ((uint32_t)r.status & 0xffu));
 }
-
-static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
 
 extern "C" void aln_shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
                                    uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t out_base, uint32_t slot, hipStream_t s)

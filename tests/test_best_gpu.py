@@ -256,6 +256,42 @@ def test_one_row_and_one_column(sset, orc, blosum62):
     assert len(held) == (status == 0).sum() > 2000
 
 
+EDGE_ROWS = 256 * 256 + 300                 # 258 tiles of 256 rows: the offsets kernel's second trip of 256 tiles begins at row 65 536
+EDGE_TARGET, EDGE_F_MIN = 7, 11.0           # against 'AW': 'WWWW' scores 11 (kept, by equality), 'AAA' 4 (below), '' fails
+
+
+def edge_ids():
+    """Content id of every query row of the 65 836 x 1 rectangle: 'WWWW', 'AAA' and '' mixed, except that tile 254 (rows 65 024 ..
+    65 279) holds no kept row, tile 255 (.. 65 535) and the last, partial tile (44 rows) only kept rows; tile 256 is mixed again and
+    begins with a kept row."""
+    i = np.arange(EDGE_ROWS)
+    ids = np.where((i * 7) % 3 == 0, 6, np.where(i % 5 == 0, 3, 2))
+    ids[254 * 256:255 * 256] = 2
+    ids[255 * 256:256 * 256] = 6
+    ids[256 * 256:256 * 256 + 2] = (6, 2)
+    ids[257 * 256:] = 6
+    return ids
+
+
+def test_one_column_into_the_second_trip_of_tiles(orc, blosum62):
+    """65 836 x 1, k = 1: 258 tiles of 256 rows, so the 64-bit tile offsets take their carry into a second trip of 256 tiles (the
+    4 200 rows above stay within 17 tiles).  Kept rows lie on both sides of row 65 535 | 65 536."""
+    of, ostatus, _ = table(orc, blosum62)
+    ids = edge_ids()
+    n = EDGE_ROWS
+    q, t = np.arange(n), np.full(n, n)
+    f, status = of[ids, EDGE_TARGET], ostatus[ids, EDGE_TARGET]
+    want_idx, want_f = rule(q, t, f, status, 1, 1, EDGE_F_MIN)
+    per_tile = np.bincount(want_idx // 256, minlength=258)
+    assert {65535, 65536} <= set(want_idx.tolist()) and 65537 not in want_idx
+    assert 0 < per_tile[253] < 256 and per_tile[254] == 0 and per_tile[255] == 256 and 0 < per_tile[256] < 256 and per_tile[257] == 44
+    assert (status != 0).sum() > 1000 and ((status == 0) & (f < EDGE_F_MIN)).sum() > 1000 and (want_f == EDGE_F_MIN).all()
+    codes = [np.asarray(Protein.str_to_vec(c), dtype=np.uint8) for c in CONTENTS]
+    with SeqSet([codes[i] for i in ids] + [codes[EDGE_TARGET]]) as s:
+        held = s.best(blosum62, DEL, EXT, 1, f_min=EDGE_F_MIN, block=rectangle(0, n, n, 1))
+        check_list(held, q, t, want_idx, want_f)
+
+
 def test_square_block_and_skip_self(sset, orc, blosum62):
     """The first 70 targets against themselves: with the flag no (i, i) is kept; without it every (i, i) that succeeds is kept, and
     is the first of its row wherever nothing earlier scores as much."""
