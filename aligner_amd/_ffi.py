@@ -44,7 +44,7 @@ EXPORTS = [
     "aln_transform_matrices",
     "aln_pairset_heuristics", "aln_pairset_reestimate", "aln_pairset_run_stored", "aln_pairset_matrices", "aln_transform_matrices_device",
     "aln_seqset_create", "aln_seqset_destroy", "aln_seqset_pairs", "aln_seqset_score", "aln_seqset_hits", "aln_seqset_held_list",
-    "aln_seqset_held_strings", "aln_seqset_stats", "aln_seqset_best",
+    "aln_seqset_held_strings", "aln_seqset_stats", "aln_seqset_best", "aln_seqset_held_significance",
     "aln_pairset_create_from_set", "aln_pairset_loop_begin", "aln_pairset_loop_step",
 ]
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
@@ -87,6 +87,16 @@ class ShuffleSpec(C.Structure):
 
 
 assert C.sizeof(ShuffleSpec) == 24
+
+
+class SignifRecord(C.Structure):
+    """aln_signif_record: what the shuffled copies of one held hit leave behind (aligner_amd/csrc/aln_signif_rules.h)."""
+    _fields_ = [("sum", C.c_double), ("sum_sq", C.c_double), ("f_max", C.c_double), ("n_ok", C.c_uint32), ("n_ge", C.c_uint32),
+                ("status", C.c_int32), ("first_bad", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(SignifRecord) == 48
+SHUFFLE_MAX_COPIES = 1 << 20      # per pair (aln_shuffle_spec.per_pair)
 
 
 class SeqsetBlock(C.Structure):
@@ -223,6 +233,8 @@ def load():
     lib.aln_seqset_held_list.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
     lib.aln_seqset_held_strings.restype = i
     lib.aln_seqset_held_strings.argtypes = [vp, vp, C.c_uint64, vp, vp, u64p]
+    lib.aln_seqset_held_significance.restype = i
+    lib.aln_seqset_held_significance.argtypes = [vp, C.POINTER(Params), sp, vp, C.c_uint64, vp, vp, vp]
     lib.aln_seqset_stats.restype = i
     lib.aln_seqset_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.aln_pairset_create_from_set.restype = vp

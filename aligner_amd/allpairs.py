@@ -11,15 +11,26 @@ residue frequencies (default: those of the FASTA over the alphabet's volume); a 
 With --best K the question is a database search's: per record, its K best partners among all the others (higher f first, equal f by
 the earlier record), optionally only those with f >= F, selected on the device; prints `q_head,rank,t_head,f`, records in input
 order, ranks from 1.  Not with --heuristic.
+
+With --shuffles N (and --best or --f-min: a held pass) every printed hit is also asked whether it is better than chance: its query
+against N trimmed and shuffled copies of its target, drawn, scored and reduced on the device; `,z,p_emp` is appended to each row
+(z = (f - mean) / sd over the copies, p_emp = (copies with f >= the hit's + 1) / (copies + 1)).  --seed S picks the copies (default
+0: the same output every run).  A hit whose target has fewer than 6 residues has no such copies (each loses up to 6 tail residues): its
+row ends in `,nan,nan`.  Not with --heuristic.
 """
 import argparse
 import sys
+
+import numpy as np
 
 from . import _ffi
 from .enums import DNA, Protein
 from .fasta import encode_records, read_fasta
 from .matrices import get_blosum62, nucleotide_matrix
 from .seqset import SeqSet
+
+
+MAX_TRIM = 6          # tail residues a shuffled copy may lose (statistics/mod.rs:312-314)
 
 
 def main(argv=None):
@@ -36,7 +47,18 @@ def main(argv=None):
     ap.add_argument("--r-squared", type=float, default=None)
     ap.add_argument("--frequencies", default=None, help="comma-separated residue frequencies, one per code of the alphabet")
     ap.add_argument("--best", type=int, default=None, metavar="K", help="per record its K best partners (1 .. %d), self pairs skipped" % _ffi.SEQSET_BEST_MAX)
+    ap.add_argument("--shuffles", type=int, default=None, metavar="N", help="append z,p_emp from N shuffled copies of each hit's target (with --best or --f-min)")
+    ap.add_argument("--seed", type=int, default=None, help="seed of the shuffled copies (default 0)")
     a = ap.parse_args(argv)
+    if a.shuffles is not None:
+        if a.heuristic:
+            ap.error("--shuffles asks about the plain alignment's score: not with --heuristic")
+        if a.best is None and a.f_min is None:
+            ap.error("--shuffles works on held hits: give --best K or --f-min F")
+        if not 1 <= a.shuffles <= _ffi.SHUFFLE_MAX_COPIES:
+            ap.error("--shuffles: N must lie in 1 .. %d" % _ffi.SHUFFLE_MAX_COPIES)
+    elif a.seed is not None:
+        ap.error("--seed picks the copies of --shuffles")
     records = read_fasta(a.input)
     if len(records) < 2:
         ap.error("%s: an all-against-all run needs two or more records" % a.input)
@@ -45,6 +67,19 @@ def main(argv=None):
     sem = _ffi.CORE_GLOBAL if a.global_ else _ffi.CORE_LOCAL
     heads = [r.head.decode("utf-8", "replace") for r in records]
     out = sys.stdout
+
+    def tail(held):
+        """`,z,p_emp` per held position, or empty strings without --shuffles"""
+        if a.shuffles is None:
+            return [""] * len(held)
+        # a copy loses up to MAX_TRIM tail residues: a target shorter than that has no such copies (the library refuses it)
+        can = np.flatnonzero(held.owner.len[held.t] >= MAX_TRIM).astype(np.uint32)
+        sig = held.significance(matrix, a.del_, a.ext, a.seed or 0, per_pair=a.shuffles, max_trim=MAX_TRIM, keep=can)
+        rows = [",nan,nan"] * len(held)
+        for h, z, p in zip(can, sig["z"], sig["p_emp"]):
+            rows[int(h)] = ",%r,%r" % (float(z), float(p))
+        return rows
+
     if a.best is not None:
         if a.heuristic:
             ap.error("--best selects by the score of the plain alignment: not with --heuristic")
@@ -52,16 +87,16 @@ def main(argv=None):
             ap.error("--best: K must lie in 1 .. %d" % _ffi.SEQSET_BEST_MAX)
         with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
             held = ss.best(matrix, a.del_, a.ext, a.best, f_min=float("-inf") if a.f_min is None else a.f_min, skip_self=True, semantics=sem)
+            more = tail(held)
             for q, pos in held.by_query():
                 for p in pos:
-                    out.write("%s,%d,%s,%r\n" % (heads[q], int(held.rank[p]) + 1, heads[int(held.t[p])], float(held.f[p])))
+                    out.write("%s,%d,%s,%r%s\n" % (heads[q], int(held.rank[p]) + 1, heads[int(held.t[p])], float(held.f[p]), more[p]))
         return 0
     if a.heuristic:
         if a.kd is None or a.r_squared is None:
             ap.error("--heuristic needs --kd and --r-squared")
         if a.global_ or a.f_min is not None:
             ap.error("--heuristic is the local loop over all pairs: no --global, no --f-min")
-        import numpy as np
         from .heuristic import align_set
         from .simple import Heuristics
         codes = encode_records(records, alphabet)
@@ -88,8 +123,8 @@ def main(argv=None):
                     k += 1
         else:
             held = ss.hits(matrix, a.del_, a.ext, a.f_min, None, semantics=sem)
-            for q, t, f in zip(held.q, held.t, held.f):
-                out.write("%s,%s,%r\n" % (heads[int(q)], heads[int(t)], float(f)))
+            for q, t, f, more in zip(held.q, held.t, held.f, tail(held)):
+                out.write("%s,%s,%r%s\n" % (heads[int(q)], heads[int(t)], float(f), more))
     return 0
 
 

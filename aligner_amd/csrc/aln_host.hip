@@ -32,6 +32,7 @@
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <numeric>
 #include <string>
 #include <chrono>
@@ -46,6 +47,7 @@
 #include "aln_seqset_rules.h"
 #include "aln_best_rules.h"
 #include "aln_shuffle_rules.h"
+#include "aln_signif_rules.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -2260,7 +2262,7 @@ static void shuffle_stage(const uint8_t *seqs, const uint64_t *q_off, const uint
     g.direct = hi - lo <= 2 * sum + 65536;
     g.lo = lo;
     g.pairs.resize(n);
-    if (!g.direct) g.packed.resize(sum);
+    if (!g.direct && seqs) g.packed.resize(sum);       // (no host residues: the caller copies the ranges on the device)
     uint64_t pos = 0, out = 0;
     for (size_t i = 0; i < n; ++i) {
         ShufflePair &P = g.pairs[i];
@@ -2271,10 +2273,10 @@ static void shuffle_stage(const uint8_t *seqs, const uint64_t *q_off, const uint
             P.t_off = P.t_len ? t_off[i] - lo : 0;
         } else {
             P.q_off = pos;
-            if (P.q_len) memcpy(g.packed.data() + pos, seqs + q_off[i], P.q_len);
+            if (P.q_len && seqs) memcpy(g.packed.data() + pos, seqs + q_off[i], P.q_len);
             pos += P.q_len;
             P.t_off = pos;
-            if (P.t_len) memcpy(g.packed.data() + pos, seqs + t_off[i], P.t_len);
+            if (P.t_len && seqs) memcpy(g.packed.data() + pos, seqs + t_off[i], P.t_len);
             pos += P.t_len;
         }
         P.out_off = out;
@@ -2332,6 +2334,131 @@ static int shuffle_upload(Slot &s, const ShuffleStage &g, const uint8_t *seqs, h
     return ALN_OK;
 }
 
+// ---- what a call that scores shuffled copies plans before anything is queued (aln_shuffle_scores, aln_seqset_held_significance):
+// the copies' lengths, the call's analysis, the staged pair table, the chunks of whole pairs and every chunk's plan
+struct ShuffleJob {
+    Call c;
+    ShuffleStage g;
+    std::vector<std::pair<size_t, size_t>> ranges;
+    std::vector<Chunk> plans;
+    uint64_t region = 0;              // the shuffled copies of a chunk lie behind the staged residues
+    uint64_t region_max = 0, seq_need = 0, copies_max = 0;
+};
+
+// stream (optional): pair i's stream index is stream[i], not spec->pair_base + i.  seqs: the caller's residues, or null when they
+// are resident on the device at the same offsets (the caller then copies them there: ShuffleStage says where).  lens (optional):
+// n * per_pair entries, written; without it the lengths are drawn again where a chunk is planned (a trim is one SplitMix64 draw),
+// so nothing on the host grows with n * per_pair beyond one chunk's tables.  n == 0: only the checks of call_init.
+static int shuffle_job_plan(const DevCtx *dev, const aln_params *params, const aln_shuffle_spec *spec, const uint64_t *stream,
+                            const uint8_t *seqs, const uint64_t *q_off, const uint64_t *q_len, const uint64_t *t_off, const uint64_t *t_len,
+                            size_t n_pairs, uint32_t *lens, ShuffleJob &job)
+{
+    const uint32_t per = spec->per_pair;
+    // every copy's length: the plan needs them, the caller gets them; the longest copy of each pair decides the routes as in
+    // aln_align_batch over the copies (call_init)
+    std::vector<uint64_t> lmax(n_pairs, 0);
+    std::vector<double> cells(n_pairs, 0.0);
+    for (size_t i = 0; i < n_pairs; ++i) {
+        uint64_t sum = 0;
+        const uint64_t id = stream ? stream[i] : spec->pair_base + i;
+        for (uint32_t s = 0; s < per; ++s) {
+            const uint32_t L = (uint32_t)t_len[i] - aln_shuffle_trim_of(spec->seed, id, s, spec->max_trim);
+            if (lens) lens[(uint64_t)i * per + s] = L;
+            lmax[i] = std::max<uint64_t>(lmax[i], L);
+            sum += L;
+        }
+        cells[i] = (double)q_len[i] * (double)sum;
+    }
+    aln_params p = *params;
+    p.outputs = ALN_OUT_SCORE;
+    Call &c = job.c;
+    int st;
+    if ((st = call_init(c, &p, q_len, lmax.data(), n_pairs, false)) != ALN_OK) return st;
+    if (n_pairs == 0) return ALN_OK;
+
+    ShuffleStage &g = job.g;
+    shuffle_stage(seqs, q_off, q_len, t_off, t_len, n_pairs, per, g);
+    // chunks: the cell bounds of make_chunks (1.6e10, three times that for the generic kernels; ALN_CHUNK_CELLS overrides)
+    double target = c.fast ? 1.6e10 : 4.8e10;
+    if (const char *e = getenv("ALN_CHUNK_CELLS")) target = std::max(1.0, atof(e));
+    shuffle_chunks(g, per, &cells, target, job.ranges);
+    job.region = align256(g.bytes);
+    // the plans of every chunk first: the copies' lengths and offsets in the residue buffer, routed and laid out by chunk_plan
+    job.plans.resize(job.ranges.size());
+    std::vector<uint64_t> qo, ql, to, tl;
+    for (size_t j = 0; j < job.ranges.size(); ++j) {
+        const size_t p0 = job.ranges[j].first, np = job.ranges[j].second;
+        const uint64_t m = (uint64_t)np * per, out_base = g.pairs[p0].out_off;
+        qo.resize(m); ql.resize(m); to.resize(m); tl.resize(m);
+        for (size_t i = p0; i < p0 + np; ++i) {
+            const ShufflePair &P = g.pairs[i];
+            const uint64_t id = stream ? stream[i] : spec->pair_base + i;
+            for (uint32_t s = 0; s < per; ++s) {
+                const uint64_t k = (uint64_t)(i - p0) * per + s;
+                qo[k] = P.q_off; ql[k] = P.q_len;
+                to[k] = job.region + (P.out_off - out_base) + (uint64_t)s * P.t_len;
+                tl[k] = lens ? lens[(uint64_t)i * per + s] : P.t_len - aln_shuffle_trim_of(spec->seed, id, s, spec->max_trim);
+            }
+        }
+        Chunk &k = job.plans[j];
+        if ((st = chunk_plan(dev, c, qo.data(), ql.data(), to.data(), tl.data(), 0, m, true, k)) != ALN_OK) return st;
+        // the descriptors are the device's (aln_shuffle_expand_kernel); the host keeps them, and the queue, only for the launches of
+        // copies routed elsewhere (scan_plan does the same)
+        if (k.single_pairs.empty() && k.wg_pairs.empty()) {
+            k.descs.clear(); k.descs.shrink_to_fit();
+            k.order.clear(); k.order.shrink_to_fit();
+        }
+        job.region_max = std::max(job.region_max, chunk_region_bytes(g, per, p0, np));
+        job.seq_need = std::max(job.seq_need, k.seq_span);
+        job.copies_max = std::max(job.copies_max, m);
+    }
+    if (trace_plan()) fprintf(stderr, "aln shuffle: pairs %zu copies %u chunks %zu\n", n_pairs, per, job.ranges.size());
+    return ALN_OK;
+}
+
+// the slot's buffers for every chunk of the job, sized before anything is queued (a buffer that grew later would be freed under a
+// running kernel); the shuffle buffer is the caller's to size
+static int shuffle_job_ensure(Slot &s, const ShuffleJob &job)
+{
+    int st;
+    if ((st = dev_ensure(s.seqs, std::max(job.region + job.region_max, job.seq_need) + 64, s.pooled)) != ALN_OK) return st;
+    for (const Chunk &k : job.plans)
+        if ((st = slot_ensure(s, job.c, k, nullptr, true)) != ALN_OK) return st;
+    return ALN_OK;
+}
+
+// chunk j on the slot's stream: its copies drawn, expanded into descriptors and filled; their summaries are in s.results afterwards
+// (stream order).  pairs_d / stream_d: the pair table and the optional stream table on the device.
+static int shuffle_job_chunk(DevCtx *dev, Slot &s, const ShuffleJob &job, size_t j, const aln_shuffle_spec *spec, const ShufflePair *pairs_d,
+                             const uint64_t *stream_d, uint64_t *up)
+{
+    hipStream_t q = s.stream;
+    const size_t p0 = job.ranges[j].first, np = job.ranges[j].second;
+    const uint32_t per = spec->per_pair;
+    const uint64_t m = (uint64_t)np * per, out_base = job.g.pairs[p0].out_off, region = job.region;
+    const Chunk &k = job.plans[j];
+    const uint32_t lds = shuffle_lds_slot(job.g, p0, np);
+    if (stream_d) {
+        aln_shuffle_launch_table(s.seqs.as<uint8_t>(), s.seqs.as<uint8_t>() + region, pairs_d, (uint32_t)p0, m, per, spec->seed, stream_d,
+                                 spec->max_trim, out_base, lds, q);
+        aln_shuffle_launch_expand_table(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), pairs_d, (uint32_t)p0, m, per, spec->seed, stream_d,
+                                        spec->max_trim, region, out_base, q);
+    } else {
+        aln_shuffle_launch(s.seqs.as<uint8_t>(), s.seqs.as<uint8_t>() + region, pairs_d, (uint32_t)p0, m, per, spec->seed, spec->pair_base,
+                           spec->max_trim, out_base, lds, q);
+        aln_shuffle_launch_expand(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), pairs_d, (uint32_t)p0, m, per, spec->seed, spec->pair_base,
+                                  spec->max_trim, region, out_base, q);
+    }
+    HIPCHK(hipGetLastError());
+    if (k.n_small != k.n && k.n_small) {             // some copies take another route: the batch kernel's queue is the plan's
+        HIPCHK(hipMemcpyAsync(s.order.p, k.order.data(), 4 * k.n_small, hipMemcpyHostToDevice, q));
+        if (up) *up += 4 * k.n_small;
+    }
+    int st;
+    if ((st = slot_launch(dev, s, job.c, k, q, nullptr, nullptr)) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    return ALN_OK;
+}
+
 extern "C" int aln_shuffle_scores(aln_ctx *ctx, const aln_params *params, const aln_shuffle_spec *spec, const uint8_t *seqs,
                                   const uint64_t *q_off, const uint64_t *q_len, const uint64_t *t_off, const uint64_t *t_len,
                                   size_t n_pairs, double *f, uint32_t *lengths, int32_t *status)
@@ -2342,77 +2469,21 @@ extern "C" int aln_shuffle_scores(aln_ctx *ctx, const aln_params *params, const 
     if (params->semantics == ALN_PWM_LOCAL) { g_err = "shuffled copies are aligned with the substitution-matrix semantics only"; return ALN_ERR_UNSUPPORTED; }
     const uint32_t per = spec->per_pair;
     const uint64_t total = (uint64_t)n_pairs * per;
-    // every copy's length: the plan needs them, the caller gets them; the longest copy of each pair decides the routes as in
-    // aln_align_batch over the copies (call_init)
     std::vector<uint32_t> own_lens;
     uint32_t *lens = lengths;
     if (!lens) { own_lens.resize(total); lens = own_lens.data(); }
-    std::vector<uint64_t> lmax(n_pairs, 0);
-    std::vector<double> cells(n_pairs, 0.0);
-    for (size_t i = 0; i < n_pairs; ++i) {
-        uint64_t sum = 0;
-        for (uint32_t s = 0; s < per; ++s) {
-            const uint32_t L = (uint32_t)t_len[i] - aln_shuffle_trim_of(spec->seed, spec->pair_base + i, s, spec->max_trim);
-            lens[(uint64_t)i * per + s] = L;
-            lmax[i] = std::max<uint64_t>(lmax[i], L);
-            sum += L;
-        }
-        cells[i] = (double)q_len[i] * (double)sum;
-    }
-    aln_params p = *params;
-    p.outputs = ALN_OUT_SCORE;
-    Call c;
-    if ((st = call_init(c, &p, q_len, lmax.data(), n_pairs, false)) != ALN_OK) return st;
-    if (n_pairs == 0) return ALN_OK;
-
-    ShuffleStage g;
-    shuffle_stage(seqs, q_off, q_len, t_off, t_len, n_pairs, per, g);
-    // chunks: the cell bounds of make_chunks (1.6e10, three times that for the generic kernels; ALN_CHUNK_CELLS overrides)
-    double target = c.fast ? 1.6e10 : 4.8e10;
-    if (const char *e = getenv("ALN_CHUNK_CELLS")) target = std::max(1.0, atof(e));
-    std::vector<std::pair<size_t, size_t>> ranges;
-    shuffle_chunks(g, per, &cells, target, ranges);
-    const uint64_t region = align256(g.bytes);        // the shuffled copies of a chunk lie behind the uploaded residues
     DevCtx *dev = ctx->devs[0];
+    ShuffleJob job;
+    if ((st = shuffle_job_plan(dev, params, spec, nullptr, seqs, q_off, q_len, t_off, t_len, n_pairs, lens, job)) != ALN_OK) return st;
+    if (n_pairs == 0) return ALN_OK;
+    const Call &c = job.c;
+    const ShuffleStage &g = job.g;
     HIPCHK(hipSetDevice(dev->device));
-    // the plans of every chunk first: the copies' lengths and offsets in the residue buffer, routed and laid out by chunk_plan
-    std::vector<Chunk> plans(ranges.size());
-    uint64_t region_max = 0, seq_need = 0;
-    {
-        std::vector<uint64_t> qo, ql, to, tl;
-        for (size_t j = 0; j < ranges.size(); ++j) {
-            const size_t p0 = ranges[j].first, np = ranges[j].second;
-            const uint64_t m = (uint64_t)np * per, out_base = g.pairs[p0].out_off;
-            qo.resize(m); ql.resize(m); to.resize(m); tl.resize(m);
-            for (size_t i = p0; i < p0 + np; ++i) {
-                const ShufflePair &P = g.pairs[i];
-                for (uint32_t s = 0; s < per; ++s) {
-                    const uint64_t k = (uint64_t)(i - p0) * per + s;
-                    qo[k] = P.q_off; ql[k] = P.q_len;
-                    to[k] = region + (P.out_off - out_base) + (uint64_t)s * P.t_len;
-                    tl[k] = lens[(uint64_t)i * per + s];
-                }
-            }
-            Chunk &k = plans[j];
-            if ((st = chunk_plan(dev, c, qo.data(), ql.data(), to.data(), tl.data(), 0, m, true, k)) != ALN_OK) return st;
-            // the descriptors are the device's (aln_shuffle_expand_kernel); the host keeps them, and the queue, only for the launches of
-            // copies routed elsewhere (scan_plan does the same)
-            if (k.single_pairs.empty() && k.wg_pairs.empty()) {
-                k.descs.clear(); k.descs.shrink_to_fit();
-                k.order.clear(); k.order.shrink_to_fit();
-            }
-            region_max = std::max(region_max, chunk_region_bytes(g, per, p0, np));
-            seq_need = std::max(seq_need, k.seq_span);
-        }
-    }
     Slot *sl[1];
     pool_lease(dev, 1, sl);
     struct Release { DevCtx *c; Slot **s; ~Release() { pool_release(c, s, 1); } } rel{dev, sl};
     Slot &s = *sl[0];
-    // every buffer is sized before anything is queued (a buffer that grew later would be freed under a running kernel)
-    if ((st = dev_ensure(s.seqs, std::max(region + region_max, seq_need) + 64, s.pooled)) != ALN_OK) return st;
-    for (const Chunk &k : plans)
-        if ((st = slot_ensure(s, c, k, nullptr, true)) != ALN_OK) return st;
+    if ((st = shuffle_job_ensure(s, job)) != ALN_OK) return st;
     const uint64_t f_off = align256(sizeof(ShufflePair) * n_pairs), first_off = align256(f_off + 8 * total);
     if ((st = dev_ensure(s.shuffle, first_off + 4ull * n_pairs, s.pooled)) != ALN_OK) return st;
     const ShufflePair *pairs_d = s.shuffle.as<ShufflePair>();
@@ -2422,19 +2493,10 @@ extern "C" int aln_shuffle_scores(aln_ctx *ctx, const aln_params *params, const 
     if ((st = shuffle_upload(s, g, seqs, q)) != ALN_OK) return st;
     HIPCHK(hipMemsetAsync(first_d, 0xff, 4ull * n_pairs, q));
     if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) return st;
-    for (size_t j = 0; j < ranges.size(); ++j) {
-        const size_t p0 = ranges[j].first, np = ranges[j].second;
-        const uint64_t m = (uint64_t)np * per, out_base = g.pairs[p0].out_off;
-        const Chunk &k = plans[j];
-        aln_shuffle_launch(s.seqs.as<uint8_t>(), s.seqs.as<uint8_t>() + region, pairs_d, (uint32_t)p0, m, per, spec->seed, spec->pair_base,
-                           spec->max_trim, out_base, shuffle_lds_slot(g, p0, np), q);
-        aln_shuffle_launch_expand(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), pairs_d, (uint32_t)p0, m, per, spec->seed, spec->pair_base,
-                                  spec->max_trim, region, out_base, q);
-        HIPCHK(hipGetLastError());
-        if (k.n_small != k.n && k.n_small)               // some copies take another route: the batch kernel's queue is the plan's
-            HIPCHK(hipMemcpyAsync(s.order.p, k.order.data(), 4 * k.n_small, hipMemcpyHostToDevice, q));
-        if ((st = slot_launch(dev, s, c, k, q, nullptr, nullptr)) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
-        aln_shuffle_launch_gather(s.results.as<aln_pair_result>(), f_d + (uint64_t)p0 * per, m, per, first_d + p0, q);
+    for (size_t j = 0; j < job.ranges.size(); ++j) {
+        const size_t p0 = job.ranges[j].first, np = job.ranges[j].second;
+        if ((st = shuffle_job_chunk(dev, s, job, j, spec, pairs_d, nullptr, nullptr)) != ALN_OK) return st;
+        aln_shuffle_launch_gather(s.results.as<aln_pair_result>(), f_d + (uint64_t)p0 * per, (uint64_t)np * per, per, first_d + p0, q);
         HIPCHK(hipGetLastError());
     }
     std::vector<uint32_t> first(n_pairs);
@@ -3620,6 +3682,127 @@ extern "C" int aln_seqset_held_strings(aln_seqset *ss, const uint32_t *keep, uin
     ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ss->bytes[0] = 12ull * n; ss->bytes[1] = sizeof(aln_pair_result) * n + (want ? total : 0);
     return ALN_OK;
+}
+
+// Significance of held hits: the listed hits as the pairs of a shuffle job (shuffle_job_plan: the planning, chunking, routing and
+// launches of aln_shuffle_scores) whose residues are the set's own.  The fill kernels take one residue base per launch and the set's
+// buffer must not grow or move (derived pair sets borrow it), so the job runs on a pool slot like any shuffle call and the listed
+// hits' queries and originals are copied device to device into that slot's residue buffer, in front of the shuffled region -- one
+// span of the set's buffer, or the ranges one by one when the hits lie far apart.  The held buffers and the set's own slot are not
+// touched.  Per chunk the copies' summaries are reduced to records (aln_signif.hip) in place of the gather of aln_shuffle_scores.
+static int seqset_held_significance(aln_seqset *ss, const aln_params *params, const aln_shuffle_spec *spec, const uint32_t *keep,
+                                    uint64_t n_keep, aln_signif_record *records, double *f, uint32_t *lengths)
+{
+    int st = seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    if (!params || !spec || (n_keep && (!keep || !records))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (spec->per_pair == 0 || spec->per_pair > ALN_SHUFFLE_MAX_COPIES) { g_err = "per_pair must be 1 .. 2^20"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_keep > 0xFFFFFFF0ull) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t held = ss->hit_pair.size();
+    for (uint64_t k = 0; k < n_keep; ++k) {
+        if (keep[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+        if (ss->len[ss->hit_t[keep[k]]] < spec->max_trim) { g_err = "a listed hit's target is shorter than max_trim"; return ALN_ERR_INVALID_ARGUMENT; }
+    }
+    if (params->semantics == ALN_PWM_LOCAL) { g_err = "shuffled copies are aligned with the substitution-matrix semantics only"; return ALN_ERR_UNSUPPORTED; }
+    const size_t n = (size_t)n_keep;
+    const uint32_t per = spec->per_pair;
+    const uint64_t total = (uint64_t)n * per;
+    // the listed hits as pairs: where they lie in the set's buffer, their streams (the pair number in the block of the held pass), their f
+    std::vector<uint64_t> q_off(n), q_len(n), t_off(n), t_len(n), stream(n);
+    std::vector<double> f_hit(n);
+    for (size_t k = 0; k < n; ++k) {
+        const uint32_t h = keep[k], sq = ss->hit_q[h], tq = ss->hit_t[h];
+        q_off[k] = ss->off[sq]; q_len[k] = ss->len[sq]; t_off[k] = ss->off[tq]; t_len[k] = ss->len[tq];
+        stream[k] = spec->pair_base + ss->hit_pair[h];
+        f_hit[k] = ss->hit_score[h];
+    }
+    // (no table of every copy's length: the plan draws the trims per chunk, and the caller's array is written at the end, once
+    // nothing can fail the call any more)
+    DevCtx *dev = ss->ctx;
+    ShuffleJob job;
+    if ((st = shuffle_job_plan(dev, params, spec, stream.data(), nullptr, q_off.data(), q_len.data(), t_off.data(), t_len.data(), n, nullptr, job)) != ALN_OK) return st;
+    if (n == 0) return ALN_OK;
+    const Call &c = job.c;
+    const ShuffleStage &g = job.g;
+    HIPCHK(hipSetDevice(dev->device));
+    HIPCHK(hipStreamSynchronize(ss->slot->stream));      // the held pass is complete; its residues are read-only from here
+    const auto t0 = std::chrono::steady_clock::now();
+    Slot *sl[1];
+    pool_lease(dev, 1, sl);
+    struct Release { DevCtx *c; Slot **s; ~Release() { pool_release(c, s, 1); } } rel{dev, sl};
+    Slot &s = *sl[0];
+    if ((st = shuffle_job_ensure(s, job)) != ALN_OK) return st;
+    // pair table | stream table | held f | records | the f of one chunk's copies: nothing here grows with n * per_pair
+    const uint64_t stream_off = align256(sizeof(ShufflePair) * n), hit_off = align256(stream_off + 8ull * n),
+                   rec_off = align256(hit_off + 8ull * n), f_off = align256(rec_off + sizeof(aln_signif_record) * n);
+    if ((st = dev_ensure(s.shuffle, f_off + (f ? 8 * job.copies_max : 0), s.pooled)) != ALN_OK) return st;
+    uint8_t *base = s.shuffle.as<uint8_t>();
+    const ShufflePair *pairs_d = s.shuffle.as<ShufflePair>();
+    const uint64_t *stream_d = reinterpret_cast<const uint64_t *>(base + stream_off);
+    const double *hit_d = reinterpret_cast<const double *>(base + hit_off);
+    aln_signif_record *rec_d = reinterpret_cast<aln_signif_record *>(base + rec_off);
+    double *f_d = f ? reinterpret_cast<double *>(base + f_off) : nullptr;
+    hipStream_t q = s.stream;
+    uint64_t up = 0;
+    const uint8_t *set_seqs = ss->slot->seqs.as<uint8_t>();
+    std::vector<aln_signif_record> rec(n);
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        if (g.direct) {
+            if (g.bytes) HIPCHK(hipMemcpyAsync(s.seqs.p, set_seqs + g.lo, g.bytes, hipMemcpyDeviceToDevice, q));
+        } else {
+            for (size_t k = 0; k < n; ++k) {
+                const ShufflePair &P = g.pairs[k];
+                if (P.q_len) HIPCHK(hipMemcpyAsync(s.seqs.as<uint8_t>() + P.q_off, set_seqs + q_off[k], P.q_len, hipMemcpyDeviceToDevice, q));
+                if (P.t_len) HIPCHK(hipMemcpyAsync(s.seqs.as<uint8_t>() + P.t_off, set_seqs + t_off[k], P.t_len, hipMemcpyDeviceToDevice, q));
+            }
+        }
+        HIPCHK(hipMemcpyAsync(base, g.pairs.data(), sizeof(ShufflePair) * n, hipMemcpyHostToDevice, q));
+        HIPCHK(hipMemcpyAsync(base + stream_off, stream.data(), 8ull * n, hipMemcpyHostToDevice, q));
+        HIPCHK(hipMemcpyAsync(base + hit_off, f_hit.data(), 8ull * n, hipMemcpyHostToDevice, q));
+        up += (sizeof(ShufflePair) + 16) * n;
+        int e = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q);
+        if (e != ALN_OK) return e;
+        up += c.md.size() * (c.is_int ? 4 : 8);
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        for (size_t j = 0; j < job.ranges.size(); ++j) {
+            const size_t p0 = job.ranges[j].first, np = job.ranges[j].second;
+            if ((e = shuffle_job_chunk(dev, s, job, j, spec, pairs_d, stream_d, &up)) != ALN_OK) return e;
+            aln_signif_launch_reduce(s.results.as<aln_pair_result>(), hit_d + p0, (uint32_t)np, per, rec_d + p0, f_d, q);
+            HIPCHK(hipGetLastError());
+            // (stream order: the next chunk's reduce writes the buffer after this copy has read it)
+            if (f) HIPCHK(hipMemcpyAsync(f + (uint64_t)p0 * per, f_d, 8ull * np * per, hipMemcpyDeviceToHost, q));
+        }
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        // (the records land in a buffer of the call's own first: an error on the way leaves the caller's array as it was)
+        HIPCHK(hipMemcpyAsync(rec.data(), rec_d, sizeof(aln_signif_record) * n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    memcpy(records, rec.data(), sizeof(aln_signif_record) * n);
+    if (lengths)
+        for (size_t k = 0; k < n; ++k)
+            for (uint32_t c = 0; c < per; ++c)
+                lengths[(uint64_t)k * per + c] = (uint32_t)t_len[k] - aln_shuffle_trim_of(spec->seed, stream[k], c, spec->max_trim);
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->bytes[0] = up; ss->bytes[1] = sizeof(aln_signif_record) * n + (f ? 8 * total : 0);
+    return ALN_OK;
+}
+
+// (host memory that cannot be had -- the tables of a chunk of 2^22 copies, the listed hits' own -- is ALN_ERR_OOM, not an exception
+// through the C boundary)
+extern "C" int aln_seqset_held_significance(aln_seqset *ss, const aln_params *params, const aln_shuffle_spec *spec, const uint32_t *keep,
+                                            uint64_t n_keep, aln_signif_record *records, double *f, uint32_t *lengths)
+{
+    try {
+        return seqset_held_significance(ss, params, spec, keep, n_keep, records, f, lengths);
+    } catch (const std::bad_alloc &) {
+        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
 }
 
 extern "C" int aln_seqset_stats(const aln_seqset *ss, double *ms, uint64_t *bytes)

@@ -1,4 +1,4 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip and aln_best.hip define
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip and aln_best.hip define
 // and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
 #pragma once
@@ -33,6 +33,15 @@ void aln_shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair *pa
 void aln_shuffle_launch_expand(PairDesc *descs, uint32_t *order, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
                                uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t region, uint64_t out_base, hipStream_t s);
 void aln_shuffle_launch_gather(const aln_pair_result *res, double *f, uint64_t n, uint32_t per_pair, uint32_t *first, hipStream_t s);
+// the same with a stream table: pair i's copies come from the streams (seed, stream[i], s)
+void aln_shuffle_launch_table(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair, uint64_t seed,
+                              const uint64_t *stream, uint32_t max_trim, uint64_t out_base, uint32_t slot, hipStream_t s);
+void aln_shuffle_launch_expand_table(PairDesc *descs, uint32_t *order, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
+                                     uint64_t seed, const uint64_t *stream, uint32_t max_trim, uint64_t region, uint64_t out_base, hipStream_t s);
+
+// ---- aln_signif.hip: the records of a chunk's hits out of their copies' summaries
+void aln_signif_launch_reduce(const aln_pair_result *res, const double *f_hit, uint32_t n_hits, uint32_t per_pair, aln_signif_record *rec,
+                              double *f, hipStream_t s);
 
 // ---- aln_pairset.hip: the held strings of a pair set, per-pair matrices
 void aln_pairset_launch_freq(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list, uint32_t n_list,

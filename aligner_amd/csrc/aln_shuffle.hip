@@ -10,6 +10,9 @@
 //   gather    f of every copy out of the 48-byte summaries (8 bytes per copy go back), and per pair the first copy whose status
 //             is not ALN_OK, as one atomicMin of (copy << 8 | status)
 //
+// The stream of copy s of pair i is (seed, pair_base + i, s); with a STREAM TABLE (aln_seqset_held_significance: the pairs are listed
+// hits of a sequence set) it is (seed, stream[i], s) instead -- the same kernels, instantiated a second time, the pair table unchanged.
+//
 // Every store is a plain C++ store of a thread (vector memory instructions).
 #include <hip/hip_runtime.h>
 
@@ -19,17 +22,19 @@
 
 // ---- the copies of pairs p0 .. of a chunk: copy k of the chunk is copy k % per_pair of pair p0 + k / per_pair, written at
 // out + (out_off - out_base) + s * t_len.  slot: LDS bytes per thread (0: no LDS; a multiple of 16, at most ALN_SHUFFLE_LDS_MAX).
+// TABLE: pair i's stream index is stream[i], not pair_base + i.
+template <bool TABLE>
 __global__ __launch_bounds__(ALN_SHUFFLE_THREADS) void aln_shuffle_kernel(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs,
                                                                           uint32_t p0, uint64_t n, uint32_t per_pair, uint64_t seed,
                                                                           uint64_t pair_base, uint32_t max_trim, uint64_t out_base,
-                                                                          uint32_t slot)
+                                                                          uint32_t slot, const uint64_t *stream)
 {
     extern __shared__ uint8_t lds[];
     const uint64_t k = (uint64_t)blockIdx.x * ALN_SHUFFLE_THREADS + threadIdx.x;
     if (k >= n) return;
     const uint32_t i = p0 + (uint32_t)(k / per_pair), s = (uint32_t)(k % per_pair);
     const ShufflePair P = pairs[i];
-    uint64_t state = aln_shuffle_state(seed, pair_base + i, s);
+    uint64_t state = aln_shuffle_state(seed, TABLE ? stream[i] : pair_base + i, s);
     const uint32_t len = P.t_len - aln_shuffle_trim(state, max_trim);     // the host checked t_len >= max_trim
     const uint8_t *src = seqs + P.t_off;
     uint8_t *dst = out + (P.out_off - out_base) + (uint64_t)s * P.t_len;
@@ -52,9 +57,10 @@ __global__ __launch_bounds__(ALN_SHUFFLE_THREADS) void aln_shuffle_kernel(const 
 
 // ---- descriptor k of a chunk = copy k: the query of its pair, the copy's residues at region + (out_off - out_base) + s * t_len
 // of the residue buffer, M = L - trim (an empty query or copy: the reference panics, ALN_ERR_EMPTY_SEQUENCE as in chunk_plan)
+template <bool TABLE>
 __global__ __launch_bounds__(256) void aln_shuffle_expand_kernel(PairDesc *descs, uint32_t *order, const ShufflePair *pairs, uint32_t p0,
                                                                  uint64_t n, uint32_t per_pair, uint64_t seed, uint64_t pair_base,
-                                                                 uint32_t max_trim, uint64_t region, uint64_t out_base)
+                                                                 uint32_t max_trim, uint64_t region, uint64_t out_base, const uint64_t *stream)
 {
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
@@ -64,7 +70,7 @@ __global__ __launch_bounds__(256) void aln_shuffle_expand_kernel(PairDesc *descs
     d.q_off = P.q_off;
     d.t_off = region + (P.out_off - out_base) + (uint64_t)s * P.t_len;
     d.N = P.q_len;
-    d.M = P.t_len - aln_shuffle_trim_of(seed, pair_base + i, s, max_trim);
+    d.M = P.t_len - aln_shuffle_trim_of(seed, TABLE ? stream[i] : pair_base + i, s, max_trim);
     d.dir_off = 0; d.tb_off = 0; d.tag_off = 0; d.h_off = 0;
     d.status = (d.N == 0 || d.M == 0) ? ALN_ERR_EMPTY_SEQUENCE : ALN_OK;
     d.layout = 0;
@@ -83,22 +89,43 @@ __global__ __launch_bounds__(256) void aln_shuffle_gather_kernel(const aln_pair_
     if (r.status != ALN_OK) atomicMin(first + k / per_pair, ((uint32_t)(k % per_pair) << 8) | ((uint32_t)r.status & 0xffu));
 }
 
-extern "C" void aln_shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
-                                   uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t out_base, uint32_t slot, hipStream_t s)
+template <bool TABLE>
+static void shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair, uint64_t seed,
+                           uint64_t pair_base, uint32_t max_trim, uint64_t out_base, uint32_t slot, const uint64_t *stream, hipStream_t s)
 {
     if (!n) return;
     const uint32_t lds = slot * ALN_SHUFFLE_THREADS;
     if (lds > 64u * 1024u)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(aln_shuffle_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(aln_shuffle_kernel, dim3(blocks_of(n, ALN_SHUFFLE_THREADS)), dim3(ALN_SHUFFLE_THREADS), lds, s, seqs, out, pairs, p0, n,
-                       per_pair, seed, pair_base, max_trim, out_base, slot);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(aln_shuffle_kernel<TABLE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(aln_shuffle_kernel<TABLE>, dim3(blocks_of(n, ALN_SHUFFLE_THREADS)), dim3(ALN_SHUFFLE_THREADS), lds, s, seqs, out, pairs, p0, n,
+                       per_pair, seed, pair_base, max_trim, out_base, slot, stream);
+}
+
+extern "C" void aln_shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
+                                   uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t out_base, uint32_t slot, hipStream_t s)
+{
+    shuffle_launch<false>(seqs, out, pairs, p0, n, per_pair, seed, pair_base, max_trim, out_base, slot, nullptr, s);
+}
+
+extern "C" void aln_shuffle_launch_table(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
+                                         uint64_t seed, const uint64_t *stream, uint32_t max_trim, uint64_t out_base, uint32_t slot, hipStream_t s)
+{
+    shuffle_launch<true>(seqs, out, pairs, p0, n, per_pair, seed, 0, max_trim, out_base, slot, stream, s);
 }
 
 extern "C" void aln_shuffle_launch_expand(PairDesc *descs, uint32_t *order, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,
                                           uint64_t seed, uint64_t pair_base, uint32_t max_trim, uint64_t region, uint64_t out_base, hipStream_t s)
 {
-    if (n) hipLaunchKernelGGL(aln_shuffle_expand_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, descs, order, pairs, p0, n, per_pair, seed,
-                              pair_base, max_trim, region, out_base);
+    if (n) hipLaunchKernelGGL(aln_shuffle_expand_kernel<false>, dim3(blocks_of(n, 256)), dim3(256), 0, s, descs, order, pairs, p0, n, per_pair, seed,
+                              pair_base, max_trim, region, out_base, nullptr);
+}
+
+extern "C" void aln_shuffle_launch_expand_table(PairDesc *descs, uint32_t *order, const ShufflePair *pairs, uint32_t p0, uint64_t n,
+                                                uint32_t per_pair, uint64_t seed, const uint64_t *stream, uint32_t max_trim, uint64_t region,
+                                                uint64_t out_base, hipStream_t s)
+{
+    if (n) hipLaunchKernelGGL(aln_shuffle_expand_kernel<true>, dim3(blocks_of(n, 256)), dim3(256), 0, s, descs, order, pairs, p0, n, per_pair, seed,
+                              (uint64_t)0, max_trim, region, out_base, stream);
 }
 
 extern "C" void aln_shuffle_launch_gather(const aln_pair_result *res, double *f, uint64_t n, uint32_t per_pair, uint32_t *first, hipStream_t s)

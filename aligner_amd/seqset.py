@@ -11,9 +11,37 @@ import numpy as np
 
 from . import _ffi
 from . import runtime
+from . import statistics
 from .alignment import Alignment
 from .batch import RESULT_DTYPE
 from .enums import Protein
+
+
+# aln_signif_record (include/aligner_hip.h) and what HeldHits.significance makes of it
+SIGNIF_RECORD_DTYPE = np.dtype([("sum", "<f8"), ("sum_sq", "<f8"), ("f_max", "<f8"), ("n_ok", "<u4"), ("n_ge", "<u4"), ("status", "<i4"),
+                                ("first_bad", "<u4"), ("reserved", "<u8")])
+SIGNIF_DTYPE = np.dtype([("mean", "<f8"), ("sd", "<f8"), ("z", "<f8"), ("p_emp", "<f8"), ("n_ok", "<u4"), ("status", "<i4")])
+assert SIGNIF_RECORD_DTYPE.itemsize == 48
+
+
+def significance_from_records(records, f_hit):
+    """mean, sd, z and the empirical p of hits with score f_hit out of their records: mean = sum / n_ok, sd = sqrt(sum_sq / n_ok -
+    mean^2) clamped at 0 (the population form, as calculate_starting_values of the repeat search, engine/calc.rs:76-84),
+    z = (f - mean) / sd, p_emp = (n_ge + 1) / (n_ok + 1).  No copy succeeded: mean, sd and z are NaN, p_emp is 1; sd = 0: z is +-inf
+    or NaN.  Nothing is raised or warned about."""
+    records = np.asarray(records, dtype=SIGNIF_RECORD_DTYPE)
+    f_hit = np.asarray(f_hit, dtype=np.float64)
+    out = np.zeros(len(records), dtype=SIGNIF_DTYPE)
+    with np.errstate(all="ignore"):
+        n = records["n_ok"].astype(np.float64)
+        mean = records["sum"] / n
+        var = records["sum_sq"] / n - mean * mean
+        sd = np.sqrt(np.where(var < 0.0, 0.0, var))
+        out["mean"], out["sd"] = mean, sd
+        out["z"] = (f_hit - mean) / sd
+        out["p_emp"] = (records["n_ge"].astype(np.float64) + 1.0) / (n + 1.0)
+    out["n_ok"], out["status"] = records["n_ok"], records["status"]
+    return out
 
 
 def _block(block, n):
@@ -182,6 +210,61 @@ class HeldHits:
             a, c = int(off[k]), int(cap[k])
             out.append((tb[a:a + n].copy(), tb[a + c:a + c + n].copy()))
         return res, out
+
+    def _keep(self, keep):
+        return np.arange(self.count, dtype=np.uint32) if keep is None else np.ascontiguousarray(keep, dtype=np.uint32)
+
+    def significance_records(self, matrix, del_, ext, seed, per_pair=statistics.SEQUENCES - 1, max_trim=6, keep=None, pair_base=0, scores=False,
+                             semantics=None, blank=98, **kw):
+        """aln_seqset_held_significance: (records, f, lengths) of the listed positions of the held list (default: all) -- the 48-byte
+        records as SIGNIF_RECORD_DTYPE, and with scores=True f float64[n, per_pair] and lengths uint32[n, per_pair] of every copy
+        (None otherwise).  Copy s of a hit comes from the stream (seed, pair_base + its .index, s).  semantics: the held pass's unless
+        given."""
+        o = self.owner
+        w = self._keep(keep)
+        if not 1 <= int(per_pair) <= _ffi.SHUFFLE_MAX_COPIES:          # (before the per-copy arrays are sized by it)
+            raise ValueError("aln_seqset_held_significance: per_pair must lie in 1 .. %d" % _ffi.SHUFFLE_MAX_COPIES)
+        p, _held = runtime.make_params(self.semantics if semantics is None else semantics, del_, ext, matrix, outputs=_ffi.OUT_SCORE,
+                                       blank=blank, **kw)
+        spec = _ffi.ShuffleSpec(int(seed) & 0xFFFFFFFFFFFFFFFF, int(pair_base) & 0xFFFFFFFFFFFFFFFF, int(per_pair), int(max_trim))
+        rec = np.zeros(len(w), dtype=SIGNIF_RECORD_DTYPE)
+        shape = (len(w), int(per_pair)) if scores else None
+        f = np.zeros(shape, dtype=np.float64) if scores else None
+        lengths = np.zeros(shape, dtype=np.uint32) if scores else None
+        st = o.lib.aln_seqset_held_significance(o.handle, C.byref(p), C.byref(spec), w.ctypes.data, len(w), rec.ctypes.data,
+                                                f.ctypes.data if scores else None, lengths.ctypes.data if scores else None)
+        runtime.raise_for_status(st, "aln_seqset_held_significance")
+        return rec, f, lengths
+
+    def significance(self, matrix, del_, ext, seed, per_pair=statistics.SEQUENCES - 1, max_trim=6, keep=None, pair_base=0, scores=False, **kw):
+        """Is a held hit better than chance?  Every listed hit's query against per_pair trimmed and shuffled copies of its target,
+        drawn, scored and reduced on the device.  Returns a SIGNIF_DTYPE array (mean, sd, z, p_emp, n_ok, status: see
+        significance_from_records); with scores=True (that, f, lengths) of every copy as well."""
+        w = self._keep(keep)
+        rec, f, lengths = self.significance_records(matrix, del_, ext, seed, per_pair, max_trim, w, pair_base, scores, **kw)
+        out = significance_from_records(rec, self.f[w])
+        return (out, f, lengths) if scores else out
+
+    def p_values(self, matrix, del_, ext, seed, per_pair=statistics.SEQUENCES - 1, max_trim=6, keep=None, pair_base=0, slice_hits=64, **kw):
+        """The reference's own p-value (calculate_p_value, statistics/mod.rs:240-307) of every listed hit: scores [f_hit] + the f of
+        its copies, lengths [len(target)] + theirs, exactly as statistics.calculate_p_values composes them, through the same
+        calculate_distribution_params / get_p_value (host numpy).  The copies' scores come down slice_hits hits at a time.  A failed
+        copy raises, as the reference's unwrap panics."""
+        o = self.owner
+        w = self._keep(keep)
+        out = np.empty(len(w), dtype=np.float64)
+        for a in range(0, len(w), max(int(slice_hits), 1)):
+            part = w[a:a + max(int(slice_hits), 1)]
+            rec, f, lengths = self.significance_records(matrix, del_, ext, seed, per_pair, max_trim, part, pair_base, True, **kw)
+            bad = rec["status"] != _ffi.OK
+            if bad.any():
+                runtime.raise_for_status(int(rec["status"][bad][0]), "aln_seqset_held_significance")
+            for i, h in enumerate(part):
+                ql, tl, fh = int(o.len[self.q[h]]), int(o.len[self.t[h]]), float(self.f[h])
+                sc = np.concatenate([[fh], f[i]])
+                ln = np.concatenate([[tl], lengths[i].astype(np.int64)])
+                out[a + i] = float(statistics.calculate_distribution_params(ql, ln, sc).get_p_value(ql, tl, fh))
+        return out
 
     def alignments(self, keep=None):
         """Alignment objects of the listed positions (default: all), coordinates as SimpleLocalAligner / SimpleGlobalAligner give them."""

@@ -375,6 +375,47 @@ int aln_seqset_stats(const aln_seqset *set, double *ms /* 4 */, uint64_t *bytes 
 int aln_seqset_best(aln_seqset *set, const aln_params *params, const aln_seqset_block *block, uint32_t k, double f_min, uint32_t flags,
                     uint64_t *count);
 
+/* ---- significance of held hits (an addition of the same ABI version): is a held hit better than chance?  For every listed position
+ * of the held list (of aln_seqset_hits or aln_seqset_best; any order, a position may be listed twice) the query, sequence q, is aligned
+ * score only against spec->per_pair trimmed and shuffled copies of the target, sequence t -- the copies of aln_shuffle_scores, drawn
+ * on the device from the set's own resident residues (none are uploaded), filled by the launches aln_shuffle_scores makes, planned
+ * and chunked as it plans and chunks (whole hits per chunk; ALN_CHUNK_CELLS overrides the cell bound) -- and what the copies of a hit
+ * leave is reduced on the device to one 48-byte record, in the order aligner_amd/csrc/aln_signif_rules.h states: 64 partial
+ * accumulators, accumulator l taking copies l, l + 64, ... in ascending order, folded at distances 32, 16, .. 1; every operation
+ * rounded on its own.  The bits of a record therefore depend on (seed, stream, scheme, the two sequences, the held f) only.
+ * stream: copy s of a hit comes from the stream (seed, pair_base + pair_index, s) of aln_shuffle_rules.h, pair_index being the hit's
+ * pair number in the block of the held pass (what held_list reports; uint64 arithmetic, wrapping) -- not its position in the held
+ * list or in keep: a pair's copies do not depend on f_min, k, the other hits or the order of keep, and are the copies
+ * aln_shuffle_scores draws for that pair under pair_base + pair_index.
+ * params: the scheme of the copies (any non-PWM semantics and every scheme aln_shuffle_scores accepts; passing the scheme of the held
+ * pass is the caller's business); outputs is ignored.  n_ge compares against the held list's f.
+ * A failed copy (trimmed to nothing: ALN_ERR_EMPTY_SEQUENCE; no positive cell: ALN_ERR_NO_POSITIVE_CELL ...) is left out of the sums
+ * and shows as n_ok < per_pair, with the first such copy and its status in the record; it fails neither the hit nor the call.
+ * f, lengths (optional, n_keep * per_pair each): entry k * per_pair + s is the f (a failed copy: as its summary has it) and the
+ * length L - trim of copy s of keep[k].  Device memory does not grow with n_keep * per_pair: the copies' scores live in a buffer of
+ * the largest chunk, and with f they come down chunk by chunk.  Up: 48 bytes per listed hit (its place in the residue buffers, its
+ * stream, its held f), the matrix, and the plan's queue for chunks with copies routed off the batch kernel.  Down: 48 bytes per hit,
+ * 8 more per copy with f.
+ * The held summaries and strings are not touched: held_list and held_strings answer afterwards as before.
+ * ALN_ERR_INVALID_ARGUMENT for the whole call, nothing written, held state intact: no held state, a keep[k] >= count, a null pointer
+ * with a non-zero length, per_pair outside 1 .. 2^20, a listed hit whose target is shorter than max_trim.  ALN_PWM_LOCAL:
+ * ALN_ERR_UNSUPPORTED.
+ * stats afterwards: ms[2] the kernels of this call (shuffle, fill, reduce, with the copies between them), ms[3] its wall time; bytes[]
+ * as above; ms[0] and ms[1] stay the held pass's. ---- */
+typedef struct aln_signif_record {
+    double   sum;        /* of f over the copies with status ALN_OK          */
+    double   sum_sq;     /* of f * f over them (product rounded, then added) */
+    double   f_max;      /* largest such f; -inf when n_ok == 0              */
+    uint32_t n_ok;       /* copies with status ALN_OK                        */
+    uint32_t n_ge;       /* of those, f_copy >= f_hit (plain IEEE compare)   */
+    int32_t  status;     /* status of the first failed copy, ALN_OK if none  */
+    uint32_t first_bad;  /* its copy number, 0xffffffff if none              */
+    uint64_t reserved;   /* 0: fills the record to 48 bytes                  */
+} aln_signif_record;     /* 48 bytes */
+
+int aln_seqset_held_significance(aln_seqset *set, const aln_params *params, const aln_shuffle_spec *spec, const uint32_t *keep,
+                                 uint64_t n_keep, aln_signif_record *records, double *f, uint32_t *lengths);
+
 /* ---- heuristic alignment of the pairs of a sequence set (additions of the same ABI version): the request path's two halves joined --
  * every pair of a FASTA (generate_pairs), each run through the loop of HeuristicAligner (heuristic/mod.rs:36-78).
  * create_from_set: a pair set whose pair i is pair first + i of the block, in the block's numbering (sequence q the query, sequence

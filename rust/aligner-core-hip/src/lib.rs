@@ -259,7 +259,20 @@ pub mod seqset {
         pub fn aln_seqset_held_strings(set: *mut AlnSeqset, keep: *const u32, n_keep: u64, results: *mut AlnPairResult, tb_buf: *mut u8,
                                        tb_off: *const u64) -> c_int;
         pub fn aln_seqset_stats(set: *const AlnSeqset, ms: *mut f64, bytes: *mut u64) -> c_int;
+        /// is a held hit better than chance: per listed position one record reduced on the device from `per_pair` shuffled copies of
+        /// its target (copy s from the stream (seed, pair_base + the hit's pair index, s)); `f` / `lengths` optional, n_keep * per_pair
+        pub fn aln_seqset_held_significance(set: *mut AlnSeqset, p: *const AlnParams, spec: *const AlnShuffleSpec, keep: *const u32, n_keep: u64,
+                                            records: *mut AlnSignifRecord, f: *mut f64, lengths: *mut u32) -> c_int;
     }
+    /// `aln_shuffle_spec`: the streams of the shuffled copies (aligner_amd/csrc/aln_shuffle_rules.h)
+    #[repr(C)]
+    #[derive(Clone, Copy, Default)]
+    pub struct AlnShuffleSpec { pub seed: u64, pub pair_base: u64, pub per_pair: u32, pub max_trim: u32 } // 24 bytes
+    /// `aln_signif_record`: sums in the order of aligner_amd/csrc/aln_signif_rules.h
+    #[repr(C)]
+    #[derive(Clone, Copy, Default)]
+    pub struct AlnSignifRecord { pub sum: f64, pub sum_sq: f64, pub f_max: f64, pub n_ok: u32, pub n_ge: u32, pub status: i32, pub first_bad: u32,
+                                 pub reserved: u64 } // 48 bytes
     /// A pair set (`aln_pairset_*`) over pairs first .. first + n_pairs - 1 of a block: it borrows the set's residues.  After
     /// `aln_pairset_heuristics`, `aln_pairset_loop_begin` and one `aln_pairset_loop_step` per iteration run the loop of
     /// HeuristicAligner (heuristic/mod.rs:36-78) for all pairs; a step returns the finished pairs, their causes (0 done, 1 failed,
