@@ -13,6 +13,9 @@
 // Batch kernels: every lane reads its column's query code from a per-wave LDS ring two steps ahead, and lane 0's boundary cell comes
 // from a second ring one step ahead (below: "the query ring"); only PWM scoring still moves its column word down the lanes with the
 // DPP wave_shr:1 that carries the boundary cell.
+// Strip 0, core local: row 1's penalty select compares against lane 0 of a register that is 2 or 1.  A run that can meet advice
+// (a re-fill, the localized repair) sets it every step from the advice byte of the column (v_readlane, v_writelane); a pair's first
+// pass, whose advice is all zero, sets it once: 2 for step 0, 1 from step 1 on (FastStrip's ADV).
 // Local end cell: per row one packed register  (T' << 11) | f(step)  updated with one v_lshl_add per cell and one v_max3
 // per two steps, folded every 2048 steps with the exact tie rule (first in row-major order: core; last in column-major
 // order: legacy).
@@ -258,7 +261,10 @@ __device__ __forceinline__ uint64_t uniform64(const void *p) { return uniform64(
 
 // PWM (position-weight-matrix scoring, batch kernels only) is a template parameter: a run-time test of it sat in the
 // hot loop of every batch fill.
-template <int SEM, int R, bool SINGLE, bool FIRST, bool LAST, bool PWM = false>
+// ADV (batch kernels, core local strip 0): this run can meet a non-zero advice byte -- a full re-fill or a localized repair.  A pair's
+// first pass, and every pass of a pair without the row-1 hazard, runs with ADV = false: the advice is all zero then, so lane 0 of
+// cmp2 is 2 in step 0 and 1 afterwards whatever memory holds, and the unmasked step carries no advice feed at all.
+template <int SEM, int R, bool SINGLE, bool FIRST, bool LAST, bool PWM = false, bool ADV = true>
 struct FastStrip {
     static constexpr int SPB = (int)aln_spb(R);
     static constexpr int RP = ProfWord<R>::RP;             // bytes between two lanes' profile words
@@ -272,6 +278,10 @@ struct FastStrip {
     static constexpr bool QRING = !SINGLE && !PWM;
     // ... and a strip with a strip above it reads the next step's boundary cell from the wave's boundary ring one step ahead (top0v)
     static constexpr bool BRING = QRING && !FIRST;
+    // strip 0, core local: the advice feed (advchunk, one v_readlane and one v_writelane per step); without it lane 0 of cmp2 is
+    // set once, in the masked step 1
+    static constexpr bool ADVFEED = SEM == ALN_CORE_LOCAL && FIRST && (SINGLE || ADV);
+    static constexpr bool ADVFREE = SEM == ALN_CORE_LOCAL && FIRST && !ADVFEED;
     // strip 0 of a local batch fill: the row above is the constant border (see topIn in step)
     static constexpr bool BORDER2 = !SINGLE && FIRST && LOCAL;
     static constexpr int QSHIFT = RP == 8 ? 9 : RP == 4 ? 8 : RP == 2 ? 7 : 6;      // a code's profile row: 64 * RP bytes
@@ -293,7 +303,8 @@ struct FastStrip {
     uint32_t advchunk, dw;
     PW pw;
     const uint8_t *prow;       // this lane's column of the profile: prof + lane*R
-    int cmp2;                  // batch kernels, core local strip 0: 2, but for lane 0, which every step rewrites (row 1's penalty select)
+    int cmp2;                  // batch kernels, core local strip 0: 2, but for lane 0 (row 1's penalty select): rewritten by every step from the
+                               // advice (ADVFEED), or 2 in step 0 and 1 from step 1 on (ADVFREE)
     uint32_t qaddr;            // batch kernels (QRING): LDS address of the code this lane reads in the first step of the current block
     uint32_t baddr;            // batch kernels (BRING): LDS address of the boundary cell read in the first step of the current block
 
@@ -346,6 +357,8 @@ struct FastStrip {
     // 8-byte granules (a store per step by lane 63 alone was 64 partial-line writes instead of four whole lines).  Before step k
     // lane l holds column k - 126 + l.  Repair run of strip 0: nothing is stored, the columns are compared with the row the
     // checkpointed pass wrote (a cell that comes out different ends the repair).
+    // (An LDS ring instead of the shift register -- lane 63 alone writing int k & 63 of the boundary ring under a scalar exec mask --
+    // was built and measured slower than the DPP and its copy: DESIGN 4.2, r14.)
     __device__ __forceinline__ void flush_below(uint32_t k, uint32_t beyond)
     {
         const uint32_t x = k - 126u + (uint32_t)lane;
@@ -389,7 +402,7 @@ struct FastStrip {
                 bring_put(in.brow_ring + 4u + 4u * (uint32_t)lane, fetch_above(xi + 1u));
                 baddr = in.brow_ring + 4u;
             } else if (!FIRST && !SINGLE) inchunk = fetch_above(xi);
-            if (SEM == ALN_CORE_LOCAL && FIRST && in.hazard) advchunk = (xi < N) ? in.advice[xi + 1] : 0u;
+            if (ADVFEED && in.hazard) advchunk = (xi < N) ? in.advice[xi + 1] : 0u;
             if (!SINGLE && PWM) qchunk = (xi + 1 < N) ? (int)in.pwm_words[xi + 1] : 0;
             // columns k + 2 .. k + 65 of the query ring: lane 0 reads column k + 2 in this very step, lane 63 read column k - 62 (the
             // oldest entry in use) in the last one; zeros beyond the query, as the flow had them
@@ -423,7 +436,7 @@ struct FastStrip {
         if (BRING) top0v = bring_get(baddr + 4u * (uint32_t)kk);
         // cross-lane reads stay in wave-uniform control flow: inside a divergent branch the compiler may compute
         // their operand for the active lanes only
-        const uint32_t adv = (SEM == ALN_CORE_LOCAL && FIRST) ? (uint32_t)__builtin_amdgcn_readlane((int)advchunk, sel) : 0u;
+        const uint32_t adv = ADVFEED ? (uint32_t)__builtin_amdgcn_readlane((int)advchunk, sel) : 0u;
         if constexpr (SINGLE) {
             pw = *reinterpret_cast<const PW *>(prow + qv);                           // step k+1: column k+1-lane
             qv = *reinterpret_cast<const uint16_t *>(qo_lane + 2 * (k + 2));         // step k+2
@@ -445,7 +458,11 @@ struct FastStrip {
             // compares against 2 when the advice says "zero" and against a value no T takes when it does not -- one
             // v_writelane instead of a select chain (batch kernels: into cmp2, whose other lanes hold 2 for the whole strip)
             int cmpv = 2;
-            if (SEM == ALN_CORE_LOCAL && FIRST) {
+            if constexpr (ADVFREE) {
+                // no advice: row 1 takes del in step 0 alone.  Step 1 lies in the first, masked quad of every strip
+                if (MASKED && k == 1u) asm("v_writelane_b32 %0, 1, 0" : "+v"(cmp2));
+                cmpv = cmp2;
+            } else if (SEM == ALN_CORE_LOCAL && FIRST) {
                 const int l0 = __builtin_amdgcn_readfirstlane(((k == 0) || (adv != 0)) ? 2 : 1);   // wave-uniform, in an SGPR
                 if constexpr (SINGLE) asm("v_writelane_b32 %0, %1, 0" : "+v"(cmpv) : "s"(l0));
                 else { asm("v_writelane_b32 %0, %1, 0" : "+v"(cmp2) : "s"(l0)); cmpv = cmp2; }
@@ -993,8 +1010,8 @@ struct FastStrip {
 // Batch kernels, skewed layout: every strip but the last has 512 rows (R = 8), the last one picks R by its row count.  A
 // cooperative re-fill (core local, no PWM scoring) instead cuts the pair into uniform strips of 64 R rows, R = 1, 2 or 4.
 // Strip 0 and the strips below it are separate functions: a call site instantiates only the strips it can reach.
-#define ALN_STRIP_CASE(RR, FIRSTV, LASTV) case RR: { FastStrip<SEM, RR, false, FIRSTV, LASTV, PWM> f(in, s); return f.run(o); }
-template <int SEM, bool PWM, bool FIRSTV>
+#define ALN_STRIP_CASE(RR, FIRSTV, LASTV) case RR: { FastStrip<SEM, RR, false, FIRSTV, LASTV, PWM, ADV> f(in, s); return f.run(o); }
+template <int SEM, bool PWM, bool FIRSTV, bool ADV>
 __device__ __forceinline__ FastOut fast_strip_of(const FastIn &in, FastOut o, uint32_t s, bool last, int R)
 {
     if (!last) {
@@ -1004,20 +1021,28 @@ __device__ __forceinline__ FastOut fast_strip_of(const FastIn &in, FastOut o, ui
             default: break;
             }
         }
-        FastStrip<SEM, ALN_FULL_R, false, FIRSTV, false, PWM> f(in, s);
+        FastStrip<SEM, ALN_FULL_R, false, FIRSTV, false, PWM, ADV> f(in, s);
         return f.run(o);
     }
     switch (R) {
     ALN_STRIP_CASE(1, FIRSTV, true) ALN_STRIP_CASE(2, FIRSTV, true) ALN_STRIP_CASE(3, FIRSTV, true) ALN_STRIP_CASE(4, FIRSTV, true)
     ALN_STRIP_CASE(5, FIRSTV, true) ALN_STRIP_CASE(6, FIRSTV, true) ALN_STRIP_CASE(7, FIRSTV, true)
-    default: { FastStrip<SEM, 8, false, FIRSTV, true, PWM> f(in, s); return f.run(o); }
+    default: { FastStrip<SEM, 8, false, FIRSTV, true, PWM, ADV> f(in, s); return f.run(o); }
     }
 }
 #undef ALN_STRIP_CASE
+// strip 0.  adv: the run can meet a non-zero advice byte (FastStrip's ADV; only core local has an advice feed to leave out, and PWM
+// scoring keeps the one form it had: its windows were not measured, and a second form would only add code)
 template <int SEM, bool PWM>
-__device__ __forceinline__ FastOut fast_strip_first(const FastIn &in, FastOut o, bool last, int R) { return fast_strip_of<SEM, PWM, true>(in, o, 0, last, R); }
+__device__ __forceinline__ FastOut fast_strip_first(const FastIn &in, FastOut o, bool last, int R, bool adv)
+{
+    if constexpr (SEM == ALN_CORE_LOCAL && !PWM) {
+        if (!adv) return fast_strip_of<SEM, PWM, true, false>(in, o, 0, last, R);
+    }
+    return fast_strip_of<SEM, PWM, true, true>(in, o, 0, last, R);
+}
 template <int SEM, bool PWM>
-__device__ __forceinline__ FastOut fast_strip_next(const FastIn &in, FastOut o, uint32_t s, bool last, int R) { return fast_strip_of<SEM, PWM, false>(in, o, s, last, R); }
+__device__ __forceinline__ FastOut fast_strip_next(const FastIn &in, FastOut o, uint32_t s, bool last, int R) { return fast_strip_of<SEM, PWM, false, true>(in, o, s, last, R); }
 
 // butterfly reduction of the per-lane end-cell candidates with the exact tie rule
 template <int SEM>

@@ -1430,7 +1430,8 @@ __device__ __forceinline__ bool fast_work(FastIn in, const FastScratch &fs, cons
             in.strip_q16 = (uint32_t)((Ru ? aln_uniform_strip_bytes(N, Ru) : aln_strip_bytes(N)) / 16u);
             in.tag_base = tag;
             in.ck_mode = (passes == 0 && can_repair) ? 1 : 0;                   // strip 0 of the first pass saves its checkpoints
-            o = fast_strip_first<SEM, PWM>(in, o, ns == 1, Ru ? (int)Ru : (ns == 1 ? aln_pick_r(M) : ALN_FULL_R));
+            // (pass 0 starts from the cleared advice, and a pair without the hazard never has any: strip 0 without the advice feed)
+            o = fast_strip_first<SEM, PWM>(in, o, ns == 1, Ru ? (int)Ru : (ns == 1 ? aln_pick_r(M) : ALN_FULL_R), in.hazard && passes != 0);
             in.ck_mode = 0;
             if (open) {
                 if (is_local<SEM>()) reduce_best<SEM>(o);
@@ -1537,7 +1538,7 @@ __device__ __forceinline__ bool fast_work(FastIn in, const FastScratch &fs, cons
                 in.last_flip = last_flip;
                 FastOut ro = o;
                 ro.repaired = false; ro.c_out = 0;
-                ro = fast_strip_first<SEM, PWM>(in, ro, ns_skew == 1, ns_skew == 1 ? aln_pick_r(M) : ALN_FULL_R);
+                ro = fast_strip_first<SEM, PWM>(in, ro, ns_skew == 1, ns_skew == 1 ? aln_pick_r(M) : ALN_FULL_R, true);
                 __threadfence_block();
                 if (!__any(ro.repaired)) { failed = true; passes |= 0x300000u; break; }       // no re-convergence (or a stale end-cell candidate)
                 if (ro.c_out != 0) { failed = true; passes |= 0x200000u; break; }            // strip 0's bottom row moved
