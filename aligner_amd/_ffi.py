@@ -45,6 +45,7 @@ EXPORTS = [
     "aln_pairset_heuristics", "aln_pairset_reestimate", "aln_pairset_run_stored", "aln_pairset_matrices", "aln_transform_matrices_device",
     "aln_seqset_create", "aln_seqset_destroy", "aln_seqset_pairs", "aln_seqset_score", "aln_seqset_hits", "aln_seqset_held_list",
     "aln_seqset_held_strings", "aln_seqset_stats", "aln_seqset_best", "aln_seqset_held_significance",
+    "aln_seqset_held_report", "aln_seqset_held_filter",
     "aln_pairset_create_from_set", "aln_pairset_loop_begin", "aln_pairset_loop_step",
 ]
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
@@ -97,6 +98,23 @@ class SignifRecord(C.Structure):
 
 assert C.sizeof(SignifRecord) == 48
 SHUFFLE_MAX_COPIES = 1 << 20      # per pair (aln_shuffle_spec.per_pair)
+REPORT_SKIP_SEED = 1              # ALN_REPORT_SKIP_SEED
+
+
+class HitReport(C.Structure):
+    """aln_hit_report: the classed columns of one held hit (aligner_amd/csrc/aln_report_rules.h)."""
+    _fields_ = [("columns", C.c_uint32), ("identical", C.c_uint32), ("positive", C.c_uint32), ("mismatch", C.c_uint32),
+                ("q_gap", C.c_uint32), ("t_gap", C.c_uint32), ("q_gap_open", C.c_uint32), ("t_gap_open", C.c_uint32),
+                ("status", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class HitFilter(C.Structure):
+    """aln_hit_filter: the thresholds of aln_seqset_held_filter."""
+    _fields_ = [("min_identity", C.c_double), ("min_q_cover", C.c_double), ("min_t_cover", C.c_double), ("min_columns", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(HitReport) == 40 and C.sizeof(HitFilter) == 32
 
 
 class SeqsetBlock(C.Structure):
@@ -235,6 +253,10 @@ def load():
     lib.aln_seqset_held_strings.argtypes = [vp, vp, C.c_uint64, vp, vp, u64p]
     lib.aln_seqset_held_significance.restype = i
     lib.aln_seqset_held_significance.argtypes = [vp, C.POINTER(Params), sp, vp, C.c_uint64, vp, vp, vp]
+    lib.aln_seqset_held_report.restype = i
+    lib.aln_seqset_held_report.argtypes = [vp, C.POINTER(Params), C.c_uint32, vp, C.c_uint64, vp]
+    lib.aln_seqset_held_filter.restype = i
+    lib.aln_seqset_held_filter.argtypes = [vp, C.POINTER(Params), C.c_uint32, C.POINTER(HitFilter), vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.aln_seqset_stats.restype = i
     lib.aln_seqset_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.aln_pairset_create_from_set.restype = vp

@@ -17,6 +17,13 @@ against N trimmed and shuffled copies of its target, drawn, scored and reduced o
 (z = (f - mean) / sd over the copies, p_emp = (copies with f >= the hit's + 1) / (copies + 1)).  --seed S picks the copies (default
 0: the same output every run).  A hit whose target has fewer than 6 residues has no such copies (each loses up to 6 tail residues): its
 row ends in `,nan,nan`.  Not with --heuristic.
+
+With --report (and --best or --f-min) every printed hit also says how identical, how covering and how gapped its alignment is:
+`,columns,identity,positives,q_cover,t_cover,gap_opens,gaps` is appended to each row (after `,z,p_emp` with --shuffles), counted on
+the device over the alignment's columns (the traceback's duplicated seed column left out): identity = identical / columns, positives
+= (identical + positive-scoring) / columns, q_cover / t_cover = aligned residues of the first / second record over its length.
+--min-identity X, --min-q-cover Y, --min-t-cover Z print only the hits the device filter keeps (with --best the K best are selected
+first, then filtered); --shuffles then runs on the kept hits only.  Not with --heuristic.
 """
 import argparse
 import sys
@@ -49,7 +56,17 @@ def main(argv=None):
     ap.add_argument("--best", type=int, default=None, metavar="K", help="per record its K best partners (1 .. %d), self pairs skipped" % _ffi.SEQSET_BEST_MAX)
     ap.add_argument("--shuffles", type=int, default=None, metavar="N", help="append z,p_emp from N shuffled copies of each hit's target (with --best or --f-min)")
     ap.add_argument("--seed", type=int, default=None, help="seed of the shuffled copies (default 0)")
+    ap.add_argument("--report", action="store_true", help="append columns,identity,positives,q_cover,t_cover,gap_opens,gaps (with --best or --f-min)")
+    ap.add_argument("--min-identity", type=float, default=None, metavar="X", help="print only hits with identical >= X * columns (with --best: the K best are selected first, then filtered)")
+    ap.add_argument("--min-q-cover", type=float, default=None, metavar="Y", help="print only hits whose alignment covers Y of the first record (with --best: selected first, then filtered)")
+    ap.add_argument("--min-t-cover", type=float, default=None, metavar="Z", help="print only hits whose alignment covers Z of the second record (with --best: selected first, then filtered)")
     a = ap.parse_args(argv)
+    filtered = a.min_identity is not None or a.min_q_cover is not None or a.min_t_cover is not None
+    if a.report or filtered:
+        if a.heuristic:
+            ap.error("--report / --min-identity / --min-q-cover / --min-t-cover describe the plain alignment: not with --heuristic")
+        if a.best is None and a.f_min is None:
+            ap.error("--report / --min-identity / --min-q-cover / --min-t-cover work on held hits: give --best K or --f-min F")
     if a.shuffles is not None:
         if a.heuristic:
             ap.error("--shuffles asks about the plain alignment's score: not with --heuristic")
@@ -68,16 +85,32 @@ def main(argv=None):
     heads = [r.head.decode("utf-8", "replace") for r in records]
     out = sys.stdout
 
-    def tail(held):
-        """`,z,p_emp` per held position, or empty strings without --shuffles"""
-        if a.shuffles is None:
-            return [""] * len(held)
-        # a copy loses up to MAX_TRIM tail residues: a target shorter than that has no such copies (the library refuses it)
-        can = np.flatnonzero(held.owner.len[held.t] >= MAX_TRIM).astype(np.uint32)
-        sig = held.significance(matrix, a.del_, a.ext, a.seed or 0, per_pair=a.shuffles, max_trim=MAX_TRIM, keep=can)
-        rows = [",nan,nan"] * len(held)
-        for h, z, p in zip(can, sig["z"], sig["p_emp"]):
-            rows[int(h)] = ",%r,%r" % (float(z), float(p))
+    def kept(held):
+        """positions of the held list that are printed (None: all) and their reports (None without --report)"""
+        if filtered:
+            got = held.filter(matrix, min_identity=a.min_identity or 0.0, min_q_cover=a.min_q_cover or 0.0, min_t_cover=a.min_t_cover or 0.0,
+                              with_reports=a.report)
+            return got if a.report else (got, None)
+        return None, (held.report(matrix) if a.report else None)
+
+    def tail(held, pos=None, reports=None):
+        """`,z,p_emp` and the report's columns per held position, or empty strings without --shuffles and --report; pos: the
+        positions that are printed (None: all)"""
+        rows = [""] * len(held)
+        shown = np.arange(len(held), dtype=np.uint32) if pos is None else np.asarray(pos, dtype=np.uint32)
+        if a.shuffles is not None:
+            # a copy loses up to MAX_TRIM tail residues: a target shorter than that has no such copies (the library refuses it)
+            can = shown[held.owner.len[held.t[shown]] >= MAX_TRIM].astype(np.uint32)
+            sig = held.significance(matrix, a.del_, a.ext, a.seed or 0, per_pair=a.shuffles, max_trim=MAX_TRIM, keep=can)
+            for h in shown:
+                rows[int(h)] = ",nan,nan"
+            for h, z, p in zip(can, sig["z"], sig["p_emp"]):
+                rows[int(h)] = ",%r,%r" % (float(z), float(p))
+        if reports is not None:
+            fr = held.fractions(reports, shown)
+            for h, r, x in zip(shown, reports, fr):
+                rows[int(h)] += ",%d,%r,%r,%r,%r,%d,%d" % (int(r["columns"]), float(x["identity"]), float(x["positives"]), float(x["q_cover"]),
+                                                            float(x["t_cover"]), int(x["gap_opens"]), int(x["gaps"]))
         return rows
 
     if a.best is not None:
@@ -87,9 +120,11 @@ def main(argv=None):
             ap.error("--best: K must lie in 1 .. %d" % _ffi.SEQSET_BEST_MAX)
         with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
             held = ss.best(matrix, a.del_, a.ext, a.best, f_min=float("-inf") if a.f_min is None else a.f_min, skip_self=True, semantics=sem)
-            more = tail(held)
+            pos_kept, reports = kept(held)
+            more = tail(held, pos_kept, reports)
+            show = np.ones(len(held), dtype=bool) if pos_kept is None else np.isin(np.arange(len(held)), pos_kept)
             for q, pos in held.by_query():
-                for p in pos:
+                for p in pos[show[pos]]:
                     out.write("%s,%d,%s,%r%s\n" % (heads[q], int(held.rank[p]) + 1, heads[int(held.t[p])], float(held.f[p]), more[p]))
         return 0
     if a.heuristic:
@@ -123,8 +158,10 @@ def main(argv=None):
                     k += 1
         else:
             held = ss.hits(matrix, a.del_, a.ext, a.f_min, None, semantics=sem)
-            for q, t, f, more in zip(held.q, held.t, held.f, tail(held)):
-                out.write("%s,%s,%r%s\n" % (heads[int(q)], heads[int(t)], float(f), more))
+            pos_kept, reports = kept(held)
+            more = tail(held, pos_kept, reports)
+            for h in (range(len(held)) if pos_kept is None else pos_kept):
+                out.write("%s,%s,%r%s\n" % (heads[int(held.q[h])], heads[int(held.t[h])], float(held.f[h]), more[int(h)]))
     return 0
 
 

@@ -11,11 +11,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libaligner_hip.so")
-SOURCES = ["aln_kernels.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip", "aln_signif.hip", "aln_pairset.hip", "aln_seqset.hip", "aln_loop.hip", "aln_best.hip"]
+SOURCES = ["aln_kernels.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip", "aln_signif.hip", "aln_pairset.hip", "aln_seqset.hip", "aln_loop.hip", "aln_best.hip", "aln_report.hip"]
 # aln_kernels.hip is compiled as several translation units side by side (-DALN_TU=<mask of its ALN_PART_* families>): the fast
 # core-local batch kernel alone is half of the compile time
 KERNEL_UNITS = [("generic", 1), ("fast_cl", 2), ("fast_rest", 4), ("single", 8), ("tb", 16), ("fast_cl_solo", 32), ("fast_rest_solo", 64)]
-HEADERS = ["aln_best_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_loop_rules.h", "aln_plan_rules.h", "aln_scheme_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_signif_rules.h", "aln_transform_rules.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h")]
+HEADERS = ["aln_best_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_loop_rules.h", "aln_plan_rules.h", "aln_report_rules.h", "aln_scheme_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_signif_rules.h", "aln_transform_rules.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h")]
 # host-only helper of the synthetic workloads (splitmix64 residues; aligner_amd/workloads.py only LOADS it)
 SYNTH_LIB = os.path.join(LIBDIR, "libaln_synth.so")
 SYNTH_SRC = os.path.join(CSRC, "aln_synth.c")

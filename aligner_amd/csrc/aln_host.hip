@@ -48,6 +48,7 @@
 #include "aln_best_rules.h"
 #include "aln_shuffle_rules.h"
 #include "aln_signif_rules.h"
+#include "aln_report_rules.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -3136,6 +3137,8 @@ struct aln_seqset {
     DevBuf held_res, held_tb, held_info, list, out_off, packed_res, packed_tb;
     // aln_seqset_best: a chunk's piece lists (key | target | count per piece) and the rows' running lists (aln_best.hip)
     DevBuf cand_key, cand_t, cand_n, run_key, run_t, run_n;
+    // aln_seqset_held_report / _filter: the scheme's bit table, the reports (of a list, or of all held hits), the kept positions | records
+    DevBuf rep_bits, reports, rep_pos, rep_out;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a chunk's launches; 4, 5: the best selection
     double ms[4] = {0, 0, 0, 0};
     uint64_t bytes[2] = {0, 0};
@@ -3165,7 +3168,7 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     for (hipEvent_t &e : ss->ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->held_res, &ss->held_tb,
                    &ss->held_info, &ss->list, &ss->out_off, &ss->packed_res, &ss->packed_tb, &ss->cand_key, &ss->cand_t, &ss->cand_n,
-                   &ss->run_key, &ss->run_t, &ss->run_n};
+                   &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
@@ -3798,6 +3801,154 @@ extern "C" int aln_seqset_held_significance(aln_seqset *ss, const aln_params *pa
 {
     try {
         return seqset_held_significance(ss, params, spec, keep, n_keep, records, f, lengths);
+    } catch (const std::bad_alloc &) {
+        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
+}
+
+// ---- reports of held hits: the columns of the held strings classed and counted on the device (aln_report.hip, aln_report_rules.h).
+// What both calls check before anything moves, and the scheme's bit table; neither call touches held_res / held_tb / held_info.
+static int seqset_report_check(aln_seqset *ss, const aln_params *params, uint32_t flags, std::vector<uint32_t> &bits)
+{
+    int st = seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    if (!params || !params->matrix) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (flags & ~ALN_REPORT_SKIP_SEED) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (params->semantics == ALN_PWM_LOCAL) { g_err = "a report classes the columns of a substitution-matrix alignment"; return ALN_ERR_UNSUPPORTED; }
+    const uint64_t entries = (uint64_t)params->rows * params->cols;
+    if (entries == 0) { g_err = "an empty matrix"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (entries > ALN_REPORT_MAX_BITS) { g_err = "rows * cols beyond 8192"; return ALN_ERR_UNSUPPORTED; }
+    bits.resize(aln_report_words(params->rows, params->cols));
+    aln_report_table(params->matrix, params->rows, params->cols, params->row_stride, bits.data());
+    return ALN_OK;
+}
+
+static int seqset_held_report(aln_seqset *ss, const aln_params *params, uint32_t flags, const uint32_t *keep, uint64_t n,
+                              aln_hit_report *reports)
+{
+    std::vector<uint32_t> bits;
+    int st = seqset_report_check(ss, params, flags, bits);
+    if (st != ALN_OK) return st;
+    if (n && (!keep || !reports)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n > 0x7FFFFFF0ull) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t held = ss->hit_pair.size();
+    for (uint64_t k = 0; k < n; ++k)
+        if (keep[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return ALN_OK;
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    if ((st = dev_ensure(ss->list, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * n, false)) != ALN_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    // (the records land in a buffer of the call's own first: an error on the way leaves the caller's array as it was)
+    std::vector<aln_hit_report> rep(n);
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        HIPCHK(hipMemcpyAsync(ss->list.p, keep, 4ull * n, hipMemcpyHostToDevice, q));
+        HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        aln_report_launch(ss->held_info.as<PairsetHeld>(), ss->held_res.as<aln_pair_result>(), ss->held_tb.as<uint8_t>(), ss->list.as<uint32_t>(),
+                          (uint32_t)n, (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols, params->blank_code, flags,
+                          ss->reports.as<aln_hit_report>(), q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(rep.data(), ss->reports.p, sizeof(aln_hit_report) * n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    memcpy(reports, rep.data(), sizeof(aln_hit_report) * n);
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->bytes[0] = 4ull * n + 4ull * bits.size(); ss->bytes[1] = sizeof(aln_hit_report) * n;
+    return ALN_OK;
+}
+
+static int seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, uint32_t *positions,
+                              aln_hit_report *reports, uint64_t capacity, uint64_t *count)
+{
+    std::vector<uint32_t> bits;
+    int st = seqset_report_check(ss, params, flags, bits);
+    if (st != ALN_OK) return st;
+    if (!filter || !count || (capacity && !positions)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (filter->reserved != 0) { g_err = "the filter's reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t held = ss->hit_pair.size();        // (<= 0xFFFFFFF0: seqset_hold_list)
+    if (held == 0) { *count = 0; return ALN_OK; }
+    const uint64_t room = std::min<uint64_t>(capacity, held);
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    uint32_t *tile_count, *tile_off;
+    if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(held), &tile_count, &tile_off)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * held, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->rep_pos, 4ull * room, false)) != ALN_OK) return st;
+    if (reports && (st = dev_ensure(ss->rep_out, sizeof(aln_hit_report) * room, false)) != ALN_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(ss->misc.as<uint8_t>() + 64);
+    uint32_t kept = 0;
+    uint64_t wrote = 0;
+    std::vector<uint32_t> pos;
+    std::vector<aln_hit_report> rep;
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        aln_report_launch(ss->held_info.as<PairsetHeld>(), ss->held_res.as<aln_pair_result>(), ss->held_tb.as<uint8_t>(), nullptr, (uint32_t)held,
+                          (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols, params->blank_code, flags,
+                          ss->reports.as<aln_hit_report>(), q);
+        HIPCHK(hipGetLastError());
+        aln_report_launch_filter(ss->reports.as<aln_hit_report>(), ss->held_info.as<PairsetHeld>(), (uint32_t)held, filter, tile_count, tile_off,
+                                 d_count, room, ss->rep_pos.as<uint32_t>(), reports ? ss->rep_out.as<aln_hit_report>() : nullptr, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(&kept, d_count, 4, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        if (kept > held) { g_err = "the selection kept more entries than are held"; return ALN_ERR_DEVICE; }
+        wrote = std::min<uint64_t>(kept, room);
+        // (the kept land in buffers of the call's own first: an error on the way leaves the caller's arrays as they were)
+        pos.resize(wrote);
+        if (reports) rep.resize(wrote);
+        if (wrote) {
+            HIPCHK(hipMemcpyAsync(pos.data(), ss->rep_pos.p, 4ull * wrote, hipMemcpyDeviceToHost, q));
+            if (reports) HIPCHK(hipMemcpyAsync(rep.data(), ss->rep_out.p, sizeof(aln_hit_report) * wrote, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipStreamSynchronize(q));
+        }
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    if (wrote) {
+        memcpy(positions, pos.data(), 4ull * wrote);
+        if (reports) memcpy(reports, rep.data(), sizeof(aln_hit_report) * wrote);
+    }
+    *count = kept;
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    // (the 4-byte count aside: what comes down per kept hit)
+    ss->bytes[0] = 4ull * bits.size(); ss->bytes[1] = wrote * (4ull + (reports ? sizeof(aln_hit_report) : 0));
+    return ALN_OK;
+}
+
+// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
+extern "C" int aln_seqset_held_report(aln_seqset *ss, const aln_params *params, uint32_t flags, const uint32_t *keep, uint64_t n_keep,
+                                      aln_hit_report *reports)
+{
+    try {
+        return seqset_held_report(ss, params, flags, keep, n_keep, reports);
+    } catch (const std::bad_alloc &) {
+        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
+}
+
+extern "C" int aln_seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter,
+                                      uint32_t *positions, aln_hit_report *reports, uint64_t capacity, uint64_t *count)
+{
+    try {
+        return seqset_held_filter(ss, params, flags, filter, positions, reports, capacity, count);
     } catch (const std::bad_alloc &) {
         if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
         g_err = "out of host memory";

@@ -71,6 +71,14 @@ void aln_seqset_launch_select(const aln_pair_result *res, uint64_t n, uint64_t k
 void aln_seqset_launch_held(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
                             const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb, hipStream_t s);
 
+// ---- aln_report.hip: reports of held hits
+void aln_report_launch(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list, uint32_t n_list,
+                       uint32_t n_held, const uint32_t *bits, uint32_t rows, uint32_t cols, uint32_t blank, uint32_t flags, aln_hit_report *rep,
+                       hipStream_t s);
+void aln_report_launch_filter(const aln_hit_report *rep, const PairsetHeld *held, uint32_t n_held, const aln_hit_filter *filter,
+                              uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint64_t cap, uint32_t *positions,
+                              aln_hit_report *out, hipStream_t s);
+
 // ---- aln_best.hip: the k best targets per query
 int aln_warm_best(void);
 void aln_best_launch_chunk(const double *f, const int32_t *status, uint64_t n, uint64_t k0, const aln_seqset_block *block, double f_min,

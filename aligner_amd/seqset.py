@@ -22,6 +22,29 @@ SIGNIF_RECORD_DTYPE = np.dtype([("sum", "<f8"), ("sum_sq", "<f8"), ("f_max", "<f
                                 ("first_bad", "<u4"), ("reserved", "<u8")])
 SIGNIF_DTYPE = np.dtype([("mean", "<f8"), ("sd", "<f8"), ("z", "<f8"), ("p_emp", "<f8"), ("n_ok", "<u4"), ("status", "<i4")])
 assert SIGNIF_RECORD_DTYPE.itemsize == 48
+# aln_hit_report (include/aligner_hip.h) and what report_fractions makes of it
+REPORT_DTYPE = np.dtype([("columns", "<u4"), ("identical", "<u4"), ("positive", "<u4"), ("mismatch", "<u4"), ("q_gap", "<u4"), ("t_gap", "<u4"),
+                         ("q_gap_open", "<u4"), ("t_gap_open", "<u4"), ("status", "<i4"), ("reserved", "<u4")])
+FRACTIONS_DTYPE = np.dtype([("identity", "<f8"), ("positives", "<f8"), ("q_cover", "<f8"), ("t_cover", "<f8"), ("gap_opens", "<u4"),
+                            ("gaps", "<u4")])
+assert REPORT_DTYPE.itemsize == 40
+
+
+def report_fractions(reports, q_len, t_len):
+    """What a user asks of a hit, out of its report and the lengths N, M of its query and target sequences: identity = identical /
+    columns, positives = (identical + positive) / columns, q_cover = (columns - q_gap) / N, t_cover = (columns - t_gap) / M,
+    gap_opens = q_gap_open + t_gap_open, gaps = q_gap + t_gap.  0 / 0 is NaN; nothing is raised or warned about."""
+    reports = np.asarray(reports, dtype=REPORT_DTYPE)
+    out = np.zeros(len(reports), dtype=FRACTIONS_DTYPE)
+    with np.errstate(all="ignore"):
+        cols = reports["columns"].astype(np.float64)
+        out["identity"] = reports["identical"].astype(np.float64) / cols
+        out["positives"] = (reports["identical"].astype(np.float64) + reports["positive"].astype(np.float64)) / cols
+        out["q_cover"] = (cols - reports["q_gap"].astype(np.float64)) / np.asarray(q_len, dtype=np.float64)
+        out["t_cover"] = (cols - reports["t_gap"].astype(np.float64)) / np.asarray(t_len, dtype=np.float64)
+    out["gap_opens"] = reports["q_gap_open"] + reports["t_gap_open"]
+    out["gaps"] = reports["q_gap"] + reports["t_gap"]
+    return out
 
 
 def significance_from_records(records, f_hit):
@@ -265,6 +288,48 @@ class HeldHits:
                 ln = np.concatenate([[tl], lengths[i].astype(np.int64)])
                 out[a + i] = float(statistics.calculate_distribution_params(ql, ln, sc).get_p_value(ql, tl, fh))
         return out
+
+    def _report_params(self, matrix, blank):
+        # (only matrix / rows / cols / row_stride / blank_code are read)
+        return runtime.make_params(self.semantics, 0.0, 0.0, matrix, outputs=_ffi.OUT_SCORE, blank=blank)
+
+    def report(self, matrix, keep=None, skip_seed=True, blank=98):
+        """aln_seqset_held_report: the classed columns of the listed positions of the held list (default: all) as a REPORT_DTYPE
+        array -- columns, identical, positive, mismatch, q_gap, t_gap, q_gap_open, t_gap_open, status -- counted on the device in the
+        classes of Alignment.get_alignment(matrix).  skip_seed leaves out the last column, the traceback's seed pair, which repeats
+        residues the walk emits itself; without it the counts are those of the reference's own midline."""
+        o = self.owner
+        w = self._keep(keep)
+        p, _held = self._report_params(matrix, blank)
+        rep = np.zeros(len(w), dtype=REPORT_DTYPE)
+        st = o.lib.aln_seqset_held_report(o.handle, C.byref(p), _ffi.REPORT_SKIP_SEED if skip_seed else 0, w.ctypes.data, len(w), rep.ctypes.data)
+        runtime.raise_for_status(st, "aln_seqset_held_report")
+        return rep
+
+    def filter(self, matrix, min_identity=0.0, min_q_cover=0.0, min_t_cover=0.0, min_columns=0, skip_seed=True, with_reports=False, blank=98,
+               capacity=None):
+        """aln_seqset_held_filter: the positions of the held hits with identical >= min_identity * columns, columns - q_gap >=
+        min_q_cover * N, columns - t_gap >= min_t_cover * M and columns >= min_columns, ascending, selected on the device; only they
+        come down.  with_reports: (positions, their REPORT_DTYPE records).  capacity (default: every held hit) bounds what is
+        written; .last_filter_count is the number kept in all."""
+        o = self.owner
+        p, _held = self._report_params(matrix, blank)
+        cap = self.count if capacity is None else int(capacity)
+        flt = _ffi.HitFilter(float(min_identity), float(min_q_cover), float(min_t_cover), int(min_columns), 0)
+        pos = np.zeros(cap, dtype=np.uint32)
+        rep = np.zeros(cap, dtype=REPORT_DTYPE) if with_reports else None
+        count = C.c_uint64(0)
+        st = o.lib.aln_seqset_held_filter(o.handle, C.byref(p), _ffi.REPORT_SKIP_SEED if skip_seed else 0, C.byref(flt), pos.ctypes.data,
+                                          rep.ctypes.data if with_reports else None, cap, C.byref(count))
+        runtime.raise_for_status(st, "aln_seqset_held_filter")
+        self.last_filter_count = int(count.value)
+        n = min(self.last_filter_count, cap)
+        return (pos[:n], rep[:n]) if with_reports else pos[:n]
+
+    def fractions(self, reports, keep=None):
+        """report_fractions of records that belong to the listed positions (default: all)."""
+        w = self._keep(keep)
+        return report_fractions(reports, self.owner.len[self.q[w]], self.owner.len[self.t[w]])
 
     def alignments(self, keep=None):
         """Alignment objects of the listed positions (default: all), coordinates as SimpleLocalAligner / SimpleGlobalAligner give them."""

@@ -416,6 +416,61 @@ typedef struct aln_signif_record {
 int aln_seqset_held_significance(aln_seqset *set, const aln_params *params, const aln_shuffle_spec *spec, const uint32_t *keep,
                                  uint64_t n_keep, aln_signif_record *records, double *f, uint32_t *lengths);
 
+/* ---- reports of held hits (additions of the same ABI version): how identical, how covering and how gapped is a held hit?  The
+ * columns of a held entry's two aligned strings (x = query[j], y = target[j], j = 0 .. aln_len - 1, as held_strings returns them) are
+ * classed and counted on the device (aln_report.hip), in the classes of the reference's midline (Alignment::get_alignment,
+ * aligner-core/src/alignment.rs:25-42); aligner_amd/csrc/aln_report_rules.h is the rule as code.
+ * columns: all aln_len of them, or with ALN_REPORT_SKIP_SEED aln_len - 1 (0 when aln_len is 0): the LAST column is the end cell's
+ * residue pair, with which the reference's traceback seeds both strings before the walk (simple/mod.rs:102-105, 213-216) and which
+ * the walk emits again itself.  Without the flag the counts are those of the reference's own midline and frequency matrix, with it
+ * the alignment's.
+ * class of a column, exactly one: identical (x == y, x != blank); positive (both non-blank, x != y, S[y][x] >= 0.0 -- a plain IEEE
+ * compare: 0.0 and -0.0 are positive, a NaN is not; a code beyond the matrix is not); mismatch (both non-blank, x != y, not
+ * positive); q_gap (x == blank, y != blank); t_gap (y == blank, x != blank); both blank: counted in `columns` only.
+ * q_gap_open: a q_gap column j with j == 0 or column j - 1 not q_gap; t_gap_open alike.
+ * A held entry whose summary status is not ALN_OK: all counts 0 and that status.
+ * params: matrix / rows / cols / row_stride / blank_code only (the scheme of the classes; passing the held pass's is the caller's
+ * business).  The one bit the rule reads of an entry goes up as a table of rows * cols bits; rows * cols > 8192: ALN_ERR_UNSUPPORTED.
+ * held_report: the listed positions of the held list (of hits or best; any order, a position may be listed twice).  Up: 4 bytes per
+ * listed hit and the bit table.  Down: 40 bytes per listed hit.
+ * held_filter: ALL held hits are reported into a buffer of the set (40 bytes each, on the device) and the entries that pass the
+ * filter are compacted in ascending held order (the ordered prefix sum of the selections: no atomic appends).  An entry is kept iff
+ * status == ALN_OK, columns >= min_columns, (double)identical >= min_identity * (double)columns, (double)(columns - q_gap) >=
+ * min_q_cover * (double)N and (double)(columns - t_gap) >= min_t_cover * (double)M, N and M the lengths of its query and target
+ * sequences; one multiplication and one compare each, rounded on its own: a NaN threshold keeps nothing.  positions (and reports,
+ * optional) receive the first `capacity` kept entries; *count is the number kept in all, also beyond capacity.  Only the kept come
+ * down: 4 bytes per written position, 40 more with its record.
+ * The held summaries and strings are not touched: held_list, held_strings and held_significance answer afterwards as before.
+ * ALN_ERR_INVALID_ARGUMENT, nothing written, held state intact: no held state, a keep[k] >= count, a null pointer with a non-zero
+ * length, a null params / matrix / filter / count, rows * cols == 0, a flag bit other than ALN_REPORT_SKIP_SEED, filter->reserved
+ * != 0.  ALN_PWM_LOCAL: ALN_ERR_UNSUPPORTED.
+ * stats afterwards: ms[2] the kernels of this call, ms[3] its wall time, bytes[] as above; ms[0] and ms[1] stay the held pass's. ---- */
+#define ALN_REPORT_SKIP_SEED 1u
+typedef struct aln_hit_report {
+    uint32_t columns;      /* columns counted                                   */
+    uint32_t identical;
+    uint32_t positive;
+    uint32_t mismatch;
+    uint32_t q_gap;        /* blank in the aligned query                        */
+    uint32_t t_gap;        /* blank in the aligned target                       */
+    uint32_t q_gap_open;   /* runs of q_gap columns                             */
+    uint32_t t_gap_open;
+    int32_t  status;       /* the held entry's; not ALN_OK: every count is 0    */
+    uint32_t reserved;     /* 0                                                 */
+} aln_hit_report;          /* 40 bytes */
+typedef struct aln_hit_filter {
+    double   min_identity; /* identical / columns                               */
+    double   min_q_cover;  /* (columns - q_gap) / N                             */
+    double   min_t_cover;  /* (columns - t_gap) / M                             */
+    uint32_t min_columns;
+    uint32_t reserved;     /* 0 */
+} aln_hit_filter;          /* 32 bytes */
+
+int aln_seqset_held_report(aln_seqset *set, const aln_params *params, uint32_t flags, const uint32_t *keep, uint64_t n_keep,
+                           aln_hit_report *reports);
+int aln_seqset_held_filter(aln_seqset *set, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, uint32_t *positions,
+                           aln_hit_report *reports /* optional */, uint64_t capacity, uint64_t *count);
+
 /* ---- heuristic alignment of the pairs of a sequence set (additions of the same ABI version): the request path's two halves joined --
  * every pair of a FASTA (generate_pairs), each run through the loop of HeuristicAligner (heuristic/mod.rs:36-78).
  * create_from_set: a pair set whose pair i is pair first + i of the block, in the block's numbering (sequence q the query, sequence

@@ -263,7 +263,26 @@ pub mod seqset {
         /// its target (copy s from the stream (seed, pair_base + the hit's pair index, s)); `f` / `lengths` optional, n_keep * per_pair
         pub fn aln_seqset_held_significance(set: *mut AlnSeqset, p: *const AlnParams, spec: *const AlnShuffleSpec, keep: *const u32, n_keep: u64,
                                             records: *mut AlnSignifRecord, f: *mut f64, lengths: *mut u32) -> c_int;
+        /// how identical, how covering, how gapped: the columns of the listed held hits' aligned strings, classed as the midline of
+        /// `Alignment::get_alignment` classes them and counted on the device (flags: ALN_REPORT_SKIP_SEED leaves the seed column out)
+        pub fn aln_seqset_held_report(set: *mut AlnSeqset, p: *const AlnParams, flags: u32, keep: *const u32, n_keep: u64,
+                                      reports: *mut AlnHitReport) -> c_int;
+        /// the held positions whose reports pass `filter`, ascending, selected on the device; `reports` optional; `count` is the
+        /// number kept in all, also beyond `capacity`
+        pub fn aln_seqset_held_filter(set: *mut AlnSeqset, p: *const AlnParams, flags: u32, filter: *const AlnHitFilter, positions: *mut u32,
+                                      reports: *mut AlnHitReport, capacity: u64, count: *mut u64) -> c_int;
     }
+    pub const ALN_REPORT_SKIP_SEED: u32 = 1;
+    /// `aln_hit_report`: the classed columns of one held hit (aligner_amd/csrc/aln_report_rules.h)
+    #[repr(C)]
+    #[derive(Clone, Copy, Default)]
+    pub struct AlnHitReport { pub columns: u32, pub identical: u32, pub positive: u32, pub mismatch: u32, pub q_gap: u32, pub t_gap: u32,
+                              pub q_gap_open: u32, pub t_gap_open: u32, pub status: i32, pub reserved: u32 } // 40 bytes
+    /// `aln_hit_filter`: kept iff identical >= min_identity * columns, columns - q_gap >= min_q_cover * N, columns - t_gap >=
+    /// min_t_cover * M and columns >= min_columns
+    #[repr(C)]
+    #[derive(Clone, Copy, Default)]
+    pub struct AlnHitFilter { pub min_identity: f64, pub min_q_cover: f64, pub min_t_cover: f64, pub min_columns: u32, pub reserved: u32 } // 32 bytes
     /// `aln_shuffle_spec`: the streams of the shuffled copies (aligner_amd/csrc/aln_shuffle_rules.h)
     #[repr(C)]
     #[derive(Clone, Copy, Default)]
