@@ -149,6 +149,7 @@ def load():
     lib.aln_last_error.restype = C.c_char_p
     lib.aln_last_error.argtypes = []
     lib.aln_abi_version.restype = i
+    lib.aln_abi_version.argtypes = []
     lib.aln_device_info.restype = i
     lib.aln_device_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
     lib.aln_align_pair.restype = i

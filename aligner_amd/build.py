@@ -47,8 +47,21 @@ HARNESS_SRC = os.path.join(HERE, "..", "tests", "abi_harness.c")
 HARNESS = os.path.join(HERE, "..", "tests", "bin", "abi_harness")
 
 
+# tests/abi_families.c: the same for every other exported family (tests/test_abi_layout_cpu.py, tests/test_abi_families_gpu.py)
+FAMILIES_SRC = os.path.join(HERE, "..", "tests", "abi_families.c")
+FAMILIES = os.path.join(HERE, "..", "tests", "bin", "abi_families")
+
+
 def build_harness(force=False):
-    src, out = os.path.abspath(HARNESS_SRC), os.path.abspath(HARNESS)
+    return _build_c_program(HARNESS_SRC, HARNESS, force)
+
+
+def build_families_harness(force=False):
+    return _build_c_program(FAMILIES_SRC, FAMILIES, force)
+
+
+def _build_c_program(src, out, force=False):
+    src, out = os.path.abspath(src), os.path.abspath(out)
     hdr = os.path.join(HERE, "..", "include", "aligner_hip.h")
     if force or not os.path.exists(out) or max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB)) > os.path.getmtime(out):
         os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -62,6 +75,7 @@ def build_harness(force=False):
 def build(force=False, remarks=False):
     lib = _build_lib(force, remarks)
     build_harness(force)
+    build_families_harness(force)
     return lib
 
 

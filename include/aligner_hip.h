@@ -175,7 +175,9 @@ void aln_batch_enable_timing(aln_batch *b, int on);
  * z >= z_min in ascending window order; those are filled again with directions and walked on the same stream.  Returns the true
  * number of hits in *count and the first min(count, cap) of them: window indices, summaries and (tb_buf optional) strings, hit h's
  * at h * aln_scan_string_stride(...) in the ALN_PWM_LOCAL layout of aln_align_batch (u32 column numbers, then the residues at
- * 4 * (cols + that window's length + 2)).  count > cap: ALN_ERR_CAPACITY.  params->outputs is ignored.
+ * 4 * (cols + that window's length + 2)).  The caller's buffers hold cap entries: 4 * cap bytes of indices, 48 * cap of results,
+ * cap * aln_scan_string_stride(...) of tb_buf; nothing beyond entry min(count, cap) - 1 is written.  count > cap: ALN_ERR_CAPACITY.
+ * params->outputs is ignored.
  * hits: a HELD select pass.  Fill, z test and compaction exactly as select; the count is read where the pass waits anyway, the
  * hit buffers are sized for it (no capacity, no second fill; ALN_ERR_OOM and nothing held if that memory cannot be had) and ALL
  * hits are filled again with directions and walked.  Summaries, strings and the hit list stay on the device; only *count comes
