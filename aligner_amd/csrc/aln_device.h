@@ -60,8 +60,8 @@ struct ShufflePair {
     uint64_t out_off;        // copy 0 in the call's shuffled region; copy s at out_off + s * t_len (L - trim bytes of it written)
     uint32_t q_len, t_len;
 };
-// one held entry of a pair set (aln_pairset_*, aln_pairset.hip): where its strings lie in the held string buffer
-struct PairsetHeld {
+// one entry of a held store (a pair set's last run, a sequence set's held hits): where its strings lie in the held string buffer
+struct HeldEntry {
     uint64_t tb_off;         // aligned query here, aligned target N + M + 2 bytes later
     uint32_t N, M;
 };
@@ -70,7 +70,7 @@ struct PairsetHeld {
 // index par[k] (k without a table) and its result goes to dst[dst_index[k]] (dst[k] without a table) unless it has no root.
 struct PairsetTransformArgs {
     const double *shared, *own;
-    const PairsetHeld *held; const aln_pair_result *res; const uint8_t *tb; const uint32_t *entry;
+    const HeldEntry *held; const aln_pair_result *res; const uint8_t *tb; const uint32_t *entry;
     const uint32_t *par, *dst_index;
     const double *freq, *kd, *r2;
     double *dst;

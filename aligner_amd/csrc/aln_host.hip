@@ -95,6 +95,25 @@ static int fail(hipError_t e, const char *what)
         if (e_ != hipSuccess) return fail(e_, #call);        \
     } while (0)
 
+static double wall_ms(const std::chrono::steady_clock::time_point &t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// what the last call on a resident handle (scan, pair set, sequence set) took and moved: aln_*_stats
+struct CallStats {
+    double ms[4] = {0, 0, 0, 0};      // three kernel times, as the family's header comment names them, and the call's wall time
+    uint64_t bytes[2] = {0, 0};       // host -> device, device -> host
+};
+static void stats_reset(CallStats &s) { s = CallStats(); }
+static int stats_get(const CallStats *s, double *ms, uint64_t *bytes)
+{
+    if (!s) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ms) for (int i = 0; i < 4; ++i) ms[i] = s->ms[i];
+    if (bytes) { bytes[0] = s->bytes[0]; bytes[1] = s->bytes[1]; }
+    return ALN_OK;
+}
+
 // ---------------------------------------------------------------- grow-only buffers
 struct DevBuf {
     void *p = nullptr;
@@ -880,6 +899,7 @@ static int upload_matrix(Slot &s, const Call &c, uint8_t *m, hipStream_t st)
 {
     size_t o = 0;
     const size_t nm = c.md.size();
+    if (nm == 0) return ALN_OK;        // per-pair matrices (aln_pairset_run): the call has none of its own
     if (c.is_int) {
         int32_t *mi = reinterpret_cast<int32_t *>(m + o);
         for (size_t i = 0; i < nm; ++i) mi[i] = (int32_t)c.md[i];
@@ -1745,15 +1765,14 @@ struct ScanPlan {
 static std::mutex g_scan_plans_mu;
 static std::vector<std::shared_ptr<ScanPlan>> g_scan_plans;
 
-struct aln_scan {
+// (ms of the last pass: fill, selection, hit re-fill + walk (kernel time), download (wall))
+struct aln_scan : CallStats {
     DevCtx *ctx = nullptr;            // one device: the context's first (as a staged batch)
     Slot *slot = nullptr;             // private slot; slot->seqs holds the forward strand at 0 and, once needed, the reversed one at len
     uint64_t len = 0;
     bool rev_ready = false;
     DevBuf fbuf, tiles, idx, misc;    // f of every window; tile counts + offsets; hit indices; [0] hit count, [1] failed-status flag
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    double ms[4] = {0, 0, 0, 0};      // last pass: fill, selection, hit re-fill + walk (kernel time), download (wall)
-    uint64_t bytes[2] = {0, 0};       // last pass: host -> device, device -> host
     // held hits (aln_scan_hits): hit h's window in idx[h], its summary in slot->results[h], its descriptor in slot->descs[h], its
     // strings in slot->tb at h * held_stride -- until the next pass on this scan
     bool held = false;
@@ -1937,8 +1956,7 @@ extern "C" int aln_scan_score(aln_scan *sc, const aln_params *params, const aln_
     const uint64_t n = scan_windows(sc->len, g);
     if (n && !f) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     sc->held = false;
-    for (double &v : sc->ms) v = 0;
-    sc->bytes[0] = sc->bytes[1] = 0;
+    stats_reset(*sc);
     if (n == 0) return ALN_OK;
     Slot &s = *sc->slot;
     std::shared_ptr<ScanPlan> pl;
@@ -1956,7 +1974,7 @@ extern "C" int aln_scan_score(aln_scan *sc, const aln_params *params, const aln_
     HIPCHK(hipMemcpyAsync(misc, sc->misc.p, 8, hipMemcpyDeviceToHost, s.stream));
     HIPCHK(hipStreamSynchronize(s.stream));
     sc->ms[0] = ev_ms(sc->ev[0], sc->ev[1]);
-    sc->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    sc->ms[3] = wall_ms(t0);
     sc->bytes[0] = c.md.size() * (c.is_int ? 4 : 8) + (c.pwm && c.fast ? 4ull * c.cols : 0);
     sc->bytes[1] = 8 * n + 8;
     if (misc[1] != ALN_OK) { g_err = "a window failed"; return misc[1]; }
@@ -1977,8 +1995,7 @@ extern "C" int aln_scan_select(aln_scan *sc, const aln_params *params, const aln
     if ((st = call_init(ct, &pt, &q1, &t1, 1, false)) != ALN_OK) return st;
     *count = 0;
     sc->held = false;
-    for (double &v : sc->ms) v = 0;
-    sc->bytes[0] = sc->bytes[1] = 0;
+    stats_reset(*sc);
     const uint64_t n = scan_windows(sc->len, g);
     if (n == 0) return ALN_OK;
     Slot &s = *sc->slot;
@@ -2022,7 +2039,7 @@ extern "C" int aln_scan_select(aln_scan *sc, const aln_params *params, const aln
     sc->ms[0] = ev_ms(sc->ev[0], sc->ev[1]);
     sc->ms[1] = ev_ms(sc->ev[1], sc->ev[2]);
     sc->ms[2] = ev_ms(sc->ev[2], sc->ev[3]);
-    sc->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    sc->ms[3] = wall_ms(t0);
     sc->bytes[0] = c.md.size() * (c.is_int ? 4 : 8) + (c.pwm && c.fast ? 4ull * c.cols : 0);
     sc->bytes[1] = 8 + got * (4 + sizeof(aln_pair_result) + (tb_buf ? ph->tb_stride : 0));
     if (hm[1] != ALN_OK) { g_err = "a window failed"; return (int)hm[1]; }
@@ -2045,8 +2062,7 @@ extern "C" int aln_scan_hits(aln_scan *sc, const aln_params *params, const aln_s
     if ((st = call_init(ct, &pt, &q1, &t1, 1, false)) != ALN_OK) return st;
     *count = 0;
     sc->held = false;
-    for (double &v : sc->ms) v = 0;
-    sc->bytes[0] = sc->bytes[1] = 0;
+    stats_reset(*sc);
     sc->held_count = 0;
     sc->held_cols = c.cols;
     sc->held_blank = ct.p.blank_code;
@@ -2118,14 +2134,13 @@ static int held_check(aln_scan *sc, const void *keep, uint64_t n_keep)
     for (uint64_t i = 0; i < n_keep; ++i)
         if (k[i] >= sc->held_count) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
     HIPCHK(hipSetDevice(sc->ctx->device));
-    for (double &v : sc->ms) v = 0;
-    sc->bytes[0] = sc->bytes[1] = 0;
+    stats_reset(*sc);
     return ALN_OK;
 }
 
 static void held_done(aln_scan *sc, const std::chrono::steady_clock::time_point &t0, uint64_t up, uint64_t down)
 {
-    sc->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    sc->ms[3] = wall_ms(t0);
     sc->bytes[0] = up; sc->bytes[1] = down;
 }
 
@@ -2209,10 +2224,7 @@ extern "C" uint64_t aln_scan_string_stride(const aln_scan *sc, uint32_t cols, co
 
 extern "C" int aln_scan_stats(const aln_scan *sc, double *ms, uint64_t *bytes)
 {
-    if (!sc) return ALN_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < 4 && ms; ++i) ms[i] = sc->ms[i];
-    for (int i = 0; i < 2 && bytes; ++i) bytes[i] = sc->bytes[i];
-    return ALN_OK;
+    return stats_get(sc, ms, bytes);
 }
 
 // ---------------------------------------------------------------- shuffled copies: calculate_p_value's batch on the device
@@ -2564,6 +2576,141 @@ extern "C" int aln_shuffle_targets(aln_ctx *ctx, const aln_shuffle_spec *spec, c
     return ALN_OK;
 }
 
+// ---------------------------------------------------------------- the held store of a pair set and of a sequence set
+// What a pair set's last run and a sequence set's held pass leave on the device: entry k's summary in res[k] and its strings in tb at
+// info_h[k].tb_off (HeldEntry).  The triple (info, res, tb) is what aln_pairset_launch_freq, the transform, aln_report_launch and the
+// loop's step read.  (A scan's held hits are PairDesc entries at a uniform stride in its slot: aln_scan_held_*.)
+struct HeldStore {
+    size_t n = 0;                     // entries
+    std::vector<HeldEntry> info_h;    // host copy of the table
+    DevBuf res, tb, info;
+    DevBuf list, out_off, packed_res, packed_tb;      // a fetch: the listed entries, their packed offsets, what goes down
+};
+
+static void held_free(HeldStore &h)
+{
+    DevBuf *d[] = {&h.res, &h.tb, &h.info, &h.list, &h.out_off, &h.packed_res, &h.packed_tb};
+    for (DevBuf *b : d) dev_free(*b);
+}
+static void held_clear(HeldStore &h) { h.n = 0; h.info_h.clear(); }
+
+// kernel times and uploaded bytes of a re-fill, added to: each family reports them its own way (a pair set fill and traceback, a
+// sequence set both as one interval, fill start to traceback end: not their sum, which counts the event between them twice)
+struct RefillStats { double fill_ms = 0, tb_ms = 0, both_ms = 0; uint64_t bytes_up = 0; };
+
+// The listed pairs as a batch of their own over resident residues (pair k's at qo[k] / to[k] of s.seqs, whose seq_span bytes are
+// there already and must not grow): the fill with directions and the traceback, chunk after chunk on the one slot, summaries and
+// strings kept in `h`.  The stream is idle on entry and on every way out; on a failure nothing is held.
+static int held_refill(HeldStore &h, DevCtx *ctx, Slot &s, const Call &c, const std::vector<uint64_t> &qo, const std::vector<uint64_t> &ql,
+                       const std::vector<uint64_t> &to, const std::vector<uint64_t> &tl, uint64_t seq_span, hipEvent_t *ev, RefillStats &acc)
+{
+    hipStream_t q = s.stream;
+    const size_t pairs = ql.size();
+    h.n = 0;
+    h.info_h.assign(pairs, HeldEntry{});
+    uint64_t tb_total = 0;
+    for (size_t k = 0; k < pairs; ++k) {
+        h.info_h[k].N = (uint32_t)ql[k]; h.info_h[k].M = (uint32_t)tl[k]; h.info_h[k].tb_off = tb_total;
+        tb_total += 2ull * (ql[k] + tl[k] + 2);      // the chunks' own layout (chunk_plan), chunk after chunk
+    }
+    std::vector<std::pair<size_t, size_t>> ranges;
+    make_chunks(c, ql.data(), tl.data(), pairs, 1, ranges);
+    Chunk k;
+    bool timed = false;
+    auto collect = [&]() {
+        if (timed) { acc.fill_ms += ev_ms(ev[0], ev[1]); acc.tb_ms += ev_ms(ev[1], ev[2]); acc.both_ms += ev_ms(ev[0], ev[2]); timed = false; }
+    };
+    int st = ALN_OK;
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        // the store, sized for exactly this count; nothing is held if the memory cannot be had
+        if ((st = dev_ensure(h.res, sizeof(aln_pair_result) * pairs, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(h.tb, tb_total, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(h.info, sizeof(HeldEntry) * pairs, false)) != ALN_OK) return st;
+        HIPCHK(hipMemcpyAsync(h.info.p, h.info_h.data(), sizeof(HeldEntry) * pairs, hipMemcpyHostToDevice, q));
+        acc.bytes_up += sizeof(HeldEntry) * pairs;
+        // the plan of chunk j + 1 is made while chunk j runs; its tables go through the slot's pinned staging, so they wait for chunk j
+        for (size_t j = 0; j < ranges.size(); ++j) {
+            const size_t first = ranges[j].first, n = ranges[j].second;
+            k.reset();
+            if ((st = chunk_plan(ctx, c, qo.data(), ql.data(), to.data(), tl.data(), first, n, ranges.size() == 1, k, ranges.size() > 4)) != ALN_OK) return st;
+            for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[first + i]; k.descs[i].t_off = to[first + i]; }      // resident residues
+            k.seq_direct = true; k.seq_lo = 0; k.seq_span = seq_span;
+            HIPCHK(hipStreamSynchronize(q));
+            collect();
+            if ((st = slot_ensure(s, c, k)) != ALN_OK) return st;
+            if ((st = slot_upload(s, c, k, nullptr, qo.data(), ql.data(), to.data(), tl.data(), q, false, true)) != ALN_OK) return st;
+            // (4 bytes per pair for the queue, as reported since the first resident run: the queue uploaded leaves out the pairs that
+            // are routed off the batch kernel, so fewer bytes may move)
+            acc.bytes_up += n * (sizeof(PairDesc) + 4);
+            if ((st = slot_launch(ctx, s, c, k, q, ev, nullptr)) != ALN_OK) return st;
+            timed = true;
+            HIPCHK(hipMemcpyAsync(h.res.as<aln_pair_result>() + first, s.results.p, n * sizeof(aln_pair_result), hipMemcpyDeviceToDevice, q));
+            if (k.tb_bytes) HIPCHK(hipMemcpyAsync(h.tb.as<uint8_t>() + h.info_h[first].tb_off, s.tb.p, k.tb_bytes, hipMemcpyDeviceToDevice, q));
+        }
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    collect();
+    h.n = pairs;
+    return ALN_OK;
+}
+
+// Summaries and both strings of the listed entries: packed on the device (aln_held_gather_kernel) for one download in the documented
+// cumulative layout, from which the caller's own offsets are served.  An entry's whole capacity goes to the caller in either layout:
+// zeros beyond aln_len, and zeros for a failed entry.  stats: ms[2], ms[3] and bytes of the fetch.
+static int held_fetch_strings(HeldStore &h, hipStream_t q, hipEvent_t *ev, const uint32_t *entries, size_t n, aln_pair_result *results,
+                              uint8_t *tb_buf, const uint64_t *tb_off, CallStats &stats)
+{
+    std::vector<uint64_t> off(n);
+    uint64_t total = 0;
+    for (size_t k = 0; k < n; ++k) { off[k] = total; total += 2ull * ((uint64_t)h.info_h[entries[k]].N + h.info_h[entries[k]].M + 2); }
+    const bool want = tb_buf != nullptr;
+    bool direct = want;
+    for (size_t k = 0; k < n && direct; ++k) direct = tb_off[k] >= tb_off[0] && tb_off[k] - tb_off[0] == off[k];
+    int st;
+    if ((st = dev_ensure(h.list, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(h.out_off, 8ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(h.packed_res, sizeof(aln_pair_result) * n, false)) != ALN_OK) return st;
+    if (want && (st = dev_ensure(h.packed_tb, total, false)) != ALN_OK) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    // (the summaries land in a buffer of the call's own first: an error on the way leaves the caller's array as it was)
+    std::vector<aln_pair_result> res(n);
+    std::vector<uint8_t> bounce;
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        HIPCHK(hipMemcpyAsync(h.list.p, entries, 4ull * n, hipMemcpyHostToDevice, q));
+        HIPCHK(hipMemcpyAsync(h.out_off.p, off.data(), 8ull * n, hipMemcpyHostToDevice, q));
+        HIPCHK(hipEventRecord(ev[0], q));
+        // (the kernel writes aln_len bytes per string: whatever else the packed span holds goes to the caller as zeros, not as what
+        // an earlier fetch left there)
+        if (want) HIPCHK(hipMemsetAsync(h.packed_tb.p, 0, total, q));
+        aln_held_launch_gather(h.info.as<HeldEntry>(), h.res.as<aln_pair_result>(), h.tb.as<uint8_t>(), h.list.as<uint32_t>(), h.out_off.as<uint64_t>(),
+                               (uint32_t)n, (uint32_t)h.n, h.packed_res.as<aln_pair_result>(), want ? h.packed_tb.as<uint8_t>() : nullptr, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev[1], q));
+        HIPCHK(hipMemcpyAsync(res.data(), h.packed_res.p, sizeof(aln_pair_result) * n, hipMemcpyDeviceToHost, q));
+        if (want) {
+            if (direct) HIPCHK(hipMemcpyAsync(tb_buf + tb_off[0], h.packed_tb.p, total, hipMemcpyDeviceToHost, q));
+            else { bounce.resize(total); HIPCHK(hipMemcpyAsync(bounce.data(), h.packed_tb.p, total, hipMemcpyDeviceToHost, q)); }
+        }
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    memcpy(results, res.data(), sizeof(aln_pair_result) * n);
+    if (want && !direct)                             // an entry's whole capacity, as the direct copy
+        for (size_t k = 0; k < n; ++k) {
+            const uint64_t cap = (uint64_t)h.info_h[entries[k]].N + h.info_h[entries[k]].M + 2;
+            memcpy(tb_buf + tb_off[k], bounce.data() + off[k], 2 * cap);
+        }
+    stats.ms[2] = ev_ms(ev[0], ev[1]);
+    stats.ms[3] = wall_ms(t0);
+    stats.bytes[0] = 12ull * n; stats.bytes[1] = sizeof(aln_pair_result) * n + (want ? total : 0);
+    return ALN_OK;
+}
+
 // ---------------------------------------------------------------- resident pair set (aln_pairset_*, include/aligner_hip.h)
 // The loop of HeuristicAligner (heuristic/mod.rs:36-78) for many pairs in lock step: the residues stay in HBM, every run aligns the
 // listed pairs under a matrix of their own (aln_fill_f64_kernel<SEM, true>: the lean f64 strip, the matrix staged per wave), and the
@@ -2572,25 +2719,23 @@ extern "C" int aln_shuffle_targets(aln_ctx *ctx, const aln_shuffle_spec *spec, c
 struct aln_seqset;
 static void seqset_derived_gone(aln_seqset *ss);
 
-struct aln_pairset {
+// (ms: last run: fill kernels, traceback kernels; last fetch: its kernels; last call: wall time of its copies)
+struct aln_pairset : CallStats {
     DevCtx *ctx = nullptr;            // one device: the context's first (as a staged batch)
     Slot *slot = nullptr;             // private slot; slot->seqs holds every pair's residues, packed in pair order
     // a pair set over a block of a sequence set (aln_pairset_create_from_set): slot->seqs is the set's residue buffer, borrowed -- never
-    // grown and never freed here; residues = its size
+    // grown and never freed here
     aln_seqset *owner = nullptr;
-    uint64_t residues = 0;
+    uint64_t residues = 0;            // bytes of residues in slot->seqs
     size_t n = 0;
     std::vector<uint64_t> q_off, q_len, t_off, t_len;      // offsets into slot->seqs
     // held state of the last run: entry k = pair active[k]
     bool held = false;
-    size_t n_held = 0;
+    HeldStore held_store;
     uint32_t rows = 0, cols = 0, blank = 0;
     std::vector<int64_t> entry_of;    // pair -> held entry, -1: not in the last run
-    std::vector<PairsetHeld> info;    // host copy of the held table
-    DevBuf matrices, held_res, held_tb, held_info, list, out_off, counts, packed_res, packed_tb;
+    DevBuf matrices, counts;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a run's launches; 4, 5: transform / pick kernels
-    double ms[4] = {0, 0, 0, 0};      // last run: fill kernels, traceback kernels; last fetch: its kernels; last call: wall time of its copies
-    uint64_t bytes[2] = {0, 0};       // last call: host -> device, device -> host
     // the heuristic loop's resident state (aln_pairset_heuristics): every pair's parameters and one matrix per pair
     bool heur = false;
     uint32_t h_rows = 0, h_cols = 0;
@@ -2610,8 +2755,8 @@ extern "C" void aln_pairset_destroy(aln_pairset *ps)
     (void)hipSetDevice(ps->ctx->device);
     if (ps->slot && ps->slot->stream) (void)hipStreamSynchronize(ps->slot->stream);
     for (hipEvent_t e : ps->ev) if (e) (void)hipEventDestroy(e);
-    DevBuf *d[] = {&ps->matrices, &ps->held_res, &ps->held_tb, &ps->held_info, &ps->list, &ps->out_off, &ps->counts, &ps->packed_res, &ps->packed_tb,
-                   &ps->h_freq, &ps->h_kd, &ps->h_r2, &ps->store, &ps->shared, &ps->h_list, &ps->h_entry, &ps->h_status, &ps->picked,
+    held_free(ps->held_store);
+    DevBuf *d[] = {&ps->matrices, &ps->counts, &ps->h_freq, &ps->h_kd, &ps->h_r2, &ps->store, &ps->shared, &ps->h_list, &ps->h_entry, &ps->h_status, &ps->picked,
                    &ps->best, &ps->going[0], &ps->going[1], &ps->cls, &ps->l_tiles, &ps->l_count, &ps->cand_pair, &ps->cand_entry, &ps->fin_pair,
                    &ps->fin_cause, &ps->fin_res};
     for (DevBuf *b : d) dev_free(*b);
@@ -2640,6 +2785,7 @@ extern "C" aln_pairset *aln_pairset_create(aln_ctx *ctx, const uint8_t *seqs, co
         ps = new aln_pairset();
         ps->ctx = ctx->devs[0];
         ps->n = n_pairs;
+        ps->residues = total;
         ps->slot = new Slot();
         ps->slot->pooled = false;
         ps->q_off.resize(n_pairs); ps->t_off.resize(n_pairs);
@@ -2708,11 +2854,10 @@ static int pairset_run(aln_pairset *ps, const aln_params *params, const double *
     hipStream_t q = s.stream;
     HIPCHK(hipStreamSynchronize(q));
     ps->held = false;
-    ps->n_held = 0;
+    held_clear(ps->held_store);
     std::fill(ps->entry_of.begin(), ps->entry_of.end(), (int64_t)-1);
-    for (double &v : ps->ms) v = 0;
-    ps->bytes[0] = ps->bytes[1] = 0;
-    if (n_active == 0) { ps->held = true; ps->rows = params->rows; ps->cols = params->cols; ps->blank = params->blank_code; ps->info.clear(); return ALN_OK; }
+    stats_reset(*ps);
+    if (n_active == 0) { ps->held = true; ps->rows = params->rows; ps->cols = params->cols; ps->blank = params->blank_code; return ALN_OK; }
 
     Call c;
     c.p = *params;
@@ -2725,24 +2870,14 @@ static int pairset_run(aln_pairset *ps, const aln_params *params, const double *
     const size_t e = (size_t)c.rows * c.cols;
 
     std::vector<uint64_t> qo(n_active), ql(n_active), to(n_active), tl(n_active);
-    ps->info.assign(n_active, PairsetHeld{});
-    uint64_t tb_total = 0;
     for (size_t k = 0; k < n_active; ++k) {
         const uint32_t i = active[k];
         qo[k] = ps->q_off[i]; ql[k] = ps->q_len[i]; to[k] = ps->t_off[i]; tl[k] = ps->t_len[i];
-        ps->info[k].N = (uint32_t)ql[k]; ps->info[k].M = (uint32_t)tl[k]; ps->info[k].tb_off = tb_total;
-        tb_total += 2ull * (ql[k] + tl[k] + 2);      // the chunks' own layout (chunk_plan), chunk after chunk
     }
-    std::vector<std::pair<size_t, size_t>> ranges;
-    make_chunks(c, ql.data(), tl.data(), n_active, 1, ranges);
-
-    // every buffer of the run that does not depend on a chunk's plan
     if ((st = dev_ensure(ps->matrices, 8ull * e * n_active, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ps->held_res, sizeof(aln_pair_result) * n_active, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ps->held_tb, tb_total, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ps->held_info, sizeof(PairsetHeld) * n_active, false)) != ALN_OK) return st;
     c.pair_matrices = ps->matrices.as<double>();
     const auto t0 = std::chrono::steady_clock::now();
+    RefillStats acc;
     if (stored) {
         // the listed store entries, gathered on the device into the compact array the fill reads
         if (!dev_list) {
@@ -2754,53 +2889,23 @@ static int pairset_run(aln_pairset *ps, const aln_params *params, const double *
                                 ps->matrices.as<double>(), q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ps->ev[5], q));
-        ps->bytes[0] = dev_list ? 0 : 4ull * n_active;
+        acc.bytes_up = dev_list ? 0 : 4ull * n_active;
     } else {
         HIPCHK(hipMemcpyAsync(ps->matrices.p, matrices, 8ull * e * n_active, hipMemcpyHostToDevice, q));
-        ps->bytes[0] = 8ull * e * n_active;
+        acc.bytes_up = 8ull * e * n_active;
     }
-    HIPCHK(hipMemcpyAsync(ps->held_info.p, ps->info.data(), sizeof(PairsetHeld) * n_active, hipMemcpyHostToDevice, q));
-    ps->bytes[0] += sizeof(PairsetHeld) * n_active;
-
-    // chunk after chunk on the one slot: the plan of chunk j + 1 is made while chunk j runs; its tables go through the slot's pinned
-    // staging, so they wait for chunk j
-    Chunk k;
-    bool timed = false;
-    auto collect = [&]() {
-        if (timed) { ps->ms[0] += ev_ms(ps->ev[0], ps->ev[1]); ps->ms[1] += ev_ms(ps->ev[1], ps->ev[2]); timed = false; }
-    };
-    for (size_t j = 0; j < ranges.size(); ++j) {
-        const size_t first = ranges[j].first, n = ranges[j].second;
-        k.reset();
-        if ((st = chunk_plan(ps->ctx, c, qo.data(), ql.data(), to.data(), tl.data(), first, n, ranges.size() == 1, k, ranges.size() > 4)) != ALN_OK) break;
-        for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[first + i]; k.descs[i].t_off = to[first + i]; }      // resident residues
-        k.seq_direct = true;
-        if (ps->owner) { k.seq_lo = 0; k.seq_span = ps->residues; }      // the set's buffer: pairs share sequences, and it must not grow
+    // (the slot's own residues, or the owner's buffer, where pairs share sequences: neither may grow)
+    if ((st = held_refill(ps->held_store, ps->ctx, s, c, qo, ql, to, tl, ps->residues, ps->ev, acc)) != ALN_OK) return st;
+    ps->ms[0] = acc.fill_ms; ps->ms[1] = acc.tb_ms;
+    ps->bytes[0] = acc.bytes_up;
+    if (results) {
+        HIPCHK(hipMemcpyAsync(results, ps->held_store.res.p, sizeof(aln_pair_result) * n_active, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
-        collect();
-        if ((st = slot_ensure(s, c, k)) != ALN_OK) break;
-        uint8_t *m = s.h_meta.as<uint8_t>();
-        memcpy(m, k.descs.data(), n * sizeof(PairDesc));
-        HIPCHK(hipMemcpyAsync(s.descs.p, m, n * sizeof(PairDesc), hipMemcpyHostToDevice, q));
-        if (!k.order.empty()) {
-            memcpy(m + n * sizeof(PairDesc), k.order.data(), k.order.size() * 4);
-            HIPCHK(hipMemcpyAsync(s.order.p, m + n * sizeof(PairDesc), k.order.size() * 4, hipMemcpyHostToDevice, q));
-        }
-        ps->bytes[0] += n * (sizeof(PairDesc) + 4);
-        if ((st = slot_launch(ps->ctx, s, c, k, q, ps->ev, nullptr)) != ALN_OK) break;
-        timed = true;
-        HIPCHK(hipMemcpyAsync(ps->held_res.as<aln_pair_result>() + first, s.results.p, n * sizeof(aln_pair_result), hipMemcpyDeviceToDevice, q));
-        if (k.tb_bytes) HIPCHK(hipMemcpyAsync(ps->held_tb.as<uint8_t>() + ps->info[first].tb_off, s.tb.p, k.tb_bytes, hipMemcpyDeviceToDevice, q));
     }
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
-    if (results) HIPCHK(hipMemcpyAsync(results, ps->held_res.p, sizeof(aln_pair_result) * n_active, hipMemcpyDeviceToHost, q));
-    HIPCHK(hipStreamSynchronize(q));
-    collect();
     if (stored) ps->ms[2] = ev_ms(ps->ev[4], ps->ev[5]);
-    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->ms[3] = wall_ms(t0);
     ps->bytes[1] = results ? sizeof(aln_pair_result) * n_active : 0;
     for (size_t kk = 0; kk < n_active; ++kk) ps->entry_of[active[kk]] = (int64_t)kk;
-    ps->n_held = n_active;
     ps->rows = c.rows; ps->cols = c.cols; ps->blank = params->blank_code;
     ps->held = true;
     return ALN_OK;
@@ -2861,7 +2966,7 @@ extern "C" int aln_pairset_heuristics(aln_pairset *ps, uint32_t rows, uint32_t c
     ps->loop = false;                    // the store is new: a loop begins again with aln_pairset_loop_begin
     ps->going_h.clear();
     ps->ms[2] = 0;
-    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->ms[3] = wall_ms(t0);
     ps->bytes[0] = want[0] + want[1] + want[2]; ps->bytes[1] = 0;
     return ALN_OK;
 }
@@ -2902,13 +3007,13 @@ extern "C" int aln_pairset_reestimate(aln_pairset *ps, const double *shared_matr
     PairsetTransformArgs a{};
     a.shared = shared_matrix ? ps->shared.as<double>() : nullptr;
     a.own = nullptr;
-    a.held = ps->held_info.as<PairsetHeld>(); a.res = ps->held_res.as<aln_pair_result>(); a.tb = ps->held_tb.as<uint8_t>();
+    a.held = ps->held_store.info.as<HeldEntry>(); a.res = ps->held_store.res.as<aln_pair_result>(); a.tb = ps->held_store.tb.as<uint8_t>();
     a.entry = ps->h_entry.as<uint32_t>();
     a.par = a.dst_index = ps->h_list.as<uint32_t>();
     a.freq = ps->h_freq.as<double>(); a.kd = ps->h_kd.as<double>(); a.r2 = ps->h_r2.as<double>();
     a.dst = ps->store.as<double>();
     a.status = ps->h_status.as<int32_t>();
-    a.n_list = (uint32_t)n; a.n_held = (uint32_t)ps->n_held; a.rows = ps->h_rows; a.cols = ps->h_cols; a.blank = ps->blank;
+    a.n_list = (uint32_t)n; a.n_held = (uint32_t)ps->held_store.n; a.rows = ps->h_rows; a.cols = ps->h_cols; a.blank = ps->blank;
     HIPCHK(hipEventRecord(ps->ev[4], q));
     if (aln_pairset_launch_transform(&a, q) != 0) { g_err = "per-pair matrices hold 1 .. 1024 entries"; return ALN_ERR_INVALID_ARGUMENT; }
     HIPCHK(hipGetLastError());
@@ -2917,7 +3022,7 @@ extern "C" int aln_pairset_reestimate(aln_pairset *ps, const double *shared_matr
     HIPCHK(hipStreamSynchronize(q));
     for (size_t k = 0; k < n; ++k) if (status[k] == 0) ps->written[which[k]] = 1;
     ps->ms[2] = ev_ms(ps->ev[4], ps->ev[5]);
-    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->ms[3] = wall_ms(t0);
     ps->bytes[0] = (shared_matrix ? 4ull * n + 8ull * e : 8ull * n); ps->bytes[1] = 4ull * n;
     return ALN_OK;
 }
@@ -2946,7 +3051,7 @@ extern "C" int aln_pairset_matrices(aln_pairset *ps, const uint32_t *which, size
     HIPCHK(hipMemcpyAsync(out, ps->picked.p, 8ull * e * n, hipMemcpyDeviceToHost, q));
     HIPCHK(hipStreamSynchronize(q));
     ps->ms[2] = ev_ms(ps->ev[4], ps->ev[5]);
-    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->ms[3] = wall_ms(t0);
     ps->bytes[0] = 4ull * n; ps->bytes[1] = 8ull * e * n;
     return ALN_OK;
 }
@@ -3002,7 +3107,7 @@ extern "C" int aln_transform_matrices_device(aln_ctx *ctx, size_t n, uint32_t ro
     return st;
 }
 
-// `which` -> held entries (uploaded into ps->list); INVALID_ARGUMENT for a pair that was not in the last run
+// `which` -> held entries; INVALID_ARGUMENT for a pair that was not in the last run
 static int pairset_list(aln_pairset *ps, const uint32_t *which, size_t n, std::vector<uint32_t> &entries)
 {
     if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
@@ -3026,19 +3131,19 @@ extern "C" int aln_pairset_frequencies(aln_pairset *ps, const uint32_t *which, s
     HIPCHK(hipSetDevice(ps->ctx->device));
     hipStream_t q = ps->slot->stream;
     const uint64_t cells = (uint64_t)ps->rows * ps->cols;
-    if ((st = dev_ensure(ps->list, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ps->held_store.list, 4ull * n, false)) != ALN_OK) return st;
     if ((st = dev_ensure(ps->counts, 4ull * cells * n, false)) != ALN_OK) return st;
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemcpyAsync(ps->list.p, entries.data(), 4ull * n, hipMemcpyHostToDevice, q));
+    HIPCHK(hipMemcpyAsync(ps->held_store.list.p, entries.data(), 4ull * n, hipMemcpyHostToDevice, q));
     HIPCHK(hipEventRecord(ps->ev[0], q));
-    aln_pairset_launch_freq(ps->held_info.as<PairsetHeld>(), ps->held_res.as<aln_pair_result>(), ps->held_tb.as<uint8_t>(), ps->list.as<uint32_t>(),
-                            (uint32_t)n, (uint32_t)ps->n_held, ps->rows, ps->cols, ps->blank, ps->counts.as<uint32_t>(), q);
+    aln_pairset_launch_freq(ps->held_store.info.as<HeldEntry>(), ps->held_store.res.as<aln_pair_result>(), ps->held_store.tb.as<uint8_t>(), ps->held_store.list.as<uint32_t>(),
+                            (uint32_t)n, (uint32_t)ps->held_store.n, ps->rows, ps->cols, ps->blank, ps->counts.as<uint32_t>(), q);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ps->ev[1], q));
     HIPCHK(hipMemcpyAsync(counts, ps->counts.p, 4ull * cells * n, hipMemcpyDeviceToHost, q));
     HIPCHK(hipStreamSynchronize(q));
     ps->ms[2] = ev_ms(ps->ev[0], ps->ev[1]);
-    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->ms[3] = wall_ms(t0);
     ps->bytes[0] = 4ull * n; ps->bytes[1] = 4ull * cells * n;
     return ALN_OK;
 }
@@ -3052,54 +3157,12 @@ extern "C" int aln_pairset_strings(aln_pairset *ps, const uint32_t *which, size_
     if (n && (!results || (tb_buf && !tb_off))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if (n == 0) return ALN_OK;
     HIPCHK(hipSetDevice(ps->ctx->device));
-    hipStream_t q = ps->slot->stream;
-    // packed for the download in the documented cumulative layout; the caller's own offsets are served from it
-    std::vector<uint64_t> off(n);
-    uint64_t total = 0;
-    for (size_t k = 0; k < n; ++k) { off[k] = total; total += 2ull * ((uint64_t)ps->info[entries[k]].N + ps->info[entries[k]].M + 2); }
-    const bool want = tb_buf != nullptr;
-    bool direct = want;
-    for (size_t k = 0; k < n && direct; ++k) direct = tb_off[k] >= tb_off[0] && tb_off[k] - tb_off[0] == off[k];
-    if ((st = dev_ensure(ps->list, 4ull * n, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ps->out_off, 8ull * n, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ps->packed_res, sizeof(aln_pair_result) * n, false)) != ALN_OK) return st;
-    if (want && (st = dev_ensure(ps->packed_tb, total, false)) != ALN_OK) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemcpyAsync(ps->list.p, entries.data(), 4ull * n, hipMemcpyHostToDevice, q));
-    HIPCHK(hipMemcpyAsync(ps->out_off.p, off.data(), 8ull * n, hipMemcpyHostToDevice, q));
-    HIPCHK(hipEventRecord(ps->ev[0], q));
-    aln_pairset_launch_gather(ps->held_info.as<PairsetHeld>(), ps->held_res.as<aln_pair_result>(), ps->held_tb.as<uint8_t>(), ps->list.as<uint32_t>(),
-                              ps->out_off.as<uint64_t>(), (uint32_t)n, (uint32_t)ps->n_held, ps->packed_res.as<aln_pair_result>(),
-                              want ? ps->packed_tb.as<uint8_t>() : nullptr, q);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ps->ev[1], q));
-    HIPCHK(hipMemcpyAsync(results, ps->packed_res.p, sizeof(aln_pair_result) * n, hipMemcpyDeviceToHost, q));
-    std::vector<uint8_t> bounce;
-    if (want) {
-        if (direct) HIPCHK(hipMemcpyAsync(tb_buf + tb_off[0], ps->packed_tb.p, total, hipMemcpyDeviceToHost, q));
-        else { bounce.resize(total); HIPCHK(hipMemcpyAsync(bounce.data(), ps->packed_tb.p, total, hipMemcpyDeviceToHost, q)); }
-    }
-    HIPCHK(hipStreamSynchronize(q));
-    if (want && !direct)
-        for (size_t k = 0; k < n; ++k) {
-            if (results[k].status != ALN_OK) continue;
-            const uint64_t cap = (uint64_t)ps->info[entries[k]].N + ps->info[entries[k]].M + 2;
-            const uint64_t len = std::min<uint64_t>(results[k].aln_len, cap);
-            memcpy(tb_buf + tb_off[k], bounce.data() + off[k], len);
-            memcpy(tb_buf + tb_off[k] + cap, bounce.data() + off[k] + cap, len);
-        }
-    ps->ms[2] = ev_ms(ps->ev[0], ps->ev[1]);
-    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ps->bytes[0] = 12ull * n; ps->bytes[1] = sizeof(aln_pair_result) * n + (want ? total : 0);
-    return ALN_OK;
+    return held_fetch_strings(ps->held_store, ps->slot->stream, ps->ev, entries.data(), n, results, tb_buf, tb_off, *ps);
 }
 
 extern "C" int aln_pairset_stats(const aln_pairset *ps, double *ms, uint64_t *bytes)
 {
-    if (!ps) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (ms) for (int i = 0; i < 4; ++i) ms[i] = ps->ms[i];
-    if (bytes) { bytes[0] = ps->bytes[0]; bytes[1] = ps->bytes[1]; }
-    return ALN_OK;
+    return stats_get(ps, ms, bytes);
 }
 
 // ---------------------------------------------------------------- resident sequence set (aln_seqset_*, include/aligner_hip.h)
@@ -3116,7 +3179,7 @@ struct BestPass { uint32_t slots; uint32_t flags; double f_min; };
 
 #define ALN_SEQSET_CHUNK_PAIRS (1ull << 22)        // per chunk: the pair limit of a chunk of aln_align_batch
 
-struct aln_seqset {
+struct aln_seqset : CallStats {
     DevCtx *ctx = nullptr;            // one device: the context's first (as a staged batch)
     Slot *slot = nullptr;             // private slot; slot->seqs holds every sequence once, packed in set order
     size_t n = 0;
@@ -3127,21 +3190,18 @@ struct aln_seqset {
     // a chunk's gathered output: f | status; tile counts | offsets; the chunk's hits (pair number, f); [0] hit count, [2..3] first failure
     DevBuf fbuf, stbuf, tiles, hit_k, hit_f, misc;
     PinBuf h_out;                     // a chunk's f | status | misc on their way to the caller
-    // held hits (aln_seqset_hits): the list lives on the host (it is what the re-fill was planned from); hit h's summary in
-    // held_res[h], its strings in held_tb at info[h].tb_off -- until the next pass on this set
+    // held hits (aln_seqset_hits): the list lives on the host (it is what the re-fill was planned from); hit h is entry h of the
+    // store -- until the next pass on this set
     bool held = false;
     std::vector<uint64_t> hit_pair;
     std::vector<double> hit_score;
     std::vector<uint32_t> hit_q, hit_t;
-    std::vector<PairsetHeld> info;
-    DevBuf held_res, held_tb, held_info, list, out_off, packed_res, packed_tb;
+    HeldStore held_store;
     // aln_seqset_best: a chunk's piece lists (key | target | count per piece) and the rows' running lists (aln_best.hip)
     DevBuf cand_key, cand_t, cand_n, run_key, run_t, run_n;
     // aln_seqset_held_report / _filter: the scheme's bit table, the reports (of a list, or of all held hits), the kept positions | records
     DevBuf rep_bits, reports, rep_pos, rep_out;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a chunk's launches; 4, 5: the best selection
-    double ms[4] = {0, 0, 0, 0};
-    uint64_t bytes[2] = {0, 0};
     // pair sets made by aln_pairset_create_from_set read the residue buffer: a destroy with some of them alive releases everything
     // else, moves the buffer here and leaves the rest to the last of them
     size_t derived = 0;
@@ -3166,8 +3226,8 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     (void)hipSetDevice(ss->ctx->device);
     if (ss->slot && ss->slot->stream) (void)hipStreamSynchronize(ss->slot->stream);
     for (hipEvent_t &e : ss->ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->held_res, &ss->held_tb,
-                   &ss->held_info, &ss->list, &ss->out_off, &ss->packed_res, &ss->packed_tb, &ss->cand_key, &ss->cand_t, &ss->cand_n,
+    held_free(ss->held_store);
+    DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
                    &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
@@ -3427,9 +3487,9 @@ static int seqset_pass(aln_seqset *ss, const Call &c, const aln_seqset_block &b,
 static void seqset_begin(aln_seqset *ss)
 {
     ss->held = false;
-    ss->hit_pair.clear(); ss->hit_score.clear(); ss->hit_q.clear(); ss->hit_t.clear(); ss->info.clear();
-    for (double &v : ss->ms) v = 0;
-    ss->bytes[0] = ss->bytes[1] = 0;
+    ss->hit_pair.clear(); ss->hit_score.clear(); ss->hit_q.clear(); ss->hit_t.clear();
+    held_clear(ss->held_store);
+    stats_reset(*ss);
 }
 
 extern "C" int aln_seqset_score(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double *f, int32_t *status)
@@ -3444,73 +3504,33 @@ extern "C" int aln_seqset_score(aln_seqset *ss, const aln_params *params, const 
     const auto t0 = std::chrono::steady_clock::now();
     int bad = ALN_OK;
     st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), f, status, false, 0.0, &bad);
-    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->ms[3] = wall_ms(t0);
     if (st != ALN_OK) return st;
     if (!status && bad != ALN_OK) { g_err = "a pair failed"; return bad; }
     return ALN_OK;
 }
 
 // Holds the ascending pair list in ss->hit_pair / hit_score (what a selection left there): the re-fill with directions, the listed
-// pairs as a batch of their own over the resident residues, chunk by chunk, summaries and strings kept in held_res / held_tb.  On a
+// pairs as a batch of their own over the resident residues (held_refill), summaries and strings kept in the set's store.  On a
 // failure nothing is held (the caller clears the list).
 static int seqset_hold_list(aln_seqset *ss, const Call &ct, const aln_seqset_block *b)
 {
-    Slot &s = *ss->slot;
-    hipStream_t q = s.stream;
-    int st = ALN_OK;
     const size_t hits = ss->hit_pair.size();
     if (hits > 0xFFFFFFF0ull) { g_err = "too many hits"; return ALN_ERR_UNSUPPORTED; }
     if (!hits) return ALN_OK;
     std::vector<uint64_t> qo(hits), ql(hits), to(hits), tl(hits);
     ss->hit_q.resize(hits); ss->hit_t.resize(hits);
-    ss->info.assign(hits, PairsetHeld{});
-    uint64_t tb_total = 0;
     for (size_t h = 0; h < hits; ++h) {
         uint64_t sq, tq;
         aln_seqset_unrank(*b, ss->hit_pair[h], &sq, &tq);
         ss->hit_q[h] = (uint32_t)sq; ss->hit_t[h] = (uint32_t)tq;
         qo[h] = ss->off[sq]; ql[h] = ss->len[sq]; to[h] = ss->off[tq]; tl[h] = ss->len[tq];
-        ss->info[h].N = (uint32_t)ql[h]; ss->info[h].M = (uint32_t)tl[h]; ss->info[h].tb_off = tb_total;
-        tb_total += 2ull * (ql[h] + tl[h] + 2);      // the chunks' own layout (chunk_plan), chunk after chunk
     }
-    std::vector<std::pair<size_t, size_t>> ranges;
-    make_chunks(ct, ql.data(), tl.data(), hits, 1, ranges);
-    // the held buffers, sized for exactly this count; nothing is held if the memory cannot be had
-    st = dev_ensure(ss->held_res, sizeof(aln_pair_result) * hits, false);
-    if (st == ALN_OK) st = dev_ensure(ss->held_tb, tb_total, false);
-    if (st == ALN_OK) st = dev_ensure(ss->held_info, sizeof(PairsetHeld) * hits, false);
-    if (st != ALN_OK) return st;
-    HIPCHK(hipMemcpyAsync(ss->held_info.p, ss->info.data(), sizeof(PairsetHeld) * hits, hipMemcpyHostToDevice, q));
-    ss->bytes[0] += sizeof(PairsetHeld) * hits;
-    Chunk k;
-    bool timed = false;
-    auto collect = [&]() {
-        if (timed) { ss->ms[1] += ev_ms(ss->ev[0], ss->ev[2]); timed = false; }
-    };
-    auto refill = [&]() -> int {      // (a HIPCHK in here leaves through the exit below, which waits for the stream)
-        for (size_t j = 0; j < ranges.size(); ++j) {
-            const size_t first = ranges[j].first, n = ranges[j].second;
-            k.reset();
-            if ((st = chunk_plan(ss->ctx, ct, qo.data(), ql.data(), to.data(), tl.data(), first, n, ranges.size() == 1, k, ranges.size() > 4)) != ALN_OK) break;
-            for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[first + i]; k.descs[i].t_off = to[first + i]; }
-            k.seq_direct = true; k.seq_lo = 0; k.seq_span = ss->total;
-            HIPCHK(hipStreamSynchronize(q));             // the tables go through the slot's pinned staging
-            collect();
-            if ((st = slot_ensure(s, ct, k)) != ALN_OK) break;
-            if ((st = slot_upload(s, ct, k, nullptr, qo.data(), ql.data(), to.data(), tl.data(), q, false, true)) != ALN_OK) break;
-            ss->bytes[0] += n * (sizeof(PairDesc) + 4);
-            if ((st = slot_launch(ss->ctx, s, ct, k, q, ss->ev, nullptr)) != ALN_OK) break;
-            timed = true;
-            HIPCHK(hipMemcpyAsync(ss->held_res.as<aln_pair_result>() + first, s.results.p, n * sizeof(aln_pair_result), hipMemcpyDeviceToDevice, q));
-            if (k.tb_bytes) HIPCHK(hipMemcpyAsync(ss->held_tb.as<uint8_t>() + ss->info[first].tb_off, s.tb.p, k.tb_bytes, hipMemcpyDeviceToDevice, q));
-        }
-        return st;
-    };
-    st = refill();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
-    HIPCHK(hipStreamSynchronize(q));
-    collect();
-    return ALN_OK;
+    RefillStats acc;
+    const int st = held_refill(ss->held_store, ss->ctx, *ss->slot, ct, qo, ql, to, tl, ss->total, ss->ev, acc);
+    ss->ms[1] += acc.both_ms;
+    ss->bytes[0] += acc.bytes_up;
+    return st;
 }
 
 extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double f_min, uint64_t *count)
@@ -3528,7 +3548,7 @@ extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const a
     int bad = ALN_OK;
     if ((st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), nullptr, nullptr, true, f_min, &bad)) != ALN_OK) { seqset_begin(ss); return st; }
     if ((st = seqset_hold_list(ss, ct, b)) != ALN_OK) { seqset_begin(ss); return st; }
-    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->ms[3] = wall_ms(t0);
     ss->held = true;
     *count = ss->hit_pair.size();
     return ALN_OK;
@@ -3603,7 +3623,7 @@ extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const a
     st = finish();
     if (st == ALN_OK) st = seqset_hold_list(ss, ct, b);
     if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_begin(ss); return st; }
-    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->ms[3] = wall_ms(t0);
     ss->held = true;
     *count = total;
     return ALN_OK;
@@ -3642,49 +3662,7 @@ extern "C" int aln_seqset_held_strings(aln_seqset *ss, const uint32_t *keep, uin
         if (keep[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
     if (n == 0) return ALN_OK;
     HIPCHK(hipSetDevice(ss->ctx->device));
-    hipStream_t q = ss->slot->stream;
-    // packed for the download in the documented cumulative layout; the caller's own offsets are served from it
-    std::vector<uint64_t> off(n);
-    uint64_t total = 0;
-    for (uint64_t k = 0; k < n; ++k) { off[k] = total; total += 2ull * ((uint64_t)ss->info[keep[k]].N + ss->info[keep[k]].M + 2); }
-    const bool want = tb_buf != nullptr;
-    bool direct = want;
-    for (uint64_t k = 0; k < n && direct; ++k) direct = tb_off[k] >= tb_off[0] && tb_off[k] - tb_off[0] == off[k];
-    if ((st = dev_ensure(ss->list, 4ull * n, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ss->out_off, 8ull * n, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ss->packed_res, sizeof(aln_pair_result) * n, false)) != ALN_OK) return st;
-    if (want && (st = dev_ensure(ss->packed_tb, total, false)) != ALN_OK) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemcpyAsync(ss->list.p, keep, 4ull * n, hipMemcpyHostToDevice, q));
-    HIPCHK(hipMemcpyAsync(ss->out_off.p, off.data(), 8ull * n, hipMemcpyHostToDevice, q));
-    HIPCHK(hipEventRecord(ss->ev[0], q));
-    // (the kernel writes aln_len bytes per string: whatever else the packed span holds goes to the caller as zeros, not as what an
-    // earlier fetch left there)
-    if (want) HIPCHK(hipMemsetAsync(ss->packed_tb.p, 0, total, q));
-    aln_seqset_launch_held(ss->held_info.as<PairsetHeld>(), ss->held_res.as<aln_pair_result>(), ss->held_tb.as<uint8_t>(), ss->list.as<uint32_t>(),
-                           ss->out_off.as<uint64_t>(), (uint32_t)n, (uint32_t)held, ss->packed_res.as<aln_pair_result>(),
-                           want ? ss->packed_tb.as<uint8_t>() : nullptr, q);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ss->ev[1], q));
-    // (the summaries land in a buffer of the call's own first: an error on the way leaves the caller's arrays as they were)
-    std::vector<aln_pair_result> res(n);
-    HIPCHK(hipMemcpyAsync(res.data(), ss->packed_res.p, sizeof(aln_pair_result) * n, hipMemcpyDeviceToHost, q));
-    std::vector<uint8_t> bounce;
-    if (want) {
-        if (direct) HIPCHK(hipMemcpyAsync(tb_buf + tb_off[0], ss->packed_tb.p, total, hipMemcpyDeviceToHost, q));
-        else { bounce.resize(total); HIPCHK(hipMemcpyAsync(bounce.data(), ss->packed_tb.p, total, hipMemcpyDeviceToHost, q)); }
-    }
-    HIPCHK(hipStreamSynchronize(q));
-    memcpy(results, res.data(), sizeof(aln_pair_result) * n);
-    if (want && !direct)                             // an entry's whole capacity, as the direct copy: zeros beyond aln_len
-        for (uint64_t k = 0; k < n; ++k) {
-            const uint64_t cap = (uint64_t)ss->info[keep[k]].N + ss->info[keep[k]].M + 2;
-            memcpy(tb_buf + tb_off[k], bounce.data() + off[k], 2 * cap);
-        }
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ss->bytes[0] = 12ull * n; ss->bytes[1] = sizeof(aln_pair_result) * n + (want ? total : 0);
-    return ALN_OK;
+    return held_fetch_strings(ss->held_store, ss->slot->stream, ss->ev, keep, n, results, tb_buf, tb_off, *ss);
 }
 
 // Significance of held hits: the listed hits as the pairs of a shuffle job (shuffle_job_plan: the planning, chunking, routing and
@@ -3789,7 +3767,7 @@ static int seqset_held_significance(aln_seqset *ss, const aln_params *params, co
             for (uint32_t c = 0; c < per; ++c)
                 lengths[(uint64_t)k * per + c] = (uint32_t)t_len[k] - aln_shuffle_trim_of(spec->seed, stream[k], c, spec->max_trim);
     ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->ms[3] = wall_ms(t0);
     ss->bytes[0] = up; ss->bytes[1] = sizeof(aln_signif_record) * n + (f ? 8 * total : 0);
     return ALN_OK;
 }
@@ -3809,7 +3787,7 @@ extern "C" int aln_seqset_held_significance(aln_seqset *ss, const aln_params *pa
 }
 
 // ---- reports of held hits: the columns of the held strings classed and counted on the device (aln_report.hip, aln_report_rules.h).
-// What both calls check before anything moves, and the scheme's bit table; neither call touches held_res / held_tb / held_info.
+// What both calls check before anything moves, and the scheme's bit table; neither call writes the held store's entries.
 static int seqset_report_check(aln_seqset *ss, const aln_params *params, uint32_t flags, std::vector<uint32_t> &bits)
 {
     int st = seqset_held_check(ss);
@@ -3839,17 +3817,17 @@ static int seqset_held_report(aln_seqset *ss, const aln_params *params, uint32_t
     if (n == 0) return ALN_OK;
     HIPCHK(hipSetDevice(ss->ctx->device));
     hipStream_t q = ss->slot->stream;
-    if ((st = dev_ensure(ss->list, 4ull * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->held_store.list, 4ull * n, false)) != ALN_OK) return st;
     if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
     if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * n, false)) != ALN_OK) return st;
     const auto t0 = std::chrono::steady_clock::now();
     // (the records land in a buffer of the call's own first: an error on the way leaves the caller's array as it was)
     std::vector<aln_hit_report> rep(n);
     auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
-        HIPCHK(hipMemcpyAsync(ss->list.p, keep, 4ull * n, hipMemcpyHostToDevice, q));
+        HIPCHK(hipMemcpyAsync(ss->held_store.list.p, keep, 4ull * n, hipMemcpyHostToDevice, q));
         HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
         HIPCHK(hipEventRecord(ss->ev[0], q));
-        aln_report_launch(ss->held_info.as<PairsetHeld>(), ss->held_res.as<aln_pair_result>(), ss->held_tb.as<uint8_t>(), ss->list.as<uint32_t>(),
+        aln_report_launch(ss->held_store.info.as<HeldEntry>(), ss->held_store.res.as<aln_pair_result>(), ss->held_store.tb.as<uint8_t>(), ss->held_store.list.as<uint32_t>(),
                           (uint32_t)n, (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols, params->blank_code, flags,
                           ss->reports.as<aln_hit_report>(), q);
         HIPCHK(hipGetLastError());
@@ -3862,7 +3840,7 @@ static int seqset_held_report(aln_seqset *ss, const aln_params *params, uint32_t
     if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
     memcpy(reports, rep.data(), sizeof(aln_hit_report) * n);
     ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->ms[3] = wall_ms(t0);
     ss->bytes[0] = 4ull * n + 4ull * bits.size(); ss->bytes[1] = sizeof(aln_hit_report) * n;
     return ALN_OK;
 }
@@ -3895,11 +3873,11 @@ static int seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t
     auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
         HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
         HIPCHK(hipEventRecord(ss->ev[0], q));
-        aln_report_launch(ss->held_info.as<PairsetHeld>(), ss->held_res.as<aln_pair_result>(), ss->held_tb.as<uint8_t>(), nullptr, (uint32_t)held,
+        aln_report_launch(ss->held_store.info.as<HeldEntry>(), ss->held_store.res.as<aln_pair_result>(), ss->held_store.tb.as<uint8_t>(), nullptr, (uint32_t)held,
                           (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols, params->blank_code, flags,
                           ss->reports.as<aln_hit_report>(), q);
         HIPCHK(hipGetLastError());
-        aln_report_launch_filter(ss->reports.as<aln_hit_report>(), ss->held_info.as<PairsetHeld>(), (uint32_t)held, filter, tile_count, tile_off,
+        aln_report_launch_filter(ss->reports.as<aln_hit_report>(), ss->held_store.info.as<HeldEntry>(), (uint32_t)held, filter, tile_count, tile_off,
                                  d_count, room, ss->rep_pos.as<uint32_t>(), reports ? ss->rep_out.as<aln_hit_report>() : nullptr, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ss->ev[1], q));
@@ -3925,7 +3903,7 @@ static int seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t
     }
     *count = kept;
     ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ss->ms[3] = wall_ms(t0);
     // (the 4-byte count aside: what comes down per kept hit)
     ss->bytes[0] = 4ull * bits.size(); ss->bytes[1] = wrote * (4ull + (reports ? sizeof(aln_hit_report) : 0));
     return ALN_OK;
@@ -3958,10 +3936,7 @@ extern "C" int aln_seqset_held_filter(aln_seqset *ss, const aln_params *params, 
 
 extern "C" int aln_seqset_stats(const aln_seqset *ss, double *ms, uint64_t *bytes)
 {
-    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (ms) for (int i = 0; i < 4; ++i) ms[i] = ss->ms[i];
-    if (bytes) { bytes[0] = ss->bytes[0]; bytes[1] = ss->bytes[1]; }
-    return ALN_OK;
+    return stats_get(ss, ms, bytes);
 }
 
 // ---------------------------------------------------------------- a pair set over a block of a sequence set, and the loop's step
@@ -4060,7 +4035,7 @@ extern "C" int aln_pairset_loop_begin(aln_pairset *ps, const double *shared_matr
         ps->ms[2] = ev_ms(ps->ev[4], ps->ev[5]);
         ps->bytes[0] = 8ull * e; ps->bytes[1] = 4ull * n;
     }
-    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->ms[3] = wall_ms(t0);
     ps->loop = true;
     return ALN_OK;
 }
@@ -4099,7 +4074,7 @@ extern "C" int aln_pairset_loop_step(aln_pairset *ps, const aln_params *params, 
     const double pick_ms = ps->ms[2];
     uint32_t *cls = ps->cls.as<uint32_t>();
     uint32_t *cnt = ps->l_count.as<uint32_t>();
-    const aln_pair_result *res = ps->held_res.as<aln_pair_result>();
+    const aln_pair_result *res = ps->held_store.res.as<aln_pair_result>();
     HIPCHK(hipEventRecord(ps->ev[4], q));
     aln_loop_launch_classify(res, going, n32, ps->best.as<double>(), cls, q);
     aln_loop_launch_select(cls, n32, 0u, going, nullptr, tile_count, tile_off, cnt, ps->cand_pair.as<uint32_t>(), ps->cand_entry.as<uint32_t>(),
@@ -4111,7 +4086,7 @@ extern "C" int aln_pairset_loop_step(aln_pairset *ps, const aln_params *params, 
     if (improved > n32) { g_err = "loop: the device's count is out of range"; return ALN_ERR_DEVICE; }
     if (improved) {
         PairsetTransformArgs a{};
-        a.held = ps->held_info.as<PairsetHeld>(); a.res = res; a.tb = ps->held_tb.as<uint8_t>();
+        a.held = ps->held_store.info.as<HeldEntry>(); a.res = res; a.tb = ps->held_store.tb.as<uint8_t>();
         a.entry = ps->cand_entry.as<uint32_t>();
         a.par = a.dst_index = ps->cand_pair.as<uint32_t>();
         a.freq = ps->h_freq.as<double>(); a.kd = ps->h_kd.as<double>(); a.r2 = ps->h_r2.as<double>();
@@ -4152,7 +4127,7 @@ extern "C" int aln_pairset_loop_step(aln_pairset *ps, const aln_params *params, 
     ps->cur ^= 1;
     counts[0] = n32; counts[1] = done; counts[2] = fin - done; counts[3] = more;
     ps->ms[2] = pick_ms + ev_ms(ps->ev[4], ps->ev[5]);
-    ps->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ps->ms[3] = wall_ms(t0);
     ps->bytes[1] += 12ull + (4ull + 4ull + sizeof(aln_pair_result)) * fin;
     return ALN_OK;
 }

@@ -43,12 +43,11 @@ void aln_shuffle_launch_expand_table(PairDesc *descs, uint32_t *order, const Shu
 void aln_signif_launch_reduce(const aln_pair_result *res, const double *f_hit, uint32_t n_hits, uint32_t per_pair, aln_signif_record *rec,
                               double *f, hipStream_t s);
 
-// ---- aln_pairset.hip: the held strings of a pair set, per-pair matrices
-void aln_pairset_launch_freq(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list, uint32_t n_list,
+// ---- aln_pairset.hip: the strings of a held store (a pair set's or a sequence set's), per-pair matrices
+void aln_pairset_launch_freq(const HeldEntry *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list, uint32_t n_list,
                              uint32_t n_held, uint32_t rows, uint32_t cols, uint32_t blank, uint32_t *counts, hipStream_t s);
-void aln_pairset_launch_gather(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
-                               const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
-                               hipStream_t s);
+void aln_held_launch_gather(const HeldEntry *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
+                            const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb, hipStream_t s);
 int aln_pairset_launch_transform(const PairsetTransformArgs *a, hipStream_t s);
 void aln_pairset_launch_pick(const double *store, const uint32_t *list, uint32_t n_list, uint32_t e, double *out, hipStream_t s);
 
@@ -68,14 +67,12 @@ void aln_seqset_launch_gather(const aln_pair_result *res, double *f, int32_t *st
 uint64_t aln_seqset_tiles(uint64_t n);
 void aln_seqset_launch_select(const aln_pair_result *res, uint64_t n, uint64_t k0, double f_min, uint32_t *tile_count, uint32_t *tile_off,
                               uint32_t *count, uint64_t *hit_k, double *hit_f, hipStream_t s);
-void aln_seqset_launch_held(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
-                            const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb, hipStream_t s);
 
 // ---- aln_report.hip: reports of held hits
-void aln_report_launch(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list, uint32_t n_list,
+void aln_report_launch(const HeldEntry *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list, uint32_t n_list,
                        uint32_t n_held, const uint32_t *bits, uint32_t rows, uint32_t cols, uint32_t blank, uint32_t flags, aln_hit_report *rep,
                        hipStream_t s);
-void aln_report_launch_filter(const aln_hit_report *rep, const PairsetHeld *held, uint32_t n_held, const aln_hit_filter *filter,
+void aln_report_launch_filter(const aln_hit_report *rep, const HeldEntry *held, uint32_t n_held, const aln_hit_filter *filter,
                               uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint64_t cap, uint32_t *positions,
                               aln_hit_report *out, hipStream_t s);
 

@@ -4,7 +4,8 @@
 //   freq      the frequency matrix (alignment.rs:13-23) of every listed pair out of its held strings: one wave per pair, lane l reads
 //             columns l, l + 64, ... of both strings, counts in a u32 histogram of rows * cols bins in the wave's own LDS, and the
 //             bins go out as plain stores.  Integer counts: exact, and the same whatever the order of arrival.
-//   gather    the listed pairs' summaries and both strings (aln_len bytes each), packed for one download
+//   gather    the listed entries' summaries and both strings (aln_len bytes each) out of a held store, packed for one download: the
+//             fetch of a pair set's held run and of a sequence set's held hits alike (held_fetch_strings, aln_host.hip)
 //   transform transform_matrix for n matrices, plain C++ on the host in the order aln_transform_rules.h fixes (aln_transform_matrices), and
 //             the same on the device (aln_pairset_transform_kernel): one wave per matrix, source, base and a product scratch in the
 //             wave's own LDS, the element-wise passes strided over the lanes, every reduction through the lane form of the rules'
@@ -23,7 +24,7 @@
 #include "aln_transform_rules.h"
 
 // ---- counts[k][t * cols + q] for listed entry k = held entry list[k]
-__global__ __launch_bounds__(256) void aln_pairset_freq_kernel(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb,
+__global__ __launch_bounds__(256) void aln_pairset_freq_kernel(const HeldEntry *held, const aln_pair_result *res, const uint8_t *tb,
                                                                const uint32_t *list, uint32_t n_list, uint32_t n_held, uint32_t rows,
                                                                uint32_t cols, uint32_t blank, uint32_t *counts)
 {
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(256) void aln_pairset_freq_kernel(const PairsetHeld
     __builtin_amdgcn_wave_barrier();
     const uint32_t h = list[k];
     if (h < n_held) {                                                // checked on the host; never read beyond the held entries
-        const PairsetHeld d = held[h];
+        const HeldEntry d = held[h];
         const aln_pair_result &r = res[h];
         if (r.status == ALN_OK) {
             const uint32_t cap = d.N + d.M + 2u;
@@ -57,17 +58,18 @@ __global__ __launch_bounds__(256) void aln_pairset_freq_kernel(const PairsetHeld
     for (uint32_t i = lane; i < cells; i += 64u) out[i] = bins[i];
 }
 
-// ---- listed entry k: its summary, and both strings at out_tb + out_off[k] (query, then target cap bytes later)
-__global__ __launch_bounds__(256) void aln_pairset_gather_kernel(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb,
-                                                                 const uint32_t *list, const uint64_t *out_off, uint32_t n_held,
-                                                                 aln_pair_result *out_res, uint8_t *out_tb)
+// ---- listed entry k of a held store (a pair set's or a sequence set's): its summary, and both strings at out_tb + out_off[k] (query,
+// then target cap bytes later)
+__global__ __launch_bounds__(256) void aln_held_gather_kernel(const HeldEntry *held, const aln_pair_result *res, const uint8_t *tb,
+                                                              const uint32_t *list, const uint64_t *out_off, uint32_t n_held,
+                                                              aln_pair_result *out_res, uint8_t *out_tb)
 {
     const uint32_t k = blockIdx.x, h = list[k];
-    if (h >= n_held) return;
+    if (h >= n_held) return;                                         // checked on the host; never read beyond the held entries
     const aln_pair_result r = res[h];
     if (threadIdx.x == 0) out_res[k] = r;
     if (r.status != ALN_OK || !out_tb) return;
-    const PairsetHeld d = held[h];
+    const HeldEntry d = held[h];
     const uint32_t cap = d.N + d.M + 2u;
     const uint32_t len = r.aln_len < cap ? r.aln_len : cap;
     const uint8_t *__restrict__ src = tb + d.tb_off;
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(256) void aln_pairset_gather_kernel(const PairsetHe
     for (uint32_t j = threadIdx.x; j < len; j += blockDim.x) { dst[j] = src[j]; dst[cap + j] = src[cap + j]; }
 }
 
-extern "C" void aln_pairset_launch_freq(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
+extern "C" void aln_pairset_launch_freq(const HeldEntry *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
                                         uint32_t n_list, uint32_t n_held, uint32_t rows, uint32_t cols, uint32_t blank, uint32_t *counts,
                                         hipStream_t s)
 {
@@ -84,11 +86,11 @@ extern "C" void aln_pairset_launch_freq(const PairsetHeld *held, const aln_pair_
                                    n_list, n_held, rows, cols, blank, counts);
 }
 
-extern "C" void aln_pairset_launch_gather(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
-                                          const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
-                                          hipStream_t s)
+extern "C" void aln_held_launch_gather(const HeldEntry *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
+                                       const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
+                                       hipStream_t s)
 {
-    if (n_list) hipLaunchKernelGGL(aln_pairset_gather_kernel, dim3(n_list), dim3(256), 0, s, held, res, tb, list, out_off, n_held, out_res, out_tb);
+    if (n_list) hipLaunchKernelGGL(aln_held_gather_kernel, dim3(n_list), dim3(256), 0, s, held, res, tb, list, out_off, n_held, out_res, out_tb);
 }
 
 // ---- transform_matrix on the device: listed entry k by wave k
@@ -144,7 +146,7 @@ __global__ __launch_bounds__(256) void aln_pairset_transform_kernel(const Pairse
         pairset_wave_sync();
         const uint32_t h = a.entry[k];
         if (h < a.n_held) {                                          // checked on the host; never read beyond the held entries
-            const PairsetHeld d = a.held[h];
+            const HeldEntry d = a.held[h];
             const aln_pair_result &r = a.res[h];
             if (r.status == ALN_OK) {
                 const uint32_t cap = d.N + d.M + 2u;

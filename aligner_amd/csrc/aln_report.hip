@@ -36,7 +36,7 @@ __device__ inline aln_hit_report report_from_lane(const aln_hit_report &a, uint3
 
 // listed entry k = held hit list[k] (k itself without a list); rep[k] its record.  bits: aln_report_words(rows, cols) <=
 // ALN_REPORT_MAX_WORDS words
-__global__ __launch_bounds__(64 * ALN_REPORT_WAVES) void aln_report_kernel(const PairsetHeld *held, const aln_pair_result *res,
+__global__ __launch_bounds__(64 * ALN_REPORT_WAVES) void aln_report_kernel(const HeldEntry *held, const aln_pair_result *res,
                                                                            const uint8_t *tb, const uint32_t *list, uint32_t n_list,
                                                                            uint32_t n_held, const uint32_t *bits, uint32_t rows,
                                                                            uint32_t cols, uint32_t blank, uint32_t flags, aln_hit_report *rep)
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(64 * ALN_REPORT_WAVES) void aln_report_kernel(const
     const aln_pair_result r = res[h];
     aln_hit_report a = aln_report_empty(r.status);
     if (r.status == ALN_OK) {                         // (the same for every lane of the wave)
-        const PairsetHeld d = held[h];
+        const HeldEntry d = held[h];
         const uint32_t cap = d.N + d.M + 2u;
         const uint32_t len = r.aln_len < cap ? r.aln_len : cap;
         const uint32_t n = aln_report_columns(len, flags);
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64 * ALN_REPORT_WAVES) void aln_report_kernel(const
 // place o: its position, and its record when asked for
 struct ReportKeep {
     const aln_hit_report *rep;
-    const PairsetHeld *held;
+    const HeldEntry *held;
     aln_hit_filter filter;
     __device__ bool operator()(uint64_t k) const { return aln_report_keep(rep[k], filter, held[k].N, held[k].M); }
 };
@@ -92,7 +92,7 @@ struct ReportEmit {
     }
 };
 
-extern "C" void aln_report_launch(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
+extern "C" void aln_report_launch(const HeldEntry *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
                                   uint32_t n_list, uint32_t n_held, const uint32_t *bits, uint32_t rows, uint32_t cols, uint32_t blank,
                                   uint32_t flags, aln_hit_report *rep, hipStream_t s)
 {
@@ -101,7 +101,7 @@ extern "C" void aln_report_launch(const PairsetHeld *held, const aln_pair_result
 }
 
 // tile_count / tile_off: aln_seqset_tiles(n_held) words each; positions (and out, optional): cap entries; count[0]: the kept entries
-extern "C" void aln_report_launch_filter(const aln_hit_report *rep, const PairsetHeld *held, uint32_t n_held, const aln_hit_filter *filter,
+extern "C" void aln_report_launch_filter(const aln_hit_report *rep, const HeldEntry *held, uint32_t n_held, const aln_hit_filter *filter,
                                          uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint64_t cap, uint32_t *positions,
                                          aln_hit_report *out, hipStream_t s)
 {

@@ -8,8 +8,8 @@
 //              the first failed pair of the chunk as one word
 //   select     status == ALN_OK and f >= f_min per pair, compacted in ascending pair order by the shared two-level prefix sum
 //              (aln_select.h; a predicate and an emitter here): the same list every run, no atomic appends
-//   held       the listed held hits' summaries and both strings (aln_len bytes each), packed for one download
 //
+// (The held hits' strings are fetched by the held store's gather, aln_pairset.hip.)
 // Every store is a plain C++ store or an atomicMax of a thread (vector memory instructions).  The threshold test is a plain IEEE
 // compare: a NaN f_min (or f) fails it.
 #include <hip/hip_runtime.h>
@@ -73,25 +73,6 @@ struct SeqsetEmit {
     __device__ void operator()(uint32_t o, uint64_t k) const { if (o < n) { hit_k[o] = k0 + k; hit_f[o] = res[k].f; } }
 };
 
-// ---- held hits: listed entry k = held hit list[k]: its summary, and both strings at out_tb + out_off[k] (query, then target cap
-// bytes later)
-__global__ __launch_bounds__(256) void aln_seqset_held_kernel(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb,
-                                                              const uint32_t *list, const uint64_t *out_off, uint32_t n_held,
-                                                              aln_pair_result *out_res, uint8_t *out_tb)
-{
-    const uint32_t k = blockIdx.x, h = list[k];
-    if (h >= n_held) return;                                         // checked on the host; never read beyond the held hits
-    const aln_pair_result r = res[h];
-    if (threadIdx.x == 0) out_res[k] = r;
-    if (r.status != ALN_OK || !out_tb) return;
-    const PairsetHeld d = held[h];
-    const uint32_t cap = d.N + d.M + 2u;
-    const uint32_t len = r.aln_len < cap ? r.aln_len : cap;
-    const uint8_t *__restrict__ src = tb + d.tb_off;
-    uint8_t *__restrict__ dst = out_tb + out_off[k];
-    for (uint32_t j = threadIdx.x; j < len; j += blockDim.x) { dst[j] = src[j]; dst[cap + j] = src[cap + j]; }
-}
-
 extern "C" void aln_seqset_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t k0, const aln_seqset_block *block,
                                          const uint64_t *seq_off, const uint32_t *seq_len, hipStream_t s)
 {
@@ -111,11 +92,4 @@ extern "C" void aln_seqset_launch_select(const aln_pair_result *res, uint64_t n,
                                          uint32_t *tile_off, uint32_t *count, uint64_t *hit_k, double *hit_f, hipStream_t s)
 {
     aln_select_launch(SeqsetKeep{res, f_min}, SeqsetEmit{res, n, k0, hit_k, hit_f}, n, tile_count, tile_off, count, s);
-}
-
-extern "C" void aln_seqset_launch_held(const PairsetHeld *held, const aln_pair_result *res, const uint8_t *tb, const uint32_t *list,
-                                       const uint64_t *out_off, uint32_t n_list, uint32_t n_held, aln_pair_result *out_res, uint8_t *out_tb,
-                                       hipStream_t s)
-{
-    if (n_list) hipLaunchKernelGGL(aln_seqset_held_kernel, dim3(n_list), dim3(256), 0, s, held, res, tb, list, out_off, n_held, out_res, out_tb);
 }

@@ -260,7 +260,8 @@ int aln_shuffle_targets(aln_ctx *ctx, const aln_shuffle_spec *spec, const uint8_
  * counted on the device in unsigned integers: exact, the same in any order.  A failed pair's counts are zero.  4 * n bytes go up,
  * 4 * rows * cols * n come back.
  * strings: summaries and strings of the listed pairs in the layout of aln_align_batch (pair which[k]: aligned query at tb_off[k],
- * aligned target q_len + t_len + 2 bytes later; tb_buf optional).
+ * aligned target q_len + t_len + 2 bytes later; tb_buf optional).  Bytes of a string's capacity beyond aln_len, and both strings of a
+ * failed pair, are zero.
  * A which[k] that was not in the last run, a fetch without a run: ALN_ERR_INVALID_ARGUMENT, nothing written.
  * stats: ms[0] fill kernels and ms[1] traceback kernels of the last run, ms[2] kernels of the last fetch, ms[3] wall time of the
  * last call; bytes moved by the last call (host -> device, device -> host).
