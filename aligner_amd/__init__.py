@@ -8,6 +8,7 @@ fails loudly if the native library or the device is missing.
 """
 from .alignment import Alignment, AlignmentResult
 from .batch import BatchResult, PairBatch, StagedBatch, align_batch
+from .cluster import Clusters, cluster_edges
 from .enums import DNA, Direction, Protein
 from .errors import AlignerError, DeviceError, ErrorKind, ReferencePanic
 from .heuristic import HeuristicAligner, HeuristicPWMAligner, get_threshold, transform_matrix
@@ -21,5 +22,5 @@ __all__ = [
     "Alignment", "AlignmentResult", "BatchResult", "PairBatch", "StagedBatch", "align_batch", "DNA", "Direction",
     "Protein", "AlignerError", "DeviceError", "ErrorKind", "ReferencePanic", "SimpleAligner", "get_blosum62",
     "nucleotide_matrix", "PWMAligner", "PWMAlignment", "align_windows", "Heuristics", "SimpleGlobalAligner", "SimpleLocalAligner",
-    "HeuristicAligner", "HeuristicPWMAligner", "get_threshold", "transform_matrix", "SeqSet", "all_pairs",
+    "HeuristicAligner", "HeuristicPWMAligner", "get_threshold", "transform_matrix", "SeqSet", "all_pairs", "Clusters", "cluster_edges",
 ]

@@ -48,6 +48,11 @@ EXPORTS = [
     "aln_seqset_held_report", "aln_seqset_held_filter",
     "aln_pairset_create_from_set", "aln_pairset_loop_begin", "aln_pairset_loop_step",
 ]
+# every symbol the companion header include/aligner_hip_cluster.h declares (the same library; the main header's list is pinned)
+CLUSTER_EXPORTS = ["aln_cluster_edges", "aln_seqset_held_cluster"]
+CLUSTER_COMPONENTS, CLUSTER_GREEDY = 0, 1       # ALN_CLUSTER_COMPONENTS, ALN_CLUSTER_GREEDY
+CLUSTER_NONE = 0xFFFFFFFF                       # ALN_CLUSTER_NONE
+CLUSTER_MAX = 0xFFFFFFF0                        # nodes, edges
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
 TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
 # aln_pairset_loop_step's causes (aligner_amd/csrc/aln_loop_rules.h)
@@ -115,6 +120,20 @@ class HitFilter(C.Structure):
 
 
 assert C.sizeof(HitReport) == 40 and C.sizeof(HitFilter) == 32
+
+
+class ClusterRecord(C.Structure):
+    """aln_cluster_record: one cluster of the list (aligner_amd/csrc/aln_cluster_rules.h)."""
+    _fields_ = [("label", C.c_uint32), ("size", C.c_uint32), ("longest", C.c_uint32), ("edges", C.c_uint32)]
+
+
+class ClusterSummary(C.Structure):
+    """aln_cluster_summary: the counts of one clustering call."""
+    _fields_ = [("nodes", C.c_uint64), ("clusters", C.c_uint64), ("edges", C.c_uint64), ("self_edges", C.c_uint64),
+                ("singletons", C.c_uint64), ("rounds", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(ClusterRecord) == 16 and C.sizeof(ClusterSummary) == 48
 
 
 class SeqsetBlock(C.Structure):
@@ -266,6 +285,11 @@ def load():
     lib.aln_pairset_loop_begin.argtypes = [vp, vp, vp]
     lib.aln_pairset_loop_step.restype = i
     lib.aln_pairset_loop_step.argtypes = [vp, C.POINTER(Params), vp, vp, vp, vp]
+    lib.aln_cluster_edges.restype = i
+    lib.aln_cluster_edges.argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(ClusterSummary)]
+    lib.aln_seqset_held_cluster.restype = i
+    lib.aln_seqset_held_cluster.argtypes = [vp, C.POINTER(Params), C.c_uint32, C.POINTER(HitFilter), C.c_uint32, vp, vp, C.c_uint64,
+                                            C.POINTER(ClusterSummary)]
     _lib = lib
     return lib
 

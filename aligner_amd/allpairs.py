@@ -24,6 +24,11 @@ the device over the alignment's columns (the traceback's duplicated seed column 
 = (identical + positive-scoring) / columns, q_cover / t_cover = aligned residues of the first / second record over its length.
 --min-identity X, --min-q-cover Y, --min-t-cover Z print only the hits the device filter keeps (with --best the K best are selected
 first, then filtered); --shuffles then runs on the kept hits only.  Not with --heuristic.
+
+With --cluster components|greedy (and --best or --f-min) the records are grouped by the held hits on the device and the hit rows are
+replaced by one row per record, in input order: `head,rep_head,cluster_size`.  components: single linkage, rep_head the first record
+of the family; greedy: longest-first representatives, a record joins the first representative it has a hit with.  The --min-*
+thresholds, when given, decide which hits count as edges.  Not with --heuristic, --shuffles or --report.
 """
 import argparse
 import sys
@@ -60,6 +65,7 @@ def main(argv=None):
     ap.add_argument("--min-identity", type=float, default=None, metavar="X", help="print only hits with identical >= X * columns (with --best: the K best are selected first, then filtered)")
     ap.add_argument("--min-q-cover", type=float, default=None, metavar="Y", help="print only hits whose alignment covers Y of the first record (with --best: selected first, then filtered)")
     ap.add_argument("--min-t-cover", type=float, default=None, metavar="Z", help="print only hits whose alignment covers Z of the second record (with --best: selected first, then filtered)")
+    ap.add_argument("--cluster", choices=("components", "greedy"), default=None, help="group the records by the held hits: prints head,rep_head,cluster_size per record (with --best or --f-min)")
     a = ap.parse_args(argv)
     filtered = a.min_identity is not None or a.min_q_cover is not None or a.min_t_cover is not None
     if a.report or filtered:
@@ -67,6 +73,13 @@ def main(argv=None):
             ap.error("--report / --min-identity / --min-q-cover / --min-t-cover describe the plain alignment: not with --heuristic")
         if a.best is None and a.f_min is None:
             ap.error("--report / --min-identity / --min-q-cover / --min-t-cover work on held hits: give --best K or --f-min F")
+    if a.cluster is not None:
+        if a.heuristic:
+            ap.error("--cluster groups by the plain alignment's hits: not with --heuristic")
+        if a.best is None and a.f_min is None:
+            ap.error("--cluster works on held hits: give --best K or --f-min F")
+        if a.shuffles is not None or a.report:
+            ap.error("--cluster replaces the hit rows: not with --shuffles or --report")
     if a.shuffles is not None:
         if a.heuristic:
             ap.error("--shuffles asks about the plain alignment's score: not with --heuristic")
@@ -92,6 +105,15 @@ def main(argv=None):
                               with_reports=a.report)
             return got if a.report else (got, None)
         return None, (held.report(matrix) if a.report else None)
+
+    def clustered(held):
+        """--cluster: one row per record that is a node, in record order"""
+        got = held.cluster(matrix if filtered else None, mode=a.cluster, min_identity=a.min_identity or 0.0, min_q_cover=a.min_q_cover or 0.0,
+                           min_t_cover=a.min_t_cover or 0.0)
+        size = dict(zip(got.records["label"].tolist(), got.records["size"].tolist()))
+        for i, lab in enumerate(got.label.tolist()):
+            if lab != _ffi.CLUSTER_NONE:
+                out.write("%s,%s,%d\n" % (heads[i], heads[lab], size[lab]))
 
     def tail(held, pos=None, reports=None):
         """`,z,p_emp` and the report's columns per held position, or empty strings without --shuffles and --report; pos: the
@@ -120,6 +142,9 @@ def main(argv=None):
             ap.error("--best: K must lie in 1 .. %d" % _ffi.SEQSET_BEST_MAX)
         with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
             held = ss.best(matrix, a.del_, a.ext, a.best, f_min=float("-inf") if a.f_min is None else a.f_min, skip_self=True, semantics=sem)
+            if a.cluster is not None:
+                clustered(held)
+                return 0
             pos_kept, reports = kept(held)
             more = tail(held, pos_kept, reports)
             show = np.ones(len(held), dtype=bool) if pos_kept is None else np.isin(np.arange(len(held)), pos_kept)
@@ -158,6 +183,9 @@ def main(argv=None):
                     k += 1
         else:
             held = ss.hits(matrix, a.del_, a.ext, a.f_min, None, semantics=sem)
+            if a.cluster is not None:
+                clustered(held)
+                return 0
             pos_kept, reports = kept(held)
             more = tail(held, pos_kept, reports)
             for h in (range(len(held)) if pos_kept is None else pos_kept):

@@ -11,11 +11,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libaligner_hip.so")
-SOURCES = ["aln_kernels.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip", "aln_signif.hip", "aln_pairset.hip", "aln_seqset.hip", "aln_loop.hip", "aln_best.hip", "aln_report.hip"]
+SOURCES = ["aln_kernels.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip", "aln_signif.hip", "aln_pairset.hip", "aln_seqset.hip", "aln_loop.hip", "aln_best.hip", "aln_report.hip", "aln_cluster.hip"]
 # aln_kernels.hip is compiled as several translation units side by side (-DALN_TU=<mask of its ALN_PART_* families>): the fast
 # core-local batch kernel alone is half of the compile time
 KERNEL_UNITS = [("generic", 1), ("fast_cl", 2), ("fast_rest", 4), ("single", 8), ("tb", 16), ("fast_cl_solo", 32), ("fast_rest_solo", 64)]
-HEADERS = ["aln_best_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_loop_rules.h", "aln_plan_rules.h", "aln_report_rules.h", "aln_scheme_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_signif_rules.h", "aln_transform_rules.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h")]
+HEADERS = ["aln_best_rules.h", "aln_cluster_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_loop_rules.h", "aln_plan_rules.h", "aln_report_rules.h", "aln_scheme_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_signif_rules.h", "aln_transform_rules.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h"),
+           os.path.join("..", "..", "include", "aligner_hip_cluster.h")]
 # host-only helper of the synthetic workloads (splitmix64 residues; aligner_amd/workloads.py only LOADS it)
 SYNTH_LIB = os.path.join(LIBDIR, "libaln_synth.so")
 SYNTH_SRC = os.path.join(CSRC, "aln_synth.c")
@@ -50,6 +51,10 @@ HARNESS = os.path.join(HERE, "..", "tests", "bin", "abi_harness")
 # tests/abi_families.c: the same for every other exported family (tests/test_abi_layout_cpu.py, tests/test_abi_families_gpu.py)
 FAMILIES_SRC = os.path.join(HERE, "..", "tests", "abi_families.c")
 FAMILIES = os.path.join(HERE, "..", "tests", "bin", "abi_families")
+# tests/abi_cluster.c: the same for the companion header include/aligner_hip_cluster.h (tests/test_cluster_rules_cpu.py,
+# tests/test_cluster_gpu.py)
+CLUSTER_SRC = os.path.join(HERE, "..", "tests", "abi_cluster.c")
+CLUSTER = os.path.join(HERE, "..", "tests", "bin", "abi_cluster")
 
 
 def build_harness(force=False):
@@ -60,10 +65,14 @@ def build_families_harness(force=False):
     return _build_c_program(FAMILIES_SRC, FAMILIES, force)
 
 
+def build_cluster_harness(force=False):
+    return _build_c_program(CLUSTER_SRC, CLUSTER, force)
+
+
 def _build_c_program(src, out, force=False):
     src, out = os.path.abspath(src), os.path.abspath(out)
-    hdr = os.path.join(HERE, "..", "include", "aligner_hip.h")
-    if force or not os.path.exists(out) or max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB)) > os.path.getmtime(out):
+    hdrs = [os.path.join(HERE, "..", "include", h) for h in ("aligner_hip.h", "aligner_hip_cluster.h")]
+    if force or not os.path.exists(out) or max([os.path.getmtime(f) for f in [src, LIB] + hdrs]) > os.path.getmtime(out):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         tmp = out + ".tmp%d" % os.getpid()
         subprocess.check_call([os.environ.get("CC", "gcc"), "-std=c99", "-Wall", "-Werror", "-I", os.path.join(HERE, "..", "include"), src, "-o", tmp,
@@ -76,6 +85,7 @@ def build(force=False, remarks=False):
     lib = _build_lib(force, remarks)
     build_harness(force)
     build_families_harness(force)
+    build_cluster_harness(force)
     return lib
 
 

@@ -49,6 +49,7 @@
 #include "aln_shuffle_rules.h"
 #include "aln_signif_rules.h"
 #include "aln_report_rules.h"
+#include "aln_cluster_rules.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -3197,10 +3198,12 @@ struct aln_seqset : CallStats {
     std::vector<double> hit_score;
     std::vector<uint32_t> hit_q, hit_t;
     HeldStore held_store;
+    aln_seqset_block held_block = {0, 0, 0, 0, 0, 0};   // the block of the held pass (aln_seqset_held_cluster: its ranges are the nodes)
     // aln_seqset_best: a chunk's piece lists (key | target | count per piece) and the rows' running lists (aln_best.hip)
     DevBuf cand_key, cand_t, cand_n, run_key, run_t, run_n;
     // aln_seqset_held_report / _filter: the scheme's bit table, the reports (of a list, or of all held hits), the kept positions | records
     DevBuf rep_bits, reports, rep_pos, rep_out;
+    DevBuf cluster;                   // aln_seqset_held_cluster: the call's tables, one arena
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a chunk's launches; 4, 5: the best selection
     // pair sets made by aln_pairset_create_from_set read the residue buffer: a destroy with some of them alive releases everything
     // else, moves the buffer here and leaves the rest to the last of them
@@ -3228,7 +3231,7 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     for (hipEvent_t &e : ss->ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     held_free(ss->held_store);
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
-                   &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out};
+                   &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
@@ -3550,6 +3553,7 @@ extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const a
     if ((st = seqset_hold_list(ss, ct, b)) != ALN_OK) { seqset_begin(ss); return st; }
     ss->ms[3] = wall_ms(t0);
     ss->held = true;
+    ss->held_block = *b;
     *count = ss->hit_pair.size();
     return ALN_OK;
 }
@@ -3625,6 +3629,7 @@ extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const a
     if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_begin(ss); return st; }
     ss->ms[3] = wall_ms(t0);
     ss->held = true;
+    ss->held_block = *b;
     *count = total;
     return ALN_OK;
 }
@@ -3937,6 +3942,245 @@ extern "C" int aln_seqset_held_filter(aln_seqset *ss, const aln_params *params, 
 extern "C" int aln_seqset_stats(const aln_seqset *ss, double *ms, uint64_t *bytes)
 {
     return stats_get(ss, ms, bytes);
+}
+
+// ---------------------------------------------------------------- clusters of an edge list (aln_cluster.hip, aln_cluster_rules.h)
+// The tables of one call, carved out of one arena (every piece 256-aligned); base == nullptr only sizes it.
+struct ClusterBufs {
+    ClusterArgs a;
+    uint32_t *ea = nullptr, *eb = nullptr, *len = nullptr, *tile_count = nullptr, *tile_off = nullptr;
+    aln_cluster_record *rec = nullptr;
+};
+static size_t cluster_carve(uint8_t *base, uint32_t mode, uint64_t n, uint64_t m, uint64_t room, bool with_len, ClusterBufs *out)
+{
+    size_t pos = 0;
+    auto take = [&](size_t bytes) -> uint8_t * {
+        uint8_t *p = base ? base + pos : nullptr;
+        pos += (size_t)align256(std::max<size_t>(bytes, 4));
+        return p;
+    };
+    const uint64_t tiles = aln_cluster_tiles(n);
+    ClusterBufs b;
+    b.a = ClusterArgs();
+    b.a.misc = reinterpret_cast<uint32_t *>(take(64));
+    b.a.label = reinterpret_cast<uint32_t *>(take(4 * n));
+    b.a.aux0 = reinterpret_cast<uint32_t *>(take(4 * n));
+    if (mode == ALN_CLUSTER_GREEDY) {
+        b.a.aux1 = reinterpret_cast<uint32_t *>(take(4 * n));
+        b.a.aux2 = reinterpret_cast<uint32_t *>(take(4 * n));
+    }
+    b.a.key = reinterpret_cast<uint64_t *>(take(8 * n));
+    b.a.size = reinterpret_cast<uint32_t *>(take(4 * n));
+    b.a.cedges = reinterpret_cast<uint32_t *>(take(4 * n));
+    b.ea = reinterpret_cast<uint32_t *>(take(4 * m));
+    b.eb = reinterpret_cast<uint32_t *>(take(4 * m));
+    if (with_len) b.len = reinterpret_cast<uint32_t *>(take(4 * n));
+    b.tile_off = reinterpret_cast<uint32_t *>(take(4 * tiles));
+    b.tile_count = reinterpret_cast<uint32_t *>(take(4 * tiles));
+    b.rec = reinterpret_cast<aln_cluster_record *>(take(sizeof(aln_cluster_record) * room));
+    b.a.mode = mode; b.a.n = n; b.a.m = m;
+    b.a.ea = b.ea; b.a.eb = b.eb; b.a.len = b.len;
+    if (out) *out = b;
+    return pos;
+}
+
+// The rounds and the finish, on a stream whose earlier work (the endpoints' upload, the held edges) is queued already.  The host reads
+// one 4-byte word per round: components the changed word, greedy the undecided count.  Labels, the first `room` records and the
+// summary land in the call's own host buffers.  On an error the caller waits for the stream.
+static int cluster_core(hipStream_t q, ClusterBufs &b, uint64_t room, std::vector<uint32_t> &label_h, std::vector<aln_cluster_record> &rec_h,
+                        aln_cluster_summary &sum, uint64_t *down)
+{
+    const ClusterArgs &a = b.a;
+    const uint64_t nodes = aln_cluster_node_count(a.nodes);
+    const uint64_t bound = a.n + 2;
+    uint32_t rounds = 0, word = 0;
+    HIPCHK(hipMemsetAsync(a.misc, 0, 64, q));
+    aln_cluster_launch_init(&a, q);
+    HIPCHK(hipGetLastError());
+    if (a.mode == ALN_CLUSTER_COMPONENTS) {
+        for (word = a.m ? 1u : 0u; word;) {
+            if (rounds >= bound) { g_err = "components: the rounds did not settle within n_nodes + 2"; return ALN_ERR_DEVICE; }
+            HIPCHK(hipMemsetAsync(a.misc, 0, 4, q));
+            aln_cluster_launch_hook(&a, q);
+            aln_cluster_launch_compress(&a, q);
+            HIPCHK(hipGetLastError());
+            ++rounds;
+            HIPCHK(hipMemcpyAsync(&word, a.misc, 4, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipStreamSynchronize(q));
+        }
+    } else {
+        for (word = nodes ? 1u : 0u; word;) {
+            if (rounds >= bound) { g_err = "greedy: the rounds did not settle within n_nodes + 2"; return ALN_ERR_DEVICE; }
+            HIPCHK(hipMemsetAsync(a.misc, 0, 4, q));
+            aln_cluster_launch_greedy_round(&a, q);
+            HIPCHK(hipGetLastError());
+            ++rounds;
+            HIPCHK(hipMemcpyAsync(&word, a.misc, 4, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipStreamSynchronize(q));
+        }
+        aln_cluster_launch_greedy_assign(&a, q);
+        HIPCHK(hipGetLastError());
+    }
+    aln_cluster_launch_finish(&a, b.tile_count, b.tile_off, a.misc + 1, room, b.rec, q);
+    HIPCHK(hipGetLastError());
+    uint32_t misc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(misc, a.misc, 32, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    const uint64_t clusters = misc[1];
+    if (clusters > nodes) { g_err = "the cluster list holds more clusters than there are nodes"; return ALN_ERR_DEVICE; }
+    const uint64_t wrote = std::min<uint64_t>(clusters, room);
+    label_h.resize(a.n);
+    rec_h.resize(wrote);
+    HIPCHK(hipMemcpyAsync(label_h.data(), a.label, 4 * a.n, hipMemcpyDeviceToHost, q));
+    if (wrote) HIPCHK(hipMemcpyAsync(rec_h.data(), b.rec, sizeof(aln_cluster_record) * wrote, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    memset(&sum, 0, sizeof sum);
+    sum.nodes = nodes;
+    sum.clusters = clusters;
+    memcpy(&sum.edges, misc + 2, 8);
+    memcpy(&sum.self_edges, misc + 4, 8);
+    memcpy(&sum.singletons, misc + 6, 8);
+    sum.rounds = rounds;
+    if (down) *down = 4 * a.n + sizeof(aln_cluster_record) * wrote + 32 + 4ull * rounds;
+    return ALN_OK;
+}
+
+static int cluster_edges(aln_ctx *ctx, uint32_t mode, uint64_t n_nodes, const uint32_t *node_len, const uint32_t *edge_a, const uint32_t *edge_b,
+                         uint64_t n_edges, uint32_t *label, aln_cluster_record *clusters, uint64_t capacity, aln_cluster_summary *summary)
+{
+    if (mode != ALN_CLUSTER_COMPONENTS && mode != ALN_CLUSTER_GREEDY) { g_err = "unknown cluster mode"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ctx || !summary) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_nodes > ALN_CLUSTER_MAX || n_edges > ALN_CLUSTER_MAX) { g_err = "more than 0xFFFFFFF0 nodes or edges"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((n_nodes && !label) || (n_edges && (!edge_a || !edge_b)) || (capacity && !clusters)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    for (uint64_t k = 0; k < n_edges; ++k)
+        if (edge_a[k] >= n_nodes || edge_b[k] >= n_nodes) { g_err = "an edge's endpoint is not a node"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_nodes == 0) { memset(summary, 0, sizeof *summary); return ALN_OK; }
+    const uint64_t room = std::min<uint64_t>(capacity, n_nodes);
+    DevCtx *dev = ctx->devs[0];
+    HIPCHK(hipSetDevice(dev->device));
+    Slot *sl[1];
+    pool_lease(dev, 1, sl);
+    struct Release { DevCtx *c; Slot **s; ~Release() { pool_release(c, s, 1); } } rel{dev, sl};
+    Slot &s = *sl[0];
+    int st;
+    if ((st = slot_init(s)) != ALN_OK) return st;
+    // (the slot's shuffle table is a call's scratch: nothing outlives the call that wrote it)
+    if ((st = dev_ensure(s.shuffle, cluster_carve(nullptr, mode, n_nodes, n_edges, room, node_len != nullptr, nullptr), s.pooled)) != ALN_OK) return st;
+    ClusterBufs b;
+    cluster_carve(s.shuffle.as<uint8_t>(), mode, n_nodes, n_edges, room, node_len != nullptr, &b);
+    b.a.nodes = aln_cluster_nodes_all(n_nodes);
+    hipStream_t q = s.stream;
+    std::vector<uint32_t> label_h;
+    std::vector<aln_cluster_record> rec_h;
+    aln_cluster_summary sum;
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        if (n_edges) {
+            HIPCHK(hipMemcpyAsync(b.ea, edge_a, 4 * n_edges, hipMemcpyHostToDevice, q));
+            HIPCHK(hipMemcpyAsync(b.eb, edge_b, 4 * n_edges, hipMemcpyHostToDevice, q));
+        }
+        if (node_len) HIPCHK(hipMemcpyAsync(b.len, node_len, 4 * n_nodes, hipMemcpyHostToDevice, q));
+        return cluster_core(q, b, room, label_h, rec_h, sum, nullptr);
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    // (everything landed in buffers of the call's own first: an error on the way left the caller's arrays as they were)
+    memcpy(label, label_h.data(), 4 * n_nodes);
+    if (!rec_h.empty()) memcpy(clusters, rec_h.data(), sizeof(aln_cluster_record) * rec_h.size());
+    *summary = sum;
+    return ALN_OK;
+}
+
+// The sequences of a set grouped by its held hits.  The endpoints go up from the host's held list (8 bytes per held hit: the list is
+// the host's, as the re-fill was planned from it); with a filter the reports of ALL held hits are written into the set's report
+// buffer as held_filter writes them, and a kernel drops the edges the rule does not keep.  The held store is only read.
+static int seqset_held_cluster(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, uint32_t mode,
+                               uint32_t *label, aln_cluster_record *clusters, uint64_t capacity, aln_cluster_summary *summary)
+{
+    std::vector<uint32_t> bits;
+    int st = filter ? seqset_report_check(ss, params, flags, bits) : seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    if (filter && filter->reserved != 0) { g_err = "the filter's reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (mode != ALN_CLUSTER_COMPONENTS && mode != ALN_CLUSTER_GREEDY) { g_err = "unknown cluster mode"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!summary || (ss->n && !label) || (capacity && !clusters)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t n = ss->n, held = ss->hit_pair.size();      // (n < 2^32 - 16 is checked below; held <= 0xFFFFFFF0: seqset_hold_list)
+    if (n > ALN_CLUSTER_MAX) { g_err = "more than 0xFFFFFFF0 sequences"; return ALN_ERR_UNSUPPORTED; }
+    const uint64_t room = std::min<uint64_t>(capacity, n);
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    if ((st = dev_ensure(ss->cluster, cluster_carve(nullptr, mode, n, held, room, false, nullptr), false)) != ALN_OK) return st;
+    if (filter && held) {
+        if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * held, false)) != ALN_OK) return st;
+    }
+    ClusterBufs b;
+    cluster_carve(ss->cluster.as<uint8_t>(), mode, n, held, room, false, &b);
+    b.a.nodes = aln_cluster_nodes_of_block(ss->held_block);
+    b.a.len = ss->d_len.as<uint32_t>();
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> label_h;
+    std::vector<aln_cluster_record> rec_h;
+    aln_cluster_summary sum;
+    uint64_t down = 0;
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        if (held) {
+            HIPCHK(hipMemcpyAsync(b.ea, ss->hit_q.data(), 4 * held, hipMemcpyHostToDevice, q));
+            HIPCHK(hipMemcpyAsync(b.eb, ss->hit_t.data(), 4 * held, hipMemcpyHostToDevice, q));
+            if (filter) HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
+        }
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        if (held) {
+            if (filter) {
+                aln_report_launch(ss->held_store.info.as<HeldEntry>(), ss->held_store.res.as<aln_pair_result>(), ss->held_store.tb.as<uint8_t>(), nullptr,
+                                  (uint32_t)held, (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols, params->blank_code, flags,
+                                  ss->reports.as<aln_hit_report>(), q);
+                HIPCHK(hipGetLastError());
+            }
+            aln_cluster_launch_held_edges(ss->held_store.res.as<aln_pair_result>(), ss->reports.as<aln_hit_report>(), ss->held_store.info.as<HeldEntry>(),
+                                          filter, held, b.ea, b.eb, q);
+            HIPCHK(hipGetLastError());
+        }
+        const int e = cluster_core(q, b, room, label_h, rec_h, sum, &down);
+        if (e != ALN_OK) return e;
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    if (n) memcpy(label, label_h.data(), 4 * n);
+    if (!rec_h.empty()) memcpy(clusters, rec_h.data(), sizeof(aln_cluster_record) * rec_h.size());
+    *summary = sum;
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 8ull * held + (filter && held ? 4ull * bits.size() : 0);
+    ss->bytes[1] = down;
+    return ALN_OK;
+}
+
+// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
+extern "C" int aln_cluster_edges(aln_ctx *ctx, uint32_t mode, uint64_t n_nodes, const uint32_t *node_len, const uint32_t *edge_a,
+                                 const uint32_t *edge_b, uint64_t n_edges, uint32_t *label, aln_cluster_record *clusters, uint64_t capacity,
+                                 aln_cluster_summary *summary)
+{
+    try {
+        return cluster_edges(ctx, mode, n_nodes, node_len, edge_a, edge_b, n_edges, label, clusters, capacity, summary);
+    } catch (const std::bad_alloc &) {
+        if (ctx) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
+}
+
+extern "C" int aln_seqset_held_cluster(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, uint32_t mode,
+                                       uint32_t *label, aln_cluster_record *clusters, uint64_t capacity, aln_cluster_summary *summary)
+{
+    try {
+        return seqset_held_cluster(ss, params, flags, filter, mode, label, clusters, capacity, summary);
+    } catch (const std::bad_alloc &) {
+        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
 }
 
 // ---------------------------------------------------------------- a pair set over a block of a sequence set, and the loop's step

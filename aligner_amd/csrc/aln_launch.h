@@ -1,10 +1,25 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip and aln_best.hip define
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip and aln_cluster.hip define
 // and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "aln_device.h"
+#include "aln_cluster_rules.h"
+
+// what every kernel of aln_cluster.hip takes: n label slots (node numbers 0 .. n - 1, those of `nodes` being nodes), m listed edges
+struct ClusterArgs {
+    aln_cluster_nodes nodes;
+    uint64_t n, m;
+    uint32_t mode;
+    const uint32_t *len;             // n lengths, or null: all equal
+    const uint32_t *ea, *eb;         // m endpoints each; ALN_CLUSTER_NONE in both: a dropped edge
+    uint32_t *label;                 // n
+    uint32_t *aux0, *aux1, *aux2;    // n each.  components: the roots (aux0).  greedy: state, mark, block
+    uint64_t *key;                   // n: greedy, a member's best representative; finish, a cluster's first in priority order
+    uint32_t *size, *cedges;         // n each, by label
+    uint32_t *misc;                  // 8 words: [0] changed | undecided, [1] clusters, then 64-bit edges, self edges, singletons
+};
 
 static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
 
@@ -75,6 +90,18 @@ void aln_report_launch(const HeldEntry *held, const aln_pair_result *res, const 
 void aln_report_launch_filter(const aln_hit_report *rep, const HeldEntry *held, uint32_t n_held, const aln_hit_filter *filter,
                               uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint64_t cap, uint32_t *positions,
                               aln_hit_report *out, hipStream_t s);
+
+// ---- aln_cluster.hip: clusters of an edge list
+void aln_cluster_launch_held_edges(const aln_pair_result *res, const aln_hit_report *rep, const HeldEntry *held, const aln_hit_filter *filter,
+                                   uint64_t m, uint32_t *ea, uint32_t *eb, hipStream_t s);
+void aln_cluster_launch_init(const ClusterArgs *a, hipStream_t s);
+void aln_cluster_launch_hook(const ClusterArgs *a, hipStream_t s);
+void aln_cluster_launch_compress(const ClusterArgs *a, hipStream_t s);
+void aln_cluster_launch_greedy_round(const ClusterArgs *a, hipStream_t s);
+void aln_cluster_launch_greedy_assign(const ClusterArgs *a, hipStream_t s);
+uint64_t aln_cluster_tiles(uint64_t n);
+void aln_cluster_launch_finish(const ClusterArgs *a, uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint64_t cap,
+                               aln_cluster_record *out, hipStream_t s);
 
 // ---- aln_best.hip: the k best targets per query
 int aln_warm_best(void);

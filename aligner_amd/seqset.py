@@ -326,6 +326,34 @@ class HeldHits:
         n = min(self.last_filter_count, cap)
         return (pos[:n], rep[:n]) if with_reports else pos[:n]
 
+    def cluster(self, matrix=None, mode="components", min_identity=0.0, min_q_cover=0.0, min_t_cover=0.0, min_columns=0, skip_seed=True, blank=98,
+                capacity=None):
+        """aln_seqset_held_cluster: the sequences of the held pass's block grouped by the held hits, on the device; 4 bytes per
+        sequence and 16 per cluster come down.  mode "components": single linkage, label = the smallest member; "greedy":
+        longest-first representatives, a sequence joins the first representative it has a kept hit with.  With a matrix the edges
+        are the hits that filter(matrix, min_...) keeps; without one (and without thresholds) every held hit that succeeded.
+        Returns a cluster.Clusters; sequences outside the block carry the label cluster.NONE."""
+        from . import cluster as _cluster
+        o = self.owner
+        thresholds = bool(min_identity or min_q_cover or min_t_cover or min_columns)
+        if matrix is None and thresholds:
+            raise ValueError("aln_seqset_held_cluster: thresholds need the matrix their classes are counted under")
+        n = len(o)
+        cap = n if capacity is None else int(capacity)
+        label = np.zeros(n, dtype=np.uint32)
+        rec = np.zeros(cap, dtype=_cluster.RECORD_DTYPE)
+        summ = _ffi.ClusterSummary()
+        if matrix is None:
+            p_ref, flt_ref, flags = None, None, 0
+        else:
+            p, _held = self._report_params(matrix, blank)
+            flt = _ffi.HitFilter(float(min_identity), float(min_q_cover), float(min_t_cover), int(min_columns), 0)
+            p_ref, flt_ref, flags = C.byref(p), C.byref(flt), _ffi.REPORT_SKIP_SEED if skip_seed else 0
+        st = o.lib.aln_seqset_held_cluster(o.handle, p_ref, flags, flt_ref, _cluster.mode_code(mode), label.ctypes.data, rec.ctypes.data if cap else None,
+                                           cap, C.byref(summ))
+        runtime.raise_for_status(st, "aln_seqset_held_cluster")
+        return _cluster.Clusters(label, rec[:min(int(summ.clusters), cap)], _cluster.summary_dict(summ))
+
     def fractions(self, reports, keep=None):
         """report_fractions of records that belong to the listed positions (default: all)."""
         w = self._keep(keep)
