@@ -53,6 +53,11 @@ CLUSTER_EXPORTS = ["aln_cluster_edges", "aln_seqset_held_cluster"]
 CLUSTER_COMPONENTS, CLUSTER_GREEDY = 0, 1       # ALN_CLUSTER_COMPONENTS, ALN_CLUSTER_GREEDY
 CLUSTER_NONE = 0xFFFFFFFF                       # ALN_CLUSTER_NONE
 CLUSTER_MAX = 0xFFFFFFF0                        # nodes, edges
+# every symbol the companion header include/aligner_hip_prefilter.h declares (the same library, as above)
+PREFILTER_EXPORTS = ["aln_seqset_kmer_index", "aln_seqset_prefilter", "aln_seqset_candidates", "aln_seqset_candidate_scores",
+                     "aln_seqset_candidate_hits"]
+PREFILTER_MAX_K, PREFILTER_MAX_BITS, PREFILTER_CHUNK_PAIRS = 8, 1 << 18, 1 << 22      # aligner_amd/csrc/aln_prefilter_rules.h
+PREFILTER_MAX_CANDIDATES = 0xFFFFFFF0
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
 TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
 # aln_pairset_loop_step's causes (aligner_amd/csrc/aln_loop_rules.h)
@@ -134,6 +139,15 @@ class ClusterSummary(C.Structure):
 
 
 assert C.sizeof(ClusterRecord) == 16 and C.sizeof(ClusterSummary) == 48
+
+
+class PrefilterSpec(C.Structure):
+    """aln_prefilter_spec: the index a prefilter call expects and its thresholds (include/aligner_hip_prefilter.h)."""
+    _fields_ = [("k", C.c_uint32), ("alphabet", C.c_uint32), ("min_shared", C.c_uint32), ("min_per_1024", C.c_uint32),
+                ("chunk_pairs", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(PrefilterSpec) == 32
 
 
 class SeqsetBlock(C.Structure):
@@ -290,6 +304,16 @@ def load():
     lib.aln_seqset_held_cluster.restype = i
     lib.aln_seqset_held_cluster.argtypes = [vp, C.POINTER(Params), C.c_uint32, C.POINTER(HitFilter), C.c_uint32, vp, vp, C.c_uint64,
                                             C.POINTER(ClusterSummary)]
+    lib.aln_seqset_kmer_index.restype = i
+    lib.aln_seqset_kmer_index.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    lib.aln_seqset_prefilter.restype = i
+    lib.aln_seqset_prefilter.argtypes = [vp, C.POINTER(PrefilterSpec), bp, C.POINTER(C.c_uint64)]
+    lib.aln_seqset_candidates.restype = i
+    lib.aln_seqset_candidates.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
+    lib.aln_seqset_candidate_scores.restype = i
+    lib.aln_seqset_candidate_scores.argtypes = [vp, C.POINTER(Params), vp, vp]
+    lib.aln_seqset_candidate_hits.restype = i
+    lib.aln_seqset_candidate_hits.argtypes = [vp, C.POINTER(Params), C.c_double, C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 

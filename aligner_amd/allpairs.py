@@ -29,6 +29,14 @@ With --cluster components|greedy (and --best or --f-min) the records are grouped
 replaced by one row per record, in input order: `head,rep_head,cluster_size`.  components: single linkage, rep_head the first record
 of the family; greedy: longest-first representatives, a record joins the first representative it has a hit with.  The --min-*
 thresholds, when given, decide which hits count as edges.  Not with --heuristic, --shuffles or --report.
+
+With --kmer K the pairs are prefiltered on the device first: only the candidates -- pairs whose records share at least --min-shared N
+distinct words of K residues (default 0) and at least P / 1024 of the smaller record's distinct words (--min-shared-per-1024 P,
+default 0) -- are aligned at all.  Words are counted over the first A codes of the alphabet (--kmer-alphabet A; default 20, the
+standard residues, or 4 with --dna); a window that touches any other code is no word; A^K may not exceed 2^18.  With --f-min F the rows
+and everything downstream (--report, --min-*, --shuffles, --cluster) are those of the candidates with f >= F; without it one row per
+candidate is printed: `q_head,t_head,f,shared`.  The surviving alignments are bit for bit those of the unfiltered run; which pairs
+survive is the thresholds' business.  Not with --best or --heuristic: a per-row selection over a sparse candidate list is not built.
 """
 import argparse
 import sys
@@ -66,7 +74,24 @@ def main(argv=None):
     ap.add_argument("--min-q-cover", type=float, default=None, metavar="Y", help="print only hits whose alignment covers Y of the first record (with --best: selected first, then filtered)")
     ap.add_argument("--min-t-cover", type=float, default=None, metavar="Z", help="print only hits whose alignment covers Z of the second record (with --best: selected first, then filtered)")
     ap.add_argument("--cluster", choices=("components", "greedy"), default=None, help="group the records by the held hits: prints head,rep_head,cluster_size per record (with --best or --f-min)")
+    ap.add_argument("--kmer", type=int, default=None, metavar="K", help="prefilter: align only the pairs that share enough words of K residues (1 .. %d)" % _ffi.PREFILTER_MAX_K)
+    ap.add_argument("--min-shared", type=int, default=None, metavar="N", help="with --kmer: candidates share at least N distinct words")
+    ap.add_argument("--min-shared-per-1024", type=int, default=None, metavar="P", help="with --kmer: candidates share at least P / 1024 of the smaller record's distinct words (0 .. 1024)")
+    ap.add_argument("--kmer-alphabet", type=int, default=None, metavar="A", help="with --kmer: words use the first A codes of the alphabet (default 20; 4 with --dna)")
     a = ap.parse_args(argv)
+    if a.kmer is None:
+        if a.min_shared is not None or a.min_shared_per_1024 is not None or a.kmer_alphabet is not None:
+            ap.error("--min-shared / --min-shared-per-1024 / --kmer-alphabet are the prefilter's thresholds: give --kmer K")
+    else:
+        if a.best is not None or a.heuristic:
+            ap.error("--kmer with --best or --heuristic: a per-row selection and the matrix loop over a sparse candidate list are not built")
+        kmer_alphabet = a.kmer_alphabet if a.kmer_alphabet is not None else (4 if a.dna else 20)
+        if not 1 <= a.kmer <= _ffi.PREFILTER_MAX_K or kmer_alphabet < 1 or kmer_alphabet ** a.kmer > _ffi.PREFILTER_MAX_BITS:
+            ap.error("--kmer: K must lie in 1 .. %d and A^K may not exceed 2^18" % _ffi.PREFILTER_MAX_K)
+        if a.min_shared is not None and not 0 <= a.min_shared < 2 ** 32:
+            ap.error("--min-shared: N must lie in 0 .. 2^32 - 1")
+        if a.min_shared_per_1024 is not None and not 0 <= a.min_shared_per_1024 <= 1024:
+            ap.error("--min-shared-per-1024: P must lie in 0 .. 1024")
     filtered = a.min_identity is not None or a.min_q_cover is not None or a.min_t_cover is not None
     if a.report or filtered:
         if a.heuristic:
@@ -174,7 +199,14 @@ def main(argv=None):
                 out.write("%s,%s,%s\n" % (heads[q], heads[t], repr(float(r.alignment.f)) if not isinstance(r, Exception) else "panic: %s" % r))
         return 0
     with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
-        if a.f_min is None:
+        if a.kmer is not None:
+            cand = ss.prefilter(a.kmer, kmer_alphabet, min_shared=a.min_shared or 0, min_per_1024=a.min_shared_per_1024 or 0)
+        if a.kmer is not None and a.f_min is None:
+            f, status = cand.score(matrix, a.del_, a.ext, semantics=sem)
+            for c in range(len(cand)):
+                out.write("%s,%s,%s,%d\n" % (heads[int(cand.q[c])], heads[int(cand.t[c])],
+                                             repr(float(f[c])) if status[c] == _ffi.OK else _ffi.STATUS_NAMES[int(status[c])], int(cand.shared[c])))
+        elif a.f_min is None:
             f, status = ss.score(matrix, a.del_, a.ext, None, semantics=sem)
             k = 0
             for i in range(len(heads)):
@@ -182,7 +214,7 @@ def main(argv=None):
                     out.write("%s,%s,%s\n" % (heads[i], heads[j], repr(float(f[k])) if status[k] == _ffi.OK else _ffi.STATUS_NAMES[int(status[k])]))
                     k += 1
         else:
-            held = ss.hits(matrix, a.del_, a.ext, a.f_min, None, semantics=sem)
+            held = cand.hits(matrix, a.del_, a.ext, a.f_min, semantics=sem) if a.kmer is not None else ss.hits(matrix, a.del_, a.ext, a.f_min, None, semantics=sem)
             if a.cluster is not None:
                 clustered(held)
                 return 0

@@ -50,6 +50,8 @@
 #include "aln_signif_rules.h"
 #include "aln_report_rules.h"
 #include "aln_cluster_rules.h"
+#include "aln_prefilter_rules.h"
+#include "../../include/aligner_hip_prefilter.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -3204,6 +3206,17 @@ struct aln_seqset : CallStats {
     // aln_seqset_held_report / _filter: the scheme's bit table, the reports (of a list, or of all held hits), the kept positions | records
     DevBuf rep_bits, reports, rep_pos, rep_out;
     DevBuf cluster;                   // aln_seqset_held_cluster: the call's tables, one arena
+    // the k-mer prefilter (aln_prefilter_rules.h).  The index: one bitmap row of kmer_stride elements and one word count per
+    // sequence, resident until the next aln_seqset_kmer_index (kmer_k == 0: none built)
+    uint32_t kmer_k = 0, kmer_alphabet = 0, kmer_stride = 0;
+    DevBuf kmer_bits, kmer_n;
+    // the candidate list of aln_seqset_prefilter: the block's pair numbers resident (cand_k) and, with shared and the sequence numbers,
+    // on the host (the later passes are planned from this copy).  Separate from the held hits: until the next index, prefilter, destroy
+    bool cand = false;
+    aln_seqset_block cand_block = {0, 0, 0, 0, 0, 0};
+    DevBuf cand_k, pf_shared, pf_keep, pf_out;      // pf_*: a sharing chunk's shared | keep flags | compacted shared
+    std::vector<uint64_t> cand_pair;
+    std::vector<uint32_t> cand_qs, cand_ts, cand_shared;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a chunk's launches; 4, 5: the best selection
     // pair sets made by aln_pairset_create_from_set read the residue buffer: a destroy with some of them alive releases everything
     // else, moves the buffer here and leaves the rest to the last of them
@@ -3231,13 +3244,14 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     for (hipEvent_t &e : ss->ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     held_free(ss->held_store);
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
-                   &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster};
+                   &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster, &ss->kmer_bits, &ss->kmer_n,
+                   &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
     slot_destroy(ss->slot);
     ss->slot = nullptr;
-    if (ss->derived) { ss->destroyed = true; ss->held = false; return; }      // the residues go with the last derived pair set
+    if (ss->derived) { ss->destroyed = true; ss->held = false; ss->cand = false; ss->kmer_k = 0; return; }      // the residues go with the last derived pair set
     delete ss;
 }
 
@@ -3335,15 +3349,23 @@ static double seqset_cells(const aln_seqset *ss, const aln_seqset_block &b)
 
 // the chunks of a pass: pair counts of consecutive ranges of the block's order, by the bounds of make_chunks (the pair limit holds for
 // every chunk: the queue entries are 32-bit and chunk-local).  One walk over the block, nothing kept per pair.
+// the cells a chunk of a pass aims at (total cells over `pairs` pairs); *forced: ALN_CHUNK_CELLS said so
+static double seqset_chunk_target(const Call &c, double total, uint64_t pairs, bool *forced)
+{
+    double target = std::min(1.6e10, std::max(5.0e9, total / 4.0));
+    if (!c.fast) target *= 3.0;
+    if (total / (double)pairs >= 3.0e6) target = std::max(target, std::min(6.4e10, 2.0 * 3072.0 * (total / (double)pairs)));
+    *forced = false;
+    if (const char *e = getenv("ALN_CHUNK_CELLS")) { target = std::max(1.0, atof(e)); *forced = true; }
+    return target;
+}
+
 static void seqset_chunks(const aln_seqset *ss, const Call &c, const aln_seqset_block &b, uint64_t pairs, std::vector<uint64_t> &counts)
 {
     counts.clear();
     const double total = seqset_cells(ss, b);
-    double target = std::min(1.6e10, std::max(5.0e9, total / 4.0));
-    if (!c.fast) target *= 3.0;
-    if (total / (double)pairs >= 3.0e6) target = std::max(target, std::min(6.4e10, 2.0 * 3072.0 * (total / (double)pairs)));
     bool forced = false;
-    if (const char *e = getenv("ALN_CHUNK_CELLS")) { target = std::max(1.0, atof(e)); forced = true; }
+    const double target = seqset_chunk_target(c, total, pairs, &forced);
     if (pairs <= ALN_SEQSET_CHUNK_PAIRS && (total <= 1.5 * target || (!forced && total <= 2.0e10))) { counts.push_back(pairs); return; }
     uint64_t q, t, n = 0;
     aln_seqset_unrank(b, 0, &q, &t);
@@ -3359,6 +3381,23 @@ static void seqset_chunks(const aln_seqset *ss, const Call &c, const aln_seqset_
         }
     }
     if (n) counts.push_back(n);
+}
+
+// what a chunk of n pairs needs of the set's buffers (the stream is idle: they may grow)
+static int seqset_chunk_ensure(aln_seqset *ss, const Call &c, const Chunk &k, uint64_t n, bool want_out, bool select, uint32_t **tile_count,
+                               uint32_t **tile_off)
+{
+    int st;
+    if ((st = slot_ensure(*ss->slot, c, k, nullptr, true)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->fbuf, 8 * n, false)) != ALN_OK) return st;
+    if ((st = dev_ensure(ss->stbuf, 4 * n, false)) != ALN_OK) return st;
+    if ((st = pin_ensure(ss->h_out, 256 + (want_out ? 12 * n : 0))) != ALN_OK) return st;
+    if (select) {
+        if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(n), tile_count, tile_off)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->hit_k, 8 * n, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->hit_f, 8 * n, false)) != ALN_OK) return st;
+    }
+    return ALN_OK;
 }
 
 // One pass over a block: every chunk expanded, filled and gathered on the set's stream.  f / status (optional): the caller's arrays.
@@ -3420,16 +3459,8 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
         HIPCHK(hipStreamSynchronize(q));
         if ((st = collect()) != ALN_OK) break;
         // the stream is idle: buffers may grow now
-        if ((st = slot_ensure(s, c, k, nullptr, true)) != ALN_OK) break;
-        if ((st = dev_ensure(ss->fbuf, 8 * n, false)) != ALN_OK) break;
-        if ((st = dev_ensure(ss->stbuf, 4 * n, false)) != ALN_OK) break;
-        if ((st = pin_ensure(ss->h_out, 256 + (want_out ? 12 * n : 0))) != ALN_OK) break;
         uint32_t *tile_count = nullptr, *tile_off = nullptr;
-        if (select) {
-            if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(n), &tile_count, &tile_off)) != ALN_OK) break;
-            if ((st = dev_ensure(ss->hit_k, 8 * n, false)) != ALN_OK) break;
-            if ((st = dev_ensure(ss->hit_f, 8 * n, false)) != ALN_OK) break;
-        }
+        if ((st = seqset_chunk_ensure(ss, c, k, n, want_out, select, &tile_count, &tile_off)) != ALN_OK) break;
         if (best) {
             const uint64_t pieces = aln_best_chunk_geometry(k0, n, b.t_count).pieces;
             if ((st = dev_ensure(ss->cand_key, 8 * pieces * best->slots, false)) != ALN_OK) break;
@@ -3632,6 +3663,371 @@ extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const a
     ss->held_block = *b;
     *count = total;
     return ALN_OK;
+}
+
+// ---------------------------------------------------------------- the k-mer prefilter (include/aligner_hip_prefilter.h)
+// Words first, the dynamic programme on the candidates only.  The index and the candidate list are state of their own beside the held
+// hits; the two candidate passes are passes like score and hits whose chunks are runs of consecutive list positions.
+static void seqset_drop_candidates(aln_seqset *ss)
+{
+    ss->cand = false;
+    ss->cand_pair.clear(); ss->cand_qs.clear(); ss->cand_ts.clear(); ss->cand_shared.clear();
+}
+
+static int seqset_kmer_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint32_t bits = aln_prefilter_bits(k, alphabet);
+    if (!bits) { g_err = "k must lie in 1 .. 8, the alphabet size be at least 1 and alphabet^k at most 2^18"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t elements = aln_prefilter_elements(bits), stride = aln_prefilter_stride(bits);
+    // the new table first: a failure leaves the old index and the candidate list as they were
+    DevBuf table, counts;
+    int st = dev_ensure(table, 4ull * stride * ss->n, false);
+    if (st == ALN_OK) st = dev_ensure(counts, 4ull * ss->n, false);
+    std::vector<uint32_t> counts_h(n_words ? ss->n : 0);
+    auto run = [&]() -> int {
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        aln_prefilter_launch_index(ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), ss->n, k, alphabet, elements,
+                                   stride, table.as<uint32_t>(), counts.as<uint32_t>(), q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        if (n_words && ss->n) HIPCHK(hipMemcpyAsync(counts_h.data(), counts.p, 4ull * ss->n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    if (st == ALN_OK) st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); dev_free(table); dev_free(counts); return st; }
+    dev_free(ss->kmer_bits); dev_free(ss->kmer_n);
+    ss->kmer_bits = table; ss->kmer_n = counts;
+    ss->kmer_k = k; ss->kmer_alphabet = alphabet; ss->kmer_stride = stride;
+    seqset_drop_candidates(ss);
+    if (n_words && ss->n) memcpy(n_words, counts_h.data(), 4ull * ss->n);
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 0;
+    ss->bytes[1] = n_words ? 4ull * ss->n : 0;
+    return ALN_OK;
+}
+
+// room for `entries` pair numbers in the resident list, the first `used` of them kept (the stream is idle)
+static int seqset_cand_room(aln_seqset *ss, uint64_t used, uint64_t entries)
+{
+    if (ss->cand_k.cap >= 8 * entries) return ALN_OK;
+    DevBuf bigger;
+    const int st = dev_ensure(bigger, std::max<uint64_t>(8 * entries, used ? 2 * ss->cand_k.cap : 0), false);
+    if (st != ALN_OK) return st;
+    if (used) {
+        const hipError_t e = hipMemcpy(bigger.p, ss->cand_k.p, 8 * used, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) { dev_free(bigger); return fail(e, "hipMemcpy"); }
+    }
+    dev_free(ss->cand_k);
+    ss->cand_k = bigger;
+    return ALN_OK;
+}
+
+static int seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *sp, const aln_seqset_block *b, uint64_t *count)
+{
+    if (!ss || !sp || !b || !count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!aln_prefilter_bits(sp->k, sp->alphabet)) { g_err = "k must lie in 1 .. 8, the alphabet size be at least 1 and alphabet^k at most 2^18"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ss->kmer_k || sp->k != ss->kmer_k || sp->alphabet != ss->kmer_alphabet) { g_err = "no k-mer index of this k and alphabet: aln_seqset_kmer_index builds it"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->min_per_1024 > ALN_PREFILTER_MAX_PER_1024) { g_err = "min_per_1024 must lie in 0 .. 1024"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->flags != 0u || sp->reserved != 0u) { g_err = "the spec's flags and reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->chunk_pairs > ALN_PREFILTER_CHUNK_PAIRS) { g_err = "chunk_pairs must lie in 0 .. 2^22"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t pairs = aln_seqset_block_pairs(ss->n, *b);
+    if (pairs == 0) { g_err = "block: a range beyond the set, unequal ranges of an upper block, a reserved word, or no pairs"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    seqset_drop_candidates(ss);
+    const uint64_t per = sp->chunk_pairs ? sp->chunk_pairs : ALN_PREFILTER_CHUNK_PAIRS;
+    const uint64_t t_end = b->t_first + b->t_count;
+    uint64_t total = 0, down = 0;
+    double kernels = 0;
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        int st;
+        for (uint64_t k0 = 0; k0 < pairs; k0 += per) {
+            const uint64_t n = std::min(per, pairs - k0);
+            // the chunk's pairs lie in query rows q_lo .. q_hi; its targets in t_lo .. (one row: exactly its own)
+            uint64_t q_lo, t_a, q_hi, t_b;
+            aln_seqset_unrank(*b, k0, &q_lo, &t_a);
+            aln_seqset_unrank(*b, k0 + n - 1, &q_hi, &t_b);
+            const uint64_t t_lo = q_lo == q_hi ? t_a : (b->upper ? q_lo + 1 : b->t_first);
+            const uint64_t t_count = q_lo == q_hi ? n : t_end - t_lo;
+            if (!aln_prefilter_share_blocks(q_hi - q_lo + 1, t_count)) { g_err = "a sharing chunk of more tiles than a grid holds"; return ALN_ERR_UNSUPPORTED; }
+            uint32_t *tile_count = nullptr, *tile_off = nullptr;
+            if ((st = dev_ensure(ss->pf_shared, 4 * n, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->pf_keep, n, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->pf_out, 4 * n, false)) != ALN_OK) return st;
+            if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(n), &tile_count, &tile_off)) != ALN_OK) return st;
+            if ((st = seqset_cand_room(ss, total, total + n)) != ALN_OK) return st;
+            uint32_t *d_count = ss->misc.as<uint32_t>() + 16;          // (words 0 .. 9 belong to the passes and to best)
+            HIPCHK(hipEventRecord(ss->ev[0], q));
+            aln_prefilter_launch_share(ss->kmer_bits.as<uint32_t>(), ss->kmer_n.as<uint32_t>(), ss->kmer_stride, b, k0, n, q_lo, q_hi - q_lo + 1, t_lo,
+                                       t_count, sp->min_shared, sp->min_per_1024, ss->pf_shared.as<uint32_t>(), ss->pf_keep.as<uint8_t>(), q);
+            HIPCHK(hipGetLastError());
+            aln_prefilter_launch_compact(ss->pf_keep.as<uint8_t>(), ss->pf_shared.as<uint32_t>(), n, k0, tile_count, tile_off, d_count, n,
+                                         ss->cand_k.as<uint64_t>() + total, ss->pf_out.as<uint32_t>(), q);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ss->ev[1], q));
+            uint32_t got = 0;
+            HIPCHK(hipMemcpyAsync(&got, d_count, 4, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipStreamSynchronize(q));
+            kernels += ev_ms(ss->ev[0], ss->ev[1]);
+            down += 8;
+            if (got > n) { g_err = "the compaction kept more pairs than the chunk holds"; return ALN_ERR_DEVICE; }
+            if (total + got > 0xFFFFFFF0ull) { g_err = "too many candidates"; return ALN_ERR_UNSUPPORTED; }
+            if (got) {
+                ss->cand_pair.resize(total + got); ss->cand_shared.resize(total + got);
+                HIPCHK(hipMemcpy(ss->cand_pair.data() + total, ss->cand_k.as<uint64_t>() + total, 8ull * got, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(ss->cand_shared.data() + total, ss->pf_out.p, 4ull * got, hipMemcpyDeviceToHost));
+                down += 12ull * got;
+                // the host indexes its tables with this list: pairs of the chunk, ascending
+                for (uint64_t h = total; h < total + got; ++h)
+                    if (ss->cand_pair[h] < k0 || ss->cand_pair[h] - k0 >= n || (h > total && ss->cand_pair[h] <= ss->cand_pair[h - 1])) { g_err = "the candidate list is not an ascending list of the chunk's pairs"; return ALN_ERR_DEVICE; }
+            }
+            total += got;
+        }
+        return ALN_OK;
+    };
+    const int st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_drop_candidates(ss); return st; }
+    ss->cand_qs.resize(total); ss->cand_ts.resize(total);
+    for (uint64_t h = 0; h < total; ++h) {
+        uint64_t sq, tq;
+        aln_seqset_unrank(*b, ss->cand_pair[h], &sq, &tq);
+        ss->cand_qs[h] = (uint32_t)sq; ss->cand_ts[h] = (uint32_t)tq;
+    }
+    ss->cand = true;
+    ss->cand_block = *b;
+    *count = total;
+    ss->ms[2] = kernels;
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 0;
+    ss->bytes[1] = down;               // 12 bytes per candidate and the 8 of a chunk's count
+    return ALN_OK;
+}
+
+static int seqset_cand_check(aln_seqset *ss)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ss->cand) { g_err = "no candidate list: aln_seqset_prefilter has not run, or a new k-mer index has replaced it"; return ALN_ERR_INVALID_ARGUMENT; }
+    return ALN_OK;
+}
+
+// the chunks of a pass over the candidate list: counts of consecutive list positions, cut as seqset_chunks cuts a block
+static void seqset_list_chunks(const aln_seqset *ss, const Call &c, std::vector<uint64_t> &counts)
+{
+    counts.clear();
+    const uint64_t pairs = ss->cand_pair.size();
+    if (!pairs) return;
+    double total = 0;
+    for (uint64_t h = 0; h < pairs; ++h) total += (double)ss->len[ss->cand_qs[h]] * (double)ss->len[ss->cand_ts[h]];
+    bool forced = false;
+    const double target = seqset_chunk_target(c, total, pairs, &forced);
+    if (pairs <= ALN_SEQSET_CHUNK_PAIRS && (total <= 1.5 * target || (!forced && total <= 2.0e10))) { counts.push_back(pairs); return; }
+    uint64_t n = 0;
+    double acc = 0, done = 0;
+    for (uint64_t h = 0; h < pairs; ++h) {
+        acc += (double)ss->len[ss->cand_qs[h]] * (double)ss->len[ss->cand_ts[h]];
+        ++n;
+        if (n >= ALN_SEQSET_CHUNK_PAIRS || (acc >= target && (total - done - acc >= 0.25 * target || h + 1 == pairs))) {
+            counts.push_back(n);
+            done += acc; acc = 0; n = 0;
+        }
+    }
+    if (n) counts.push_back(n);
+}
+
+// One pass over the candidate list, as seqset_pass_chunks runs one over a block: per chunk the list expansion, chunk_plan, the staged
+// batch's launches and the gather.  f / status (optional) are indexed by list position.  select: the list POSITIONS of the candidates
+// with status ALN_OK and f >= f_min are appended to ss->hit_pair (the caller turns them into pair numbers), their f to hit_score.
+static int seqset_list_pass_chunks(aln_seqset *ss, const Call &c, double *f, int32_t *status, bool select, double f_min, int *first_bad, Chunk *plans)
+{
+    Slot &s = *ss->slot;
+    hipStream_t q = s.stream;
+    std::vector<uint64_t> counts;
+    seqset_list_chunks(ss, c, counts);
+    const bool want_out = f != nullptr || status != nullptr;
+    std::vector<uint64_t> qo, ql, to, tl;
+    uint64_t prev_k0 = 0, prev_n = 0;
+    bool timed = false;
+    int st = ALN_OK;
+    auto collect = [&]() -> int {
+        if (timed) { ss->ms[0] += ev_ms(ss->ev[0], ss->ev[1]); timed = false; }
+        if (!prev_n) return ALN_OK;
+        const uint8_t *h = ss->h_out.as<uint8_t>();
+        const uint64_t *misc = reinterpret_cast<const uint64_t *>(h);
+        if (f) memcpy(f + prev_k0, h + 256, 8 * prev_n);
+        if (status) memcpy(status + prev_k0, h + 256 + 8 * prev_n, 4 * prev_n);
+        if (*first_bad == ALN_OK && misc[1] != 0) *first_bad = (int)(misc[1] & 0xffu);
+        const uint64_t got = (uint32_t)misc[0];
+        if (select && got) {
+            const size_t at = ss->hit_pair.size();
+            ss->hit_pair.resize(at + got); ss->hit_score.resize(at + got);
+            HIPCHK(hipMemcpy(ss->hit_pair.data() + at, ss->hit_k.p, 8 * got, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(ss->hit_score.data() + at, ss->hit_f.p, 8 * got, hipMemcpyDeviceToHost));
+            ss->bytes[1] += 16 * got;
+        }
+        prev_n = 0;
+        return ALN_OK;
+    };
+    uint64_t k0 = 0;
+    for (size_t j = 0; j < counts.size(); ++j) {
+        const uint64_t n = counts[j];
+        Chunk &k = plans[j & 1];
+        qo.resize(n); ql.resize(n); to.resize(n); tl.resize(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint32_t cq = ss->cand_qs[k0 + i], ct = ss->cand_ts[k0 + i];
+            qo[i] = ss->off[cq]; ql[i] = ss->len[cq]; to[i] = ss->off[ct]; tl[i] = ss->len[ct];
+        }
+        k.reset();
+        if ((st = chunk_plan(ss->ctx, c, qo.data(), ql.data(), to.data(), tl.data(), 0, n, counts.size() == 1, k, counts.size() > 4)) != ALN_OK) break;
+        for (uint64_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[i]; k.descs[i].t_off = to[i]; }
+        k.seq_direct = true; k.seq_lo = 0; k.seq_span = ss->total;
+        bool identity = k.n_small == n;
+        for (uint64_t i = 0; i < n && identity; ++i) identity = k.order[i] == (uint32_t)i;
+        HIPCHK(hipStreamSynchronize(q));
+        if ((st = collect()) != ALN_OK) break;
+        uint32_t *tile_count = nullptr, *tile_off = nullptr;
+        if ((st = seqset_chunk_ensure(ss, c, k, n, want_out, select, &tile_count, &tile_off)) != ALN_OK) break;
+        if (j == 0) {
+            if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) break;
+            ss->bytes[0] += c.md.size() * (c.is_int ? 4 : 8);
+        }
+        HIPCHK(hipMemsetAsync(ss->misc.p, 0, 16, q));
+        aln_prefilter_launch_expand_list(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), n, ss->cand_k.as<uint64_t>() + k0, &ss->cand_block,
+                                         ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), q);
+        HIPCHK(hipGetLastError());
+        if (!identity && k.n_small) {
+            HIPCHK(hipMemcpyAsync(s.order.p, k.order.data(), 4 * k.n_small, hipMemcpyHostToDevice, q));
+            ss->bytes[0] += 4 * k.n_small;
+        }
+        if ((st = slot_launch(ss->ctx, s, c, k, q, ss->ev, nullptr)) != ALN_OK) break;
+        timed = true;
+        aln_seqset_launch_gather(s.results.as<aln_pair_result>(), ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), n,
+                                 reinterpret_cast<unsigned long long *>(ss->misc.as<uint8_t>() + 8), q);
+        HIPCHK(hipGetLastError());
+        if (select) {
+            aln_seqset_launch_select(s.results.as<aln_pair_result>(), n, k0, f_min, tile_count, tile_off, ss->misc.as<uint32_t>(), ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
+            HIPCHK(hipGetLastError());
+        }
+        uint8_t *h = ss->h_out.as<uint8_t>();
+        HIPCHK(hipMemcpyAsync(h, ss->misc.p, 16, hipMemcpyDeviceToHost, q));
+        ss->bytes[1] += 16;
+        if (f) { HIPCHK(hipMemcpyAsync(h + 256, ss->fbuf.p, 8 * n, hipMemcpyDeviceToHost, q)); ss->bytes[1] += 8 * n; }
+        if (status) { HIPCHK(hipMemcpyAsync(h + 256 + 8 * n, ss->stbuf.p, 4 * n, hipMemcpyDeviceToHost, q)); ss->bytes[1] += 4 * n; }
+        prev_k0 = k0; prev_n = n;
+        k0 += n;
+    }
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    HIPCHK(hipStreamSynchronize(q));
+    return collect();
+}
+
+static int seqset_list_pass(aln_seqset *ss, const Call &c, double *f, int32_t *status, bool select, double f_min, int *first_bad)
+{
+    Chunk plans[2];
+    const int st = seqset_list_pass_chunks(ss, c, f, status, select, f_min, first_bad, plans);
+    if (st != ALN_OK) (void)hipStreamSynchronize(ss->slot->stream);
+    return st;
+}
+
+static int seqset_candidate_scores(aln_seqset *ss, const aln_params *params, double *f, int32_t *status)
+{
+    int st = seqset_cand_check(ss);
+    if (st != ALN_OK) return st;
+    Call c;
+    if ((st = seqset_call(ss, params, &ss->cand_block, ALN_OUT_SCORE, c)) != ALN_OK) return st;
+    if (!f) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    HIPCHK(hipStreamSynchronize(ss->slot->stream));
+    seqset_begin(ss);
+    const auto t0 = std::chrono::steady_clock::now();
+    int bad = ALN_OK;
+    st = seqset_list_pass(ss, c, f, status, false, 0.0, &bad);
+    ss->ms[3] = wall_ms(t0);
+    if (st != ALN_OK) return st;
+    if (!status && bad != ALN_OK) { g_err = "a pair failed"; return bad; }
+    return ALN_OK;
+}
+
+static int seqset_candidate_hits(aln_seqset *ss, const aln_params *params, double f_min, uint64_t *count)
+{
+    int st = seqset_cand_check(ss);
+    if (st != ALN_OK) return st;
+    Call c, ct;
+    const aln_seqset_block *b = &ss->cand_block;
+    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE, c)) != ALN_OK) return st;
+    if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE | ALN_OUT_TRACEBACK, ct)) != ALN_OK) return st;
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    HIPCHK(hipStreamSynchronize(ss->slot->stream));
+    seqset_begin(ss);
+    *count = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    int bad = ALN_OK;
+    if ((st = seqset_list_pass(ss, c, nullptr, nullptr, true, f_min, &bad)) != ALN_OK) { seqset_begin(ss); return st; }
+    // the selection numbered the candidates by list position: the held list speaks of pairs of the block
+    for (uint64_t &p : ss->hit_pair) {
+        if (p >= ss->cand_pair.size()) { g_err = "the selection's list leaves the candidate list"; seqset_begin(ss); return ALN_ERR_DEVICE; }
+        p = ss->cand_pair[p];
+    }
+    if ((st = seqset_hold_list(ss, ct, b)) != ALN_OK) { seqset_begin(ss); return st; }
+    ss->ms[3] = wall_ms(t0);
+    ss->held = true;
+    ss->held_block = *b;
+    *count = ss->hit_pair.size();
+    return ALN_OK;
+}
+
+// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
+#define ALN_PREFILTER_GUARDED(ss, call)                                                           \
+    try {                                                                                         \
+        return call;                                                                              \
+    } catch (const std::bad_alloc &) {                                                            \
+        if ((ss) && (ss)->slot && (ss)->slot->stream) (void)hipDeviceSynchronize();               \
+        g_err = "out of host memory";                                                             \
+        return ALN_ERR_OOM;                                                                       \
+    }
+
+extern "C" int aln_seqset_kmer_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
+{
+    ALN_PREFILTER_GUARDED(ss, seqset_kmer_index(ss, k, alphabet, n_words))
+}
+
+extern "C" int aln_seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *spec, const aln_seqset_block *b, uint64_t *count)
+{
+    ALN_PREFILTER_GUARDED(ss, seqset_prefilter(ss, spec, b, count))
+}
+
+extern "C" int aln_seqset_candidates(aln_seqset *ss, uint64_t first, uint64_t n, uint64_t *pair_index, uint32_t *q_seq, uint32_t *t_seq,
+                                     uint32_t *shared)
+{
+    int st = seqset_cand_check(ss);
+    if (st != ALN_OK) return st;
+    const uint64_t have = ss->cand_pair.size();
+    if (first > have || n > have - first) { g_err = "range beyond the candidate list"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && (!pair_index || !q_seq || !t_seq || !shared)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    for (uint64_t i = 0; i < n; ++i) {
+        pair_index[i] = ss->cand_pair[first + i]; q_seq[i] = ss->cand_qs[first + i]; t_seq[i] = ss->cand_ts[first + i];
+        shared[i] = ss->cand_shared[first + i];
+    }
+    return ALN_OK;                       // (no byte moves and no kernel runs: the stats stay as they are)
+}
+
+extern "C" int aln_seqset_candidate_scores(aln_seqset *ss, const aln_params *params, double *f, int32_t *status)
+{
+    ALN_PREFILTER_GUARDED(ss, seqset_candidate_scores(ss, params, f, status))
+}
+
+extern "C" int aln_seqset_candidate_hits(aln_seqset *ss, const aln_params *params, double f_min, uint64_t *count)
+{
+    ALN_PREFILTER_GUARDED(ss, seqset_candidate_hits(ss, params, f_min, count))
 }
 
 static int seqset_held_check(aln_seqset *ss)

@@ -1,4 +1,4 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip and aln_cluster.hip define
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip and aln_prefilter.hip define
 // and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
 #pragma once
@@ -112,5 +112,24 @@ uint64_t aln_best_tiles(uint64_t rows);
 void aln_best_launch_count(const uint32_t *run_n, uint64_t rows, uint32_t *tile_count, uint64_t *tile_off, uint64_t *total, hipStream_t s);
 void aln_best_launch_emit(const uint64_t *run_key, const uint32_t *run_t, const uint32_t *run_n, uint64_t rows, uint32_t slots,
                           const aln_seqset_block *block, const uint64_t *tile_off, uint64_t cap, uint64_t *out_k, double *out_f, hipStream_t s);
+
+// ---- aln_prefilter.hip: the k-mer prefilter of a sequence set (aln_prefilter_rules.h)
+// table: n_seqs rows of `stride` elements; n_words: n_seqs
+void aln_prefilter_launch_index(const uint8_t *seqs, const uint64_t *seq_off, const uint32_t *seq_len, uint64_t n_seqs, uint32_t k,
+                                uint32_t alphabet, uint32_t elements, uint32_t stride, uint32_t *table, uint32_t *n_words, hipStream_t s);
+// workgroups of the sharing kernel for query rows q_rows and targets t_count (0: more than a grid holds)
+uint32_t aln_prefilter_share_blocks(uint64_t q_rows, uint64_t t_count);
+// pairs k0 .. k0 + n - 1 of the block, whose queries are rows q_lo .. q_lo + q_rows - 1 and whose targets lie in t_lo .. t_lo +
+// t_count - 1 (absolute sequence numbers): shared[k - k0] and keep[k - k0] of every one of them
+void aln_prefilter_launch_share(const uint32_t *table, const uint32_t *n_words, uint32_t stride, const aln_seqset_block *block, uint64_t k0,
+                                uint64_t n, uint64_t q_lo, uint64_t q_rows, uint64_t t_lo, uint64_t t_count, uint32_t min_shared,
+                                uint32_t min_per_1024, uint32_t *shared, uint8_t *keep, hipStream_t s);
+// tile_count / tile_off: aln_seqset_tiles(n) words each; the kept pairs of the chunk in ascending order: out_k (block pair numbers)
+// and out_shared, `room` entries each; count[0]: how many
+void aln_prefilter_launch_compact(const uint8_t *keep, const uint32_t *shared, uint64_t n, uint64_t k0, uint32_t *tile_count,
+                                  uint32_t *tile_off, uint32_t *count, uint64_t room, uint64_t *out_k, uint32_t *out_shared, hipStream_t s);
+// descriptor i of the chunk = pair list[i] of the block (the sibling of aln_seqset_launch_expand)
+void aln_prefilter_launch_expand_list(PairDesc *descs, uint32_t *order, uint64_t n, const uint64_t *list, const aln_seqset_block *block,
+                                      const uint64_t *seq_off, const uint32_t *seq_len, hipStream_t s);
 
 }

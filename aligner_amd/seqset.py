@@ -188,11 +188,76 @@ class SeqSet:
         runtime.raise_for_status(st, "aln_seqset_best")
         return BestHits(self, int(count.value), semantics)
 
+    def kmer_index(self, k, alphabet_size):
+        """aln_seqset_kmer_index: builds (or replaces) the resident k-mer bitmaps -- words of k residues with every code below
+        alphabet_size, alphabet_size ** k <= 2 ** 18 -- and returns n(s), the number of distinct words, of every sequence (uint32).
+        Any candidate list is dropped."""
+        n_words = np.zeros(len(self), dtype=np.uint32)
+        st = self.lib.aln_seqset_kmer_index(self.handle, int(k), int(alphabet_size), n_words.ctypes.data)
+        runtime.raise_for_status(st, "aln_seqset_kmer_index")
+        self._kmer = (int(k), int(alphabet_size))
+        return n_words
+
+    def prefilter(self, k, alphabet_size, min_shared=0, min_per_1024=0, block=None, chunk_pairs=0):
+        """aln_seqset_prefilter: the pairs of the block whose sequences share at least min_shared distinct words, and at least
+        min_per_1024 / 1024 of the smaller of their two word counts (integer rule: aligner_amd/csrc/aln_prefilter_rules.h), selected
+        on the device.  Builds the index if none of this (k, alphabet_size) is there.  Returns a Candidates (valid until the next
+        kmer_index / prefilter on this set; score, hits and best leave it alone)."""
+        b, n = self._checked(block)
+        if getattr(self, "_kmer", None) != (int(k), int(alphabet_size)):
+            self.kmer_index(k, alphabet_size)
+        spec = _ffi.PrefilterSpec(int(k), int(alphabet_size), int(min_shared), int(min_per_1024), int(chunk_pairs), 0, 0)
+        count = C.c_uint64(0)
+        st = self.lib.aln_seqset_prefilter(self.handle, C.byref(spec), C.byref(b), C.byref(count))
+        runtime.raise_for_status(st, "aln_seqset_prefilter")
+        return Candidates(self, int(count.value))
+
     def stats(self):
-        """(after best, fetch_kernel_ms is the selection kernels' time until a held fetch overwrites it)"""
+        """(after best, fetch_kernel_ms is the selection kernels' time until a held fetch overwrites it; after kmer_index and
+        prefilter it is the index and sharing kernels' time)"""
         ms, by = (C.c_double * 4)(), (C.c_uint64 * 2)()
         runtime.raise_for_status(self.lib.aln_seqset_stats(self.handle, ms, by), "aln_seqset_stats")
         return dict(fill_ms=ms[0], refill_ms=ms[1], fetch_kernel_ms=ms[2], wall_ms=ms[3], bytes_up=int(by[0]), bytes_down=int(by[1]))
+
+
+class Candidates:
+    """The candidate list of SeqSet.prefilter: .index (pair numbers in the block), .q, .t (sequence numbers) and .shared (distinct
+    words both sequences hold) in ascending pair order.  .score(...) aligns the candidates only, .hits(...) holds those at or above
+    a threshold as SeqSet.hits would."""
+
+    def __init__(self, owner, count):
+        self.owner, self.count = owner, count
+        self.index = np.zeros(count, dtype=np.uint64)
+        self.q = np.zeros(count, dtype=np.uint32)
+        self.t = np.zeros(count, dtype=np.uint32)
+        self.shared = np.zeros(count, dtype=np.uint32)
+        if count:
+            st = owner.lib.aln_seqset_candidates(owner.handle, 0, count, self.index.ctypes.data, self.q.ctypes.data, self.t.ctypes.data,
+                                                 self.shared.ctypes.data)
+            runtime.raise_for_status(st, "aln_seqset_candidates")
+
+    def __len__(self):
+        return self.count
+
+    def score(self, matrix, del_, ext, semantics=_ffi.CORE_LOCAL, blank=98, **kw):
+        """(f, status) of every candidate, in list order: what SeqSet.score gives for those pairs, bit for bit."""
+        o = self.owner
+        p, keep = runtime.make_params(semantics, del_, ext, matrix, outputs=_ffi.OUT_SCORE, blank=blank, **kw)
+        f = np.zeros(self.count, dtype=np.float64)
+        status = np.zeros(self.count, dtype=np.int32)
+        st = o.lib.aln_seqset_candidate_scores(o.handle, C.byref(p), f.ctypes.data, status.ctypes.data)
+        runtime.raise_for_status(st, "aln_seqset_candidate_scores")
+        return f, status
+
+    def hits(self, matrix, del_, ext, f_min, semantics=_ffi.CORE_LOCAL, blank=98, **kw):
+        """A held pass over the candidates: those with f >= f_min, aligned.  Returns a HeldHits whose .index are pair numbers of
+        the prefilter's block."""
+        o = self.owner
+        p, keep = runtime.make_params(semantics, del_, ext, matrix, blank=blank, **kw)
+        count = C.c_uint64(0)
+        st = o.lib.aln_seqset_candidate_hits(o.handle, C.byref(p), float(f_min), C.byref(count))
+        runtime.raise_for_status(st, "aln_seqset_candidate_hits")
+        return HeldHits(o, int(count.value), semantics)
 
 
 class HeldHits:
@@ -407,11 +472,19 @@ class BestHits(HeldHits):
                 yield int(self.q[part[0]]), part
 
 
-def all_pairs(records, matrix, del_, ext, f_min=None, alphabet=Protein, semantics=_ffi.CORE_LOCAL, device=None, **kw):
+def all_pairs(records, matrix, del_, ext, f_min=None, alphabet=Protein, semantics=_ffi.CORE_LOCAL, device=None, prefilter=None, **kw):
     """Every pair i < j of `records` (code arrays or strings) in generate_pairs order.  Without f_min: (q, t, f, status) arrays over
-    all pairs.  With f_min: (q, t, f, alignments) of the pairs with f >= f_min."""
+    all pairs.  With f_min: (q, t, f, alignments) of the pairs with f >= f_min.  prefilter=dict(k=, alphabet_size=[, min_shared=,
+    min_per_1024=]): only the candidates of SeqSet.prefilter are aligned, and the arrays run over them."""
     with SeqSet(records, alphabet, device=device) as ss:
         n = len(ss)
+        if prefilter is not None:
+            cand = ss.prefilter(block=None, **prefilter)
+            if f_min is None:
+                f, status = cand.score(matrix, del_, ext, semantics=semantics, **kw)
+                return cand.q, cand.t, f, status
+            held = cand.hits(matrix, del_, ext, f_min, semantics=semantics, **kw)
+            return held.q, held.t, held.f, held.alignments()
         if f_min is None:
             f, status = ss.score(matrix, del_, ext, None, semantics=semantics, **kw)
             q, t = np.triu_indices(n, 1)
