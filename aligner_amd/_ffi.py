@@ -58,6 +58,8 @@ PREFILTER_EXPORTS = ["aln_seqset_kmer_index", "aln_seqset_prefilter", "aln_seqse
                      "aln_seqset_candidate_hits"]
 PREFILTER_MAX_K, PREFILTER_MAX_BITS, PREFILTER_CHUNK_PAIRS = 8, 1 << 18, 1 << 22      # aligner_amd/csrc/aln_prefilter_rules.h
 PREFILTER_MAX_CANDIDATES = 0xFFFFFFF0
+# every symbol the companion header include/aligner_hip_search.h declares (the same library, as above)
+SEARCH_EXPORTS = ["aln_seqset_candidate_best"]
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
 TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
 # aln_pairset_loop_step's causes (aligner_amd/csrc/aln_loop_rules.h)
@@ -314,6 +316,8 @@ def load():
     lib.aln_seqset_candidate_scores.argtypes = [vp, C.POINTER(Params), vp, vp]
     lib.aln_seqset_candidate_hits.restype = i
     lib.aln_seqset_candidate_hits.argtypes = [vp, C.POINTER(Params), C.c_double, C.POINTER(C.c_uint64)]
+    lib.aln_seqset_candidate_best.restype = i
+    lib.aln_seqset_candidate_best.argtypes = [vp, C.POINTER(Params), C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 

@@ -36,7 +36,13 @@ default 0) -- are aligned at all.  Words are counted over the first A codes of t
 standard residues, or 4 with --dna); a window that touches any other code is no word; A^K may not exceed 2^18.  With --f-min F the rows
 and everything downstream (--report, --min-*, --shuffles, --cluster) are those of the candidates with f >= F; without it one row per
 candidate is printed: `q_head,t_head,f,shared`.  The surviving alignments are bit for bit those of the unfiltered run; which pairs
-survive is the thresholds' business.  Not with --best or --heuristic: a per-row selection over a sparse candidate list is not built.
+survive is the thresholds' business.  Not with --best (which aligns every pair; see --best-candidates) or --heuristic.
+
+With --kmer K --best-candidates N the question of --best is asked of the candidates only: per record, its N best partners among the
+records it shares enough words with, optionally only those with f >= F (--f-min is the floor, as with --best), selected on the
+device; prints --best's rows, `q_head,rank,t_head,f`, and takes --report, --min-*, --shuffles and --cluster on top.  The prefilter
+runs on the full square of the records, which lists (q, t), (t, q) and every record's pair with itself: the self pairs are aligned
+and then skipped.  Not with --best or --heuristic.
 """
 import argparse
 import sys
@@ -47,7 +53,7 @@ from . import _ffi
 from .enums import DNA, Protein
 from .fasta import encode_records, read_fasta
 from .matrices import get_blosum62, nucleotide_matrix
-from .seqset import SeqSet
+from .seqset import SeqSet, rectangle
 
 
 MAX_TRIM = 6          # tail residues a shuffled copy may lose (statistics/mod.rs:312-314)
@@ -78,13 +84,26 @@ def main(argv=None):
     ap.add_argument("--min-shared", type=int, default=None, metavar="N", help="with --kmer: candidates share at least N distinct words")
     ap.add_argument("--min-shared-per-1024", type=int, default=None, metavar="P", help="with --kmer: candidates share at least P / 1024 of the smaller record's distinct words (0 .. 1024)")
     ap.add_argument("--kmer-alphabet", type=int, default=None, metavar="A", help="with --kmer: words use the first A codes of the alphabet (default 20; 4 with --dna)")
+    ap.add_argument("--best-candidates", type=int, default=None, metavar="N",
+                    help="with --kmer: per record its N best partners (1 .. %d) among its candidates on the full square; self pairs are aligned, then skipped" % _ffi.SEQSET_BEST_MAX)
     a = ap.parse_args(argv)
+    if a.best_candidates is not None:
+        if a.kmer is None:
+            ap.error("--best-candidates selects among the prefilter's candidates: give --kmer K")
+        if a.best is not None:
+            ap.error("--best-candidates with --best: --best aligns every pair, --best-candidates only the candidates of --kmer; give one")
+        if a.heuristic:
+            ap.error("--best-candidates selects by the score of the plain alignment: not with --heuristic")
+        if not 1 <= a.best_candidates <= _ffi.SEQSET_BEST_MAX:
+            ap.error("--best-candidates: N must lie in 1 .. %d" % _ffi.SEQSET_BEST_MAX)
     if a.kmer is None:
         if a.min_shared is not None or a.min_shared_per_1024 is not None or a.kmer_alphabet is not None:
             ap.error("--min-shared / --min-shared-per-1024 / --kmer-alphabet are the prefilter's thresholds: give --kmer K")
     else:
-        if a.best is not None or a.heuristic:
-            ap.error("--kmer with --best or --heuristic: a per-row selection and the matrix loop over a sparse candidate list are not built")
+        if a.best is not None:
+            ap.error("--kmer with --best: --best aligns every pair; the per-record selection among the candidates is --best-candidates N")
+        if a.heuristic:
+            ap.error("--kmer with --heuristic: the matrix loop over a sparse candidate list is not built")
         kmer_alphabet = a.kmer_alphabet if a.kmer_alphabet is not None else (4 if a.dna else 20)
         if not 1 <= a.kmer <= _ffi.PREFILTER_MAX_K or kmer_alphabet < 1 or kmer_alphabet ** a.kmer > _ffi.PREFILTER_MAX_BITS:
             ap.error("--kmer: K must lie in 1 .. %d and A^K may not exceed 2^18" % _ffi.PREFILTER_MAX_K)
@@ -96,20 +115,20 @@ def main(argv=None):
     if a.report or filtered:
         if a.heuristic:
             ap.error("--report / --min-identity / --min-q-cover / --min-t-cover describe the plain alignment: not with --heuristic")
-        if a.best is None and a.f_min is None:
-            ap.error("--report / --min-identity / --min-q-cover / --min-t-cover work on held hits: give --best K or --f-min F")
+        if a.best is None and a.best_candidates is None and a.f_min is None:
+            ap.error("--report / --min-identity / --min-q-cover / --min-t-cover work on held hits: give --best K, --best-candidates N or --f-min F")
     if a.cluster is not None:
         if a.heuristic:
             ap.error("--cluster groups by the plain alignment's hits: not with --heuristic")
-        if a.best is None and a.f_min is None:
-            ap.error("--cluster works on held hits: give --best K or --f-min F")
+        if a.best is None and a.best_candidates is None and a.f_min is None:
+            ap.error("--cluster works on held hits: give --best K, --best-candidates N or --f-min F")
         if a.shuffles is not None or a.report:
             ap.error("--cluster replaces the hit rows: not with --shuffles or --report")
     if a.shuffles is not None:
         if a.heuristic:
             ap.error("--shuffles asks about the plain alignment's score: not with --heuristic")
-        if a.best is None and a.f_min is None:
-            ap.error("--shuffles works on held hits: give --best K or --f-min F")
+        if a.best is None and a.best_candidates is None and a.f_min is None:
+            ap.error("--shuffles works on held hits: give --best K, --best-candidates N or --f-min F")
         if not 1 <= a.shuffles <= _ffi.SHUFFLE_MAX_COPIES:
             ap.error("--shuffles: N must lie in 1 .. %d" % _ffi.SHUFFLE_MAX_COPIES)
     elif a.seed is not None:
@@ -160,13 +179,19 @@ def main(argv=None):
                                                             float(x["t_cover"]), int(x["gap_opens"]), int(x["gaps"]))
         return rows
 
-    if a.best is not None:
+    if a.best is not None or a.best_candidates is not None:
         if a.heuristic:
             ap.error("--best selects by the score of the plain alignment: not with --heuristic")
-        if not 1 <= a.best <= _ffi.SEQSET_BEST_MAX:
+        if a.best is not None and not 1 <= a.best <= _ffi.SEQSET_BEST_MAX:
             ap.error("--best: K must lie in 1 .. %d" % _ffi.SEQSET_BEST_MAX)
+        floor = float("-inf") if a.f_min is None else a.f_min
         with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
-            held = ss.best(matrix, a.del_, a.ext, a.best, f_min=float("-inf") if a.f_min is None else a.f_min, skip_self=True, semantics=sem)
+            if a.best is not None:
+                held = ss.best(matrix, a.del_, a.ext, a.best, f_min=floor, skip_self=True, semantics=sem)
+            else:
+                cand = ss.prefilter(a.kmer, kmer_alphabet, min_shared=a.min_shared or 0, min_per_1024=a.min_shared_per_1024 or 0,
+                                    block=rectangle(0, len(ss), 0, len(ss)))
+                held = cand.best(matrix, a.del_, a.ext, a.best_candidates, f_min=floor, skip_self=True, semantics=sem)
             if a.cluster is not None:
                 clustered(held)
                 return 0

@@ -46,6 +46,7 @@
 #include "aln_scheme_rules.h"
 #include "aln_seqset_rules.h"
 #include "aln_best_rules.h"
+#include "aln_search_rules.h"
 #include "aln_shuffle_rules.h"
 #include "aln_signif_rules.h"
 #include "aln_report_rules.h"
@@ -299,7 +300,7 @@ static void warm_context(aln_ctx *c)
         if (hipSetDevice(c->devs[d]->device) != hipSuccess) continue;
         (void)aln_warm_single(); (void)aln_warm_tb(); (void)aln_warm_generic();
         (void)aln_warm_fast_cl(); (void)aln_warm_fast_cl_solo(); (void)aln_warm_fast_rest(); (void)aln_warm_fast_rest_solo();
-        (void)aln_warm_best();
+        (void)aln_warm_best(); (void)aln_warm_search();
         aln_pair_result r;
         (void)aln_align_pair(c, &p, q.data(), L, t.data(), L, &r, qa.data(), ta.data(), nullptr, nullptr);   // devices in turn
     }
@@ -3203,6 +3204,7 @@ struct aln_seqset : CallStats {
     aln_seqset_block held_block = {0, 0, 0, 0, 0, 0};   // the block of the held pass (aln_seqset_held_cluster: its ranges are the nodes)
     // aln_seqset_best: a chunk's piece lists (key | target | count per piece) and the rows' running lists (aln_best.hip)
     DevBuf cand_key, cand_t, cand_n, run_key, run_t, run_n;
+    DevBuf row_first;                 // aln_seqset_candidate_best: where every row of the block starts in the candidate list (aln_search.hip)
     // aln_seqset_held_report / _filter: the scheme's bit table, the reports (of a list, or of all held hits), the kept positions | records
     DevBuf rep_bits, reports, rep_pos, rep_out;
     DevBuf cluster;                   // aln_seqset_held_cluster: the call's tables, one arena
@@ -3245,7 +3247,7 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     held_free(ss->held_store);
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
                    &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster, &ss->kmer_bits, &ss->kmer_n,
-                   &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out};
+                   &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
@@ -3589,6 +3591,47 @@ extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const a
     return ALN_OK;
 }
 
+// The finish of a per-row selection (aln_seqset_best, aln_seqset_candidate_best): the rows' counts -> offsets and the total, then
+// (sized for exactly the total) the ascending pair list of block b in ss->hit_pair / hit_score.  On a failure the caller waits for
+// the stream and clears the list.
+static int seqset_best_finish(aln_seqset *ss, const aln_seqset_block *b, uint32_t slots, uint32_t *tile_count, uint64_t *tile_off, uint64_t *out_total)
+{
+    hipStream_t q = ss->slot->stream;
+    const uint64_t rows = b->q_count;
+    uint64_t *d_total = reinterpret_cast<uint64_t *>(ss->misc.as<uint8_t>() + 32);
+    uint64_t total = 0;
+    HIPCHK(hipEventRecord(ss->ev[4], q));
+    aln_best_launch_count(ss->run_n.as<uint32_t>(), rows, tile_count, tile_off, d_total, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, q));
+    HIPCHK(hipStreamSynchronize(q));
+    ss->bytes[1] += 8;
+    if (total > 0xFFFFFFF0ull) { g_err = "too many hits"; return ALN_ERR_UNSUPPORTED; }
+    if (total) {
+        int e = dev_ensure(ss->hit_k, 8 * total, false);
+        if (e == ALN_OK) e = dev_ensure(ss->hit_f, 8 * total, false);
+        if (e != ALN_OK) return e;
+        aln_best_launch_emit(ss->run_key.as<uint64_t>(), ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), rows, slots, b, tile_off, total,
+                             ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(ss->ev[5], q));
+    ss->hit_pair.resize(total); ss->hit_score.resize(total);
+    if (total) {
+        HIPCHK(hipMemcpyAsync(ss->hit_pair.data(), ss->hit_k.p, 8 * total, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(ss->hit_score.data(), ss->hit_f.p, 8 * total, hipMemcpyDeviceToHost, q));
+        ss->bytes[1] += 16 * total;
+    }
+    HIPCHK(hipStreamSynchronize(q));
+    ss->ms[2] += ev_ms(ss->ev[4], ss->ev[5]);
+    // the host indexes its tables with this list: pairs of the block, ascending
+    const uint64_t pairs = aln_seqset_block_pairs(ss->n, *b);
+    for (uint64_t h = 0; h < total; ++h)
+        if (ss->hit_pair[h] >= pairs || (h && ss->hit_pair[h] <= ss->hit_pair[h - 1])) { g_err = "the selection's list is not an ascending list of the block's pairs"; return ALN_ERR_DEVICE; }
+    *out_total = total;
+    return ALN_OK;
+}
+
 // The k best targets per query row: the pass of hits with the per-row selection of aln_best.hip in place of the threshold's, then the
 // rows' lists as one ascending pair list, held like the hits.
 extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, uint32_t k, double f_min, uint32_t flags,
@@ -3621,41 +3664,8 @@ extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const a
     HIPCHK(hipMemsetAsync(ss->run_n.p, 0, 4 * rows, q));
     int bad = ALN_OK;
     if ((st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), nullptr, nullptr, false, 0.0, &bad, &best)) != ALN_OK) { seqset_begin(ss); return st; }
-    // finish: the rows' counts -> offsets and the total, then (sized for exactly the total) the ascending list
-    uint64_t *d_total = reinterpret_cast<uint64_t *>(ss->misc.as<uint8_t>() + 32);
     uint64_t total = 0;
-    auto finish = [&]() -> int {       // (a HIPCHK in here leaves through the exit below, which waits for the stream)
-        HIPCHK(hipEventRecord(ss->ev[4], q));
-        aln_best_launch_count(ss->run_n.as<uint32_t>(), rows, tile_count, tile_off, d_total, q);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, q));
-        HIPCHK(hipStreamSynchronize(q));
-        ss->bytes[1] += 8;
-        if (total > 0xFFFFFFF0ull) { g_err = "too many hits"; return ALN_ERR_UNSUPPORTED; }
-        if (total) {
-            int e = dev_ensure(ss->hit_k, 8 * total, false);
-            if (e == ALN_OK) e = dev_ensure(ss->hit_f, 8 * total, false);
-            if (e != ALN_OK) return e;
-            aln_best_launch_emit(ss->run_key.as<uint64_t>(), ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), rows, best.slots, b, tile_off, total,
-                                 ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipEventRecord(ss->ev[5], q));
-        ss->hit_pair.resize(total); ss->hit_score.resize(total);
-        if (total) {
-            HIPCHK(hipMemcpyAsync(ss->hit_pair.data(), ss->hit_k.p, 8 * total, hipMemcpyDeviceToHost, q));
-            HIPCHK(hipMemcpyAsync(ss->hit_score.data(), ss->hit_f.p, 8 * total, hipMemcpyDeviceToHost, q));
-            ss->bytes[1] += 16 * total;
-        }
-        HIPCHK(hipStreamSynchronize(q));
-        ss->ms[2] += ev_ms(ss->ev[4], ss->ev[5]);
-        // the host indexes its tables with this list: pairs of the block, ascending
-        const uint64_t pairs = aln_seqset_block_pairs(ss->n, *b);
-        for (uint64_t h = 0; h < total; ++h)
-            if (ss->hit_pair[h] >= pairs || (h && ss->hit_pair[h] <= ss->hit_pair[h - 1])) { g_err = "the selection's list is not an ascending list of the block's pairs"; return ALN_ERR_DEVICE; }
-        return ALN_OK;
-    };
-    st = finish();
+    st = seqset_best_finish(ss, b, best.slots, tile_count, tile_off, &total);
     if (st == ALN_OK) st = seqset_hold_list(ss, ct, b);
     if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_begin(ss); return st; }
     ss->ms[3] = wall_ms(t0);
@@ -3846,7 +3856,10 @@ static void seqset_list_chunks(const aln_seqset *ss, const Call &c, std::vector<
 // One pass over the candidate list, as seqset_pass_chunks runs one over a block: per chunk the list expansion, chunk_plan, the staged
 // batch's launches and the gather.  f / status (optional) are indexed by list position.  select: the list POSITIONS of the candidates
 // with status ALN_OK and f >= f_min are appended to ss->hit_pair (the caller turns them into pair numbers), their f to hit_score.
-static int seqset_list_pass_chunks(aln_seqset *ss, const Call &c, double *f, int32_t *status, bool select, double f_min, int *first_bad, Chunk *plans)
+// best: the chunk's f / status go through the list piece and list merge kernels (aln_search.hip) into the rows' running lists
+// (ss->run_*, zeroed by the caller; ss->row_first filled by the caller).
+static int seqset_list_pass_chunks(aln_seqset *ss, const Call &c, double *f, int32_t *status, bool select, double f_min, int *first_bad, Chunk *plans,
+                                   const BestPass *best)
 {
     Slot &s = *ss->slot;
     hipStream_t q = s.stream;
@@ -3858,6 +3871,7 @@ static int seqset_list_pass_chunks(aln_seqset *ss, const Call &c, double *f, int
     bool timed = false;
     int st = ALN_OK;
     auto collect = [&]() -> int {
+        if (timed && best) ss->ms[2] += ev_ms(ss->ev[4], ss->ev[5]);
         if (timed) { ss->ms[0] += ev_ms(ss->ev[0], ss->ev[1]); timed = false; }
         if (!prev_n) return ALN_OK;
         const uint8_t *h = ss->h_out.as<uint8_t>();
@@ -3895,6 +3909,10 @@ static int seqset_list_pass_chunks(aln_seqset *ss, const Call &c, double *f, int
         if ((st = collect()) != ALN_OK) break;
         uint32_t *tile_count = nullptr, *tile_off = nullptr;
         if ((st = seqset_chunk_ensure(ss, c, k, n, want_out, select, &tile_count, &tile_off)) != ALN_OK) break;
+        if (best) {                                    // the chunk's sorted pieces, by chunk position
+            if ((st = dev_ensure(ss->cand_key, 8 * n, false)) != ALN_OK) break;
+            if ((st = dev_ensure(ss->cand_t, 4 * n, false)) != ALN_OK) break;
+        }
         if (j == 0) {
             if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) break;
             ss->bytes[0] += c.md.size() * (c.is_int ? 4 : 8);
@@ -3916,6 +3934,16 @@ static int seqset_list_pass_chunks(aln_seqset *ss, const Call &c, double *f, int
             aln_seqset_launch_select(s.results.as<aln_pair_result>(), n, k0, f_min, tile_count, tile_off, ss->misc.as<uint32_t>(), ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
             HIPCHK(hipGetLastError());
         }
+        if (best) {
+            const uint64_t t_count = ss->cand_block.t_count;
+            const uint64_t row0 = aln_search_row(ss->cand_pair[k0], t_count), row1 = aln_search_row(ss->cand_pair[k0 + n - 1], t_count);
+            HIPCHK(hipEventRecord(ss->ev[4], q));
+            aln_search_launch_chunk(ss->cand_k.as<uint64_t>(), ss->row_first.as<uint32_t>(), ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), k0, n, row0,
+                                    row1 - row0 + 1, &ss->cand_block, best->f_min, best->flags, best->slots, ss->cand_key.as<uint64_t>(),
+                                    ss->cand_t.as<uint32_t>(), ss->run_key.as<uint64_t>(), ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), q);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ss->ev[5], q));
+        }
         uint8_t *h = ss->h_out.as<uint8_t>();
         HIPCHK(hipMemcpyAsync(h, ss->misc.p, 16, hipMemcpyDeviceToHost, q));
         ss->bytes[1] += 16;
@@ -3929,10 +3957,11 @@ static int seqset_list_pass_chunks(aln_seqset *ss, const Call &c, double *f, int
     return collect();
 }
 
-static int seqset_list_pass(aln_seqset *ss, const Call &c, double *f, int32_t *status, bool select, double f_min, int *first_bad)
+static int seqset_list_pass(aln_seqset *ss, const Call &c, double *f, int32_t *status, bool select, double f_min, int *first_bad,
+                            const BestPass *best = nullptr)
 {
     Chunk plans[2];
-    const int st = seqset_list_pass_chunks(ss, c, f, status, select, f_min, first_bad, plans);
+    const int st = seqset_list_pass_chunks(ss, c, f, status, select, f_min, first_bad, plans, best);
     if (st != ALN_OK) (void)hipStreamSynchronize(ss->slot->stream);
     return st;
 }
@@ -3985,6 +4014,60 @@ static int seqset_candidate_hits(aln_seqset *ss, const aln_params *params, doubl
     return ALN_OK;
 }
 
+// The k best targets per query row among the candidates: the list pass with the per-row selection of aln_search.hip, then the finish
+// of aln_seqset_best, held on the prefilter's block.
+static int seqset_candidate_best(aln_seqset *ss, const aln_params *params, uint32_t k, double f_min, uint32_t flags, uint64_t *count)
+{
+    int st = seqset_cand_check(ss);
+    if (st != ALN_OK) return st;
+    Call c, ct;
+    const aln_seqset_block *b = &ss->cand_block;
+    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE, c)) != ALN_OK) return st;
+    if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (k < 1u || k > ALN_SEQSET_BEST_MAX) { g_err = "k must lie in 1 .. ALN_SEQSET_BEST_MAX"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (flags & ~ALN_BEST_SKIP_SELF) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (b->upper) { g_err = "the k best per query are defined on a rectangle: a pair of an upper block belongs to both of its sequences"; return ALN_ERR_UNSUPPORTED; }
+    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE | ALN_OUT_TRACEBACK, ct)) != ALN_OK) return st;
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    seqset_begin(ss);
+    *count = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t rows = b->q_count, listed = ss->cand_pair.size();
+    BestPass best;
+    best.slots = aln_best_slots(k, b->t_count); best.flags = flags; best.f_min = f_min;
+    // the rows' running lists and their places in the candidate list, for this call
+    st = dev_ensure(ss->run_key, 8 * rows * best.slots, false);
+    if (st == ALN_OK) st = dev_ensure(ss->run_t, 4 * rows * best.slots, false);
+    if (st == ALN_OK) st = dev_ensure(ss->run_n, 4 * rows, false);
+    if (st == ALN_OK) st = dev_ensure(ss->row_first, 4 * (rows + 1), false);
+    uint32_t *tile_count;
+    uint64_t *tile_off;
+    if (st == ALN_OK) st = tiles_ensure(ss->tiles, aln_best_tiles(rows), &tile_count, &tile_off);
+    if (st != ALN_OK) return st;
+    HIPCHK(hipMemsetAsync(ss->run_n.p, 0, 4 * rows, q));
+    if (listed) {
+        HIPCHK(hipEventRecord(ss->ev[4], q));
+        aln_search_launch_rows(ss->cand_k.as<uint64_t>(), listed, rows, b->t_count, ss->row_first.as<uint32_t>(), q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[5], q));
+        HIPCHK(hipStreamSynchronize(q));
+        ss->ms[2] += ev_ms(ss->ev[4], ss->ev[5]);
+    }
+    int bad = ALN_OK;
+    if ((st = seqset_list_pass(ss, c, nullptr, nullptr, false, 0.0, &bad, &best)) != ALN_OK) { seqset_begin(ss); return st; }
+    uint64_t total = 0;
+    st = seqset_best_finish(ss, b, best.slots, tile_count, tile_off, &total);
+    if (st == ALN_OK) st = seqset_hold_list(ss, ct, b);
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_begin(ss); return st; }
+    ss->ms[3] = wall_ms(t0);
+    ss->held = true;
+    ss->held_block = *b;
+    *count = total;
+    return ALN_OK;
+}
+
 // (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
 #define ALN_PREFILTER_GUARDED(ss, call)                                                           \
     try {                                                                                         \
@@ -4028,6 +4111,11 @@ extern "C" int aln_seqset_candidate_scores(aln_seqset *ss, const aln_params *par
 extern "C" int aln_seqset_candidate_hits(aln_seqset *ss, const aln_params *params, double f_min, uint64_t *count)
 {
     ALN_PREFILTER_GUARDED(ss, seqset_candidate_hits(ss, params, f_min, count))
+}
+
+extern "C" int aln_seqset_candidate_best(aln_seqset *ss, const aln_params *params, uint32_t k, double f_min, uint32_t flags, uint64_t *count)
+{
+    ALN_PREFILTER_GUARDED(ss, seqset_candidate_best(ss, params, k, f_min, flags, count))
 }
 
 static int seqset_held_check(aln_seqset *ss)

@@ -132,4 +132,14 @@ void aln_prefilter_launch_compact(const uint8_t *keep, const uint32_t *shared, u
 void aln_prefilter_launch_expand_list(PairDesc *descs, uint32_t *order, uint64_t n, const uint64_t *list, const aln_seqset_block *block,
                                       const uint64_t *seq_off, const uint32_t *seq_len, hipStream_t s);
 
+// ---- aln_search.hip: the k best targets per query over a candidate list (aln_search_rules.h)
+int aln_warm_search(void);
+// row_first: q_count + 1 words
+void aln_search_launch_rows(const uint64_t *list, uint64_t count, uint64_t q_count, uint64_t t_count, uint32_t *row_first, hipStream_t s);
+// list positions c0 .. c0 + n - 1 (f / status by chunk position) -> the running lists of the touched rows row0 .. row0 + rows - 1;
+// piece_key / piece_t: n entries
+void aln_search_launch_chunk(const uint64_t *list, const uint32_t *row_first, const double *f, const int32_t *status, uint64_t c0, uint64_t n,
+                             uint64_t row0, uint64_t rows, const aln_seqset_block *block, double f_min, uint32_t flags, uint32_t slots,
+                             uint64_t *piece_key, uint32_t *piece_t, uint64_t *run_key, uint32_t *run_t, uint32_t *run_n, hipStream_t s);
+
 }

@@ -223,7 +223,7 @@ class SeqSet:
 class Candidates:
     """The candidate list of SeqSet.prefilter: .index (pair numbers in the block), .q, .t (sequence numbers) and .shared (distinct
     words both sequences hold) in ascending pair order.  .score(...) aligns the candidates only, .hits(...) holds those at or above
-    a threshold as SeqSet.hits would."""
+    a threshold as SeqSet.hits would, .best(...) the k best of every query's candidates as SeqSet.best would."""
 
     def __init__(self, owner, count):
         self.owner, self.count = owner, count
@@ -258,6 +258,19 @@ class Candidates:
         st = o.lib.aln_seqset_candidate_hits(o.handle, C.byref(p), float(f_min), C.byref(count))
         runtime.raise_for_status(st, "aln_seqset_candidate_hits")
         return HeldHits(o, int(count.value), semantics)
+
+    def best(self, matrix, del_, ext, k, f_min=float("-inf"), skip_self=False, semantics=_ffi.CORE_LOCAL, blank=98, **kw):
+        """A held pass over the candidates: of every query of the prefilter's rectangle the k best targets among its candidates that
+        succeeded with f >= f_min -- higher f first, equal f by the lower target number -- selected on the device and aligned.
+        skip_self leaves a listed (i, i) out (it is aligned, then skipped).  Returns a BestHits whose .index are pair numbers of the
+        prefilter's block; the candidate list stays."""
+        o = self.owner
+        p, keep = runtime.make_params(semantics, del_, ext, matrix, blank=blank, **kw)
+        count = C.c_uint64(0)
+        st = o.lib.aln_seqset_candidate_best(o.handle, C.byref(p), int(k), float(f_min), _ffi.BEST_SKIP_SELF if skip_self else 0,
+                                             C.byref(count))
+        runtime.raise_for_status(st, "aln_seqset_candidate_best")
+        return BestHits(o, int(count.value), semantics)
 
 
 class HeldHits:
