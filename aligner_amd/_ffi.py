@@ -60,6 +60,10 @@ PREFILTER_MAX_K, PREFILTER_MAX_BITS, PREFILTER_CHUNK_PAIRS = 8, 1 << 18, 1 << 22
 PREFILTER_MAX_CANDIDATES = 0xFFFFFFF0
 # every symbol the companion header include/aligner_hip_search.h declares (the same library, as above)
 SEARCH_EXPORTS = ["aln_seqset_candidate_best"]
+# every symbol the companion header include/aligner_hip_profile.h declares (the same library, as above)
+PROFILE_EXPORTS = ["aln_seqset_profile_elements", "aln_seqset_held_profiles"]
+PROFILE_SKIP_SEED = 1           # ALN_PROFILE_SKIP_SEED
+PROFILE_MAX_CODES = 64          # ALN_PROFILE_MAX_CODES
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
 TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
 # aln_pairset_loop_step's causes (aligner_amd/csrc/aln_loop_rules.h)
@@ -141,6 +145,20 @@ class ClusterSummary(C.Structure):
 
 
 assert C.sizeof(ClusterRecord) == 16 and C.sizeof(ClusterSummary) == 48
+
+
+class ProfileRecord(C.Structure):
+    """aln_profile_record: one centre's counters (aligner_amd/csrc/aln_profile_rules.h)."""
+    _fields_ = [("center", C.c_uint32), ("hits", C.c_uint32), ("matched", C.c_uint32), ("deleted", C.c_uint32)]
+
+
+class ProfileSummary(C.Structure):
+    """aln_profile_summary: the counts of one profile call."""
+    _fields_ = [("held", C.c_uint64), ("contributing", C.c_uint64), ("self_pairs", C.c_uint32), ("between_members", C.c_uint32),
+                ("unlisted", C.c_uint32), ("overflow", C.c_uint32), ("elements", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(ProfileRecord) == 16 and C.sizeof(ProfileSummary) == 48
 
 
 class PrefilterSpec(C.Structure):
@@ -318,6 +336,11 @@ def load():
     lib.aln_seqset_candidate_hits.argtypes = [vp, C.POINTER(Params), C.c_double, C.POINTER(C.c_uint64)]
     lib.aln_seqset_candidate_best.restype = i
     lib.aln_seqset_candidate_best.argtypes = [vp, C.POINTER(Params), C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.aln_seqset_profile_elements.restype = i
+    lib.aln_seqset_profile_elements.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.aln_seqset_held_profiles.restype = i
+    lib.aln_seqset_held_profiles.argtypes = [vp, C.POINTER(Params), C.c_uint32, C.POINTER(HitFilter), vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp,
+                                             C.POINTER(ProfileSummary)]
     _lib = lib
     return lib
 

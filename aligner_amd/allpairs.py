@@ -30,6 +30,12 @@ replaced by one row per record, in input order: `head,rep_head,cluster_size`.  c
 of the family; greedy: longest-first representatives, a record joins the first representative it has a hit with.  The --min-*
 thresholds, when given, decide which hits count as edges.  Not with --heuristic, --shuffles or --report.
 
+With --cluster ... --profiles FILE the profile of every family of two or more records is written to FILE as well, counted on the device
+over the same hits: a header line `>rep_head hits=N` (N: the hits between the representative and a member of its family), then one
+line per residue position of the representative with the comma-separated counts of the members' aligned codes -- one per code of the
+alphabet, then deletions, then every other code (the traceback's duplicated seed column left out).  A hit between two members of a
+family counts for no profile.
+
 With --kmer K the pairs are prefiltered on the device first: only the candidates -- pairs whose records share at least --min-shared N
 distinct words of K residues (default 0) and at least P / 1024 of the smaller record's distinct words (--min-shared-per-1024 P,
 default 0) -- are aligned at all.  Words are counted over the first A codes of the alphabet (--kmer-alphabet A; default 20, the
@@ -80,6 +86,7 @@ def main(argv=None):
     ap.add_argument("--min-q-cover", type=float, default=None, metavar="Y", help="print only hits whose alignment covers Y of the first record (with --best: selected first, then filtered)")
     ap.add_argument("--min-t-cover", type=float, default=None, metavar="Z", help="print only hits whose alignment covers Z of the second record (with --best: selected first, then filtered)")
     ap.add_argument("--cluster", choices=("components", "greedy"), default=None, help="group the records by the held hits: prints head,rep_head,cluster_size per record (with --best or --f-min)")
+    ap.add_argument("--profiles", default=None, metavar="FILE", help="with --cluster: write every family's per-position residue counts to FILE")
     ap.add_argument("--kmer", type=int, default=None, metavar="K", help="prefilter: align only the pairs that share enough words of K residues (1 .. %d)" % _ffi.PREFILTER_MAX_K)
     ap.add_argument("--min-shared", type=int, default=None, metavar="N", help="with --kmer: candidates share at least N distinct words")
     ap.add_argument("--min-shared-per-1024", type=int, default=None, metavar="P", help="with --kmer: candidates share at least P / 1024 of the smaller record's distinct words (0 .. 1024)")
@@ -117,6 +124,8 @@ def main(argv=None):
             ap.error("--report / --min-identity / --min-q-cover / --min-t-cover describe the plain alignment: not with --heuristic")
         if a.best is None and a.best_candidates is None and a.f_min is None:
             ap.error("--report / --min-identity / --min-q-cover / --min-t-cover work on held hits: give --best K, --best-candidates N or --f-min F")
+    if a.profiles is not None and a.cluster is None:
+        ap.error("--profiles counts the families of --cluster: give --cluster components|greedy")
     if a.cluster is not None:
         if a.heuristic:
             ap.error("--cluster groups by the plain alignment's hits: not with --heuristic")
@@ -158,6 +167,14 @@ def main(argv=None):
         for i, lab in enumerate(got.label.tolist()):
             if lab != _ffi.CLUSTER_NONE:
                 out.write("%s,%s,%d\n" % (heads[i], heads[lab], size[lab]))
+        if a.profiles is not None:
+            prof = held.profiles(got, matrix=matrix if filtered else None, min_identity=a.min_identity or 0.0, min_q_cover=a.min_q_cover or 0.0,
+                                 min_t_cover=a.min_t_cover or 0.0)
+            with open(a.profiles, "w") as fh:
+                for i, r in enumerate(prof.records):
+                    fh.write(">%s hits=%d\n" % (heads[int(r["center"])], int(r["hits"])))
+                    for column in prof.counts(i).T.tolist():
+                        fh.write(",".join(str(x) for x in column) + "\n")
 
     def tail(held, pos=None, reports=None):
         """`,z,p_emp` and the report's columns per held position, or empty strings without --shuffles and --report; pos: the

@@ -300,7 +300,7 @@ static void warm_context(aln_ctx *c)
         if (hipSetDevice(c->devs[d]->device) != hipSuccess) continue;
         (void)aln_warm_single(); (void)aln_warm_tb(); (void)aln_warm_generic();
         (void)aln_warm_fast_cl(); (void)aln_warm_fast_cl_solo(); (void)aln_warm_fast_rest(); (void)aln_warm_fast_rest_solo();
-        (void)aln_warm_best(); (void)aln_warm_search();
+        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile();
         aln_pair_result r;
         (void)aln_align_pair(c, &p, q.data(), L, t.data(), L, &r, qa.data(), ta.data(), nullptr, nullptr);   // devices in turn
     }
@@ -3208,6 +3208,8 @@ struct aln_seqset : CallStats {
     // aln_seqset_held_report / _filter: the scheme's bit table, the reports (of a list, or of all held hits), the kept positions | records
     DevBuf rep_bits, reports, rep_pos, rep_out;
     DevBuf cluster;                   // aln_seqset_held_cluster: the call's tables, one arena
+    DevBuf profile;                   // aln_seqset_held_profiles: the call's tables and its output, one arena
+    uint8_t held_blank = 0;           // the blank code of the held pass (aln_seqset_held_profiles without params)
     // the k-mer prefilter (aln_prefilter_rules.h).  The index: one bitmap row of kmer_stride elements and one word count per
     // sequence, resident until the next aln_seqset_kmer_index (kmer_k == 0: none built)
     uint32_t kmer_k = 0, kmer_alphabet = 0, kmer_stride = 0;
@@ -3247,7 +3249,7 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     held_free(ss->held_store);
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
                    &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster, &ss->kmer_bits, &ss->kmer_n,
-                   &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first};
+                   &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first, &ss->profile};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
@@ -3553,6 +3555,7 @@ static int seqset_hold_list(aln_seqset *ss, const Call &ct, const aln_seqset_blo
 {
     const size_t hits = ss->hit_pair.size();
     if (hits > 0xFFFFFFF0ull) { g_err = "too many hits"; return ALN_ERR_UNSUPPORTED; }
+    ss->held_blank = ct.p.blank_code;
     if (!hits) return ALN_OK;
     std::vector<uint64_t> qo(hits), ql(hits), to(hits), tl(hits);
     ss->hit_q.resize(hits); ss->hit_t.resize(hits);
@@ -4660,6 +4663,173 @@ extern "C" int aln_seqset_held_cluster(aln_seqset *ss, const aln_params *params,
 {
     try {
         return seqset_held_cluster(ss, params, flags, filter, mode, label, clusters, capacity, summary);
+    } catch (const std::bad_alloc &) {
+        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
+}
+
+// ---------------------------------------------------------------- profiles of a set's families (aln_profile.hip, aln_profile_rules.h)
+// The tables of one call, carved out of one arena (every piece 256-aligned); base == nullptr only sizes it.
+struct ProfileBufs {
+    unsigned long long *misc = nullptr;
+    uint32_t *hit_q = nullptr, *hit_t = nullptr, *label = nullptr, *slot_of = nullptr, *centers = nullptr, *out = nullptr;
+    uint64_t *off = nullptr;
+    aln_profile_record *rec = nullptr;
+};
+static size_t profile_carve(uint8_t *base, uint64_t n, uint64_t held, uint64_t n_centers, uint64_t total, ProfileBufs *out)
+{
+    size_t pos = 0;
+    auto take = [&](size_t bytes) -> uint8_t * {
+        uint8_t *p = base ? base + pos : nullptr;
+        pos += (size_t)align256(std::max<size_t>(bytes, 4));
+        return p;
+    };
+    ProfileBufs b;
+    b.misc = reinterpret_cast<unsigned long long *>(take(8 * ALN_PROFILE_MISC_WORDS));
+    b.hit_q = reinterpret_cast<uint32_t *>(take(4 * held));
+    b.hit_t = reinterpret_cast<uint32_t *>(take(4 * held));
+    b.label = reinterpret_cast<uint32_t *>(take(4 * n));
+    b.slot_of = reinterpret_cast<uint32_t *>(take(4 * n));
+    b.centers = reinterpret_cast<uint32_t *>(take(4 * n_centers));
+    b.off = reinterpret_cast<uint64_t *>(take(8 * n_centers));
+    b.rec = reinterpret_cast<aln_profile_record *>(take(sizeof(aln_profile_record) * n_centers));
+    b.out = reinterpret_cast<uint32_t *>(take(4 * total));
+    if (out) *out = b;
+    return pos;
+}
+
+// what both calls check of the centres and n_codes
+static int profile_layout_check(const aln_seqset *ss, const uint32_t *centers, uint64_t n_centers, uint32_t n_codes)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ss->destroyed) { g_err = "the set was destroyed"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!aln_profile_codes_ok(n_codes)) { g_err = "n_codes must lie in 1 .. 64"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_centers && !centers) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_centers > ss->n || !aln_profile_centers_ok(centers, n_centers, ss->n)) {
+        g_err = "the centres must be strictly ascending sequence numbers of the set";
+        return ALN_ERR_INVALID_ARGUMENT;
+    }
+    return ALN_OK;
+}
+
+extern "C" int aln_seqset_profile_elements(const aln_seqset *ss, const uint32_t *centers, uint64_t n_centers, uint32_t n_codes, uint64_t *total)
+{
+    int st = profile_layout_check(ss, centers, n_centers, n_codes);
+    if (st != ALN_OK) return st;
+    if (!total) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    *total = aln_profile_layout(ss->len.data(), centers, n_centers, n_codes, nullptr);
+    return ALN_OK;
+}
+
+// The held hits' columns counted into the profiles of the listed centres.  Up go the endpoints from the host's held list (as the
+// cluster call uploads them), the labels, the centres and their offsets; with a filter the reports of ALL held hits are written into
+// the set's report buffer as held_filter writes them.  The held store is only read; the output lives in the call's own arena.
+static int seqset_held_profiles(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, const uint32_t *label,
+                                const uint32_t *centers, uint64_t n_centers, uint32_t n_codes, uint32_t *out, uint64_t capacity,
+                                aln_profile_record *records, aln_profile_summary *summary)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((params != nullptr) != (filter != nullptr)) { g_err = "params and filter come together: the filter's reports are classed under params"; return ALN_ERR_INVALID_ARGUMENT; }
+    std::vector<uint32_t> bits;
+    int st = filter ? seqset_report_check(ss, params, flags, bits) : seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    if (flags & ~ALN_PROFILE_SKIP_SEED) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (filter && filter->reserved != 0) { g_err = "the filter's reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = profile_layout_check(ss, centers, n_centers, n_codes)) != ALN_OK) return st;
+    const uint64_t n = ss->n, held = ss->hit_pair.size();      // (n < 2^32: aln_seqset_create; held <= 0xFFFFFFF0: seqset_hold_list)
+    if (!summary || (n && !label) || (n_centers && !records)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    std::vector<uint64_t> off(n_centers);
+    const uint64_t total = aln_profile_layout(ss->len.data(), centers, n_centers, n_codes, off.data());
+    if (capacity < total) { g_err = "capacity_elements is below aln_seqset_profile_elements"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (total && !out) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (total > (1ull << 40)) { g_err = "more than 2^40 profile elements"; return ALN_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    if ((st = dev_ensure(ss->profile, profile_carve(nullptr, n, held, n_centers, total, nullptr), false)) != ALN_OK) return st;
+    if (filter && held) {
+        if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * held, false)) != ALN_OK) return st;
+    }
+    ProfileBufs b;
+    profile_carve(ss->profile.as<uint8_t>(), n, held, n_centers, total, &b);
+    ProfileArgs a;
+    memset(&a, 0, sizeof a);
+    a.held = ss->held_store.info.as<HeldEntry>(); a.res = ss->held_store.res.as<aln_pair_result>(); a.tb = ss->held_store.tb.as<uint8_t>();
+    a.rep = filter && held ? ss->reports.as<aln_hit_report>() : nullptr;
+    if (filter) a.filter = *filter;
+    a.hit_q = b.hit_q; a.hit_t = b.hit_t; a.label = b.label; a.len = ss->d_len.as<uint32_t>(); a.slot_of = b.slot_of; a.off = b.off;
+    a.n_held = (uint32_t)held; a.n_seqs = (uint32_t)n; a.n_centers = (uint32_t)n_centers; a.n_codes = n_codes;
+    a.blank = params ? params->blank_code : ss->held_blank;
+    a.flags = flags;
+    a.out = b.out; a.rec = b.rec; a.misc = b.misc;
+    const auto t0 = std::chrono::steady_clock::now();
+    // (everything lands in buffers of the call's own first: an error on the way leaves the caller's arrays as they were)
+    std::vector<uint32_t> out_h(total);
+    std::vector<aln_profile_record> rec_h(n_centers);
+    unsigned long long misc[ALN_PROFILE_MISC_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        if (held) {
+            HIPCHK(hipMemcpyAsync(b.hit_q, ss->hit_q.data(), 4 * held, hipMemcpyHostToDevice, q));
+            HIPCHK(hipMemcpyAsync(b.hit_t, ss->hit_t.data(), 4 * held, hipMemcpyHostToDevice, q));
+            if (filter) HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
+        }
+        if (n) HIPCHK(hipMemcpyAsync(b.label, label, 4 * n, hipMemcpyHostToDevice, q));
+        if (n_centers) {
+            HIPCHK(hipMemcpyAsync(b.centers, centers, 4 * n_centers, hipMemcpyHostToDevice, q));
+            HIPCHK(hipMemcpyAsync(b.off, off.data(), 8 * n_centers, hipMemcpyHostToDevice, q));
+        }
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        HIPCHK(hipMemsetAsync(b.misc, 0, 8 * ALN_PROFILE_MISC_WORDS, q));
+        if (n) HIPCHK(hipMemsetAsync(b.slot_of, 0xFF, 4 * n, q));
+        if (n_centers) HIPCHK(hipMemsetAsync(b.rec, 0, sizeof(aln_profile_record) * n_centers, q));
+        if (total) HIPCHK(hipMemsetAsync(b.out, 0, 4 * total, q));
+        aln_profile_launch_slots(b.centers, (uint32_t)n_centers, (uint32_t)n, b.slot_of, b.rec, q);
+        HIPCHK(hipGetLastError());
+        if (held) {
+            if (filter) {
+                aln_report_launch(a.held, a.res, a.tb, nullptr, (uint32_t)held, (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols,
+                                  params->blank_code, flags, ss->reports.as<aln_hit_report>(), q);
+                HIPCHK(hipGetLastError());
+            }
+            aln_profile_launch(&a, q);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(misc, b.misc, 8 * ALN_PROFILE_MISC_WORDS, hipMemcpyDeviceToHost, q));
+        if (n_centers) HIPCHK(hipMemcpyAsync(rec_h.data(), b.rec, sizeof(aln_profile_record) * n_centers, hipMemcpyDeviceToHost, q));
+        if (total) HIPCHK(hipMemcpyAsync(out_h.data(), b.out, 4 * total, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    if (total) memcpy(out, out_h.data(), 4 * total);
+    if (n_centers) memcpy(records, rec_h.data(), sizeof(aln_profile_record) * n_centers);
+    auto word = [](unsigned long long v) { return (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull); };
+    memset(summary, 0, sizeof *summary);
+    summary->held = held;
+    summary->contributing = misc[ALN_PROFILE_COUNTS];
+    summary->self_pairs = word(misc[ALN_PROFILE_SELF]);
+    summary->between_members = word(misc[ALN_PROFILE_BETWEEN]);
+    summary->unlisted = word(misc[ALN_PROFILE_UNLISTED]);
+    summary->overflow = word(misc[ALN_PROFILE_MISC_OVERFLOW]);
+    summary->elements = total;
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 8ull * held + 4ull * n + 12ull * n_centers + (filter && held ? 4ull * bits.size() : 0);
+    ss->bytes[1] = 4ull * total + sizeof(aln_profile_record) * n_centers + 8ull * ALN_PROFILE_MISC_WORDS;
+    return ALN_OK;
+}
+
+// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
+extern "C" int aln_seqset_held_profiles(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, const uint32_t *label,
+                                        const uint32_t *centers, uint64_t n_centers, uint32_t n_codes, uint32_t *out, uint64_t capacity,
+                                        aln_profile_record *records, aln_profile_summary *summary)
+{
+    try {
+        return seqset_held_profiles(ss, params, flags, filter, label, centers, n_centers, n_codes, out, capacity, records, summary);
     } catch (const std::bad_alloc &) {
         if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
         g_err = "out of host memory";

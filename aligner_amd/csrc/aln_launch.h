@@ -1,4 +1,4 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip and aln_prefilter.hip define
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip and aln_profile.hip define
 // and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
 #pragma once
@@ -6,6 +6,7 @@
 
 #include "aln_device.h"
 #include "aln_cluster_rules.h"
+#include "aln_profile_rules.h"
 
 // what every kernel of aln_cluster.hip takes: n label slots (node numbers 0 .. n - 1, those of `nodes` being nodes), m listed edges
 struct ClusterArgs {
@@ -19,6 +20,21 @@ struct ClusterArgs {
     uint64_t *key;                   // n: greedy, a member's best representative; finish, a cluster's first in priority order
     uint32_t *size, *cedges;         // n each, by label
     uint32_t *misc;                  // 8 words: [0] changed | undecided, [1] clusters, then 64-bit edges, self edges, singletons
+};
+
+// what aln_profile_kernel takes: the held store (read only), the hits' endpoints, the labelling, the centres' slots and the outputs
+struct ProfileArgs {
+    const HeldEntry *held; const aln_pair_result *res; const uint8_t *tb;      // n_held entries of the held store
+    const aln_hit_report *rep;       // n_held reports, or null: no filter
+    aln_hit_filter filter;
+    const uint32_t *hit_q, *hit_t;   // n_held endpoints each
+    const uint32_t *label, *len;     // n_seqs each
+    const uint32_t *slot_of;         // n_seqs: the profile of a centre, ALN_CLUSTER_NONE without one
+    const uint64_t *off;             // n_centers: profile i's first element of out
+    uint32_t n_held, n_seqs, n_centers, n_codes, blank, flags;
+    uint32_t *out;                   // the profiles, zeroed
+    aln_profile_record *rec;         // n_centers
+    unsigned long long *misc;        // ALN_PROFILE_MISC_WORDS counters, zeroed
 };
 
 static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
@@ -141,5 +157,10 @@ void aln_search_launch_rows(const uint64_t *list, uint64_t count, uint64_t q_cou
 void aln_search_launch_chunk(const uint64_t *list, const uint32_t *row_first, const double *f, const int32_t *status, uint64_t c0, uint64_t n,
                              uint64_t row0, uint64_t rows, const aln_seqset_block *block, double f_min, uint32_t flags, uint32_t slots,
                              uint64_t *piece_key, uint32_t *piece_t, uint64_t *run_key, uint32_t *run_t, uint32_t *run_n, hipStream_t s);
+
+// ---- aln_profile.hip: the profiles of a sequence set's families (aln_profile_rules.h)
+int aln_warm_profile(void);
+void aln_profile_launch_slots(const uint32_t *centers, uint32_t n_centers, uint32_t n_seqs, uint32_t *slot_of, aln_profile_record *rec, hipStream_t s);
+void aln_profile_launch(const ProfileArgs *a, hipStream_t s);
 
 }

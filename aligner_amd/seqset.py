@@ -432,6 +432,47 @@ class HeldHits:
         runtime.raise_for_status(st, "aln_seqset_held_cluster")
         return _cluster.Clusters(label, rec[:min(int(summ.clusters), cap)], _cluster.summary_dict(summ))
 
+    def profiles(self, labels, centers=None, n_codes=None, matrix=None, min_identity=0.0, min_q_cover=0.0, min_t_cover=0.0, min_columns=0,
+                 skip_seed=True, blank=98):
+        """aln_seqset_held_profiles: for every centre and every residue position of it, how often each residue code, a deletion or
+        any other code of its family's members is aligned to it in the held hits -- counted on the device; one uint32 matrix per
+        centre comes down.  labels: one per sequence (an array, or the Clusters of .cluster); a hit (q, t) counts iff both carry the
+        same label and exactly one of them is that label, the centre.  centers (default: the labels that have at least one other
+        member): ascending sequence numbers.  n_codes (default: alphabet.volume()): the codes with a row of their own.  With a
+        matrix only the hits that filter(matrix, min_...) keeps count.  Returns a profile.Profiles."""
+        from . import profile as _profile
+        o = self.owner
+        thresholds = bool(min_identity or min_q_cover or min_t_cover or min_columns)
+        if matrix is None and thresholds:
+            raise ValueError("aln_seqset_held_profiles: thresholds need the matrix their classes are counted under")
+        label = _profile.labels_of(labels)
+        if label.shape != (len(o),):
+            raise ValueError("aln_seqset_held_profiles: one label per sequence of the set")
+        cen = _profile.default_centers(label) if centers is None else np.ascontiguousarray(centers, dtype=np.uint32)
+        codes = _profile.check_codes(o.alphabet.volume() if n_codes is None else n_codes)
+        total = C.c_uint64(0)
+        st = o.lib.aln_seqset_profile_elements(o.handle, cen.ctypes.data if len(cen) else None, len(cen), codes, C.byref(total))
+        runtime.raise_for_status(st, "aln_seqset_profile_elements")
+        out = np.zeros(int(total.value), dtype=np.uint32)
+        rec = np.zeros(len(cen), dtype=_profile.RECORD_DTYPE)
+        summ = _ffi.ProfileSummary()
+        if matrix is None:
+            p_ref, flt_ref = None, None
+        else:
+            p, _held = self._report_params(matrix, blank)
+            flt = _ffi.HitFilter(float(min_identity), float(min_q_cover), float(min_t_cover), int(min_columns), 0)
+            p_ref, flt_ref = C.byref(p), C.byref(flt)
+        st = o.lib.aln_seqset_held_profiles(o.handle, p_ref, _ffi.PROFILE_SKIP_SEED if skip_seed else 0, flt_ref, label.ctypes.data if len(label) else None,
+                                            cen.ctypes.data if len(cen) else None, len(cen), codes, out.ctypes.data if len(out) else None, len(out),
+                                            rec.ctypes.data if len(cen) else None, C.byref(summ))
+        runtime.raise_for_status(st, "aln_seqset_held_profiles")
+
+        def own(i):
+            a = int(o.off[cen[i]])
+            return o.seqs[a:a + int(o.len[cen[i]])]
+
+        return _profile.Profiles(cen, o.len, own, codes, out, rec, _profile.summary_dict(summ))
+
     def fractions(self, reports, keep=None):
         """report_fractions of records that belong to the listed positions (default: all)."""
         w = self._keep(keep)
