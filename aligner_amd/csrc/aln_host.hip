@@ -830,6 +830,15 @@ static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, c
     return ALN_OK;
 }
 
+// A planned chunk whose residues are resident: pair i's lie at qo[i] / to[i] of one device buffer of seq_span bytes, which is there
+// already and must not grow.  The descriptors (the device's, and the host's copy that the launches of pairs routed off the batch
+// kernel read) carry those offsets, and nothing is staged.
+static void chunk_resident(Chunk &k, const uint64_t *qo, const uint64_t *to, size_t n, uint64_t seq_span)
+{
+    for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[i]; k.descs[i].t_off = to[i]; }
+    k.seq_direct = true; k.seq_lo = 0; k.seq_span = seq_span;
+}
+
 // upper bounds over the chunks of a pipelined call: a slot is sized for the largest chunk the first time it is touched, so no
 // buffer grows (hipFree + hipMalloc stall every stream) in the middle of the pipeline
 struct Need {
@@ -2637,8 +2646,7 @@ static int held_refill(HeldStore &h, DevCtx *ctx, Slot &s, const Call &c, const 
             const size_t first = ranges[j].first, n = ranges[j].second;
             k.reset();
             if ((st = chunk_plan(ctx, c, qo.data(), ql.data(), to.data(), tl.data(), first, n, ranges.size() == 1, k, ranges.size() > 4)) != ALN_OK) return st;
-            for (size_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[first + i]; k.descs[i].t_off = to[first + i]; }      // resident residues
-            k.seq_direct = true; k.seq_lo = 0; k.seq_span = seq_span;
+            chunk_resident(k, qo.data() + first, to.data() + first, n, seq_span);
             HIPCHK(hipStreamSynchronize(q));
             collect();
             if ((st = slot_ensure(s, c, k)) != ALN_OK) return st;
@@ -3341,19 +3349,72 @@ static int seqset_call(aln_seqset *ss, const aln_params *params, const aln_seqse
     return call_init(c, &p, &q1, &t1, 1, false);
 }
 
-// cells of a block (as a double, like make_chunks) out of the length sums
-static double seqset_cells(const aln_seqset *ss, const aln_seqset_block &b)
+static int seqset_cand_check(aln_seqset *ss)
 {
-    double sq = 0, st = 0, s2 = 0;
-    for (uint64_t i = b.q_first; i < b.q_first + b.q_count; ++i) { sq += (double)ss->len[i]; s2 += (double)ss->len[i] * (double)ss->len[i]; }
-    if (b.upper) return (sq * sq - s2) / 2.0;
-    for (uint64_t i = b.t_first; i < b.t_first + b.t_count; ++i) st += (double)ss->len[i];
-    return sq * st;
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ss->cand) { g_err = "no candidate list: aln_seqset_prefilter has not run, or a new k-mer index has replaced it"; return ALN_ERR_INVALID_ARGUMENT; }
+    return ALN_OK;
 }
 
-// the chunks of a pass: pair counts of consecutive ranges of the block's order, by the bounds of make_chunks (the pair limit holds for
-// every chunk: the queue entries are 32-bit and chunk-local).  One walk over the block, nothing kept per pair.
-// the cells a chunk of a pass aims at (total cells over `pairs` pairs); *forced: ALN_CHUNK_CELLS said so
+// What a pass runs over: every pair of a block in the block's order (position k is pair k), or the set's candidate list (position h
+// is the list's entry h, a pair of the prefilter's block).  A block is walked, by one aln_seqset_unrank and aln_seqset_next after
+// it: it may hold far more pairs than a host table should, so nothing is kept per pair beyond what a caller asks for at a time.
+struct PairSource {
+    aln_seqset *ss;
+    bool list;
+    const aln_seqset_block *b;        // the block the pair numbers belong to (a list: the prefilter's, once check() has passed)
+    uint64_t at = ~0ull, cq = 0, ct = 0;      // the walk: the next position (none before the first seek) and, of a block, its pair
+
+    // what a source refuses before the call's own checks: a list that does not exist
+    int check()
+    {
+        if (!list) return ALN_OK;
+        const int st = seqset_cand_check(ss);
+        if (st == ALN_OK) b = &ss->cand_block;
+        return st;
+    }
+    uint64_t positions() const { return list ? ss->cand_pair.size() : aln_seqset_block_pairs(ss->n, *b); }
+    // cells of all positions together (as a double, like make_chunks): a block's out of the length sums
+    double cells() const
+    {
+        if (list) {
+            double sum = 0;
+            for (size_t h = 0; h < ss->cand_pair.size(); ++h) sum += (double)ss->len[ss->cand_qs[h]] * (double)ss->len[ss->cand_ts[h]];
+            return sum;
+        }
+        double sq = 0, st = 0, s2 = 0;
+        for (uint64_t i = b->q_first; i < b->q_first + b->q_count; ++i) { sq += (double)ss->len[i]; s2 += (double)ss->len[i] * (double)ss->len[i]; }
+        if (b->upper) return (sq * sq - s2) / 2.0;
+        for (uint64_t i = b->t_first; i < b->t_first + b->t_count; ++i) st += (double)ss->len[i];
+        return sq * st;
+    }
+    void seek(uint64_t k)             // k < positions()
+    {
+        at = k;
+        if (!list) aln_seqset_unrank(*b, k, &cq, &ct);
+    }
+    // the sequence numbers of position `at`, and on to the next
+    void step(uint64_t *q, uint64_t *t)
+    {
+        if (list) { *q = ss->cand_qs[at]; *t = ss->cand_ts[at]; }
+        else { *q = cq; *t = ct; aln_seqset_next(*b, &cq, &ct); }
+        ++at;
+    }
+    // the sequence numbers of positions k0 .. k0 + n - 1 (no seek where the walk stands at k0 already: chunk after chunk)
+    void window(uint64_t k0, uint64_t n, std::vector<uint32_t> &q, std::vector<uint32_t> &t)
+    {
+        if (at != k0) seek(k0);
+        q.resize(n); t.resize(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            uint64_t sq, st;
+            step(&sq, &st);
+            q[i] = (uint32_t)sq; t[i] = (uint32_t)st;
+        }
+    }
+};
+
+// the cells a chunk of a pass aims at (total cells over `pairs` pairs); *forced: ALN_CHUNK_CELLS said so.  Where the chunks are cut
+// is aln_seqset_cut's rule (aln_seqset_rules.h)
 static double seqset_chunk_target(const Call &c, double total, uint64_t pairs, bool *forced)
 {
     double target = std::min(1.6e10, std::max(5.0e9, total / 4.0));
@@ -3362,29 +3423,6 @@ static double seqset_chunk_target(const Call &c, double total, uint64_t pairs, b
     *forced = false;
     if (const char *e = getenv("ALN_CHUNK_CELLS")) { target = std::max(1.0, atof(e)); *forced = true; }
     return target;
-}
-
-static void seqset_chunks(const aln_seqset *ss, const Call &c, const aln_seqset_block &b, uint64_t pairs, std::vector<uint64_t> &counts)
-{
-    counts.clear();
-    const double total = seqset_cells(ss, b);
-    bool forced = false;
-    const double target = seqset_chunk_target(c, total, pairs, &forced);
-    if (pairs <= ALN_SEQSET_CHUNK_PAIRS && (total <= 1.5 * target || (!forced && total <= 2.0e10))) { counts.push_back(pairs); return; }
-    uint64_t q, t, n = 0;
-    aln_seqset_unrank(b, 0, &q, &t);
-    double acc = 0, done = 0;
-    for (uint64_t k = 0; k < pairs; ++k) {
-        acc += (double)ss->len[q] * (double)ss->len[t];
-        ++n;
-        aln_seqset_next(b, &q, &t);
-        // (a short tail joins the chunk before it, unless that chunk is full)
-        if (n >= ALN_SEQSET_CHUNK_PAIRS || (acc >= target && (total - done - acc >= 0.25 * target || k + 1 == pairs))) {
-            counts.push_back(n);
-            done += acc; acc = 0; n = 0;
-        }
-    }
-    if (n) counts.push_back(n);
 }
 
 // what a chunk of n pairs needs of the set's buffers (the stream is idle: they may grow)
@@ -3404,21 +3442,29 @@ static int seqset_chunk_ensure(aln_seqset *ss, const Call &c, const Chunk &k, ui
     return ALN_OK;
 }
 
-// One pass over a block: every chunk expanded, filled and gathered on the set's stream.  f / status (optional): the caller's arrays.
-// select: the chunk's pairs with status ALN_OK and f >= f_min are appended to ss->hit_pair / hit_score.  *first_bad: the status of
-// the first failed pair, ALN_OK if none failed.  best: the chunk's f / status go through the piece and merge kernels into the rows'
-// running lists (ss->run_*, zeroed by the caller).
-static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_block &b, uint64_t pairs, double *f, int32_t *status, bool select,
-                              double f_min, int *first_bad, Chunk *plans, const BestPass *best)
+// One pass over a source: its positions cut into chunks (aln_seqset_cut, by the cell bounds of make_chunks and the pair limit of a
+// chunk), every chunk expanded, filled and gathered on the set's stream.  f / status (optional): the caller's arrays, by position.
+// select: the POSITIONS of the chunk's pairs with status ALN_OK and f >= f_min are appended to ss->hit_pair (of a list, the caller
+// turns them into pair numbers), their f to hit_score.  *first_bad: the status of the first failed pair, ALN_OK if none failed.
+// best: the chunk's f / status go through the piece and merge kernels (a block: aln_best.hip; a list: aln_search.hip, with
+// ss->row_first filled by the caller) into the rows' running lists (ss->run_*, zeroed by the caller).
+static int seqset_pass_chunks(aln_seqset *ss, const Call &c, PairSource &src, double *f, int32_t *status, bool select, double f_min, int *first_bad,
+                              Chunk *plans, const BestPass *best)
 {
     Slot &s = *ss->slot;
     hipStream_t q = s.stream;
     std::vector<uint64_t> counts;
-    seqset_chunks(ss, c, b, pairs, counts);
+    if (const uint64_t positions = src.positions()) {
+        const double total = src.cells();
+        bool forced = false;
+        const double target = seqset_chunk_target(c, total, positions, &forced);
+        src.seek(0);
+        aln_seqset_cut([&]() { uint64_t sq, sx; src.step(&sq, &sx); return (double)ss->len[sq] * (double)ss->len[sx]; }, positions, total, target,
+                       forced, ALN_SEQSET_CHUNK_PAIRS, counts);
+    }
     const bool want_out = f != nullptr || status != nullptr;
+    std::vector<uint32_t> qs, ts;                  // one chunk's tables: its sequence numbers, then what chunk_plan reads
     std::vector<uint64_t> qo, ql, to, tl;
-    uint64_t cq, ct;
-    aln_seqset_unrank(b, 0, &cq, &ct);
     // what the chunk in flight leaves behind, collected where the pass waits for it anyway
     uint64_t prev_k0 = 0, prev_n = 0;
     bool timed = false;
@@ -3447,17 +3493,12 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
     for (size_t j = 0; j < counts.size(); ++j) {
         const uint64_t n = counts[j];
         Chunk &k = plans[j & 1];
+        src.window(k0, n, qs, ts);
         qo.resize(n); ql.resize(n); to.resize(n); tl.resize(n);
-        for (uint64_t i = 0; i < n; ++i) {
-            qo[i] = ss->off[cq]; ql[i] = ss->len[cq]; to[i] = ss->off[ct]; tl[i] = ss->len[ct];
-            aln_seqset_next(b, &cq, &ct);
-        }
+        for (uint64_t i = 0; i < n; ++i) { qo[i] = ss->off[qs[i]]; ql[i] = ss->len[qs[i]]; to[i] = ss->off[ts[i]]; tl[i] = ss->len[ts[i]]; }
         k.reset();
         if ((st = chunk_plan(ss->ctx, c, qo.data(), ql.data(), to.data(), tl.data(), 0, n, counts.size() == 1, k, counts.size() > 4)) != ALN_OK) break;
-        // the residues are resident: the descriptors (the device's, and the host's copy that the launches of pairs routed off the batch
-        // kernel read) carry offsets into the set's own buffer, which must not grow
-        for (uint64_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[i]; k.descs[i].t_off = to[i]; }
-        k.seq_direct = true; k.seq_lo = 0; k.seq_span = ss->total;
+        chunk_resident(k, qo.data(), to.data(), n, ss->total);          // the set's own buffer
         bool identity = k.n_small == n;
         for (uint64_t i = 0; i < n && identity; ++i) identity = k.order[i] == (uint32_t)i;
         HIPCHK(hipStreamSynchronize(q));
@@ -3465,8 +3506,11 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
         // the stream is idle: buffers may grow now
         uint32_t *tile_count = nullptr, *tile_off = nullptr;
         if ((st = seqset_chunk_ensure(ss, c, k, n, want_out, select, &tile_count, &tile_off)) != ALN_OK) break;
-        if (best) {
-            const uint64_t pieces = aln_best_chunk_geometry(k0, n, b.t_count).pieces;
+        if (best && src.list) {                        // the chunk's sorted pieces, by chunk position
+            if ((st = dev_ensure(ss->cand_key, 8 * n, false)) != ALN_OK) break;
+            if ((st = dev_ensure(ss->cand_t, 4 * n, false)) != ALN_OK) break;
+        } else if (best) {                             // a list of `slots` per piece of a row
+            const uint64_t pieces = aln_best_chunk_geometry(k0, n, src.b->t_count).pieces;
             if ((st = dev_ensure(ss->cand_key, 8 * pieces * best->slots, false)) != ALN_OK) break;
             if ((st = dev_ensure(ss->cand_t, 4 * pieces * best->slots, false)) != ALN_OK) break;
             if ((st = dev_ensure(ss->cand_n, 4 * pieces, false)) != ALN_OK) break;
@@ -3476,7 +3520,11 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
             ss->bytes[0] += c.md.size() * (c.is_int ? 4 : 8);
         }
         HIPCHK(hipMemsetAsync(ss->misc.p, 0, 16, q));
-        aln_seqset_launch_expand(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), n, k0, &b, ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), q);
+        if (src.list)
+            aln_prefilter_launch_expand_list(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), n, ss->cand_k.as<uint64_t>() + k0, src.b, ss->d_off.as<uint64_t>(),
+                                             ss->d_len.as<uint32_t>(), q);
+        else
+            aln_seqset_launch_expand(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), n, k0, src.b, ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), q);
         HIPCHK(hipGetLastError());
         if (!identity && k.n_small) {                  // the plan's queue: longest pairs first, without the pairs routed elsewhere
             HIPCHK(hipMemcpyAsync(s.order.p, k.order.data(), 4 * k.n_small, hipMemcpyHostToDevice, q));
@@ -3493,9 +3541,16 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
         }
         if (best) {
             HIPCHK(hipEventRecord(ss->ev[4], q));
-            aln_best_launch_chunk(ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), n, k0, &b, best->f_min, best->flags, best->slots,
-                                  ss->cand_key.as<uint64_t>(), ss->cand_t.as<uint32_t>(), ss->cand_n.as<uint32_t>(), ss->run_key.as<uint64_t>(),
-                                  ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), q);
+            if (src.list) {                            // the rows the chunk's candidates lie in
+                const uint64_t t_count = src.b->t_count;
+                const uint64_t row0 = aln_search_row(ss->cand_pair[k0], t_count), row1 = aln_search_row(ss->cand_pair[k0 + n - 1], t_count);
+                aln_search_launch_chunk(ss->cand_k.as<uint64_t>(), ss->row_first.as<uint32_t>(), ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), k0, n, row0,
+                                        row1 - row0 + 1, src.b, best->f_min, best->flags, best->slots, ss->cand_key.as<uint64_t>(),
+                                        ss->cand_t.as<uint32_t>(), ss->run_key.as<uint64_t>(), ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), q);
+            } else
+                aln_best_launch_chunk(ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), n, k0, src.b, best->f_min, best->flags, best->slots,
+                                      ss->cand_key.as<uint64_t>(), ss->cand_t.as<uint32_t>(), ss->cand_n.as<uint32_t>(), ss->run_key.as<uint64_t>(),
+                                      ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), q);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(ss->ev[5], q));
         }
@@ -3513,11 +3568,11 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, const aln_seqset_bl
 }
 
 // (every way out of a failed pass waits for the stream: queued work reads the plans' queues and writes the pinned staging)
-static int seqset_pass(aln_seqset *ss, const Call &c, const aln_seqset_block &b, uint64_t pairs, double *f, int32_t *status, bool select,
-                       double f_min, int *first_bad, const BestPass *best = nullptr)
+static int seqset_pass(aln_seqset *ss, const Call &c, PairSource &src, double *f, int32_t *status, bool select, double f_min, int *first_bad,
+                       const BestPass *best = nullptr)
 {
     Chunk plans[2];                    // chunk j's queue may still be on its way while chunk j + 1 is planned
-    const int st = seqset_pass_chunks(ss, c, b, pairs, f, status, select, f_min, first_bad, plans, best);
+    const int st = seqset_pass_chunks(ss, c, src, f, status, select, f_min, first_bad, plans, best);
     if (st != ALN_OK) (void)hipStreamSynchronize(ss->slot->stream);
     return st;
 }
@@ -3530,18 +3585,21 @@ static void seqset_begin(aln_seqset *ss)
     stats_reset(*ss);
 }
 
-extern "C" int aln_seqset_score(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double *f, int32_t *status)
+// f and status of every position of a source (aln_seqset_score, aln_seqset_candidate_scores)
+static int seqset_run_score(PairSource src, const aln_params *params, double *f, int32_t *status)
 {
-    Call c;
-    int st = seqset_call(ss, params, b, ALN_OUT_SCORE, c);
+    aln_seqset *ss = src.ss;
+    int st = src.check();
     if (st != ALN_OK) return st;
+    Call c;
+    if ((st = seqset_call(ss, params, src.b, ALN_OUT_SCORE, c)) != ALN_OK) return st;
     if (!f) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     HIPCHK(hipSetDevice(ss->ctx->device));
     HIPCHK(hipStreamSynchronize(ss->slot->stream));
     seqset_begin(ss);
     const auto t0 = std::chrono::steady_clock::now();
     int bad = ALN_OK;
-    st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), f, status, false, 0.0, &bad);
+    st = seqset_pass(ss, c, src, f, status, false, 0.0, &bad);
     ss->ms[3] = wall_ms(t0);
     if (st != ALN_OK) return st;
     if (!status && bad != ALN_OK) { g_err = "a pair failed"; return bad; }
@@ -3572,11 +3630,16 @@ static int seqset_hold_list(aln_seqset *ss, const Call &ct, const aln_seqset_blo
     return st;
 }
 
-extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double f_min, uint64_t *count)
+// The positions of a source at or above a threshold, held (aln_seqset_hits, aln_seqset_candidate_hits): the held state after a
+// list is exactly what a block pass would hold for those pairs.
+static int seqset_run_hits(PairSource src, const aln_params *params, double f_min, uint64_t *count)
 {
-    Call c, ct;
-    int st = seqset_call(ss, params, b, ALN_OUT_SCORE, c);
+    aln_seqset *ss = src.ss;
+    int st = src.check();
     if (st != ALN_OK) return st;
+    Call c, ct;
+    const aln_seqset_block *b = src.b;
+    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE, c)) != ALN_OK) return st;
     if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE | ALN_OUT_TRACEBACK, ct)) != ALN_OK) return st;
     HIPCHK(hipSetDevice(ss->ctx->device));
@@ -3585,7 +3648,13 @@ extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const a
     *count = 0;
     const auto t0 = std::chrono::steady_clock::now();
     int bad = ALN_OK;
-    if ((st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), nullptr, nullptr, true, f_min, &bad)) != ALN_OK) { seqset_begin(ss); return st; }
+    if ((st = seqset_pass(ss, c, src, nullptr, nullptr, true, f_min, &bad)) != ALN_OK) { seqset_begin(ss); return st; }
+    // the selection numbered a list's candidates by list position: the held list speaks of pairs of the block
+    if (src.list)
+        for (uint64_t &p : ss->hit_pair) {
+            if (p >= ss->cand_pair.size()) { g_err = "the selection's list leaves the candidate list"; seqset_begin(ss); return ALN_ERR_DEVICE; }
+            p = ss->cand_pair[p];
+        }
     if ((st = seqset_hold_list(ss, ct, b)) != ALN_OK) { seqset_begin(ss); return st; }
     ss->ms[3] = wall_ms(t0);
     ss->held = true;
@@ -3635,14 +3704,17 @@ static int seqset_best_finish(aln_seqset *ss, const aln_seqset_block *b, uint32_
     return ALN_OK;
 }
 
-// The k best targets per query row: the pass of hits with the per-row selection of aln_best.hip in place of the threshold's, then the
-// rows' lists as one ascending pair list, held like the hits.
-extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, uint32_t k, double f_min, uint32_t flags,
-                               uint64_t *count)
+// The k best targets per query row of a source (aln_seqset_best, aln_seqset_candidate_best): the pass of hits with the per-row
+// selection of aln_best.hip (a list: of aln_search.hip, which finds a row's candidates through row_first) in place of the
+// threshold's, then the rows' lists as one ascending pair list, held like the hits.
+static int seqset_run_best(PairSource src, const aln_params *params, uint32_t k, double f_min, uint32_t flags, uint64_t *count)
 {
-    Call c, ct;
-    int st = seqset_call(ss, params, b, ALN_OUT_SCORE, c);
+    aln_seqset *ss = src.ss;
+    int st = src.check();
     if (st != ALN_OK) return st;
+    Call c, ct;
+    const aln_seqset_block *b = src.b;
+    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE, c)) != ALN_OK) return st;
     if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if (k < 1u || k > ALN_SEQSET_BEST_MAX) { g_err = "k must lie in 1 .. ALN_SEQSET_BEST_MAX"; return ALN_ERR_INVALID_ARGUMENT; }
     if (flags & ~ALN_BEST_SKIP_SELF) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
@@ -3652,21 +3724,31 @@ extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const a
     hipStream_t q = ss->slot->stream;
     HIPCHK(hipStreamSynchronize(q));
     seqset_begin(ss);
+    if (src.list) *count = 0;          // (a block's best leaves *count alone unless it succeeds, as it always has)
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t rows = b->q_count;
+    const uint64_t rows = b->q_count, listed = src.list ? src.positions() : 0;
     BestPass best;
     best.slots = aln_best_slots(k, b->t_count); best.flags = flags; best.f_min = f_min;
-    // the rows' running lists, for this call
+    // the rows' running lists and, for a list, their places in it, for this call
     st = dev_ensure(ss->run_key, 8 * rows * best.slots, false);
     if (st == ALN_OK) st = dev_ensure(ss->run_t, 4 * rows * best.slots, false);
     if (st == ALN_OK) st = dev_ensure(ss->run_n, 4 * rows, false);
+    if (st == ALN_OK && src.list) st = dev_ensure(ss->row_first, 4 * (rows + 1), false);
     uint32_t *tile_count;
     uint64_t *tile_off;
     if (st == ALN_OK) st = tiles_ensure(ss->tiles, aln_best_tiles(rows), &tile_count, &tile_off);
     if (st != ALN_OK) return st;
     HIPCHK(hipMemsetAsync(ss->run_n.p, 0, 4 * rows, q));
+    if (listed) {
+        HIPCHK(hipEventRecord(ss->ev[4], q));
+        aln_search_launch_rows(ss->cand_k.as<uint64_t>(), listed, rows, b->t_count, ss->row_first.as<uint32_t>(), q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[5], q));
+        HIPCHK(hipStreamSynchronize(q));
+        ss->ms[2] += ev_ms(ss->ev[4], ss->ev[5]);
+    }
     int bad = ALN_OK;
-    if ((st = seqset_pass(ss, c, *b, aln_seqset_block_pairs(ss->n, *b), nullptr, nullptr, false, 0.0, &bad, &best)) != ALN_OK) { seqset_begin(ss); return st; }
+    if ((st = seqset_pass(ss, c, src, nullptr, nullptr, false, 0.0, &bad, &best)) != ALN_OK) { seqset_begin(ss); return st; }
     uint64_t total = 0;
     st = seqset_best_finish(ss, b, best.slots, tile_count, tile_off, &total);
     if (st == ALN_OK) st = seqset_hold_list(ss, ct, b);
@@ -3678,9 +3760,36 @@ extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const a
     return ALN_OK;
 }
 
+// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
+#define ALN_SEQSET_GUARDED(ss, call)                                                              \
+    try {                                                                                         \
+        return call;                                                                              \
+    } catch (const std::bad_alloc &) {                                                            \
+        if ((ss) && (ss)->slot && (ss)->slot->stream) (void)hipDeviceSynchronize();               \
+        g_err = "out of host memory";                                                             \
+        return ALN_ERR_OOM;                                                                       \
+    }
+
+extern "C" int aln_seqset_score(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double *f, int32_t *status)
+{
+    ALN_SEQSET_GUARDED(ss, seqset_run_score(PairSource{ss, false, b}, params, f, status))
+}
+
+extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double f_min, uint64_t *count)
+{
+    ALN_SEQSET_GUARDED(ss, seqset_run_hits(PairSource{ss, false, b}, params, f_min, count))
+}
+
+extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, uint32_t k, double f_min, uint32_t flags,
+                               uint64_t *count)
+{
+    ALN_SEQSET_GUARDED(ss, seqset_run_best(PairSource{ss, false, b}, params, k, f_min, flags, count))
+}
+
 // ---------------------------------------------------------------- the k-mer prefilter (include/aligner_hip_prefilter.h)
 // Words first, the dynamic programme on the candidates only.  The index and the candidate list are state of their own beside the held
-// hits; the two candidate passes are passes like score and hits whose chunks are runs of consecutive list positions.
+// hits; the candidate passes are the passes of score, hits and best over a PairSource that names the list: their chunks are runs of
+// consecutive list positions.
 static void seqset_drop_candidates(aln_seqset *ss)
 {
     ss->cand = false;
@@ -3825,270 +3934,14 @@ static int seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *sp, const 
     return ALN_OK;
 }
 
-static int seqset_cand_check(aln_seqset *ss)
-{
-    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (!ss->cand) { g_err = "no candidate list: aln_seqset_prefilter has not run, or a new k-mer index has replaced it"; return ALN_ERR_INVALID_ARGUMENT; }
-    return ALN_OK;
-}
-
-// the chunks of a pass over the candidate list: counts of consecutive list positions, cut as seqset_chunks cuts a block
-static void seqset_list_chunks(const aln_seqset *ss, const Call &c, std::vector<uint64_t> &counts)
-{
-    counts.clear();
-    const uint64_t pairs = ss->cand_pair.size();
-    if (!pairs) return;
-    double total = 0;
-    for (uint64_t h = 0; h < pairs; ++h) total += (double)ss->len[ss->cand_qs[h]] * (double)ss->len[ss->cand_ts[h]];
-    bool forced = false;
-    const double target = seqset_chunk_target(c, total, pairs, &forced);
-    if (pairs <= ALN_SEQSET_CHUNK_PAIRS && (total <= 1.5 * target || (!forced && total <= 2.0e10))) { counts.push_back(pairs); return; }
-    uint64_t n = 0;
-    double acc = 0, done = 0;
-    for (uint64_t h = 0; h < pairs; ++h) {
-        acc += (double)ss->len[ss->cand_qs[h]] * (double)ss->len[ss->cand_ts[h]];
-        ++n;
-        if (n >= ALN_SEQSET_CHUNK_PAIRS || (acc >= target && (total - done - acc >= 0.25 * target || h + 1 == pairs))) {
-            counts.push_back(n);
-            done += acc; acc = 0; n = 0;
-        }
-    }
-    if (n) counts.push_back(n);
-}
-
-// One pass over the candidate list, as seqset_pass_chunks runs one over a block: per chunk the list expansion, chunk_plan, the staged
-// batch's launches and the gather.  f / status (optional) are indexed by list position.  select: the list POSITIONS of the candidates
-// with status ALN_OK and f >= f_min are appended to ss->hit_pair (the caller turns them into pair numbers), their f to hit_score.
-// best: the chunk's f / status go through the list piece and list merge kernels (aln_search.hip) into the rows' running lists
-// (ss->run_*, zeroed by the caller; ss->row_first filled by the caller).
-static int seqset_list_pass_chunks(aln_seqset *ss, const Call &c, double *f, int32_t *status, bool select, double f_min, int *first_bad, Chunk *plans,
-                                   const BestPass *best)
-{
-    Slot &s = *ss->slot;
-    hipStream_t q = s.stream;
-    std::vector<uint64_t> counts;
-    seqset_list_chunks(ss, c, counts);
-    const bool want_out = f != nullptr || status != nullptr;
-    std::vector<uint64_t> qo, ql, to, tl;
-    uint64_t prev_k0 = 0, prev_n = 0;
-    bool timed = false;
-    int st = ALN_OK;
-    auto collect = [&]() -> int {
-        if (timed && best) ss->ms[2] += ev_ms(ss->ev[4], ss->ev[5]);
-        if (timed) { ss->ms[0] += ev_ms(ss->ev[0], ss->ev[1]); timed = false; }
-        if (!prev_n) return ALN_OK;
-        const uint8_t *h = ss->h_out.as<uint8_t>();
-        const uint64_t *misc = reinterpret_cast<const uint64_t *>(h);
-        if (f) memcpy(f + prev_k0, h + 256, 8 * prev_n);
-        if (status) memcpy(status + prev_k0, h + 256 + 8 * prev_n, 4 * prev_n);
-        if (*first_bad == ALN_OK && misc[1] != 0) *first_bad = (int)(misc[1] & 0xffu);
-        const uint64_t got = (uint32_t)misc[0];
-        if (select && got) {
-            const size_t at = ss->hit_pair.size();
-            ss->hit_pair.resize(at + got); ss->hit_score.resize(at + got);
-            HIPCHK(hipMemcpy(ss->hit_pair.data() + at, ss->hit_k.p, 8 * got, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(ss->hit_score.data() + at, ss->hit_f.p, 8 * got, hipMemcpyDeviceToHost));
-            ss->bytes[1] += 16 * got;
-        }
-        prev_n = 0;
-        return ALN_OK;
-    };
-    uint64_t k0 = 0;
-    for (size_t j = 0; j < counts.size(); ++j) {
-        const uint64_t n = counts[j];
-        Chunk &k = plans[j & 1];
-        qo.resize(n); ql.resize(n); to.resize(n); tl.resize(n);
-        for (uint64_t i = 0; i < n; ++i) {
-            const uint32_t cq = ss->cand_qs[k0 + i], ct = ss->cand_ts[k0 + i];
-            qo[i] = ss->off[cq]; ql[i] = ss->len[cq]; to[i] = ss->off[ct]; tl[i] = ss->len[ct];
-        }
-        k.reset();
-        if ((st = chunk_plan(ss->ctx, c, qo.data(), ql.data(), to.data(), tl.data(), 0, n, counts.size() == 1, k, counts.size() > 4)) != ALN_OK) break;
-        for (uint64_t i = 0; i < n; ++i) { k.descs[i].q_off = qo[i]; k.descs[i].t_off = to[i]; }
-        k.seq_direct = true; k.seq_lo = 0; k.seq_span = ss->total;
-        bool identity = k.n_small == n;
-        for (uint64_t i = 0; i < n && identity; ++i) identity = k.order[i] == (uint32_t)i;
-        HIPCHK(hipStreamSynchronize(q));
-        if ((st = collect()) != ALN_OK) break;
-        uint32_t *tile_count = nullptr, *tile_off = nullptr;
-        if ((st = seqset_chunk_ensure(ss, c, k, n, want_out, select, &tile_count, &tile_off)) != ALN_OK) break;
-        if (best) {                                    // the chunk's sorted pieces, by chunk position
-            if ((st = dev_ensure(ss->cand_key, 8 * n, false)) != ALN_OK) break;
-            if ((st = dev_ensure(ss->cand_t, 4 * n, false)) != ALN_OK) break;
-        }
-        if (j == 0) {
-            if ((st = upload_matrix(s, c, s.h_meta.as<uint8_t>(), q)) != ALN_OK) break;
-            ss->bytes[0] += c.md.size() * (c.is_int ? 4 : 8);
-        }
-        HIPCHK(hipMemsetAsync(ss->misc.p, 0, 16, q));
-        aln_prefilter_launch_expand_list(s.descs.as<PairDesc>(), s.order.as<uint32_t>(), n, ss->cand_k.as<uint64_t>() + k0, &ss->cand_block,
-                                         ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), q);
-        HIPCHK(hipGetLastError());
-        if (!identity && k.n_small) {
-            HIPCHK(hipMemcpyAsync(s.order.p, k.order.data(), 4 * k.n_small, hipMemcpyHostToDevice, q));
-            ss->bytes[0] += 4 * k.n_small;
-        }
-        if ((st = slot_launch(ss->ctx, s, c, k, q, ss->ev, nullptr)) != ALN_OK) break;
-        timed = true;
-        aln_seqset_launch_gather(s.results.as<aln_pair_result>(), ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), n,
-                                 reinterpret_cast<unsigned long long *>(ss->misc.as<uint8_t>() + 8), q);
-        HIPCHK(hipGetLastError());
-        if (select) {
-            aln_seqset_launch_select(s.results.as<aln_pair_result>(), n, k0, f_min, tile_count, tile_off, ss->misc.as<uint32_t>(), ss->hit_k.as<uint64_t>(), ss->hit_f.as<double>(), q);
-            HIPCHK(hipGetLastError());
-        }
-        if (best) {
-            const uint64_t t_count = ss->cand_block.t_count;
-            const uint64_t row0 = aln_search_row(ss->cand_pair[k0], t_count), row1 = aln_search_row(ss->cand_pair[k0 + n - 1], t_count);
-            HIPCHK(hipEventRecord(ss->ev[4], q));
-            aln_search_launch_chunk(ss->cand_k.as<uint64_t>(), ss->row_first.as<uint32_t>(), ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), k0, n, row0,
-                                    row1 - row0 + 1, &ss->cand_block, best->f_min, best->flags, best->slots, ss->cand_key.as<uint64_t>(),
-                                    ss->cand_t.as<uint32_t>(), ss->run_key.as<uint64_t>(), ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), q);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(ss->ev[5], q));
-        }
-        uint8_t *h = ss->h_out.as<uint8_t>();
-        HIPCHK(hipMemcpyAsync(h, ss->misc.p, 16, hipMemcpyDeviceToHost, q));
-        ss->bytes[1] += 16;
-        if (f) { HIPCHK(hipMemcpyAsync(h + 256, ss->fbuf.p, 8 * n, hipMemcpyDeviceToHost, q)); ss->bytes[1] += 8 * n; }
-        if (status) { HIPCHK(hipMemcpyAsync(h + 256 + 8 * n, ss->stbuf.p, 4 * n, hipMemcpyDeviceToHost, q)); ss->bytes[1] += 4 * n; }
-        prev_k0 = k0; prev_n = n;
-        k0 += n;
-    }
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
-    HIPCHK(hipStreamSynchronize(q));
-    return collect();
-}
-
-static int seqset_list_pass(aln_seqset *ss, const Call &c, double *f, int32_t *status, bool select, double f_min, int *first_bad,
-                            const BestPass *best = nullptr)
-{
-    Chunk plans[2];
-    const int st = seqset_list_pass_chunks(ss, c, f, status, select, f_min, first_bad, plans, best);
-    if (st != ALN_OK) (void)hipStreamSynchronize(ss->slot->stream);
-    return st;
-}
-
-static int seqset_candidate_scores(aln_seqset *ss, const aln_params *params, double *f, int32_t *status)
-{
-    int st = seqset_cand_check(ss);
-    if (st != ALN_OK) return st;
-    Call c;
-    if ((st = seqset_call(ss, params, &ss->cand_block, ALN_OUT_SCORE, c)) != ALN_OK) return st;
-    if (!f) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    HIPCHK(hipSetDevice(ss->ctx->device));
-    HIPCHK(hipStreamSynchronize(ss->slot->stream));
-    seqset_begin(ss);
-    const auto t0 = std::chrono::steady_clock::now();
-    int bad = ALN_OK;
-    st = seqset_list_pass(ss, c, f, status, false, 0.0, &bad);
-    ss->ms[3] = wall_ms(t0);
-    if (st != ALN_OK) return st;
-    if (!status && bad != ALN_OK) { g_err = "a pair failed"; return bad; }
-    return ALN_OK;
-}
-
-static int seqset_candidate_hits(aln_seqset *ss, const aln_params *params, double f_min, uint64_t *count)
-{
-    int st = seqset_cand_check(ss);
-    if (st != ALN_OK) return st;
-    Call c, ct;
-    const aln_seqset_block *b = &ss->cand_block;
-    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE, c)) != ALN_OK) return st;
-    if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE | ALN_OUT_TRACEBACK, ct)) != ALN_OK) return st;
-    HIPCHK(hipSetDevice(ss->ctx->device));
-    HIPCHK(hipStreamSynchronize(ss->slot->stream));
-    seqset_begin(ss);
-    *count = 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    int bad = ALN_OK;
-    if ((st = seqset_list_pass(ss, c, nullptr, nullptr, true, f_min, &bad)) != ALN_OK) { seqset_begin(ss); return st; }
-    // the selection numbered the candidates by list position: the held list speaks of pairs of the block
-    for (uint64_t &p : ss->hit_pair) {
-        if (p >= ss->cand_pair.size()) { g_err = "the selection's list leaves the candidate list"; seqset_begin(ss); return ALN_ERR_DEVICE; }
-        p = ss->cand_pair[p];
-    }
-    if ((st = seqset_hold_list(ss, ct, b)) != ALN_OK) { seqset_begin(ss); return st; }
-    ss->ms[3] = wall_ms(t0);
-    ss->held = true;
-    ss->held_block = *b;
-    *count = ss->hit_pair.size();
-    return ALN_OK;
-}
-
-// The k best targets per query row among the candidates: the list pass with the per-row selection of aln_search.hip, then the finish
-// of aln_seqset_best, held on the prefilter's block.
-static int seqset_candidate_best(aln_seqset *ss, const aln_params *params, uint32_t k, double f_min, uint32_t flags, uint64_t *count)
-{
-    int st = seqset_cand_check(ss);
-    if (st != ALN_OK) return st;
-    Call c, ct;
-    const aln_seqset_block *b = &ss->cand_block;
-    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE, c)) != ALN_OK) return st;
-    if (!count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (k < 1u || k > ALN_SEQSET_BEST_MAX) { g_err = "k must lie in 1 .. ALN_SEQSET_BEST_MAX"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (flags & ~ALN_BEST_SKIP_SELF) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (b->upper) { g_err = "the k best per query are defined on a rectangle: a pair of an upper block belongs to both of its sequences"; return ALN_ERR_UNSUPPORTED; }
-    if ((st = seqset_call(ss, params, b, ALN_OUT_SCORE | ALN_OUT_TRACEBACK, ct)) != ALN_OK) return st;
-    HIPCHK(hipSetDevice(ss->ctx->device));
-    hipStream_t q = ss->slot->stream;
-    HIPCHK(hipStreamSynchronize(q));
-    seqset_begin(ss);
-    *count = 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t rows = b->q_count, listed = ss->cand_pair.size();
-    BestPass best;
-    best.slots = aln_best_slots(k, b->t_count); best.flags = flags; best.f_min = f_min;
-    // the rows' running lists and their places in the candidate list, for this call
-    st = dev_ensure(ss->run_key, 8 * rows * best.slots, false);
-    if (st == ALN_OK) st = dev_ensure(ss->run_t, 4 * rows * best.slots, false);
-    if (st == ALN_OK) st = dev_ensure(ss->run_n, 4 * rows, false);
-    if (st == ALN_OK) st = dev_ensure(ss->row_first, 4 * (rows + 1), false);
-    uint32_t *tile_count;
-    uint64_t *tile_off;
-    if (st == ALN_OK) st = tiles_ensure(ss->tiles, aln_best_tiles(rows), &tile_count, &tile_off);
-    if (st != ALN_OK) return st;
-    HIPCHK(hipMemsetAsync(ss->run_n.p, 0, 4 * rows, q));
-    if (listed) {
-        HIPCHK(hipEventRecord(ss->ev[4], q));
-        aln_search_launch_rows(ss->cand_k.as<uint64_t>(), listed, rows, b->t_count, ss->row_first.as<uint32_t>(), q);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ss->ev[5], q));
-        HIPCHK(hipStreamSynchronize(q));
-        ss->ms[2] += ev_ms(ss->ev[4], ss->ev[5]);
-    }
-    int bad = ALN_OK;
-    if ((st = seqset_list_pass(ss, c, nullptr, nullptr, false, 0.0, &bad, &best)) != ALN_OK) { seqset_begin(ss); return st; }
-    uint64_t total = 0;
-    st = seqset_best_finish(ss, b, best.slots, tile_count, tile_off, &total);
-    if (st == ALN_OK) st = seqset_hold_list(ss, ct, b);
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_begin(ss); return st; }
-    ss->ms[3] = wall_ms(t0);
-    ss->held = true;
-    ss->held_block = *b;
-    *count = total;
-    return ALN_OK;
-}
-
-// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
-#define ALN_PREFILTER_GUARDED(ss, call)                                                           \
-    try {                                                                                         \
-        return call;                                                                              \
-    } catch (const std::bad_alloc &) {                                                            \
-        if ((ss) && (ss)->slot && (ss)->slot->stream) (void)hipDeviceSynchronize();               \
-        g_err = "out of host memory";                                                             \
-        return ALN_ERR_OOM;                                                                       \
-    }
-
 extern "C" int aln_seqset_kmer_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
 {
-    ALN_PREFILTER_GUARDED(ss, seqset_kmer_index(ss, k, alphabet, n_words))
+    ALN_SEQSET_GUARDED(ss, seqset_kmer_index(ss, k, alphabet, n_words))
 }
 
 extern "C" int aln_seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *spec, const aln_seqset_block *b, uint64_t *count)
 {
-    ALN_PREFILTER_GUARDED(ss, seqset_prefilter(ss, spec, b, count))
+    ALN_SEQSET_GUARDED(ss, seqset_prefilter(ss, spec, b, count))
 }
 
 extern "C" int aln_seqset_candidates(aln_seqset *ss, uint64_t first, uint64_t n, uint64_t *pair_index, uint32_t *q_seq, uint32_t *t_seq,
@@ -4108,17 +3961,17 @@ extern "C" int aln_seqset_candidates(aln_seqset *ss, uint64_t first, uint64_t n,
 
 extern "C" int aln_seqset_candidate_scores(aln_seqset *ss, const aln_params *params, double *f, int32_t *status)
 {
-    ALN_PREFILTER_GUARDED(ss, seqset_candidate_scores(ss, params, f, status))
+    ALN_SEQSET_GUARDED(ss, seqset_run_score(PairSource{ss, true, nullptr}, params, f, status))
 }
 
 extern "C" int aln_seqset_candidate_hits(aln_seqset *ss, const aln_params *params, double f_min, uint64_t *count)
 {
-    ALN_PREFILTER_GUARDED(ss, seqset_candidate_hits(ss, params, f_min, count))
+    ALN_SEQSET_GUARDED(ss, seqset_run_hits(PairSource{ss, true, nullptr}, params, f_min, count))
 }
 
 extern "C" int aln_seqset_candidate_best(aln_seqset *ss, const aln_params *params, uint32_t k, double f_min, uint32_t flags, uint64_t *count)
 {
-    ALN_PREFILTER_GUARDED(ss, seqset_candidate_best(ss, params, k, f_min, flags, count))
+    ALN_SEQSET_GUARDED(ss, seqset_run_best(PairSource{ss, true, nullptr}, params, k, f_min, flags, count))
 }
 
 static int seqset_held_check(aln_seqset *ss)

@@ -8,8 +8,12 @@
 //              r (2n - r - 1) / 2.  The row of a k is found by binary search on that closed form in uint64_t: a floating-point square
 //              root rounds wrongly near row boundaries once n approaches 2^32.
 //   sizes      n_seqs < 2^32, so a rectangle has fewer than 2^64 pairs and a triangle fewer than 2^63: every product below fits
+//   chunks     aln_seqset_cut: where a pass over a block or over a candidate list is cut (host only; cells are doubles, as the
+//              host's sums of them are)
 #pragma once
 #include <stdint.h>
+
+#include <vector>
 
 #include "../../include/aligner_hip.h"
 
@@ -87,4 +91,29 @@ inline void aln_seqset_window(const aln_seqset_block &b, uint64_t first, uint64_
         q[i] = cq; t[i] = ct;
         if (i + 1 < n) aln_seqset_next(b, &cq, &ct);
     }
+}
+
+// The chunks of a pass over `positions` consecutive positions (the pairs of a block in its order, or the entries of a candidate
+// list) of `total` cells together: appends the chunks' position counts.  next_cells() yields the cells of the next position, first
+// to last; it is not called when one chunk takes everything, so a pass that fits costs no walk.  A chunk ends where its cells reach
+// `target`, unless what is left after it is a tail of under a quarter of the target, which joins it; no chunk holds more than `cap`
+// positions (the queue entries are 32-bit and chunk-local).  forced: the target is a caller's order, not the set's own estimate,
+// which otherwise lets everything up to 2e10 cells run as one chunk.
+template <class NextCells>
+inline void aln_seqset_cut(NextCells next_cells, uint64_t positions, double total, double target, bool forced, uint64_t cap,
+                           std::vector<uint64_t> &counts)
+{
+    if (positions == 0) return;
+    if (positions <= cap && (total <= 1.5 * target || (!forced && total <= 2.0e10))) { counts.push_back(positions); return; }
+    uint64_t n = 0;
+    double acc = 0, done = 0;
+    for (uint64_t k = 0; k < positions; ++k) {
+        acc += next_cells();
+        ++n;
+        if (n >= cap || (acc >= target && (total - done - acc >= 0.25 * target || k + 1 == positions))) {
+            counts.push_back(n);
+            done += acc; acc = 0; n = 0;
+        }
+    }
+    if (n) counts.push_back(n);
 }

@@ -232,13 +232,14 @@ def expect_hits(f, status, f_min):
         return np.flatnonzero((status == OK) & (f >= f_min))
 
 
-def chunk_counts(lengths, q, t, target):
+def chunk_counts(lengths, q, t, target, cap=None):
     """Restatement of the set's chunking with ALN_CHUNK_CELLS = target: consecutive pairs until their cells reach the target, a tail
-    of less than a quarter of the target joins the chunk before it.  (All cell sums here are small integers: exact in doubles.)"""
+    of less than a quarter of the target joins the chunk before it.  cap: no chunk holds more pairs than this (None: no limit).
+    (All cell sums here are small integers: exact in doubles.)"""
     cells = (lengths[q] * lengths[t]).astype(np.float64)
     total = float(cells.sum())
     pairs = len(cells)
-    if total <= 1.5 * target:
+    if total <= 1.5 * target and (cap is None or pairs <= cap):
         return [pairs]
     cum = np.cumsum(cells)
     counts, start, done = [], 0, 0.0
@@ -246,6 +247,8 @@ def chunk_counts(lengths, q, t, target):
         k = int(np.searchsorted(cum, done + target, side="left"))       # the first pair at which the chunk's cells reach the target
         while k < pairs and not (total - cum[k] >= 0.25 * target or k + 1 == pairs):
             k += 1
+        if cap is not None:
+            k = min(k, start + cap - 1)                                  # ... or the pair that fills the chunk
         if k >= pairs:
             counts.append(pairs - start)
             break

@@ -7,6 +7,7 @@ The sharing kernel's tile is 16 queries x 256 targets (ALN_PF_QT x ALN_PF_TT, al
 tile 2048 pairs (aln_select.h), its offsets kernel's trip 256 tiles = 524 288 pairs."""
 import ctypes as C
 import hashlib
+import json
 import os
 import struct
 import subprocess
@@ -268,6 +269,83 @@ def test_chunked_list_pass_is_byte_identical(sset):
     digest, chunks = candidate_digest(sset)
     assert tok[0] == digest
     assert int(tok[1]) >= 3 and max(chunks) == 1
+
+
+def mixed_sources_run():
+    """Block and candidate passes taking turns on one set (they share one pass loop, one pair of plans and one set of growing
+    buffers), each result beside the same call made first on a set of its own.  A held pass is recorded as its list and the
+    summaries and both strings of its first, last and three middle positions, a score pass as its f and statuses.
+    -> {"pairs", "candidates", "calls": [[name, n and sha-256 on the fresh set, n and sha-256 in the sequence, bytes_up, bytes_down]]}"""
+    sem, m, d, e, kw = T.schemes()["core_local_11_2"]
+    seqs = T.make_set()
+    blk = rectangle(*T.RECT)
+    calls = [("block best", lambda s, c: s.best(m, d, e, 3, block=blk, semantics=sem)),
+             ("candidate best", lambda s, c: c.best(m, d, e, 3, semantics=sem)),
+             ("block hits", lambda s, c: s.hits(m, d, e, F_MIN, blk, semantics=sem)),
+             ("candidate hits", lambda s, c: c.hits(m, d, e, F_MIN, semantics=sem)),
+             ("candidate score", lambda s, c: c.score(m, d, e, semantics=sem)),
+             ("block score", lambda s, c: s.score(m, d, e, blk, semantics=sem))]
+
+    def record(out):
+        h = hashlib.sha256()
+        if isinstance(out, tuple):
+            f, status = out
+            h.update(f.tobytes()); h.update(status.tobytes())
+            return [len(f), h.hexdigest()]
+        n = len(out)
+        for a in (out.index, out.q, out.t, out.f):
+            h.update(a.tobytes())
+        res, strs = out.strings(np.array(sorted({0, n // 4, n // 2, 3 * n // 4, n - 1}) if n else [], dtype=np.uint32))
+        for name in T.FIELDS:
+            h.update(np.ascontiguousarray(res[name]).tobytes())
+        for qa, ta in strs:
+            h.update(qa.tobytes()); h.update(b"|"); h.update(ta.tobytes()); h.update(b"/")
+        return [n, h.hexdigest()]
+
+    fresh = []
+    for name, call in calls:
+        with SeqSet(seqs) as s:
+            fresh.append(record(call(s, s.prefilter(*K3, block=blk, **SELECTIVE))))
+    rows = []
+    with SeqSet(seqs) as s:
+        cand = s.prefilter(*K3, block=blk, **SELECTIVE)
+        for (name, call), alone in zip(calls, fresh):
+            out = call(s, cand)
+            st = s.stats()                                            # (before record fetches strings: a fetch has stats of its own)
+            rows.append([name, alone, record(out), st["bytes_up"], st["bytes_down"]])
+        return dict(pairs=s.pairs(blk), candidates=len(cand), calls=rows)
+
+
+MIXED_CHILD = r"""
+import json, sys
+sys.path.insert(0, %(root)r)
+sys.path.insert(0, %(tests)r)
+import test_prefilter_gpu as P
+print("MIXED", json.dumps(P.mixed_sources_run()))
+"""
+
+# bytes_up, bytes_down of the six calls of mixed_sources_run, in its order.  They are the parent commit's: the library built from the
+# commit before the two pass loops became one ran mixed_sources_run once (ALN_CHUNK_CELLS = 250 000, the library named by ALN_LIB).
+# (Both score passes: 12 bytes per position and 16 per chunk down, so 8 chunks each.)
+MIXED_BYTES = [(4244, 472), (3924, 424), (5504, 704), (5016, 624), (2412, 500), (2480, 716)]
+
+
+def test_block_and_candidate_passes_take_turns_on_one_set():
+    """ALN_CHUNK_CELLS = 250 000 in a child, as above, so that every pass runs in several chunks and its plans and buffers are the
+    ones the pass before it (over the other kind of source) left behind."""
+    env = dict(os.environ, ALN_CHUNK_CELLS="250000")
+    code = MIXED_CHILD % dict(root=ROOT, tests=os.path.join(ROOT, "tests"))
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "MIXED" in out.stdout, out.stdout + out.stderr
+    got = json.loads(out.stdout.split("MIXED")[1])
+    print(got)
+    assert 0 < got["candidates"] < got["pairs"] == 49
+    assert [r[0] for r in got["calls"]] == ["block best", "candidate best", "block hits", "candidate hits", "candidate score", "block score"]
+    for name, alone, mixed, up, down in got["calls"]:
+        assert mixed == alone and alone[0] > 0, name
+    assert got["calls"][4][1][0] == got["candidates"] and got["calls"][5][1][0] == got["pairs"]
+    assert (got["calls"][4][4] - 12 * got["candidates"]) // 16 >= 3 and (got["calls"][5][4] - 12 * got["pairs"]) // 16 >= 3      # chunks
+    assert [(r[3], r[4]) for r in got["calls"]] == MIXED_BYTES
 
 
 # ---------------------------------------------------------------- state

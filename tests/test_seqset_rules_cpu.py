@@ -1,7 +1,8 @@
 """The pair order of aln_seqset_* (aln_seqset_rules.h; no GPU): the header compiled into a driver with the host compiler against the
 independent restatement in seqset_ref.py -- every pair of every small block, rank as the inverse of unrank, the row boundaries of
 squares up to n = 2^32 - 1 (where a floating-point square root would round wrongly), the upper order against a literal restatement
-of generate_pairs -- plus the exported symbols and the C layout of aln_seqset_block against the ctypes struct."""
+of generate_pairs -- plus the exported symbols and the C layout of aln_seqset_block against the ctypes struct.  The header's chunk
+cutter (aln_seqset_cut) runs in the same driver against select_cases.chunk_counts, the restatement of the forced rule."""
 import ctypes as C
 import os
 import re
@@ -9,10 +10,12 @@ import shutil
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import select_cases as SC  # noqa: E402
 import seqset_ref  # noqa: E402
 
 from aligner_amd import _ffi  # noqa: E402
@@ -26,6 +29,7 @@ DRIVER = r"""
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 #include "aln_seqset_rules.h"
 static aln_seqset_block blk(char **a)
 {
@@ -39,6 +43,18 @@ int main(int argc, char **argv)
     // pairs <n_seqs> <block: 6 numbers>                  -> the number of pairs
     // all <n_seqs> <block>                               -> per pair "q t rank(q, t)", by unrank and, on the same line, by next
     // at <n_seqs> <block> <k> ...                        -> per k "q t rank(q, t)"
+    // cut <target> <forced> <cap>, cells on stdin        -> the chunk counts of aln_seqset_cut over those positions, on one line
+    if (argc == 5 && !strcmp(argv[1], "cut")) {
+        std::vector<double> cells;
+        double v, total = 0;
+        while (scanf("%lf", &v) == 1) { cells.push_back(v); total += v; }
+        size_t at = 0;
+        std::vector<uint64_t> counts;
+        aln_seqset_cut([&]() { return cells[at++]; }, cells.size(), total, atof(argv[2]), atoi(argv[3]) != 0, strtoull(argv[4], 0, 10), counts);
+        for (uint64_t c : counts) printf("%llu ", (unsigned long long)c);
+        printf("\n");
+        return 0;
+    }
     if (argc < 9) return 2;
     const uint64_t n_seqs = strtoull(argv[2], 0, 10);
     const aln_seqset_block b = blk(argv + 3);
@@ -173,6 +189,74 @@ def test_invalid_blocks_have_no_pairs(driver):
         assert _run(driver, "pairs", n_seqs, *b) == [[0]], b
         assert seqset_ref.block_pairs(n_seqs, *b) == 0, b
     assert _run(driver, "pairs", 10, 0, 10, 0, 10, 0, 0) == [[100]]
+
+
+# ---------------------------------------------------------------- where a pass is cut (aln_seqset_cut)
+CAP = 1 << 22                 # the pair limit of a chunk (ALN_SEQSET_CHUNK_PAIRS)
+
+
+def _cut(drv, cells, target, forced=True, cap=CAP):
+    text = "\n".join(str(int(c)) for c in cells) + "\n"
+    out = subprocess.run([drv, "cut", repr(float(target)), str(int(forced)), str(cap)], input=text, check=True, capture_output=True, text=True).stdout
+    return [int(v) for v in out.split()]
+
+
+def _restated(cells, target, cap=None):
+    """select_cases.chunk_counts over a hand-made cell list: position i is the pair (sequence i, a sequence of length 1)"""
+    n = len(cells)
+    lengths = np.array(list(cells) + [1], dtype=np.int64)
+    return SC.chunk_counts(lengths, np.arange(n), np.full(n, n), float(target), cap)
+
+
+@pytest.mark.parametrize("block", [("full",), ("upper", 0, SC.S), ("rect",) + SC.RECT_INNER], ids=lambda b: b[0])
+def test_cut_of_the_select_cases_set(driver, block):
+    """The header's cutter against the restatement at chunk_cells(): the block's own order, and every third pair of it as an ascending
+    sublist, as a candidate list is one."""
+    L = SC.set_lengths()
+    target = SC.chunk_cells()
+    q, t = SC.block_pairs_qt(block)
+    for step in (1, 3):
+        qs, ts = q[::step], t[::step]
+        want = SC.chunk_counts(L, qs, ts, float(target))
+        got = _cut(driver, L[qs] * L[ts], target)
+        assert got == want and sum(got) == len(qs), (block, step)
+        assert got == SC.chunk_counts(L, qs, ts, float(target), CAP)            # the cap is far away: it changes nothing
+    if block[0] != "rect":
+        assert len(SC.chunk_counts(L, q, t, float(target))) >= 3                # (the inner rectangle fits one chunk)
+
+
+CUT_EDGES = [
+    # name, cells, target, expected counts (worked out by hand from the rule)
+    ("total_is_1.5_targets", [10] * 15, 100, [15]),
+    ("one_cell_more", [10] * 14 + [11], 100, [10, 5]),
+    ("tail_under_a_quarter", [50, 50, 50, 50, 24], 100, [2, 3]),
+    ("tail_a_quarter", [50, 50, 50, 50, 25], 100, [2, 2, 1]),
+    ("first_pair_exceeds_the_target", [500] + [10] * 12, 100, [1, 12]),
+    ("last_position_reaches_the_target", [60, 60, 30, 30, 40], 100, [2, 3]),
+]
+
+
+@pytest.mark.parametrize("name,cells,target,want", CUT_EDGES, ids=[c[0] for c in CUT_EDGES])
+def test_cut_edges(driver, name, cells, target, want):
+    assert len(cells) <= 20
+    assert _restated(cells, target) == want
+    assert _cut(driver, cells, target) == want
+
+
+def test_cut_unforced_and_capped(driver):
+    cells = [10] * 20
+    # not forced and under 2e10 cells: one chunk whatever the target; forced, the target rules
+    for target in (1, 25, 1000):
+        assert _cut(driver, cells, target, forced=False) == [20]
+        assert _cut(driver, cells, target, forced=True) == _restated(cells, target)
+    assert _cut(driver, cells, 25) == [3, 3, 3, 3, 3, 3, 2]
+    # a cap of 7: it cuts where the cells alone would not (they fit one chunk, or reach the target only at 9 pairs), and stays out of
+    # the way where the cells cut sooner
+    for target, want in ((1000, [7, 7, 6]), (90, [7, 7, 6]), (30, [3, 3, 3, 3, 3, 3, 2])):
+        got = _cut(driver, cells, target, cap=7)
+        assert got == want == _restated(cells, target, cap=7)
+        assert max(got) <= 7 and sum(got) == 20
+    assert _cut(driver, [], 100) == []
 
 
 @pytest.fixture(scope="module")
