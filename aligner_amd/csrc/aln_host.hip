@@ -506,6 +506,8 @@ static int coop_lean_setting()
     return v;
 }
 // ALN_TRACE_PLAN=1 (read once): one stderr line per chunk that could share -- which build it runs, and the figures that decided it
+// ("aln plan:") -- and one per planned chunk, at the end of chunk_plan, that names its route ("aln route:": pairs of the batch
+// kernel, of the single-pair route, of the one-workgroup route, two pairs per wave, overlapped traceback, shared passes, kernel family)
 static bool trace_plan()
 {
     static const bool v = getenv("ALN_TRACE_PLAN") != nullptr;
@@ -827,6 +829,11 @@ static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, c
             k.grid = std::max(1u, std::min((items + 3u) / 4u, (uint32_t)ctx->cus * 3u));
         }
     }
+    // ALN_TRACE_PLAN's second line, for every planned chunk: which route serves it (a score pass brings no flags word back)
+    if (trace_plan())
+        fprintf(stderr, "aln route: pairs %zu small %zu single %zu wg %zu duo %d overlap %d share %s kernels %s\n", n, k.n_small,
+                k.single_pairs.size(), k.wg_pairs.size(), k.duo_qo ? 1 : 0, k.overlap ? 1 : 0, k.coop ? "coop" : k.coop_lean ? "lean" : "none",
+                c.fast ? "fast" : c.is_int ? "int" : "f64");
     return ALN_OK;
 }
 
