@@ -1181,6 +1181,28 @@ static void coop_stats_slot(Slot &s, const Chunk &k)
         }
     }
 }
+// ALN_TRACE_TB=1 (read once): one stderr line per chunk whose results are down -- how the parallel traceback crossed the strips of the
+// last pair of the chunk that went through aln_launch_traceback_single ("aln tb:": the chunk's pair index, rows per lane, strips, and
+// per strip the class aln_tb_single_chain_kernel left in seg[s].w: 0 not visited, 1 the end cell's own strip, 2 by its exit-map entry,
+// 3 entered outside the band, 4 inside the band but the map's walk had given up).  Unset: no copy, no synchronisation.
+static bool trace_tb()
+{
+    static const bool v = getenv("ALN_TRACE_TB") != nullptr;
+    return v;
+}
+static void trace_tb_slot(Slot &s, const Call &c, const Chunk &k)
+{
+    if (!trace_tb() || !(c.want_tb && c.store_dirs) || (k.single_pairs.empty() && k.wg_pairs.empty())) return;
+    const bool wg = !k.wg_pairs.empty();                       // launched after the single-pair route's pairs (slot_launch)
+    const uint32_t pair = wg ? k.wg_pairs.back() : k.single_pairs.back(), R = wg ? k.wg_r.back() : k.single_r.back();
+    const PairDesc &d = k.descs[pair];
+    const uint32_t ns = (d.M + 64 * R - 1) / (64 * R);
+    std::vector<uint32_t> seg(4 * (size_t)ns);
+    if (hipMemcpy(seg.data(), s.tbmap.as<uint4>() + (uint64_t)ns * (d.N + 1), seg.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return;
+    std::string digits(ns, '0');
+    for (uint32_t i = 0; i < ns; ++i) digits[i] = (char)('0' + (seg[4 * (size_t)i + 3] < 10u ? seg[4 * (size_t)i + 3] : 9u));
+    fprintf(stderr, "aln tb: pair %u R %u strips %u classes %s\n", pair, R, ns, digits.c_str());
+}
 // D2H of one chunk on `st`, then a stream sync: summaries into results[first ..], strings into tb_buf.  When the caller's
 // tb_off is the documented cumulative layout the chunk's strings are ONE span of tb_buf and are copied there directly;
 // any other layout goes through pinned staging and one memcpy per string.
@@ -1203,6 +1225,7 @@ static int slot_download(Slot &s, const Call &c, const Chunk &k, hipStream_t st,
     }
     HIPCHK(hipStreamSynchronize(st));
     coop_stats_slot(s, k);
+    trace_tb_slot(s, c, k);
     if (want && !direct) {
         const uint8_t *h = s.h_out.as<uint8_t>();
         for (size_t i = 0; i < k.n; ++i) {
@@ -1734,6 +1757,7 @@ extern "C" int aln_align_pair(aln_ctx *ctx, const aln_params *params, const uint
         HIPCHK(hipMemcpyAsync(s.h_out.p, s.tb.p, k.tb_bytes, hipMemcpyDeviceToHost, s.stream));
     }
     HIPCHK(hipStreamSynchronize(s.stream));
+    trace_tb_slot(s, c, k);
     if (out->status == ALN_OK && ok_shape) {
         if (want_tb) {
             const uint8_t *h = s.h_out.as<uint8_t>();

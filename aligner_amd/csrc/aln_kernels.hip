@@ -2728,10 +2728,13 @@ extern "C" __global__ void aln_tb_single_chain_kernel(TraceSingleArgs a)
         const uint32_t ey = cy_start, ex = cx_start;
         while (!stopped && s > 0) {
             --s;
-            a.seg[s] = make_uint4(cy, cx, off, 1);
             uint32_t c_lo, c_hi;
             uint4 m = make_uint4(0, 0, 0, 2);
-            if (tb_band(ey, ex, cy, d.N, c_lo, c_hi) && cx >= c_lo && cx <= c_hi) m = a.map[(size_t)s * (d.N + 1) + cx];
+            const bool in_band = tb_band(ey, ex, cy, d.N, c_lo, c_hi) && cx >= c_lo && cx <= c_hi;
+            if (in_band) m = a.map[(size_t)s * (d.N + 1) + cx];
+            // .w: how this strip is crossed (ALN_TRACE_TB prints it; the segments kernel only asks whether it is 0) -- 2 = by its map
+            // entry, 3 = entered outside the band, 4 = inside, but the map's walk had given up; 1 = the end cell's own strip
+            a.seg[s] = make_uint4(cy, cx, off, m.w != 2u ? 2u : in_band ? 4u : 3u);
             if (m.w != 2u) {
                 cx = m.x; cy = m.y; off += m.z; stopped = m.w != 0;
             } else {                                             // outside the band, or an entry the map gave up on: walk this strip here
