@@ -64,6 +64,8 @@ SEARCH_EXPORTS = ["aln_seqset_candidate_best"]
 PROFILE_EXPORTS = ["aln_seqset_profile_elements", "aln_seqset_held_profiles"]
 PROFILE_SKIP_SEED = 1           # ALN_PROFILE_SKIP_SEED
 PROFILE_MAX_CODES = 64          # ALN_PROFILE_MAX_CODES
+# every symbol the companion header include/aligner_hip_msa.h declares (the same library, as above)
+MSA_EXPORTS = ["aln_seqset_held_msa_fill", "aln_seqset_held_msa_plan"]
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
 TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
 # aln_pairset_loop_step's causes (aligner_amd/csrc/aln_loop_rules.h)
@@ -159,6 +161,20 @@ class ProfileSummary(C.Structure):
 
 
 assert C.sizeof(ProfileRecord) == 16 and C.sizeof(ProfileSummary) == 48
+
+
+class MsaRecord(C.Structure):
+    """aln_msa_record: one family alignment's shape (aligner_amd/csrc/aln_msa_rules.h)."""
+    _fields_ = [("center", C.c_uint32), ("rows", C.c_uint32), ("width", C.c_uint32), ("inserted", C.c_uint32)]
+
+
+class MsaSummary(C.Structure):
+    """aln_msa_summary: the counts and totals of one plan."""
+    _fields_ = [("held", C.c_uint64), ("contributing", C.c_uint64), ("self_pairs", C.c_uint32), ("between_members", C.c_uint32),
+                ("unlisted", C.c_uint32), ("overflow", C.c_uint32), ("bytes", C.c_uint64), ("total_rows", C.c_uint64)]
+
+
+assert C.sizeof(MsaRecord) == 16 and C.sizeof(MsaSummary) == 48
 
 
 class PrefilterSpec(C.Structure):
@@ -341,6 +357,10 @@ def load():
     lib.aln_seqset_held_profiles.restype = i
     lib.aln_seqset_held_profiles.argtypes = [vp, C.POINTER(Params), C.c_uint32, C.POINTER(HitFilter), vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp,
                                              C.POINTER(ProfileSummary)]
+    lib.aln_seqset_held_msa_plan.restype = i
+    lib.aln_seqset_held_msa_plan.argtypes = [vp, C.POINTER(Params), C.c_uint32, C.POINTER(HitFilter), vp, vp, C.c_uint64, vp, C.POINTER(MsaSummary)]
+    lib.aln_seqset_held_msa_fill.restype = i
+    lib.aln_seqset_held_msa_fill.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
     _lib = lib
     return lib
 

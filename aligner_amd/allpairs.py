@@ -36,6 +36,11 @@ line per residue position of the representative with the comma-separated counts 
 alphabet, then deletions, then every other code (the traceback's duplicated seed column left out).  A hit between two members of a
 family counts for no profile.
 
+With --cluster ... --msa FILE the alignment of every family of two or more records is written to FILE as aligned FASTA, merged on the
+device from the same hits (centre-star: every member as it is aligned to the representative, the members' inserts in columns of their
+own): one block per family -- `>rep_head` and the representative's row, then `>member_head hit=H` and the row of every hit between
+the representative and a member (H: the hit's position among the held hits) -- and a blank line; `-` where a row has no residue.
+
 With --kmer K the pairs are prefiltered on the device first: only the candidates -- pairs whose records share at least --min-shared N
 distinct words of K residues (default 0) and at least P / 1024 of the smaller record's distinct words (--min-shared-per-1024 P,
 default 0) -- are aligned at all.  Words are counted over the first A codes of the alphabet (--kmer-alphabet A; default 20, the
@@ -87,6 +92,7 @@ def main(argv=None):
     ap.add_argument("--min-t-cover", type=float, default=None, metavar="Z", help="print only hits whose alignment covers Z of the second record (with --best: selected first, then filtered)")
     ap.add_argument("--cluster", choices=("components", "greedy"), default=None, help="group the records by the held hits: prints head,rep_head,cluster_size per record (with --best or --f-min)")
     ap.add_argument("--profiles", default=None, metavar="FILE", help="with --cluster: write every family's per-position residue counts to FILE")
+    ap.add_argument("--msa", default=None, metavar="FILE", help="with --cluster: write every family's alignment to FILE as aligned FASTA")
     ap.add_argument("--kmer", type=int, default=None, metavar="K", help="prefilter: align only the pairs that share enough words of K residues (1 .. %d)" % _ffi.PREFILTER_MAX_K)
     ap.add_argument("--min-shared", type=int, default=None, metavar="N", help="with --kmer: candidates share at least N distinct words")
     ap.add_argument("--min-shared-per-1024", type=int, default=None, metavar="P", help="with --kmer: candidates share at least P / 1024 of the smaller record's distinct words (0 .. 1024)")
@@ -126,6 +132,8 @@ def main(argv=None):
             ap.error("--report / --min-identity / --min-q-cover / --min-t-cover work on held hits: give --best K, --best-candidates N or --f-min F")
     if a.profiles is not None and a.cluster is None:
         ap.error("--profiles counts the families of --cluster: give --cluster components|greedy")
+    if a.msa is not None and a.cluster is None:
+        ap.error("--msa aligns the families of --cluster: give --cluster components|greedy")
     if a.cluster is not None:
         if a.heuristic:
             ap.error("--cluster groups by the plain alignment's hits: not with --heuristic")
@@ -175,6 +183,15 @@ def main(argv=None):
                     fh.write(">%s hits=%d\n" % (heads[int(r["center"])], int(r["hits"])))
                     for column in prof.counts(i).T.tolist():
                         fh.write(",".join(str(x) for x in column) + "\n")
+        if a.msa is not None:
+            fam = held.msa(got, matrix=matrix if filtered else None, min_identity=a.min_identity or 0.0, min_q_cover=a.min_q_cover or 0.0,
+                           min_t_cover=a.min_t_cover or 0.0)
+            with open(a.msa, "w") as fh:
+                for i in range(len(fam)):
+                    names = [">%s" % heads[int(fam.centers[i])]] + [">%s hit=%d" % (heads[int(m)], int(h)) for m, h in zip(fam.members(i)[1:], fam.hits(i))]
+                    for name, row in zip(names, fam.text(i)):
+                        fh.write("%s\n%s\n" % (name, row))
+                    fh.write("\n")
 
     def tail(held, pos=None, reports=None):
         """`,z,p_emp` and the report's columns per held position, or empty strings without --shuffles and --report; pos: the

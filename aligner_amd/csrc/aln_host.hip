@@ -300,7 +300,7 @@ static void warm_context(aln_ctx *c)
         if (hipSetDevice(c->devs[d]->device) != hipSuccess) continue;
         (void)aln_warm_single(); (void)aln_warm_tb(); (void)aln_warm_generic();
         (void)aln_warm_fast_cl(); (void)aln_warm_fast_cl_solo(); (void)aln_warm_fast_rest(); (void)aln_warm_fast_rest_solo();
-        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile();
+        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile(); (void)aln_warm_msa();
         aln_pair_result r;
         (void)aln_align_pair(c, &p, q.data(), L, t.data(), L, &r, qa.data(), ta.data(), nullptr, nullptr);   // devices in turn
     }
@@ -3249,6 +3249,16 @@ struct aln_seqset : CallStats {
     DevBuf cluster;                   // aln_seqset_held_cluster: the call's tables, one arena
     DevBuf profile;                   // aln_seqset_held_profiles: the call's tables and its output, one arena
     uint8_t held_blank = 0;           // the blank code of the held pass (aln_seqset_held_profiles without params)
+    // aln_seqset_held_msa_plan / _fill: the plan's tables and the fill's tables and output, an arena each; the passes that replaced the
+    // held hits so far, and what the host keeps of the last plan (valid: there is one)
+    DevBuf msa, msa_out;
+    uint64_t held_passes = 0;
+    struct MsaPlan {
+        bool valid = false;
+        uint64_t passes = 0, n = 0, held = 0, n_centers = 0, n_ins = 0, bytes = 0, total_rows = 0;
+        uint32_t blank = 0;
+        std::vector<uint64_t> byte_off, row_off;
+    } msa_plan;
     // the k-mer prefilter (aln_prefilter_rules.h).  The index: one bitmap row of kmer_stride elements and one word count per
     // sequence, resident until the next aln_seqset_kmer_index (kmer_k == 0: none built)
     uint32_t kmer_k = 0, kmer_alphabet = 0, kmer_stride = 0;
@@ -3288,7 +3298,7 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     held_free(ss->held_store);
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
                    &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster, &ss->kmer_bits, &ss->kmer_n,
-                   &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first, &ss->profile};
+                   &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first, &ss->profile, &ss->msa, &ss->msa_out};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
@@ -3611,6 +3621,7 @@ static int seqset_pass(aln_seqset *ss, const Call &c, PairSource &src, double *f
 static void seqset_begin(aln_seqset *ss)
 {
     ss->held = false;
+    ++ss->held_passes;                // (a plan of aln_seqset_held_msa_plan is a plan of the held hits it saw)
     ss->hit_pair.clear(); ss->hit_score.clear(); ss->hit_q.clear(); ss->hit_t.clear();
     held_clear(ss->held_store);
     stats_reset(*ss);
@@ -4714,6 +4725,260 @@ extern "C" int aln_seqset_held_profiles(aln_seqset *ss, const aln_params *params
 {
     try {
         return seqset_held_profiles(ss, params, flags, filter, label, centers, n_centers, n_codes, out, capacity, records, summary);
+    } catch (const std::bad_alloc &) {
+        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
+}
+
+// ---------------------------------------------------------------- family alignments of a set (aln_msa.hip, aln_msa_rules.h)
+// The plan's tables, carved out of one arena (every piece 256-aligned); base == nullptr only sizes it.
+struct MsaPlanBufs {
+    unsigned long long *misc = nullptr;
+    uint32_t *hit_q = nullptr, *hit_t = nullptr, *label = nullptr, *slot_of = nullptr, *centers = nullptr, *mark = nullptr, *ins = nullptr, *col = nullptr;
+    uint64_t *ins_off = nullptr;
+    aln_msa_record *rec = nullptr;
+};
+static size_t msa_plan_carve(uint8_t *base, uint64_t n, uint64_t held, uint64_t n_centers, uint64_t n_ins, MsaPlanBufs *out)
+{
+    size_t pos = 0;
+    auto take = [&](size_t bytes) -> uint8_t * {
+        uint8_t *p = base ? base + pos : nullptr;
+        pos += (size_t)align256(std::max<size_t>(bytes, 4));
+        return p;
+    };
+    MsaPlanBufs b;
+    b.misc = reinterpret_cast<unsigned long long *>(take(8 * ALN_MSA_MISC_WORDS));
+    b.hit_q = reinterpret_cast<uint32_t *>(take(4 * held));
+    b.hit_t = reinterpret_cast<uint32_t *>(take(4 * held));
+    b.label = reinterpret_cast<uint32_t *>(take(4 * n));
+    b.slot_of = reinterpret_cast<uint32_t *>(take(4 * n));
+    b.centers = reinterpret_cast<uint32_t *>(take(4 * n_centers));
+    b.ins_off = reinterpret_cast<uint64_t *>(take(8 * n_centers));
+    b.rec = reinterpret_cast<aln_msa_record *>(take(sizeof(aln_msa_record) * n_centers));
+    b.mark = reinterpret_cast<uint32_t *>(take(4 * held));
+    b.ins = reinterpret_cast<uint32_t *>(take(4 * n_ins));
+    b.col = reinterpret_cast<uint32_t *>(take(4 * n_ins));
+    if (out) *out = b;
+    return pos;
+}
+// The fill's tables and its output, an arena of their own (sized when the plan's totals are known).
+struct MsaFillBufs {
+    uint64_t *byte_off = nullptr, *row_off = nullptr;
+    uint32_t *taken = nullptr, *list = nullptr, *hit_row = nullptr, *row_hit = nullptr;
+    uint8_t *out = nullptr;
+};
+static size_t msa_fill_carve(uint8_t *base, uint64_t held, uint64_t n_centers, uint64_t bytes, uint64_t total_rows, MsaFillBufs *out)
+{
+    size_t pos = 0;
+    auto take = [&](size_t room) -> uint8_t * {
+        uint8_t *p = base ? base + pos : nullptr;
+        pos += (size_t)align256(std::max<size_t>(room, 4));
+        return p;
+    };
+    MsaFillBufs b;
+    b.byte_off = reinterpret_cast<uint64_t *>(take(8 * n_centers));
+    b.row_off = reinterpret_cast<uint64_t *>(take(8 * n_centers));
+    b.taken = reinterpret_cast<uint32_t *>(take(4 * n_centers));
+    b.list = reinterpret_cast<uint32_t *>(take(4 * total_rows));
+    b.hit_row = reinterpret_cast<uint32_t *>(take(4 * held));
+    b.row_hit = reinterpret_cast<uint32_t *>(take(4 * total_rows));
+    b.out = take(bytes);
+    if (out) *out = b;
+    return pos;
+}
+
+// what both calls hand the kernels of the plan's arena
+static void msa_args(const aln_seqset *ss, const MsaPlanBufs &b, uint64_t n, uint64_t held, uint64_t n_centers, uint64_t n_ins, uint32_t blank, MsaArgs *a)
+{
+    memset(a, 0, sizeof *a);
+    a->held = ss->held_store.info.as<HeldEntry>(); a->res = ss->held_store.res.as<aln_pair_result>(); a->tb = ss->held_store.tb.as<uint8_t>();
+    a->hit_q = b.hit_q; a->hit_t = b.hit_t; a->label = b.label; a->len = ss->d_len.as<uint32_t>(); a->slot_of = b.slot_of; a->ins_off = b.ins_off;
+    a->n_ins = n_ins;
+    a->n_held = (uint32_t)held; a->n_seqs = (uint32_t)n; a->n_centers = (uint32_t)n_centers; a->blank = blank;
+    a->ins = b.ins; a->col = b.col; a->mark = b.mark; a->rec = b.rec; a->misc = b.misc;
+    a->seqs = ss->slot->seqs.as<uint8_t>(); a->seq_off = ss->d_off.as<uint64_t>();
+}
+
+// Who contributes, the inserts and the columns of every listed centre.  Up go what the profile call uploads (the offsets are those of
+// the centres' ins / col tables); down come the records and the counters.  The held store is only read.  A refusal leaves the plan
+// before it as it was; once the tables are being rewritten there is no plan until this one has gone well.
+static int seqset_held_msa_plan(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, const uint32_t *label,
+                                const uint32_t *centers, uint64_t n_centers, aln_msa_record *records, aln_msa_summary *summary)
+{
+    // (what needs no set comes first)
+    if (flags != 0) { g_err = "flags must be 0: the seed column is never part of a family alignment"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((params != nullptr) != (filter != nullptr)) { g_err = "params and filter come together: the filter's reports are classed under params"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_centers && !centers) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!aln_profile_centers_ok(centers, n_centers, 1ull << 32)) {
+        g_err = "the centres must be strictly ascending sequence numbers of the set";
+        return ALN_ERR_INVALID_ARGUMENT;
+    }
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    std::vector<uint32_t> bits;
+    int st = filter ? seqset_report_check(ss, params, ALN_REPORT_SKIP_SEED, bits) : seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    if (filter && filter->reserved != 0) { g_err = "the filter's reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ss->destroyed) { g_err = "the set was destroyed"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n_centers > ss->n || !aln_profile_centers_ok(centers, n_centers, ss->n)) {
+        g_err = "the centres must be strictly ascending sequence numbers of the set";
+        return ALN_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t n = ss->n, held = ss->hit_pair.size();      // (n < 2^32: aln_seqset_create; held <= 0xFFFFFFF0: seqset_hold_list)
+    if (!summary || (n && !label) || (n_centers && !records)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    std::vector<uint64_t> ins_off(n_centers);
+    uint64_t n_ins = 0;
+    for (uint64_t i = 0; i < n_centers; ++i) { ins_off[i] = n_ins; n_ins += (uint64_t)ss->len[centers[i]] + 1ull; }
+    if (n_ins > (1ull << 38)) { g_err = "more than 2^38 centre positions"; return ALN_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    // (growing the arena drops the tables of the plan before: it is given up here, before anything else moves)
+    if (ss->msa.cap < msa_plan_carve(nullptr, n, held, n_centers, n_ins, nullptr)) ss->msa_plan.valid = false;
+    if ((st = dev_ensure(ss->msa, msa_plan_carve(nullptr, n, held, n_centers, n_ins, nullptr), false)) != ALN_OK) return st;
+    if (filter && held) {
+        if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * held, false)) != ALN_OK) return st;
+    }
+    ss->msa_plan.valid = false;           // (the tables are rewritten from here on)
+    MsaPlanBufs b;
+    msa_plan_carve(ss->msa.as<uint8_t>(), n, held, n_centers, n_ins, &b);
+    const uint32_t blank = params ? params->blank_code : ss->held_blank;
+    MsaArgs a;
+    msa_args(ss, b, n, held, n_centers, n_ins, blank, &a);
+    a.rep = filter && held ? ss->reports.as<aln_hit_report>() : nullptr;
+    if (filter) a.filter = *filter;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<aln_msa_record> rec_h(n_centers);
+    unsigned long long misc[ALN_MSA_MISC_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        if (held) {
+            HIPCHK(hipMemcpyAsync(b.hit_q, ss->hit_q.data(), 4 * held, hipMemcpyHostToDevice, q));
+            HIPCHK(hipMemcpyAsync(b.hit_t, ss->hit_t.data(), 4 * held, hipMemcpyHostToDevice, q));
+            if (filter) HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
+        }
+        if (n) HIPCHK(hipMemcpyAsync(b.label, label, 4 * n, hipMemcpyHostToDevice, q));
+        if (n_centers) {
+            HIPCHK(hipMemcpyAsync(b.centers, centers, 4 * n_centers, hipMemcpyHostToDevice, q));
+            HIPCHK(hipMemcpyAsync(b.ins_off, ins_off.data(), 8 * n_centers, hipMemcpyHostToDevice, q));
+        }
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        HIPCHK(hipMemsetAsync(b.misc, 0, 8 * ALN_MSA_MISC_WORDS, q));
+        if (n) HIPCHK(hipMemsetAsync(b.slot_of, 0xFF, 4 * n, q));
+        if (n_centers) HIPCHK(hipMemsetAsync(b.rec, 0, sizeof(aln_msa_record) * n_centers, q));
+        if (n_ins) HIPCHK(hipMemsetAsync(b.ins, 0, 4 * n_ins, q));
+        if (held && filter) {
+            aln_report_launch(a.held, a.res, a.tb, nullptr, (uint32_t)held, (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols,
+                              params->blank_code, ALN_REPORT_SKIP_SEED, ss->reports.as<aln_hit_report>(), q);
+            HIPCHK(hipGetLastError());
+        }
+        aln_msa_launch_plan(&a, b.centers, b.slot_of, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(misc, b.misc, 8 * ALN_MSA_MISC_WORDS, hipMemcpyDeviceToHost, q));
+        if (n_centers) HIPCHK(hipMemcpyAsync(rec_h.data(), b.rec, sizeof(aln_msa_record) * n_centers, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    if (misc[ALN_MSA_MISC_TOO_WIDE]) { g_err = "a family's width does not fit 32 bits"; return ALN_ERR_UNSUPPORTED; }
+    aln_seqset::MsaPlan plan;
+    plan.byte_off.resize(n_centers); plan.row_off.resize(n_centers);
+    if (!aln_msa_offsets(rec_h.data(), n_centers, plan.byte_off.data(), plan.row_off.data(), &plan.bytes, &plan.total_rows) || plan.bytes > (1ull << 46)) {
+        g_err = "the family alignments take more than 2^46 bytes";
+        return ALN_ERR_UNSUPPORTED;
+    }
+    plan.valid = true; plan.passes = ss->held_passes; plan.n = n; plan.held = held; plan.n_centers = n_centers; plan.n_ins = n_ins; plan.blank = blank;
+    ss->msa_plan = std::move(plan);
+    if (n_centers) memcpy(records, rec_h.data(), sizeof(aln_msa_record) * n_centers);
+    auto word = [](unsigned long long v) { return (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull); };
+    memset(summary, 0, sizeof *summary);
+    summary->held = held;
+    summary->contributing = misc[ALN_PROFILE_COUNTS];
+    summary->self_pairs = word(misc[ALN_PROFILE_SELF]);
+    summary->between_members = word(misc[ALN_PROFILE_BETWEEN]);
+    summary->unlisted = word(misc[ALN_PROFILE_UNLISTED]);
+    summary->overflow = word(misc[ALN_PROFILE_MISC_OVERFLOW]);
+    summary->bytes = ss->msa_plan.bytes;
+    summary->total_rows = ss->msa_plan.total_rows;
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 8ull * held + 4ull * n + 12ull * n_centers + (filter && held ? 4ull * bits.size() : 0);
+    ss->bytes[1] = sizeof(aln_msa_record) * n_centers + 8ull * ALN_MSA_MISC_WORDS;
+    return ALN_OK;
+}
+
+// The matrices and row lists of the last plan.  Nothing is decided again: the marks, the inserts and the columns are the plan's, resident.
+static int seqset_held_msa_fill(aln_seqset *ss, uint8_t *out, uint64_t capacity_bytes, uint32_t *row_hit, uint64_t capacity_rows)
+{
+    int st = seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    const aln_seqset::MsaPlan &plan = ss->msa_plan;
+    if (!plan.valid) { g_err = "no plan: aln_seqset_held_msa_plan has not run on this set"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (plan.passes != ss->held_passes || plan.held != ss->hit_pair.size() || plan.n != ss->n) {
+        g_err = "the plan is of held hits that another pass has replaced";
+        return ALN_ERR_INVALID_ARGUMENT;
+    }
+    if (capacity_bytes < plan.bytes || capacity_rows < plan.total_rows) { g_err = "a capacity is below the plan's totals"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((plan.bytes && !out) || (plan.total_rows && !row_hit)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t n = plan.n, held = plan.held, n_centers = plan.n_centers;
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    if ((st = dev_ensure(ss->msa_out, msa_fill_carve(nullptr, held, n_centers, plan.bytes, plan.total_rows, nullptr), false)) != ALN_OK) return st;
+    MsaPlanBufs b;
+    msa_plan_carve(ss->msa.as<uint8_t>(), n, held, n_centers, plan.n_ins, &b);
+    MsaFillBufs f;
+    msa_fill_carve(ss->msa_out.as<uint8_t>(), held, n_centers, plan.bytes, plan.total_rows, &f);
+    MsaArgs a;
+    msa_args(ss, b, n, held, n_centers, plan.n_ins, plan.blank, &a);
+    a.byte_off = f.byte_off; a.row_off = f.row_off; a.taken = f.taken; a.list = f.list; a.hit_row = f.hit_row; a.row_hit = f.row_hit; a.out = f.out;
+    a.bytes = plan.bytes; a.total_rows = plan.total_rows;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        if (n_centers) {
+            HIPCHK(hipMemcpyAsync(f.byte_off, plan.byte_off.data(), 8 * n_centers, hipMemcpyHostToDevice, q));
+            HIPCHK(hipMemcpyAsync(f.row_off, plan.row_off.data(), 8 * n_centers, hipMemcpyHostToDevice, q));
+        }
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        if (n_centers) HIPCHK(hipMemsetAsync(f.taken, 0, 4 * n_centers, q));
+        if (plan.total_rows) HIPCHK(hipMemsetAsync(f.list, 0xFF, 4 * plan.total_rows, q));
+        if (plan.total_rows) HIPCHK(hipMemsetAsync(f.row_hit, 0xFF, 4 * plan.total_rows, q));
+        if (plan.bytes) HIPCHK(hipMemsetAsync(f.out, (int)plan.blank, plan.bytes, q));
+        aln_msa_launch_fill(&a, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        if (plan.bytes) HIPCHK(hipMemcpyAsync(out, f.out, plan.bytes, hipMemcpyDeviceToHost, q));
+        if (plan.total_rows) HIPCHK(hipMemcpyAsync(row_hit, f.row_hit, 4 * plan.total_rows, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 16ull * n_centers;
+    ss->bytes[1] = plan.bytes + 4ull * plan.total_rows;
+    return ALN_OK;
+}
+
+// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
+extern "C" int aln_seqset_held_msa_plan(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, const uint32_t *label,
+                                        const uint32_t *centers, uint64_t n_centers, aln_msa_record *records, aln_msa_summary *summary)
+{
+    try {
+        return seqset_held_msa_plan(ss, params, flags, filter, label, centers, n_centers, records, summary);
+    } catch (const std::bad_alloc &) {
+        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
+}
+
+extern "C" int aln_seqset_held_msa_fill(aln_seqset *ss, uint8_t *out, uint64_t capacity_bytes, uint32_t *row_hit, uint64_t capacity_rows)
+{
+    try {
+        return seqset_held_msa_fill(ss, out, capacity_bytes, row_hit, capacity_rows);
     } catch (const std::bad_alloc &) {
         if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
         g_err = "out of host memory";

@@ -1,4 +1,4 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip and aln_profile.hip define
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip and aln_msa.hip define
 // and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
 #pragma once
@@ -7,6 +7,7 @@
 #include "aln_device.h"
 #include "aln_cluster_rules.h"
 #include "aln_profile_rules.h"
+#include "aln_msa_rules.h"
 
 // what every kernel of aln_cluster.hip takes: n label slots (node numbers 0 .. n - 1, those of `nodes` being nodes), m listed edges
 struct ClusterArgs {
@@ -35,6 +36,32 @@ struct ProfileArgs {
     uint32_t *out;                   // the profiles, zeroed
     aln_profile_record *rec;         // n_centers
     unsigned long long *misc;        // ALN_PROFILE_MISC_WORDS counters, zeroed
+};
+
+// what the kernels of aln_msa.hip take: the held store (read only), the plan's tables and, for the fill, the offsets and the outputs
+struct MsaArgs {
+    const HeldEntry *held; const aln_pair_result *res; const uint8_t *tb;      // n_held entries of the held store
+    const aln_hit_report *rep;       // n_held reports, or null: no filter (the plan only)
+    aln_hit_filter filter;
+    const uint32_t *hit_q, *hit_t;   // n_held endpoints each
+    const uint32_t *label, *len;     // n_seqs each
+    const uint32_t *slot_of;         // n_seqs: the family of a centre, ALN_CLUSTER_NONE without one
+    const uint64_t *ins_off;         // n_centers: centre i's first entry of ins and col (len + 1 entries each)
+    uint64_t n_ins;                  // the entries of ins, and of col
+    uint32_t n_held, n_seqs, n_centers, blank;
+    uint32_t *ins, *col;             // the insert widths (zeroed before the plan) and the columns of the residues
+    uint32_t *mark;                  // n_held: the slot of a contributing hit, else ALN_CLUSTER_NONE
+    aln_msa_record *rec;             // n_centers
+    unsigned long long *misc;        // ALN_MSA_MISC_WORDS counters, zeroed before the plan
+    // the fill
+    const uint8_t *seqs; const uint64_t *seq_off;   // the set's residues and where every sequence starts
+    const uint64_t *byte_off, *row_off;             // n_centers each: family i's first byte of out and first entry of list / row_hit
+    uint32_t *taken;                 // n_centers tickets, zeroed before the fill
+    uint32_t *list;                  // total_rows: a family's contributing hits in ticket order (entry 0 of a family unused)
+    uint32_t *hit_row;               // n_held: the row of a contributing hit
+    uint32_t *row_hit;               // total_rows: the held position of every row
+    uint8_t *out;                    // bytes, filled with the blank code before the fill
+    uint64_t bytes, total_rows;
 };
 
 static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
@@ -162,5 +189,10 @@ void aln_search_launch_chunk(const uint64_t *list, const uint32_t *row_first, co
 int aln_warm_profile(void);
 void aln_profile_launch_slots(const uint32_t *centers, uint32_t n_centers, uint32_t n_seqs, uint32_t *slot_of, aln_profile_record *rec, hipStream_t s);
 void aln_profile_launch(const ProfileArgs *a, hipStream_t s);
+
+// ---- aln_msa.hip: the family alignments of a sequence set (aln_msa_rules.h)
+int aln_warm_msa(void);
+void aln_msa_launch_plan(const MsaArgs *a, const uint32_t *centers, uint32_t *slot_of, hipStream_t s);
+void aln_msa_launch_fill(const MsaArgs *a, hipStream_t s);
 
 }

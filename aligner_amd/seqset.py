@@ -473,6 +473,42 @@ class HeldHits:
 
         return _profile.Profiles(cen, o.len, own, codes, out, rec, _profile.summary_dict(summ))
 
+    def msa(self, labels, centers=None, matrix=None, min_identity=0.0, min_q_cover=0.0, min_t_cover=0.0, min_columns=0, blank=98):
+        """aln_seqset_held_msa_plan + aln_seqset_held_msa_fill: for every centre one matrix of residue codes -- row 0 the centre, then
+        one row per held hit between the centre and a member of its family, in ascending held position -- in one set of columns, the
+        members' inserts included (centre-star), laid out and written on the device; only the matrices and row lists come down.
+        labels, centers, matrix and the thresholds as .profiles takes them; the traceback's seed column is never part of it.  Returns
+        an msa.FamilyAlignments."""
+        from . import msa as _msa
+        from . import profile as _profile
+        o = self.owner
+        thresholds = bool(min_identity or min_q_cover or min_t_cover or min_columns)
+        if matrix is None and thresholds:
+            raise ValueError("aln_seqset_held_msa_plan: thresholds need the matrix their classes are counted under")
+        label = _profile.labels_of(labels)
+        if label.shape != (len(o),):
+            raise ValueError("aln_seqset_held_msa_plan: one label per sequence of the set")
+        cen = _profile.default_centers(label) if centers is None else np.ascontiguousarray(centers, dtype=np.uint32)
+        rec = np.zeros(len(cen), dtype=_msa.RECORD_DTYPE)
+        summ = _ffi.MsaSummary()
+        if matrix is None:
+            p_ref, flt_ref = None, None
+        else:
+            p, _held = self._report_params(matrix, blank)
+            flt = _ffi.HitFilter(float(min_identity), float(min_q_cover), float(min_t_cover), int(min_columns), 0)
+            p_ref, flt_ref = C.byref(p), C.byref(flt)
+        st = o.lib.aln_seqset_held_msa_plan(o.handle, p_ref, 0, flt_ref, label.ctypes.data if len(label) else None, cen.ctypes.data if len(cen) else None,
+                                            len(cen), rec.ctypes.data if len(cen) else None, C.byref(summ))
+        runtime.raise_for_status(st, "aln_seqset_held_msa_plan")
+        self.last_msa_plan_stats = o.stats()
+        out = np.zeros(int(summ.bytes), dtype=np.uint8)
+        row_hit = np.zeros(int(summ.total_rows), dtype=np.uint32)
+        st = o.lib.aln_seqset_held_msa_fill(o.handle, out.ctypes.data if len(out) else None, len(out), row_hit.ctypes.data if len(row_hit) else None,
+                                            len(row_hit))
+        runtime.raise_for_status(st, "aln_seqset_held_msa_fill")
+        # (without a matrix the device used the held pass's blank code: the one the pass was given)
+        return _msa.FamilyAlignments(cen, rec, _msa.summary_dict(summ), out, row_hit, self.q, self.t, o.alphabet, blank)
+
     def fractions(self, reports, keep=None):
         """report_fractions of records that belong to the listed positions (default: all)."""
         w = self._keep(keep)
