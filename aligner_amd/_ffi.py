@@ -66,6 +66,10 @@ PROFILE_SKIP_SEED = 1           # ALN_PROFILE_SKIP_SEED
 PROFILE_MAX_CODES = 64          # ALN_PROFILE_MAX_CODES
 # every symbol the companion header include/aligner_hip_msa.h declares (the same library, as above)
 MSA_EXPORTS = ["aln_seqset_held_msa_fill", "aln_seqset_held_msa_plan"]
+# every symbol the companion header include/aligner_hip_cigar.h declares (the same library, as above)
+CIGAR_EXPORTS = ["aln_seqset_held_cigar_fill", "aln_seqset_held_cigar_plan"]
+CIGAR_EXTENDED = 1              # ALN_CIGAR_EXTENDED
+CIGAR_CLIPS = 2                 # ALN_CIGAR_CLIPS
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
 TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
 # aln_pairset_loop_step's causes (aligner_amd/csrc/aln_loop_rules.h)
@@ -175,6 +179,21 @@ class MsaSummary(C.Structure):
 
 
 assert C.sizeof(MsaRecord) == 16 and C.sizeof(MsaSummary) == 48
+
+
+class CigarRecord(C.Structure):
+    """aln_cigar_record: one listed hit's coordinates and counts (aligner_amd/csrc/aln_cigar_rules.h)."""
+    _fields_ = [("n_ops", C.c_uint32), ("q_start", C.c_uint32), ("q_end", C.c_uint32), ("t_start", C.c_uint32), ("t_end", C.c_uint32),
+                ("matches", C.c_uint32), ("block", C.c_uint32), ("status", C.c_int32)]
+
+
+class CigarSummary(C.Structure):
+    """aln_cigar_summary: the counts and the total of one plan."""
+    _fields_ = [("held", C.c_uint64), ("listed", C.c_uint64), ("total_ops", C.c_uint64), ("failed", C.c_uint32), ("padded", C.c_uint32),
+                ("overflow", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(CigarRecord) == 32 and C.sizeof(CigarSummary) == 48
 
 
 class PrefilterSpec(C.Structure):
@@ -361,6 +380,10 @@ def load():
     lib.aln_seqset_held_msa_plan.argtypes = [vp, C.POINTER(Params), C.c_uint32, C.POINTER(HitFilter), vp, vp, C.c_uint64, vp, C.POINTER(MsaSummary)]
     lib.aln_seqset_held_msa_fill.restype = i
     lib.aln_seqset_held_msa_fill.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+    lib.aln_seqset_held_cigar_plan.restype = i
+    lib.aln_seqset_held_cigar_plan.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, C.POINTER(CigarSummary)]
+    lib.aln_seqset_held_cigar_fill.restype = i
+    lib.aln_seqset_held_cigar_fill.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
     _lib = lib
     return lib
 

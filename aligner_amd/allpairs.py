@@ -41,6 +41,12 @@ device from the same hits (centre-star: every member as it is aligned to the rep
 own): one block per family -- `>rep_head` and the representative's row, then `>member_head hit=H` and the row of every hit between
 the representative and a member (H: the hit's position among the held hits) -- and a blank line; `-` where a row has no residue.
 
+With --paf FILE (and --best, --best-candidates or --f-min: a held pass) every printed hit is also written to FILE as one PAF line, its
+alignment run-length encoded on the device from the held strings: the 12 standard columns -- q_head, its length, start and end (0-based,
+end exclusive), strand `+`, t_head, its length, start and end, the matching residues, the alignment's columns (the traceback's
+duplicated seed column left out), mapping quality 255 -- then `af:f:<f>` and `cg:Z:<cigar>`; --eqx writes `=` / `X` in place of `M`.
+The lines follow the rows' order; with --min-* only the kept hits are written.  Not with --heuristic or --cluster.
+
 With --kmer K the pairs are prefiltered on the device first: only the candidates -- pairs whose records share at least --min-shared N
 distinct words of K residues (default 0) and at least P / 1024 of the smaller record's distinct words (--min-shared-per-1024 P,
 default 0) -- are aligned at all.  Words are counted over the first A codes of the alphabet (--kmer-alphabet A; default 20, the
@@ -93,6 +99,8 @@ def main(argv=None):
     ap.add_argument("--cluster", choices=("components", "greedy"), default=None, help="group the records by the held hits: prints head,rep_head,cluster_size per record (with --best or --f-min)")
     ap.add_argument("--profiles", default=None, metavar="FILE", help="with --cluster: write every family's per-position residue counts to FILE")
     ap.add_argument("--msa", default=None, metavar="FILE", help="with --cluster: write every family's alignment to FILE as aligned FASTA")
+    ap.add_argument("--paf", default=None, metavar="FILE", help="write every printed hit to FILE as a PAF line with its CIGAR (with --best, --best-candidates or --f-min)")
+    ap.add_argument("--eqx", action="store_true", help="with --paf: = and X in place of M")
     ap.add_argument("--kmer", type=int, default=None, metavar="K", help="prefilter: align only the pairs that share enough words of K residues (1 .. %d)" % _ffi.PREFILTER_MAX_K)
     ap.add_argument("--min-shared", type=int, default=None, metavar="N", help="with --kmer: candidates share at least N distinct words")
     ap.add_argument("--min-shared-per-1024", type=int, default=None, metavar="P", help="with --kmer: candidates share at least P / 1024 of the smaller record's distinct words (0 .. 1024)")
@@ -130,6 +138,15 @@ def main(argv=None):
             ap.error("--report / --min-identity / --min-q-cover / --min-t-cover describe the plain alignment: not with --heuristic")
         if a.best is None and a.best_candidates is None and a.f_min is None:
             ap.error("--report / --min-identity / --min-q-cover / --min-t-cover work on held hits: give --best K, --best-candidates N or --f-min F")
+    if a.eqx and a.paf is None:
+        ap.error("--eqx chooses the ops of --paf: give --paf FILE")
+    if a.paf is not None:
+        if a.heuristic:
+            ap.error("--paf writes the plain alignment's hits: not with --heuristic")
+        if a.cluster is not None:
+            ap.error("--paf writes the hit rows, which --cluster replaces: not with --cluster")
+        if a.best is None and a.best_candidates is None and a.f_min is None:
+            ap.error("--paf works on held hits: give --best K, --best-candidates N or --f-min F")
     if a.profiles is not None and a.cluster is None:
         ap.error("--profiles counts the families of --cluster: give --cluster components|greedy")
     if a.msa is not None and a.cluster is None:
@@ -193,6 +210,16 @@ def main(argv=None):
                         fh.write("%s\n%s\n" % (name, row))
                     fh.write("\n")
 
+    def write_paf(held, order):
+        """--paf: one line per printed hit, `order` their held positions in the rows' order"""
+        order = np.asarray(order, dtype=np.uint32)
+        got = held.cigars(keep=order, extended=a.eqx)
+        length = held.owner.len
+        with open(a.paf, "w") as fh:
+            for i, h in enumerate(order.tolist()):
+                q, t = int(held.q[h]), int(held.t[h])
+                fh.write(got.paf(i, heads[q], length[q], heads[t], length[t], held.f[h]) + "\n")
+
     def tail(held, pos=None, reports=None):
         """`,z,p_emp` and the report's columns per held position, or empty strings without --shuffles and --report; pos: the
         positions that are printed (None: all)"""
@@ -232,9 +259,13 @@ def main(argv=None):
             pos_kept, reports = kept(held)
             more = tail(held, pos_kept, reports)
             show = np.ones(len(held), dtype=bool) if pos_kept is None else np.isin(np.arange(len(held)), pos_kept)
+            printed = []
             for q, pos in held.by_query():
                 for p in pos[show[pos]]:
                     out.write("%s,%d,%s,%r%s\n" % (heads[q], int(held.rank[p]) + 1, heads[int(held.t[p])], float(held.f[p]), more[p]))
+                    printed.append(int(p))
+            if a.paf is not None:
+                write_paf(held, printed)
         return 0
     if a.heuristic:
         if a.kd is None or a.r_squared is None:
@@ -281,6 +312,8 @@ def main(argv=None):
             more = tail(held, pos_kept, reports)
             for h in (range(len(held)) if pos_kept is None else pos_kept):
                 out.write("%s,%s,%r%s\n" % (heads[int(held.q[h])], heads[int(held.t[h])], float(held.f[h]), more[int(h)]))
+            if a.paf is not None:
+                write_paf(held, np.arange(len(held)) if pos_kept is None else pos_kept)
     return 0
 
 

@@ -300,7 +300,7 @@ static void warm_context(aln_ctx *c)
         if (hipSetDevice(c->devs[d]->device) != hipSuccess) continue;
         (void)aln_warm_single(); (void)aln_warm_tb(); (void)aln_warm_generic();
         (void)aln_warm_fast_cl(); (void)aln_warm_fast_cl_solo(); (void)aln_warm_fast_rest(); (void)aln_warm_fast_rest_solo();
-        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile(); (void)aln_warm_msa();
+        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile(); (void)aln_warm_msa(); (void)aln_warm_cigar();
         aln_pair_result r;
         (void)aln_align_pair(c, &p, q.data(), L, t.data(), L, &r, qa.data(), ta.data(), nullptr, nullptr);   // devices in turn
     }
@@ -3259,6 +3259,14 @@ struct aln_seqset : CallStats {
         uint32_t blank = 0;
         std::vector<uint64_t> byte_off, row_off;
     } msa_plan;
+    // aln_seqset_held_cigar_plan / _fill: the plan's tables (the listed positions, the records, the offsets) and the fill's words, an
+    // arena each, and what the host keeps of the last plan
+    DevBuf cigar, cigar_out;
+    struct CigarPlan {
+        bool valid = false;
+        uint64_t passes = 0, n = 0, held = 0, total_ops = 0;
+        uint32_t flags = 0, blank = 0;
+    } cigar_plan;
     // the k-mer prefilter (aln_prefilter_rules.h).  The index: one bitmap row of kmer_stride elements and one word count per
     // sequence, resident until the next aln_seqset_kmer_index (kmer_k == 0: none built)
     uint32_t kmer_k = 0, kmer_alphabet = 0, kmer_stride = 0;
@@ -3298,7 +3306,8 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     held_free(ss->held_store);
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
                    &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster, &ss->kmer_bits, &ss->kmer_n,
-                   &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first, &ss->profile, &ss->msa, &ss->msa_out};
+                   &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first, &ss->profile, &ss->msa, &ss->msa_out, &ss->cigar,
+                   &ss->cigar_out};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
@@ -3621,7 +3630,7 @@ static int seqset_pass(aln_seqset *ss, const Call &c, PairSource &src, double *f
 static void seqset_begin(aln_seqset *ss)
 {
     ss->held = false;
-    ++ss->held_passes;                // (a plan of aln_seqset_held_msa_plan is a plan of the held hits it saw)
+    ++ss->held_passes;                // (a plan of aln_seqset_held_msa_plan / _cigar_plan is a plan of the held hits it saw)
     ss->hit_pair.clear(); ss->hit_score.clear(); ss->hit_q.clear(); ss->hit_t.clear();
     held_clear(ss->held_store);
     stats_reset(*ss);
@@ -4979,6 +4988,178 @@ extern "C" int aln_seqset_held_msa_fill(aln_seqset *ss, uint8_t *out, uint64_t c
 {
     try {
         return seqset_held_msa_fill(ss, out, capacity_bytes, row_hit, capacity_rows);
+    } catch (const std::bad_alloc &) {
+        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
+}
+
+// ---------------------------------------------------------------- CIGARs of a set's held hits (aln_cigar.hip, aln_cigar_rules.h)
+// The plan's tables, carved out of one arena (every piece 256-aligned); base == nullptr only sizes it.
+struct CigarBufs {
+    unsigned long long *misc = nullptr;
+    uint32_t *list = nullptr;
+    aln_cigar_record *rec = nullptr;
+    uint64_t *off = nullptr, *tile_sum = nullptr, *tile_off = nullptr;
+};
+static size_t cigar_carve(uint8_t *base, uint64_t n, CigarBufs *out)
+{
+    size_t pos = 0;
+    auto take = [&](size_t bytes) -> uint8_t * {
+        uint8_t *p = base ? base + pos : nullptr;
+        pos += (size_t)align256(std::max<size_t>(bytes, 4));
+        return p;
+    };
+    CigarBufs b;
+    b.misc = reinterpret_cast<unsigned long long *>(take(8 * ALN_CIGAR_MISC_WORDS));
+    b.list = reinterpret_cast<uint32_t *>(take(4 * n));
+    b.rec = reinterpret_cast<aln_cigar_record *>(take(sizeof(aln_cigar_record) * n));
+    b.off = reinterpret_cast<uint64_t *>(take(8 * (n + 1)));
+    b.tile_sum = reinterpret_cast<uint64_t *>(take(8 * aln_cigar_tiles(n)));
+    b.tile_off = reinterpret_cast<uint64_t *>(take(8 * aln_cigar_tiles(n)));
+    if (out) *out = b;
+    return pos;
+}
+
+// what both calls hand the kernels of the plan's arena
+static void cigar_args(const aln_seqset *ss, const CigarBufs &b, uint64_t n, uint64_t held, uint32_t flags, uint32_t blank, CigarArgs *a)
+{
+    memset(a, 0, sizeof *a);
+    a->held = ss->held_store.info.as<HeldEntry>(); a->res = ss->held_store.res.as<aln_pair_result>(); a->tb = ss->held_store.tb.as<uint8_t>();
+    a->list = b.list; a->n_list = (uint32_t)n; a->n_held = (uint32_t)held; a->blank = blank; a->flags = flags; a->tiles = aln_cigar_tiles(n);
+    a->rec = b.rec; a->off = b.off; a->tile_sum = b.tile_sum; a->tile_off = b.tile_off; a->misc = b.misc;
+}
+
+// Every listed hit counted and classed, the offsets of their words.  Up go the listed positions; down come the records and the
+// counters.  The held store is only read.  A refusal leaves the plan before it as it was; once the tables are being rewritten there is
+// no plan until this one has gone well.
+static int seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t *which, uint64_t n, aln_cigar_record *records,
+                                  aln_cigar_summary *summary)
+{
+    // (what needs no set comes first)
+    if (!aln_cigar_flags_ok(flags)) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!summary || (n && (!which || !records))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n > 0x7FFFFFF0ull) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
+    int st = seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    if (ss->destroyed) { g_err = "the set was destroyed"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t held = ss->hit_pair.size();        // (<= 0xFFFFFFF0: seqset_hold_list)
+    for (uint64_t k = 0; k < n; ++k)
+        if (which[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+    uint64_t longest = 0;
+    for (uint64_t i = 0; i < ss->n; ++i) longest = std::max<uint64_t>(longest, ss->len[i]);
+    if (!aln_cigar_supported(longest)) { g_err = "a run must fit 28 bits: some N + M + 2 of the set reaches 2^28"; return ALN_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    // (growing the arena drops the tables of the plan before: it is given up here, before anything else moves)
+    if (ss->cigar.cap < cigar_carve(nullptr, n, nullptr)) ss->cigar_plan.valid = false;
+    if ((st = dev_ensure(ss->cigar, cigar_carve(nullptr, n, nullptr), false)) != ALN_OK) return st;
+    ss->cigar_plan.valid = false;         // (the tables are rewritten from here on)
+    CigarBufs b;
+    cigar_carve(ss->cigar.as<uint8_t>(), n, &b);
+    const uint32_t blank = ss->held_blank;
+    CigarArgs a;
+    cigar_args(ss, b, n, held, flags, blank, &a);
+    const auto t0 = std::chrono::steady_clock::now();
+    // (the records land in a buffer of the call's own first: an error on the way leaves the caller's array as it was)
+    std::vector<aln_cigar_record> rec_h(n);
+    unsigned long long misc[ALN_CIGAR_MISC_WORDS] = {0, 0, 0, 0};
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        if (n) HIPCHK(hipMemcpyAsync(b.list, which, 4 * n, hipMemcpyHostToDevice, q));
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        HIPCHK(hipMemsetAsync(b.misc, 0, 8 * ALN_CIGAR_MISC_WORDS, q));
+        aln_cigar_launch_plan(&a, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(misc, b.misc, 8 * ALN_CIGAR_MISC_WORDS, hipMemcpyDeviceToHost, q));
+        if (n) HIPCHK(hipMemcpyAsync(rec_h.data(), b.rec, sizeof(aln_cigar_record) * n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    aln_seqset::CigarPlan plan;
+    plan.valid = true; plan.passes = ss->held_passes; plan.n = n; plan.held = held; plan.total_ops = misc[ALN_CIGAR_MISC_TOTAL];
+    plan.flags = flags; plan.blank = blank;
+    ss->cigar_plan = plan;
+    if (n) memcpy(records, rec_h.data(), sizeof(aln_cigar_record) * n);
+    auto word = [](unsigned long long v) { return (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull); };
+    memset(summary, 0, sizeof *summary);
+    summary->held = held;
+    summary->listed = n;
+    summary->total_ops = plan.total_ops;
+    summary->failed = word(misc[ALN_CIGAR_MISC_FAILED]);
+    summary->padded = word(misc[ALN_CIGAR_MISC_PADDED]);
+    summary->overflow = word(misc[ALN_CIGAR_MISC_OVERFLOW]);
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 4ull * n;
+    ss->bytes[1] = sizeof(aln_cigar_record) * n + 8ull * ALN_CIGAR_MISC_WORDS;
+    return ALN_OK;
+}
+
+// The words of the last plan, and its offsets when asked for.  Nothing is decided again: the listed positions, the records and the
+// offsets are the plan's, resident.
+static int seqset_held_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capacity_ops, uint64_t *offsets, uint64_t capacity_offsets)
+{
+    int st = seqset_held_check(ss);
+    if (st != ALN_OK) return st;
+    const aln_seqset::CigarPlan plan = ss->cigar_plan;
+    if (!plan.valid) { g_err = "no plan: aln_seqset_held_cigar_plan has not run on this set"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (plan.passes != ss->held_passes || plan.held != ss->hit_pair.size()) {
+        g_err = "the plan is of held hits that another pass has replaced";
+        return ALN_ERR_INVALID_ARGUMENT;
+    }
+    if (capacity_ops < plan.total_ops || (offsets && capacity_offsets < plan.n + 1)) { g_err = "a capacity is below the plan's totals"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (plan.total_ops && !ops) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    if ((st = dev_ensure(ss->cigar_out, 4ull * std::max<uint64_t>(plan.total_ops, 1), false)) != ALN_OK) return st;
+    CigarBufs b;
+    cigar_carve(ss->cigar.as<uint8_t>(), plan.n, &b);
+    CigarArgs a;
+    cigar_args(ss, b, plan.n, plan.held, plan.flags, plan.blank, &a);
+    a.ops = ss->cigar_out.as<uint32_t>();
+    a.total = plan.total_ops;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        if (plan.total_ops) HIPCHK(hipMemsetAsync(a.ops, 0, 4 * plan.total_ops, q));
+        aln_cigar_launch_fill(&a, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        if (plan.total_ops) HIPCHK(hipMemcpyAsync(ops, a.ops, 4 * plan.total_ops, hipMemcpyDeviceToHost, q));
+        if (offsets) HIPCHK(hipMemcpyAsync(offsets, b.off, 8 * (plan.n + 1), hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 0;
+    ss->bytes[1] = 4ull * plan.total_ops + (offsets ? 8ull * (plan.n + 1) : 0);
+    return ALN_OK;
+}
+
+// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
+extern "C" int aln_seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t *which, uint64_t n, aln_cigar_record *records,
+                                          aln_cigar_summary *summary)
+{
+    try {
+        return seqset_held_cigar_plan(ss, flags, which, n, records, summary);
+    } catch (const std::bad_alloc &) {
+        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
+        g_err = "out of host memory";
+        return ALN_ERR_OOM;
+    }
+}
+
+extern "C" int aln_seqset_held_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capacity_ops, uint64_t *offsets, uint64_t capacity_offsets)
+{
+    try {
+        return seqset_held_cigar_fill(ss, ops, capacity_ops, offsets, capacity_offsets);
     } catch (const std::bad_alloc &) {
         if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
         g_err = "out of host memory";

@@ -1,4 +1,4 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip and aln_msa.hip define
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip, aln_msa.hip and aln_cigar.hip define
 // and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
 #pragma once
@@ -8,6 +8,7 @@
 #include "aln_cluster_rules.h"
 #include "aln_profile_rules.h"
 #include "aln_msa_rules.h"
+#include "aln_cigar_rules.h"
 
 // what every kernel of aln_cluster.hip takes: n label slots (node numbers 0 .. n - 1, those of `nodes` being nodes), m listed edges
 struct ClusterArgs {
@@ -62,6 +63,21 @@ struct MsaArgs {
     uint32_t *row_hit;               // total_rows: the held position of every row
     uint8_t *out;                    // bytes, filled with the blank code before the fill
     uint64_t bytes, total_rows;
+};
+
+// what the kernels of aln_cigar.hip take: the held store (read only), the plan's tables and, for the fill, the words
+struct CigarArgs {
+    const HeldEntry *held; const aln_pair_result *res; const uint8_t *tb;      // n_held entries of the held store
+    const uint32_t *list;            // n_list listed positions
+    uint32_t n_list, n_held, blank, flags;
+    uint64_t tiles;                  // tiles of 256 listed hits
+    aln_cigar_record *rec;           // n_list
+    uint64_t *off;                   // n_list + 1: where every listed hit's words start, and the total
+    uint64_t *tile_sum, *tile_off;   // tiles each
+    unsigned long long *misc;        // ALN_CIGAR_MISC_WORDS counters, zeroed before the plan
+    // the fill
+    uint32_t *ops;                   // total words
+    uint64_t total;
 };
 
 static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
@@ -194,5 +210,10 @@ void aln_profile_launch(const ProfileArgs *a, hipStream_t s);
 int aln_warm_msa(void);
 void aln_msa_launch_plan(const MsaArgs *a, const uint32_t *centers, uint32_t *slot_of, hipStream_t s);
 void aln_msa_launch_fill(const MsaArgs *a, hipStream_t s);
+
+// ---- aln_cigar.hip: the CIGARs of a sequence set's held hits (aln_cigar_rules.h)
+int aln_warm_cigar(void);
+void aln_cigar_launch_plan(const CigarArgs *a, hipStream_t s);
+void aln_cigar_launch_fill(const CigarArgs *a, hipStream_t s);
 
 }

@@ -509,6 +509,27 @@ class HeldHits:
         # (without a matrix the device used the held pass's blank code: the one the pass was given)
         return _msa.FamilyAlignments(cen, rec, _msa.summary_dict(summ), out, row_hit, self.q, self.t, o.alphabet, blank)
 
+    def cigars(self, keep=None, extended=False, clips=False):
+        """aln_seqset_held_cigar_plan + aln_seqset_held_cigar_fill: the alignments of the listed positions of the held list (default:
+        all) as CIGARs, run-length encoded on the device from the held strings -- per hit a few 32-bit words in BAM's encoding and a
+        32-byte record (coordinates, matches, block length); the strings stay where they are.  extended: `=` / `X` in place of `M`;
+        clips: soft clips for the query's residues outside the alignment.  Returns a cigar.Cigars."""
+        from . import cigar as _cigar
+        o = self.owner
+        w = self._keep(keep)
+        flags = (_ffi.CIGAR_EXTENDED if extended else 0) | (_ffi.CIGAR_CLIPS if clips else 0)
+        rec = np.zeros(len(w), dtype=_cigar.RECORD_DTYPE)
+        summ = _ffi.CigarSummary()
+        st = o.lib.aln_seqset_held_cigar_plan(o.handle, flags, w.ctypes.data if len(w) else None, len(w), rec.ctypes.data if len(w) else None,
+                                              C.byref(summ))
+        runtime.raise_for_status(st, "aln_seqset_held_cigar_plan")
+        self.last_cigar_plan_stats = o.stats()
+        words = np.zeros(int(summ.total_ops), dtype=np.uint32)
+        offsets = np.zeros(len(w) + 1, dtype=np.uint64)
+        st = o.lib.aln_seqset_held_cigar_fill(o.handle, words.ctypes.data if len(words) else None, len(words), offsets.ctypes.data, len(offsets))
+        runtime.raise_for_status(st, "aln_seqset_held_cigar_fill")
+        return _cigar.Cigars(w, rec, _cigar.summary_dict(summ), offsets, words, flags)
+
     def fractions(self, reports, keep=None):
         """report_fractions of records that belong to the listed positions (default: all)."""
         w = self._keep(keep)
