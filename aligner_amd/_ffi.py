@@ -58,6 +58,10 @@ PREFILTER_EXPORTS = ["aln_seqset_kmer_index", "aln_seqset_prefilter", "aln_seqse
                      "aln_seqset_candidate_hits"]
 PREFILTER_MAX_K, PREFILTER_MAX_BITS, PREFILTER_CHUNK_PAIRS = 8, 1 << 18, 1 << 22      # aligner_amd/csrc/aln_prefilter_rules.h
 PREFILTER_MAX_CANDIDATES = 0xFFFFFFF0
+# every symbol the companion header include/aligner_hip_wordjoin.h declares (the same library, as above)
+WORDJOIN_EXPORTS = ["aln_seqset_word_index", "aln_seqset_word_join"]
+WORDJOIN_MAX_K, WORDJOIN_MAX_WORDS = 8, 1 << 32             # aligner_amd/csrc/aln_wordjoin_rules.h
+WORDJOIN_CHUNK_OCCURRENCES, WORDJOIN_MAX_CHUNK_OCCURRENCES = 1 << 24, 1 << 26
 # every symbol the companion header include/aligner_hip_search.h declares (the same library, as above)
 SEARCH_EXPORTS = ["aln_seqset_candidate_best"]
 # every symbol the companion header include/aligner_hip_profile.h declares (the same library, as above)
@@ -203,6 +207,15 @@ class PrefilterSpec(C.Structure):
 
 
 assert C.sizeof(PrefilterSpec) == 32
+
+
+class WordjoinSpec(C.Structure):
+    """aln_wordjoin_spec: the word index a join expects and its thresholds (include/aligner_hip_wordjoin.h)."""
+    _fields_ = [("k", C.c_uint32), ("alphabet", C.c_uint32), ("min_shared", C.c_uint32), ("min_per_1024", C.c_uint32),
+                ("chunk_occurrences", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(WordjoinSpec) == 32
 
 
 class SeqsetBlock(C.Structure):
@@ -363,6 +376,10 @@ def load():
     lib.aln_seqset_kmer_index.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
     lib.aln_seqset_prefilter.restype = i
     lib.aln_seqset_prefilter.argtypes = [vp, C.POINTER(PrefilterSpec), bp, C.POINTER(C.c_uint64)]
+    lib.aln_seqset_word_index.restype = i
+    lib.aln_seqset_word_index.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    lib.aln_seqset_word_join.restype = i
+    lib.aln_seqset_word_join.argtypes = [vp, C.POINTER(WordjoinSpec), bp, C.POINTER(C.c_uint64)]
     lib.aln_seqset_candidates.restype = i
     lib.aln_seqset_candidates.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
     lib.aln_seqset_candidate_scores.restype = i

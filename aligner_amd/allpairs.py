@@ -60,6 +60,11 @@ records it shares enough words with, optionally only those with f >= F (--f-min 
 device; prints --best's rows, `q_head,rank,t_head,f`, and takes --report, --min-*, --shuffles and --cluster on top.  The prefilter
 runs on the full square of the records, which lists (q, t), (t, q) and every record's pair with itself: the self pairs are aligned
 and then skipped.  Not with --best or --heuristic.
+
+With --kmer K --word-join the same candidates come from a sorted word index instead of the bitmaps: every (word, record) is sorted once
+and the records that carry a word name the pairs that share it, so the work follows what is shared and A^K may be as large as 2^32
+(proteins: K up to 7).  --min-shared defaults to 1 here and may not be 0: a join sees only pairs that share a word.  Everything that
+combines with --kmer combines with --kmer --word-join; where both routes apply they print the same rows.
 """
 import argparse
 import sys
@@ -107,7 +112,10 @@ def main(argv=None):
     ap.add_argument("--kmer-alphabet", type=int, default=None, metavar="A", help="with --kmer: words use the first A codes of the alphabet (default 20; 4 with --dna)")
     ap.add_argument("--best-candidates", type=int, default=None, metavar="N",
                     help="with --kmer: per record its N best partners (1 .. %d) among its candidates on the full square; self pairs are aligned, then skipped" % _ffi.SEQSET_BEST_MAX)
+    ap.add_argument("--word-join", action="store_true", help="with --kmer: the candidates by a join over a sorted word index; A^K up to 2^32, --min-shared at least 1 (default 1)")
     a = ap.parse_args(argv)
+    if a.word_join and a.kmer is None:
+        ap.error("--word-join is a route of the prefilter: give --kmer K")
     if a.best_candidates is not None:
         if a.kmer is None:
             ap.error("--best-candidates selects among the prefilter's candidates: give --kmer K")
@@ -126,7 +134,12 @@ def main(argv=None):
         if a.heuristic:
             ap.error("--kmer with --heuristic: the matrix loop over a sparse candidate list is not built")
         kmer_alphabet = a.kmer_alphabet if a.kmer_alphabet is not None else (4 if a.dna else 20)
-        if not 1 <= a.kmer <= _ffi.PREFILTER_MAX_K or kmer_alphabet < 1 or kmer_alphabet ** a.kmer > _ffi.PREFILTER_MAX_BITS:
+        if a.word_join:
+            if not 1 <= a.kmer <= _ffi.WORDJOIN_MAX_K or kmer_alphabet < 1 or kmer_alphabet ** a.kmer > _ffi.WORDJOIN_MAX_WORDS:
+                ap.error("--kmer with --word-join: K must lie in 1 .. %d and A^K may not exceed 2^32" % _ffi.WORDJOIN_MAX_K)
+            if a.min_shared is not None and a.min_shared < 1:
+                ap.error("--min-shared with --word-join: N must be at least 1, a join sees only pairs that share a word")
+        elif not 1 <= a.kmer <= _ffi.PREFILTER_MAX_K or kmer_alphabet < 1 or kmer_alphabet ** a.kmer > _ffi.PREFILTER_MAX_BITS:
             ap.error("--kmer: K must lie in 1 .. %d and A^K may not exceed 2^18" % _ffi.PREFILTER_MAX_K)
         if a.min_shared is not None and not 0 <= a.min_shared < 2 ** 32:
             ap.error("--min-shared: N must lie in 0 .. 2^32 - 1")
@@ -240,6 +253,13 @@ def main(argv=None):
                                                             float(x["t_cover"]), int(x["gap_opens"]), int(x["gaps"]))
         return rows
 
+    def candidates(ss, block):
+        """the candidate list of --kmer over the block, by the bitmaps or, with --word-join, by the sorted word index"""
+        if a.word_join:
+            return ss.word_join(a.kmer, kmer_alphabet, min_shared=1 if a.min_shared is None else a.min_shared,
+                                min_per_1024=a.min_shared_per_1024 or 0, block=block)
+        return ss.prefilter(a.kmer, kmer_alphabet, min_shared=a.min_shared or 0, min_per_1024=a.min_shared_per_1024 or 0, block=block)
+
     if a.best is not None or a.best_candidates is not None:
         if a.heuristic:
             ap.error("--best selects by the score of the plain alignment: not with --heuristic")
@@ -250,8 +270,7 @@ def main(argv=None):
             if a.best is not None:
                 held = ss.best(matrix, a.del_, a.ext, a.best, f_min=floor, skip_self=True, semantics=sem)
             else:
-                cand = ss.prefilter(a.kmer, kmer_alphabet, min_shared=a.min_shared or 0, min_per_1024=a.min_shared_per_1024 or 0,
-                                    block=rectangle(0, len(ss), 0, len(ss)))
+                cand = candidates(ss, rectangle(0, len(ss), 0, len(ss)))
                 held = cand.best(matrix, a.del_, a.ext, a.best_candidates, f_min=floor, skip_self=True, semantics=sem)
             if a.cluster is not None:
                 clustered(held)
@@ -290,7 +309,7 @@ def main(argv=None):
         return 0
     with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
         if a.kmer is not None:
-            cand = ss.prefilter(a.kmer, kmer_alphabet, min_shared=a.min_shared or 0, min_per_1024=a.min_shared_per_1024 or 0)
+            cand = candidates(ss, None)
         if a.kmer is not None and a.f_min is None:
             f, status = cand.score(matrix, a.del_, a.ext, semantics=sem)
             for c in range(len(cand)):

@@ -53,6 +53,8 @@
 #include "aln_cluster_rules.h"
 #include "aln_prefilter_rules.h"
 #include "../../include/aligner_hip_prefilter.h"
+#include "aln_wordjoin_rules.h"
+#include "../../include/aligner_hip_wordjoin.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -300,7 +302,7 @@ static void warm_context(aln_ctx *c)
         if (hipSetDevice(c->devs[d]->device) != hipSuccess) continue;
         (void)aln_warm_single(); (void)aln_warm_tb(); (void)aln_warm_generic();
         (void)aln_warm_fast_cl(); (void)aln_warm_fast_cl_solo(); (void)aln_warm_fast_rest(); (void)aln_warm_fast_rest_solo();
-        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile(); (void)aln_warm_msa(); (void)aln_warm_cigar();
+        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile(); (void)aln_warm_msa(); (void)aln_warm_cigar(); (void)aln_warm_wordjoin();
         aln_pair_result r;
         (void)aln_align_pair(c, &p, q.data(), L, t.data(), L, &r, qa.data(), ta.data(), nullptr, nullptr);   // devices in turn
     }
@@ -3278,6 +3280,13 @@ struct aln_seqset : CallStats {
     DevBuf cand_k, pf_shared, pf_keep, pf_out;      // pf_*: a sharing chunk's shared | keep flags | compacted shared
     std::vector<uint64_t> cand_pair;
     std::vector<uint32_t> cand_qs, cand_ts, cand_shared;
+    // the sorted word index (aln_wordjoin_rules.h): the distinct (word, sequence) keys ascending and the word count per sequence,
+    // resident until the next aln_seqset_word_index (word_k == 0: none built); beside the bitmap index, not in its place.  wj_*: what
+    // a join plans with (where each entry's piece starts | its length | its offset in a chunk | the occurrences per query row) and a
+    // chunk's pair numbers before and after the sort, with the sort's own storage
+    uint32_t word_k = 0, word_alphabet = 0;
+    uint64_t word_entries = 0;
+    DevBuf word_e, word_n, wj_first, wj_len, wj_off, wj_occ, wj_a, wj_b, wj_temp;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a chunk's launches; 4, 5: the best selection
     // pair sets made by aln_pairset_create_from_set read the residue buffer: a destroy with some of them alive releases everything
     // else, moves the buffer here and leaves the rest to the last of them
@@ -3307,13 +3316,13 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
                    &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster, &ss->kmer_bits, &ss->kmer_n,
                    &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first, &ss->profile, &ss->msa, &ss->msa_out, &ss->cigar,
-                   &ss->cigar_out};
+                   &ss->cigar_out, &ss->word_e, &ss->word_n, &ss->wj_first, &ss->wj_len, &ss->wj_off, &ss->wj_occ, &ss->wj_a, &ss->wj_b, &ss->wj_temp};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
     slot_destroy(ss->slot);
     ss->slot = nullptr;
-    if (ss->derived) { ss->destroyed = true; ss->held = false; ss->cand = false; ss->kmer_k = 0; return; }      // the residues go with the last derived pair set
+    if (ss->derived) { ss->destroyed = true; ss->held = false; ss->cand = false; ss->kmer_k = 0; ss->word_k = 0; return; }      // the residues go with the last derived pair set
     delete ss;
 }
 
@@ -4023,6 +4032,217 @@ extern "C" int aln_seqset_candidate_hits(aln_seqset *ss, const aln_params *param
 extern "C" int aln_seqset_candidate_best(aln_seqset *ss, const aln_params *params, uint32_t k, double f_min, uint32_t flags, uint64_t *count)
 {
     ALN_SEQSET_GUARDED(ss, seqset_run_best(PairSource{ss, true, nullptr}, params, k, f_min, flags, count))
+}
+
+// ---------------------------------------------------------------- the sorted word index and its join (include/aligner_hip_wordjoin.h)
+// The prefilter's candidate list by another road: every (word, sequence) sorted once, the pairs named by the posting lists.  What it
+// leaves behind is the candidate state above, so the candidate passes, aln_seqset_candidates and the held calls know no difference.
+static const char *const WORDJOIN_RANGE = "k must lie in 1 .. 8, the alphabet size be at least 1 and alphabet^k at most 2^32";
+
+static int seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t words = aln_wordjoin_words(k, alphabet);
+    if (!words) { g_err = WORDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ss->total > 0x7FFFFFFFull) { g_err = "a word index holds fewer than 2^31 residue positions"; return ALN_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t total = ss->total;
+    uint32_t seq_end, word_end;
+    aln_wordjoin_sort_bits(words, ss->n, &seq_end, &word_end);
+    // everything new first: a failure leaves the old index and the candidate list as they were
+    DevBuf keys_a, keys_b, temp, entries, counts;
+    std::vector<uint32_t> counts_h(n_words ? ss->n : 0);
+    uint32_t got = 0;
+    auto run = [&]() -> int {
+        int st;
+        size_t temp_bytes = 0;
+        HIPCHK((hipError_t)aln_wordjoin_sort_temp_bytes(total, &temp_bytes));
+        if ((st = dev_ensure(keys_a, 8 * total, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(keys_b, 8 * total, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(temp, temp_bytes, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(counts, 4ull * ss->n, false)) != ALN_OK) return st;
+        uint32_t *tile_count = nullptr, *tile_off = nullptr;
+        if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(total), &tile_count, &tile_off)) != ALN_OK) return st;
+        uint32_t *d_count = ss->misc.as<uint32_t>() + 20;
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        HIPCHK(hipMemsetAsync(counts.p, 0, std::max<size_t>(4ull * ss->n, 4), q));
+        aln_wordjoin_launch_keys(ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), ss->n, total, k, alphabet,
+                                 keys_a.as<uint64_t>(), q);
+        HIPCHK(hipGetLastError());
+        // a full word field is sorted as the whole key in one pass (what the launcher asks of a range that ends at bit 64): the bits
+        // between the fields are zero in every word's key, so the order is that of the two passes
+        if (word_end == 64u) {
+            HIPCHK((hipError_t)aln_wordjoin_launch_sort(temp.p, temp.cap, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), total, 0, 64, q));
+            std::swap(keys_a, keys_b);
+        } else {
+            HIPCHK((hipError_t)aln_wordjoin_launch_sort(temp.p, temp.cap, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), total, 0, seq_end, q));
+            HIPCHK((hipError_t)aln_wordjoin_launch_sort(temp.p, temp.cap, keys_b.as<uint64_t>(), keys_a.as<uint64_t>(), total, 32, word_end, q));
+        }
+        aln_wordjoin_launch_distinct(keys_a.as<uint64_t>(), total, tile_count, tile_off, d_count, total, keys_b.as<uint64_t>(), ss->n,
+                                     counts.as<uint32_t>(), q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(&got, d_count, 4, hipMemcpyDeviceToHost, q));
+        if (n_words && ss->n) HIPCHK(hipMemcpyAsync(counts_h.data(), counts.p, 4ull * ss->n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        if (got > total) { g_err = "the word index holds more entries than the set has windows"; return ALN_ERR_DEVICE; }
+        // the resident list at its own size; the sort's buffers go
+        if ((st = dev_ensure(entries, 8ull * got, false)) != ALN_OK) return st;
+        if (got) HIPCHK(hipMemcpy(entries.p, keys_b.p, 8ull * got, hipMemcpyDeviceToDevice));
+        return ALN_OK;
+    };
+    const int st = run();
+    if (st != ALN_OK) (void)hipStreamSynchronize(q);
+    dev_free(keys_a); dev_free(keys_b); dev_free(temp);
+    if (st != ALN_OK) { dev_free(entries); dev_free(counts); return st; }
+    dev_free(ss->word_e); dev_free(ss->word_n);
+    ss->word_e = entries; ss->word_n = counts;
+    ss->word_k = k; ss->word_alphabet = alphabet; ss->word_entries = got;
+    seqset_drop_candidates(ss);
+    if (n_words && ss->n) memcpy(n_words, counts_h.data(), 4ull * ss->n);
+    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 0;
+    ss->bytes[1] = 4 + (n_words ? 4ull * ss->n : 0);
+    return ALN_OK;
+}
+
+static int seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *sp, const aln_seqset_block *b, uint64_t *count)
+{
+    if (!ss || !sp || !b || !count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!aln_wordjoin_words(sp->k, sp->alphabet)) { g_err = WORDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ss->word_k || sp->k != ss->word_k || sp->alphabet != ss->word_alphabet) { g_err = "no word index of this k and alphabet: aln_seqset_word_index builds it"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->min_shared == 0u) { g_err = "min_shared must be at least 1: a join sees only the pairs that share a word"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->min_per_1024 > ALN_PREFILTER_MAX_PER_1024) { g_err = "min_per_1024 must lie in 0 .. 1024"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->flags != 0u || sp->reserved != 0u) { g_err = "the spec's flags and reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->chunk_occurrences > ALN_WORDJOIN_MAX_CHUNK_OCCURRENCES) { g_err = "chunk_occurrences must lie in 0 .. 2^26"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t pairs = aln_seqset_block_pairs(ss->n, *b);
+    if (pairs == 0) { g_err = "block: a range beyond the set, unequal ranges of an upper block, a reserved word, or no pairs"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t cap = sp->chunk_occurrences ? sp->chunk_occurrences : ALN_WORDJOIN_CHUNK_OCCURRENCES;
+    const uint64_t n_e = ss->word_entries, rows = b->q_count;
+    const uint32_t pair_bits = std::max<uint32_t>(aln_wordjoin_bits_needed(pairs), 1u);
+    uint64_t total = 0, down = 0;
+    double kernels = 0;
+    int st;
+    // ---- the plan: nothing of the set's state is touched before the rows are cut
+    std::vector<uint64_t> occ(rows, 0);
+    std::vector<uint64_t> chunk_first, chunk_rows, chunk_occ;
+    auto plan = [&]() -> int {
+        if ((st = dev_ensure(ss->wj_first, 4 * n_e, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->wj_len, 4 * n_e, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->wj_off, 4 * n_e, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->wj_occ, 8 * rows, false)) != ALN_OK) return st;
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        HIPCHK(hipMemsetAsync(ss->wj_occ.p, 0, 8 * rows, q));
+        aln_wordjoin_launch_plan(ss->word_e.as<uint64_t>(), n_e, b, ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(), ss->wj_occ.as<uint64_t>(), q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(occ.data(), ss->wj_occ.p, 8 * rows, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        kernels += ev_ms(ss->ev[0], ss->ev[1]);
+        down += 8 * rows;
+        for (uint64_t first = 0; first < rows;) {
+            const uint64_t n = aln_wordjoin_cut(occ.data(), rows, first, cap);
+            if (!n) { g_err = "one query row of the block has more occurrences than chunk_occurrences allows"; return ALN_ERR_CAPACITY; }
+            uint64_t sum = 0;
+            for (uint64_t r = first; r < first + n; ++r) sum += occ[r];
+            if (sum) { chunk_first.push_back(first); chunk_rows.push_back(n); chunk_occ.push_back(sum); }
+            first += n;
+        }
+        return ALN_OK;
+    };
+    if ((st = plan()) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    seqset_drop_candidates(ss);
+    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+        if ((st = seqset_cand_room(ss, 0, 1)) != ALN_OK) return st;      // (an empty list is resident too, as the prefilter's is)
+        for (size_t c = 0; c < chunk_first.size(); ++c) {
+            const uint64_t m = chunk_occ[c], q_lo = b->q_first + chunk_first[c], q_rows = chunk_rows[c];
+            // the chunk's pairs: the pair numbers of its rows
+            const uint64_t k_lo = b->upper ? aln_seqset_row_start(rows, chunk_first[c]) : chunk_first[c] * b->t_count;
+            const uint64_t k_end = b->upper ? aln_seqset_row_start(rows, chunk_first[c] + q_rows) : (chunk_first[c] + q_rows) * b->t_count;
+            const uint64_t room = std::min(m, k_end - k_lo);
+            size_t temp_bytes = 0;
+            HIPCHK((hipError_t)aln_wordjoin_sort_temp_bytes(m, &temp_bytes));
+            uint32_t *tile_count = nullptr, *tile_off = nullptr;
+            if ((st = dev_ensure(ss->wj_a, 8 * m, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->wj_b, 8 * m, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->wj_temp, temp_bytes, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->pf_shared, 4 * m, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->pf_keep, m, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->pf_out, 4 * room, false)) != ALN_OK) return st;
+            if ((st = tiles_ensure(ss->tiles, std::max(aln_seqset_tiles(n_e), aln_seqset_tiles(m)), &tile_count, &tile_off)) != ALN_OK) return st;
+            if ((st = seqset_cand_room(ss, total, total + room)) != ALN_OK) return st;
+            uint32_t *d_words = ss->misc.as<uint32_t>() + 20;          // [0] kept pairs, [1] positions without a pair, [2] occurrences scanned
+            HIPCHK(hipEventRecord(ss->ev[0], q));
+            HIPCHK(hipMemsetAsync(d_words, 0, 12, q));
+            aln_wordjoin_launch_offsets(ss->word_e.as<uint64_t>(), ss->wj_len.as<uint32_t>(), n_e, q_lo, q_rows, tile_count, tile_off, d_words + 2,
+                                        ss->wj_off.as<uint32_t>(), q);
+            HIPCHK(hipGetLastError());
+            aln_wordjoin_launch_expand(ss->word_e.as<uint64_t>(), ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(), ss->wj_off.as<uint32_t>(), n_e, m,
+                                       b, pairs, q_lo, q_rows, ss->wj_a.as<uint64_t>(), d_words + 1, q);
+            HIPCHK(hipGetLastError());
+            HIPCHK((hipError_t)aln_wordjoin_launch_sort(ss->wj_temp.p, ss->wj_temp.cap, ss->wj_a.as<uint64_t>(), ss->wj_b.as<uint64_t>(), m, 0, pair_bits, q));
+            aln_wordjoin_launch_append(ss->wj_b.as<uint64_t>(), m, b, pairs, ss->word_n.as<uint32_t>(), ss->n, sp->min_shared, sp->min_per_1024,
+                                       ss->pf_shared.as<uint32_t>(), ss->pf_keep.as<uint8_t>(), tile_count, tile_off, d_words, room,
+                                       ss->cand_k.as<uint64_t>() + total, ss->pf_out.as<uint32_t>(), q);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ss->ev[1], q));
+            uint32_t h[3] = {0, 0, 0};
+            HIPCHK(hipMemcpyAsync(h, d_words, 12, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipStreamSynchronize(q));
+            kernels += ev_ms(ss->ev[0], ss->ev[1]);
+            down += 12;
+            const uint64_t got = h[0];
+            if (h[2] != m) { g_err = "a chunk's occurrences differ from the plan's"; return ALN_ERR_DEVICE; }
+            if (h[1]) { g_err = "an occurrence of the join names no pair of the block"; return ALN_ERR_DEVICE; }
+            if (got > room) { g_err = "the join kept more pairs than the chunk's rows hold"; return ALN_ERR_DEVICE; }
+            if (total + got > 0xFFFFFFF0ull) { g_err = "too many candidates"; return ALN_ERR_UNSUPPORTED; }
+            if (got) {
+                ss->cand_pair.resize(total + got); ss->cand_shared.resize(total + got);
+                HIPCHK(hipMemcpy(ss->cand_pair.data() + total, ss->cand_k.as<uint64_t>() + total, 8ull * got, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(ss->cand_shared.data() + total, ss->pf_out.p, 4ull * got, hipMemcpyDeviceToHost));
+                down += 12ull * got;
+                // the host indexes its tables with this list: pairs of the chunk's rows, ascending
+                for (uint64_t i = total; i < total + got; ++i)
+                    if (ss->cand_pair[i] < k_lo || ss->cand_pair[i] >= k_end || (i > total && ss->cand_pair[i] <= ss->cand_pair[i - 1])) { g_err = "the candidate list is not an ascending list of the chunk's pairs"; return ALN_ERR_DEVICE; }
+            }
+            total += got;
+        }
+        return ALN_OK;
+    };
+    st = run();
+    if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_drop_candidates(ss); return st; }
+    ss->cand_qs.resize(total); ss->cand_ts.resize(total);
+    for (uint64_t i = 0; i < total; ++i) {
+        uint64_t sq, tq;
+        aln_seqset_unrank(*b, ss->cand_pair[i], &sq, &tq);
+        ss->cand_qs[i] = (uint32_t)sq; ss->cand_ts[i] = (uint32_t)tq;
+    }
+    ss->cand = true;
+    ss->cand_block = *b;
+    *count = total;
+    ss->ms[2] = kernels;
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 0;
+    ss->bytes[1] = down;               // 8 bytes per query row, 12 per chunk and 12 per candidate
+    return ALN_OK;
+}
+
+extern "C" int aln_seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
+{
+    ALN_SEQSET_GUARDED(ss, seqset_word_index(ss, k, alphabet, n_words))
+}
+
+extern "C" int aln_seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *spec, const aln_seqset_block *b, uint64_t *count)
+{
+    ALN_SEQSET_GUARDED(ss, seqset_word_join(ss, spec, b, count))
 }
 
 static int seqset_held_check(aln_seqset *ss)

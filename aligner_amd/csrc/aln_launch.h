@@ -1,4 +1,4 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip, aln_msa.hip and aln_cigar.hip define
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip, aln_msa.hip, aln_cigar.hip and aln_wordjoin.hip define
 // and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
 #pragma once
@@ -215,5 +215,36 @@ void aln_msa_launch_fill(const MsaArgs *a, hipStream_t s);
 int aln_warm_cigar(void);
 void aln_cigar_launch_plan(const CigarArgs *a, hipStream_t s);
 void aln_cigar_launch_fill(const CigarArgs *a, hipStream_t s);
+
+// ---- aln_wordjoin.hip: the sorted word index of a sequence set and the join over its posting lists (aln_wordjoin_rules.h)
+int aln_warm_wordjoin(void);
+// rocPRIM's device radix sort of n 64-bit numbers over bits begin_bit .. end_bit - 1, in -> out; the host owns the temporary storage,
+// whose size for n numbers the first call gives.  Both return a hipError_t; n < 2^31; a range that ends at bit 64 begins at bit 0
+int aln_wordjoin_sort_temp_bytes(uint64_t n, size_t *bytes);
+int aln_wordjoin_launch_sort(void *temp, size_t temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, uint32_t begin_bit, uint32_t end_bit,
+                             hipStream_t s);
+// keys: `total` entries, one per residue position of the packed set
+void aln_wordjoin_launch_keys(const uint8_t *seqs, const uint64_t *seq_off, const uint32_t *seq_len, uint64_t n_seqs, uint64_t total, uint32_t k,
+                              uint32_t alphabet, uint64_t *keys, hipStream_t s);
+// sorted: n keys ascending -> entries: the distinct keys that are words, ascending (`room` entries), count[0]: how many; n_words (n_seqs,
+// zeroed before): the entries per sequence.  tile_count / tile_off: aln_select_tiles(n) words each
+void aln_wordjoin_launch_distinct(const uint64_t *sorted, uint64_t n, uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint64_t room,
+                                  uint64_t *entries, uint64_t n_seqs, uint32_t *n_words, hipStream_t s);
+// piece_first / piece_len: n_entries each; occ: block->q_count totals, zeroed before
+void aln_wordjoin_launch_plan(const uint64_t *entries, uint64_t n_entries, const aln_seqset_block *block, uint32_t *piece_first, uint32_t *piece_len,
+                              uint64_t *occ, hipStream_t s);
+// offsets: n_entries exclusive sums of the piece lengths of the entries whose query lies in q_lo .. q_lo + q_rows - 1; total[0]: their
+// sum (the host has bounded it below 2^32).  tile_count / tile_off: aln_select_tiles(n_entries) words each
+void aln_wordjoin_launch_offsets(const uint64_t *entries, const uint32_t *piece_len, uint64_t n_entries, uint64_t q_lo, uint64_t q_rows,
+                                 uint32_t *tile_count, uint32_t *tile_off, uint32_t *total, uint32_t *offsets, hipStream_t s);
+// out: n_out pair numbers of the block (`pairs` pairs); errors[0] counts the positions that found none
+void aln_wordjoin_launch_expand(const uint64_t *entries, const uint32_t *piece_first, const uint32_t *piece_len, const uint32_t *offsets,
+                                uint64_t n_entries, uint64_t n_out, const aln_seqset_block *block, uint64_t pairs, uint64_t q_lo, uint64_t q_rows,
+                                uint64_t *out, uint32_t *errors, hipStream_t s);
+// sorted: n pair numbers ascending -> the kept (pair number, shared) appended in order: out_k and out_shared, `room` entries each;
+// count[0]: how many.  shared (n words) and keep (n bytes) are scratch; tile_count / tile_off: aln_select_tiles(n) words each
+void aln_wordjoin_launch_append(const uint64_t *sorted, uint64_t n, const aln_seqset_block *block, uint64_t pairs, const uint32_t *n_words,
+                                uint64_t n_seqs, uint32_t min_shared, uint32_t min_per_1024, uint32_t *shared, uint8_t *keep, uint32_t *tile_count,
+                                uint32_t *tile_off, uint32_t *count, uint64_t room, uint64_t *out_k, uint32_t *out_shared, hipStream_t s);
 
 }

@@ -121,6 +121,7 @@ class SeqSet:
         if not self.handle:
             runtime.raise_for_status(st.value, "aln_seqset_create")
             raise RuntimeError("aln_seqset_create returned NULL")
+        self._word = None          # the (k, alphabet_size) of the word index this object built (word_index), if any
 
     def __len__(self):
         return len(self.len)
@@ -210,6 +211,30 @@ class SeqSet:
         count = C.c_uint64(0)
         st = self.lib.aln_seqset_prefilter(self.handle, C.byref(spec), C.byref(b), C.byref(count))
         runtime.raise_for_status(st, "aln_seqset_prefilter")
+        return Candidates(self, int(count.value))
+
+    def word_index(self, k, alphabet_size):
+        """aln_seqset_word_index: builds (or replaces) the resident sorted list of the distinct (word, sequence) of the set -- words of
+        k residues with every code below alphabet_size, alphabet_size ** k <= 2 ** 32 -- and returns n(s), the number of distinct
+        words, of every sequence (uint32): what kmer_index returns where both build.  Any candidate list is dropped; the bitmaps of
+        kmer_index stay."""
+        n_words = np.zeros(len(self), dtype=np.uint32)
+        st = self.lib.aln_seqset_word_index(self.handle, int(k), int(alphabet_size), n_words.ctypes.data)
+        runtime.raise_for_status(st, "aln_seqset_word_index")
+        self._word = (int(k), int(alphabet_size))
+        return n_words
+
+    def word_join(self, k, alphabet_size, min_shared=1, min_per_1024=0, block=None, chunk_occurrences=0):
+        """aln_seqset_word_join: the candidates of prefilter(k, alphabet_size, min_shared, min_per_1024, block) with min_shared >= 1,
+        the same list entry for entry, by a join over the posting lists of the sorted word index: work follows what the sequences
+        share, not the number of pairs.  Builds the word index if none of this (k, alphabet_size) is there.  Returns a Candidates."""
+        b, n = self._checked(block)
+        if self._word != (int(k), int(alphabet_size)):
+            self.word_index(k, alphabet_size)
+        spec = _ffi.WordjoinSpec(int(k), int(alphabet_size), int(min_shared), int(min_per_1024), int(chunk_occurrences), 0, 0)
+        count = C.c_uint64(0)
+        st = self.lib.aln_seqset_word_join(self.handle, C.byref(spec), C.byref(b), C.byref(count))
+        runtime.raise_for_status(st, "aln_seqset_word_join")
         return Candidates(self, int(count.value))
 
     def stats(self):
