@@ -391,10 +391,11 @@ struct FastStrip {
     }
 
     // kk: the step's number within its block (a constant after unrolling: the immediate offset of the query ring read)
-    template <bool MASKED>
+    // REFILL: this step can be a multiple of 64 (the first step of a quad alone: a quad's 4 * SPB steps divide 64)
+    template <bool MASKED, bool REFILL = true>
     __device__ __forceinline__ void step(const uint32_t k, const int kk)
     {
-        if ((k & 63u) == 0) {                                   // wave-uniform: refill the 64-column input chunks
+        if (REFILL && (k & 63u) == 0) {                         // wave-uniform: refill the 64-column input chunks
             const uint32_t xi = k + (uint32_t)lane;             // 0-based column
             if (!SINGLE && in.fair) fair_prio();
             if (!SINGLE && !LAST && k >= 64u) flush_below(k, 0u);
@@ -565,8 +566,7 @@ struct FastStrip {
         gpre = (lane < 16 && ncol < N) ? granule_load(in.gin + ncol) : 0u;       // group j+1, consumed next time
     }
 
-    // four blocks of SPB steps -> one 16-byte store per lane (1 KiB per wave, coalesced).  The block loop is a real
-    // loop (not unrolled): unrolling 4*SPB steps makes the scheduler hoist every step's uniform values and spill.
+    // four blocks of SPB steps -> one 16-byte store per lane (1 KiB per wave, coalesced): see block() and quad() below.
     // the bottom-row zero flags (row-1 hazard) travel as the direction words of the lane that owns row M (tag 3 =
     // Beginning <=> H == 0): one dword per block instead of a select chain and a byte store per step
     __device__ __forceinline__ void store_zdw(uint32_t block)
@@ -722,27 +722,64 @@ struct FastStrip {
         return kb_end;
     }
 
+    // block J of a quad: SPB steps, then the block's direction word is the quad's component J as it stands -- J is a constant, so
+    // there is nothing to choose and nothing to copy.  k0 comes in wave-uniform by construction and is said to be so (in strip 0 of
+    // a hazard pair, and wherever the strip's shape comes out of a vector load -- the batch kernels -- the compiler otherwise
+    // carries the step counter in a VGPR and pays for it in every step: four VALU instructions per step, measured as 5 % of the
+    // C5 fill).  It leaves through an empty asm statement together with the block's direction word: the next block's step counter,
+    // and every uniform value derived from it, cannot be computed before this block's last cell -- without that the scheduler
+    // hoists the uniform values of all 4 * SPB steps to the top of the body and spills.
+    template <bool MASKED, int J>
+    __device__ __forceinline__ uint32_t block(uint32_t &k0, const uint32_t kb)
+    {
+        static_assert(64 % (4 * SPB) == 0, "only a quad's first step can be a multiple of 64");
+        static_assert(!SINGLE, "batch kernels only");
+#pragma unroll
+        for (int kk = 0; kk < SPB; ++kk) {
+            if (J == 0 && kk == 0) step<MASKED, true>(k0, 0);
+            else step<MASKED, false>(k0 + kk, kk);
+        }
+        if constexpr (QRING) qaddr += (uint32_t)SPB;
+        if constexpr (BRING) baddr += 4u * (uint32_t)SPB;
+        store_zdw(kb + J);
+        k0 += (uint32_t)SPB;
+        asm volatile("" : "+s"(k0), "+v"(dw));
+        // ... and so does the lane's state: the counter alone left the next block's loads, ring reads and address adds free to move
+        // up into this block, and the longer live ranges doubled the kernel's register spills around the step loops (66 -> 138)
+#pragma unroll
+        for (int r = 0; r < R; ++r) asm volatile("" : "+v"(Tl[r]), "+v"(rbv[r]));
+        asm volatile("" : "+v"(hdiag), "+v"(outq), "+v"(qaddr), "+v"(baddr), "+v"(qv), "+v"(top0v));
+        return dw;
+    }
+
+    // kb: a multiple of 4 (all segment ends are whole quads)
     template <bool MASKED>
     __device__ __forceinline__ void quad(uint4 *dirq, const uint32_t kb)
     {
         uint4 v = make_uint4(0, 0, 0, 0);
+        if constexpr (SINGLE) {
+            // the single-pair kernel keeps the block loop (its C++ quads are ramps and strip 0's tail; its steady state is the asm).
+            // A real loop, not unrolled: unrolling 4 * SPB steps plainly makes the scheduler hoist every step's uniform values and
+            // spill; with block()'s fences this kernel faulted on the GPU for a reason not found
 #pragma unroll 1
-        for (uint32_t j = 0; j < 4; ++j) {
-            // wave-uniform by construction; say so (in strip 0 of a hazard pair, and wherever the strip's shape comes out of
-            // a vector load -- the batch kernels -- the compiler otherwise carries the step counter in a VGPR and pays for
-            // it in every step: four VALU instructions per step, measured as 5 % of the C5 fill)
-            const uint32_t k0 = (FIRST || !SINGLE) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)((kb + j) * SPB)) : (kb + j) * SPB;
-            if (SINGLE && !FIRST && ((k0 + SPB) & 15u) == 0) stage_boundary16((k0 + SPB) >> 4);   // one block ahead
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t k0 = FIRST ? (uint32_t)__builtin_amdgcn_readfirstlane((int)((kb + j) * SPB)) : (kb + j) * SPB;
+                if (!FIRST && ((k0 + SPB) & 15u) == 0) stage_boundary16((k0 + SPB) >> 4);   // one block ahead
 #pragma unroll
-            for (int kk = 0; kk < SPB; ++kk) step<MASKED>(k0 + kk, kk);
-            if constexpr (QRING) qaddr += (uint32_t)SPB;
-            if constexpr (BRING) baddr += 4u * (uint32_t)SPB;
-            if (SINGLE && !LAST && k0 + SPB >= 64u && ((k0 + SPB) & 15u) == 0) publish(k0 + SPB - 1);
-            store_zdw(kb + j);
-            if (j == 0) v.x = dw;
-            else if (j == 1) v.y = dw;
-            else if (j == 2) v.z = dw;
-            else v.w = dw;
+                for (int kk = 0; kk < SPB; ++kk) step<MASKED>(k0 + kk, kk);
+                if (!LAST && k0 + SPB >= 64u && ((k0 + SPB) & 15u) == 0) publish(k0 + SPB - 1);
+                store_zdw(kb + j);
+                if (j == 0) v.x = dw;
+                else if (j == 1) v.y = dw;
+                else if (j == 2) v.z = dw;
+                else v.w = dw;
+            }
+        } else {
+            uint32_t k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(kb * SPB));
+            v.x = block<MASKED, 0>(k0, kb);
+            v.y = block<MASKED, 1>(k0, kb);
+            v.z = block<MASKED, 2>(k0, kb);
+            v.w = block<MASKED, 3>(k0, kb);
         }
         if (in.store_dirs) {
             uint4 *p = dirq + (size_t)(kb >> 2) * 64;
