@@ -2285,7 +2285,16 @@ extern "C" int aln_scan_stats(const aln_scan *sc, double *ms, uint64_t *bytes)
 #define ALN_SHUFFLE_CHUNK_COPIES (1ull << 22)      // per chunk: the pair limit of a chunk of aln_align_batch
 #define ALN_SHUFFLE_CHUNK_BYTES (1ull << 30)       // shuffled residues per chunk
 
-static inline uint64_t align256(uint64_t v) { return (v + 255) & ~255ull; }
+#include "aln_arena_rules.h"      // align256, and the arenas of the calls on a sequence set
+
+// A body of queued work: a lambda whose HIPCHKs and checks return on the first thing that goes wrong.  Any way out of it but ALN_OK
+// waits for the stream before the caller sees the status, so nothing queued still reads or writes the call's buffers by then.
+template <class Body> static int run_queued(hipStream_t q, Body &&body)
+{
+    const int st = body();
+    if (st != ALN_OK) (void)hipStreamSynchronize(q);
+    return st;
+}
 
 static int shuffle_check(aln_ctx *ctx, const aln_shuffle_spec *sp, const uint8_t *seqs, const uint64_t *t_off, const uint64_t *t_len, size_t n)
 {
@@ -2639,6 +2648,9 @@ static void held_free(HeldStore &h)
     for (DevBuf *b : d) dev_free(*b);
 }
 static void held_clear(HeldStore &h) { h.n = 0; h.info_h.clear(); }
+// what every reader of a store takes: the triple on the device
+struct HeldView { const HeldEntry *info; const aln_pair_result *res; const uint8_t *tb; };
+static HeldView held_view(const HeldStore &h) { return HeldView{h.info.as<HeldEntry>(), h.res.as<aln_pair_result>(), h.tb.as<uint8_t>()}; }
 
 // kernel times and uploaded bytes of a re-fill, added to: each family reports them its own way (a pair set fill and traceback, a
 // sequence set both as one interval, fill start to traceback end: not their sum, which counts the event between them twice)
@@ -2667,7 +2679,7 @@ static int held_refill(HeldStore &h, DevCtx *ctx, Slot &s, const Call &c, const 
         if (timed) { acc.fill_ms += ev_ms(ev[0], ev[1]); acc.tb_ms += ev_ms(ev[1], ev[2]); acc.both_ms += ev_ms(ev[0], ev[2]); timed = false; }
     };
     int st = ALN_OK;
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    st = run_queued(q, [&]() -> int {
         // the store, sized for exactly this count; nothing is held if the memory cannot be had
         if ((st = dev_ensure(h.res, sizeof(aln_pair_result) * pairs, false)) != ALN_OK) return st;
         if ((st = dev_ensure(h.tb, tb_total, false)) != ALN_OK) return st;
@@ -2694,9 +2706,8 @@ static int held_refill(HeldStore &h, DevCtx *ctx, Slot &s, const Call &c, const 
         }
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     collect();
     h.n = pairs;
     return ALN_OK;
@@ -2723,15 +2734,16 @@ static int held_fetch_strings(HeldStore &h, hipStream_t q, hipEvent_t *ev, const
     // (the summaries land in a buffer of the call's own first: an error on the way leaves the caller's array as it was)
     std::vector<aln_pair_result> res(n);
     std::vector<uint8_t> bounce;
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    st = run_queued(q, [&]() -> int {
         HIPCHK(hipMemcpyAsync(h.list.p, entries, 4ull * n, hipMemcpyHostToDevice, q));
         HIPCHK(hipMemcpyAsync(h.out_off.p, off.data(), 8ull * n, hipMemcpyHostToDevice, q));
         HIPCHK(hipEventRecord(ev[0], q));
         // (the kernel writes aln_len bytes per string: whatever else the packed span holds goes to the caller as zeros, not as what
         // an earlier fetch left there)
         if (want) HIPCHK(hipMemsetAsync(h.packed_tb.p, 0, total, q));
-        aln_held_launch_gather(h.info.as<HeldEntry>(), h.res.as<aln_pair_result>(), h.tb.as<uint8_t>(), h.list.as<uint32_t>(), h.out_off.as<uint64_t>(),
-                               (uint32_t)n, (uint32_t)h.n, h.packed_res.as<aln_pair_result>(), want ? h.packed_tb.as<uint8_t>() : nullptr, q);
+        const HeldView v = held_view(h);
+        aln_held_launch_gather(v.info, v.res, v.tb, h.list.as<uint32_t>(), h.out_off.as<uint64_t>(), (uint32_t)n, (uint32_t)h.n,
+                               h.packed_res.as<aln_pair_result>(), want ? h.packed_tb.as<uint8_t>() : nullptr, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev[1], q));
         HIPCHK(hipMemcpyAsync(res.data(), h.packed_res.p, sizeof(aln_pair_result) * n, hipMemcpyDeviceToHost, q));
@@ -2741,9 +2753,8 @@ static int held_fetch_strings(HeldStore &h, hipStream_t q, hipEvent_t *ev, const
         }
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     memcpy(results, res.data(), sizeof(aln_pair_result) * n);
     if (want && !direct)                             // an entry's whole capacity, as the direct copy
         for (size_t k = 0; k < n; ++k) {
@@ -3645,6 +3656,19 @@ static void seqset_begin(aln_seqset *ss)
     stats_reset(*ss);
 }
 
+// The stats of a call that went well, as held_done writes a scan's: its kernels (ev[0] to ev[1], or the sum over its chunks), its wall
+// time, the bytes up and down.  Only on success: a refusal or an error leaves the stats of the call before in place.
+static void seqset_done(aln_seqset *ss, const std::chrono::steady_clock::time_point &t0, uint64_t up, uint64_t down, double kernel_ms)
+{
+    ss->ms[2] = kernel_ms;
+    ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = up; ss->bytes[1] = down;
+}
+static void seqset_done(aln_seqset *ss, const std::chrono::steady_clock::time_point &t0, uint64_t up, uint64_t down)
+{
+    seqset_done(ss, t0, up, down, ev_ms(ss->ev[0], ss->ev[1]));
+}
+
 // f and status of every position of a source (aln_seqset_score, aln_seqset_candidate_scores)
 static int seqset_run_score(PairSource src, const aln_params *params, double *f, int32_t *status)
 {
@@ -3820,30 +3844,32 @@ static int seqset_run_best(PairSource src, const aln_params *params, uint32_t k,
     return ALN_OK;
 }
 
-// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
-#define ALN_SEQSET_GUARDED(ss, call)                                                              \
+// The one way through the C boundary for every call below that allocates host memory: what cannot be had is ALN_ERR_OOM, not an
+// exception, and with a device behind the handle (`live`) everything queued has finished before the caller hears of it.
+#define ALN_GUARDED(live, call)                                                                   \
     try {                                                                                         \
         return call;                                                                              \
     } catch (const std::bad_alloc &) {                                                            \
-        if ((ss) && (ss)->slot && (ss)->slot->stream) (void)hipDeviceSynchronize();               \
+        if (live) (void)hipDeviceSynchronize();                                                   \
         g_err = "out of host memory";                                                             \
         return ALN_ERR_OOM;                                                                       \
     }
+static bool seqset_live(const aln_seqset *ss) { return ss && ss->slot && ss->slot->stream; }
 
 extern "C" int aln_seqset_score(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double *f, int32_t *status)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_run_score(PairSource{ss, false, b}, params, f, status))
+    ALN_GUARDED(seqset_live(ss), seqset_run_score(PairSource{ss, false, b}, params, f, status))
 }
 
 extern "C" int aln_seqset_hits(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, double f_min, uint64_t *count)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_run_hits(PairSource{ss, false, b}, params, f_min, count))
+    ALN_GUARDED(seqset_live(ss), seqset_run_hits(PairSource{ss, false, b}, params, f_min, count))
 }
 
 extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const aln_seqset_block *b, uint32_t k, double f_min, uint32_t flags,
                                uint64_t *count)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_run_best(PairSource{ss, false, b}, params, k, f_min, flags, count))
+    ALN_GUARDED(seqset_live(ss), seqset_run_best(PairSource{ss, false, b}, params, k, f_min, flags, count))
 }
 
 // ---------------------------------------------------------------- the k-mer prefilter (include/aligner_hip_prefilter.h)
@@ -3871,7 +3897,7 @@ static int seqset_kmer_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint
     int st = dev_ensure(table, 4ull * stride * ss->n, false);
     if (st == ALN_OK) st = dev_ensure(counts, 4ull * ss->n, false);
     std::vector<uint32_t> counts_h(n_words ? ss->n : 0);
-    auto run = [&]() -> int {
+    if (st == ALN_OK) st = run_queued(q, [&]() -> int {
         HIPCHK(hipEventRecord(ss->ev[0], q));
         aln_prefilter_launch_index(ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), ss->n, k, alphabet, elements,
                                    stride, table.as<uint32_t>(), counts.as<uint32_t>(), q);
@@ -3880,18 +3906,14 @@ static int seqset_kmer_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint
         if (n_words && ss->n) HIPCHK(hipMemcpyAsync(counts_h.data(), counts.p, 4ull * ss->n, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    if (st == ALN_OK) st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); dev_free(table); dev_free(counts); return st; }
+    });
+    if (st != ALN_OK) { dev_free(table); dev_free(counts); return st; }
     dev_free(ss->kmer_bits); dev_free(ss->kmer_n);
     ss->kmer_bits = table; ss->kmer_n = counts;
     ss->kmer_k = k; ss->kmer_alphabet = alphabet; ss->kmer_stride = stride;
     seqset_drop_candidates(ss);
     if (n_words && ss->n) memcpy(n_words, counts_h.data(), 4ull * ss->n);
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 0;
-    ss->bytes[1] = n_words ? 4ull * ss->n : 0;
+    seqset_done(ss, t0, 0, n_words ? 4ull * ss->n : 0);
     return ALN_OK;
 }
 
@@ -3930,7 +3952,7 @@ static int seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *sp, const 
     const uint64_t t_end = b->t_first + b->t_count;
     uint64_t total = 0, down = 0;
     double kernels = 0;
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    const int st = run_queued(q, [&]() -> int {
         int st;
         for (uint64_t k0 = 0; k0 < pairs; k0 += per) {
             const uint64_t n = std::min(per, pairs - k0);
@@ -3975,9 +3997,8 @@ static int seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *sp, const 
             total += got;
         }
         return ALN_OK;
-    };
-    const int st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_drop_candidates(ss); return st; }
+    });
+    if (st != ALN_OK) { seqset_drop_candidates(ss); return st; }
     ss->cand_qs.resize(total); ss->cand_ts.resize(total);
     for (uint64_t h = 0; h < total; ++h) {
         uint64_t sq, tq;
@@ -3987,21 +4008,18 @@ static int seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *sp, const 
     ss->cand = true;
     ss->cand_block = *b;
     *count = total;
-    ss->ms[2] = kernels;
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 0;
-    ss->bytes[1] = down;               // 12 bytes per candidate and the 8 of a chunk's count
+    seqset_done(ss, t0, 0, down, kernels);          // 12 bytes per candidate and the 8 of a chunk's count
     return ALN_OK;
 }
 
 extern "C" int aln_seqset_kmer_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_kmer_index(ss, k, alphabet, n_words))
+    ALN_GUARDED(seqset_live(ss), seqset_kmer_index(ss, k, alphabet, n_words))
 }
 
 extern "C" int aln_seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *spec, const aln_seqset_block *b, uint64_t *count)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_prefilter(ss, spec, b, count))
+    ALN_GUARDED(seqset_live(ss), seqset_prefilter(ss, spec, b, count))
 }
 
 extern "C" int aln_seqset_candidates(aln_seqset *ss, uint64_t first, uint64_t n, uint64_t *pair_index, uint32_t *q_seq, uint32_t *t_seq,
@@ -4021,17 +4039,17 @@ extern "C" int aln_seqset_candidates(aln_seqset *ss, uint64_t first, uint64_t n,
 
 extern "C" int aln_seqset_candidate_scores(aln_seqset *ss, const aln_params *params, double *f, int32_t *status)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_run_score(PairSource{ss, true, nullptr}, params, f, status))
+    ALN_GUARDED(seqset_live(ss), seqset_run_score(PairSource{ss, true, nullptr}, params, f, status))
 }
 
 extern "C" int aln_seqset_candidate_hits(aln_seqset *ss, const aln_params *params, double f_min, uint64_t *count)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_run_hits(PairSource{ss, true, nullptr}, params, f_min, count))
+    ALN_GUARDED(seqset_live(ss), seqset_run_hits(PairSource{ss, true, nullptr}, params, f_min, count))
 }
 
 extern "C" int aln_seqset_candidate_best(aln_seqset *ss, const aln_params *params, uint32_t k, double f_min, uint32_t flags, uint64_t *count)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_run_best(PairSource{ss, true, nullptr}, params, k, f_min, flags, count))
+    ALN_GUARDED(seqset_live(ss), seqset_run_best(PairSource{ss, true, nullptr}, params, k, f_min, flags, count))
 }
 
 // ---------------------------------------------------------------- the sorted word index and its join (include/aligner_hip_wordjoin.h)
@@ -4056,7 +4074,7 @@ static int seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint
     DevBuf keys_a, keys_b, temp, entries, counts;
     std::vector<uint32_t> counts_h(n_words ? ss->n : 0);
     uint32_t got = 0;
-    auto run = [&]() -> int {
+    const int st = run_queued(q, [&]() -> int {
         int st;
         size_t temp_bytes = 0;
         HIPCHK((hipError_t)aln_wordjoin_sort_temp_bytes(total, &temp_bytes));
@@ -4093,9 +4111,7 @@ static int seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint
         if ((st = dev_ensure(entries, 8ull * got, false)) != ALN_OK) return st;
         if (got) HIPCHK(hipMemcpy(entries.p, keys_b.p, 8ull * got, hipMemcpyDeviceToDevice));
         return ALN_OK;
-    };
-    const int st = run();
-    if (st != ALN_OK) (void)hipStreamSynchronize(q);
+    });
     dev_free(keys_a); dev_free(keys_b); dev_free(temp);
     if (st != ALN_OK) { dev_free(entries); dev_free(counts); return st; }
     dev_free(ss->word_e); dev_free(ss->word_n);
@@ -4103,10 +4119,7 @@ static int seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint
     ss->word_k = k; ss->word_alphabet = alphabet; ss->word_entries = got;
     seqset_drop_candidates(ss);
     if (n_words && ss->n) memcpy(n_words, counts_h.data(), 4ull * ss->n);
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 0;
-    ss->bytes[1] = 4 + (n_words ? 4ull * ss->n : 0);
+    seqset_done(ss, t0, 0, 4 + (n_words ? 4ull * ss->n : 0));
     return ALN_OK;
 }
 
@@ -4134,7 +4147,7 @@ static int seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *sp, const a
     // ---- the plan: nothing of the set's state is touched before the rows are cut
     std::vector<uint64_t> occ(rows, 0);
     std::vector<uint64_t> chunk_first, chunk_rows, chunk_occ;
-    auto plan = [&]() -> int {
+    st = run_queued(q, [&]() -> int {
         if ((st = dev_ensure(ss->wj_first, 4 * n_e, false)) != ALN_OK) return st;
         if ((st = dev_ensure(ss->wj_len, 4 * n_e, false)) != ALN_OK) return st;
         if ((st = dev_ensure(ss->wj_off, 4 * n_e, false)) != ALN_OK) return st;
@@ -4157,10 +4170,10 @@ static int seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *sp, const a
             first += n;
         }
         return ALN_OK;
-    };
-    if ((st = plan()) != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     seqset_drop_candidates(ss);
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    st = run_queued(q, [&]() -> int {
         if ((st = seqset_cand_room(ss, 0, 1)) != ALN_OK) return st;      // (an empty list is resident too, as the prefilter's is)
         for (size_t c = 0; c < chunk_first.size(); ++c) {
             const uint64_t m = chunk_occ[c], q_lo = b->q_first + chunk_first[c], q_rows = chunk_rows[c];
@@ -4216,9 +4229,8 @@ static int seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *sp, const a
             total += got;
         }
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); seqset_drop_candidates(ss); return st; }
+    });
+    if (st != ALN_OK) { seqset_drop_candidates(ss); return st; }
     ss->cand_qs.resize(total); ss->cand_ts.resize(total);
     for (uint64_t i = 0; i < total; ++i) {
         uint64_t sq, tq;
@@ -4228,21 +4240,18 @@ static int seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *sp, const a
     ss->cand = true;
     ss->cand_block = *b;
     *count = total;
-    ss->ms[2] = kernels;
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 0;
-    ss->bytes[1] = down;               // 8 bytes per query row, 12 per chunk and 12 per candidate
+    seqset_done(ss, t0, 0, down, kernels);          // 8 bytes per query row, 12 per chunk and 12 per candidate
     return ALN_OK;
 }
 
 extern "C" int aln_seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_word_index(ss, k, alphabet, n_words))
+    ALN_GUARDED(seqset_live(ss), seqset_word_index(ss, k, alphabet, n_words))
 }
 
 extern "C" int aln_seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *spec, const aln_seqset_block *b, uint64_t *count)
 {
-    ALN_SEQSET_GUARDED(ss, seqset_word_join(ss, spec, b, count))
+    ALN_GUARDED(seqset_live(ss), seqset_word_join(ss, spec, b, count))
 }
 
 static int seqset_held_check(aln_seqset *ss)
@@ -4250,6 +4259,28 @@ static int seqset_held_check(aln_seqset *ss)
     if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if (!ss->held) { g_err = "no held hits: aln_seqset_hits has not run, or another pass has replaced them"; return ALN_ERR_INVALID_ARGUMENT; }
     return ALN_OK;
+}
+
+// A list of held positions: no longer than the caller's own limit, every entry a held hit.  `each` sees every position once it is known
+// to be one, in list order, so that a caller's own per-hit refusal keeps its place among these.  The length alone is a check of its
+// own for the plans whose refusals that need no set come first.
+static int held_length_check(uint64_t n, uint64_t limit)
+{
+    if (n > limit) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
+    return ALN_OK;
+}
+template <class Each> static int held_list_check(const uint32_t *list, uint64_t n, uint64_t held, uint64_t limit, Each &&each)
+{
+    int st = held_length_check(n, limit);
+    for (uint64_t k = 0; k < n && st == ALN_OK; ++k) {
+        if (list[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+        st = each(list[k]);
+    }
+    return st;
+}
+static int held_list_check(const uint32_t *list, uint64_t n, uint64_t held, uint64_t limit)
+{
+    return held_list_check(list, n, held, limit, [](uint32_t) { return (int)ALN_OK; });
 }
 
 extern "C" int aln_seqset_held_list(aln_seqset *ss, uint64_t first, uint64_t n, uint64_t *pair_index, uint32_t *q_seq, uint32_t *t_seq, double *f)
@@ -4266,19 +4297,21 @@ extern "C" int aln_seqset_held_list(aln_seqset *ss, uint64_t first, uint64_t n, 
     return ALN_OK;                       // (no byte moves and no kernel runs: the stats of the pass stay as they are)
 }
 
-extern "C" int aln_seqset_held_strings(aln_seqset *ss, const uint32_t *keep, uint64_t n, aln_pair_result *results, uint8_t *tb_buf,
-                                       const uint64_t *tb_off)
+static int seqset_held_strings(aln_seqset *ss, const uint32_t *keep, uint64_t n, aln_pair_result *results, uint8_t *tb_buf, const uint64_t *tb_off)
 {
     int st = seqset_held_check(ss);
     if (st != ALN_OK) return st;
     if (n && (!keep || !results || (tb_buf && !tb_off))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (n > 0x7FFFFFF0ull) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
-    const uint64_t held = ss->hit_pair.size();
-    for (uint64_t k = 0; k < n; ++k)
-        if (keep[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = held_list_check(keep, n, ss->hit_pair.size(), 0x7FFFFFF0ull)) != ALN_OK) return st;
     if (n == 0) return ALN_OK;
     HIPCHK(hipSetDevice(ss->ctx->device));
     return held_fetch_strings(ss->held_store, ss->slot->stream, ss->ev, keep, n, results, tb_buf, tb_off, *ss);
+}
+
+extern "C" int aln_seqset_held_strings(aln_seqset *ss, const uint32_t *keep, uint64_t n, aln_pair_result *results, uint8_t *tb_buf,
+                                       const uint64_t *tb_off)
+{
+    ALN_GUARDED(seqset_live(ss), seqset_held_strings(ss, keep, n, results, tb_buf, tb_off))
 }
 
 // Significance of held hits: the listed hits as the pairs of a shuffle job (shuffle_job_plan: the planning, chunking, routing and
@@ -4294,12 +4327,11 @@ static int seqset_held_significance(aln_seqset *ss, const aln_params *params, co
     if (st != ALN_OK) return st;
     if (!params || !spec || (n_keep && (!keep || !records))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if (spec->per_pair == 0 || spec->per_pair > ALN_SHUFFLE_MAX_COPIES) { g_err = "per_pair must be 1 .. 2^20"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (n_keep > 0xFFFFFFF0ull) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
-    const uint64_t held = ss->hit_pair.size();
-    for (uint64_t k = 0; k < n_keep; ++k) {
-        if (keep[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
-        if (ss->len[ss->hit_t[keep[k]]] < spec->max_trim) { g_err = "a listed hit's target is shorter than max_trim"; return ALN_ERR_INVALID_ARGUMENT; }
-    }
+    st = held_list_check(keep, n_keep, ss->hit_pair.size(), 0xFFFFFFF0ull, [&](uint32_t h) -> int {
+        if (ss->len[ss->hit_t[h]] < spec->max_trim) { g_err = "a listed hit's target is shorter than max_trim"; return ALN_ERR_INVALID_ARGUMENT; }
+        return ALN_OK;
+    });
+    if (st != ALN_OK) return st;
     if (params->semantics == ALN_PWM_LOCAL) { g_err = "shuffled copies are aligned with the substitution-matrix semantics only"; return ALN_ERR_UNSUPPORTED; }
     const size_t n = (size_t)n_keep;
     const uint32_t per = spec->per_pair;
@@ -4343,7 +4375,7 @@ static int seqset_held_significance(aln_seqset *ss, const aln_params *params, co
     uint64_t up = 0;
     const uint8_t *set_seqs = ss->slot->seqs.as<uint8_t>();
     std::vector<aln_signif_record> rec(n);
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    st = run_queued(q, [&]() -> int {
         if (g.direct) {
             if (g.bytes) HIPCHK(hipMemcpyAsync(s.seqs.p, set_seqs + g.lo, g.bytes, hipMemcpyDeviceToDevice, q));
         } else {
@@ -4374,17 +4406,14 @@ static int seqset_held_significance(aln_seqset *ss, const aln_params *params, co
         HIPCHK(hipMemcpyAsync(rec.data(), rec_d, sizeof(aln_signif_record) * n, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     memcpy(records, rec.data(), sizeof(aln_signif_record) * n);
     if (lengths)
         for (size_t k = 0; k < n; ++k)
             for (uint32_t c = 0; c < per; ++c)
                 lengths[(uint64_t)k * per + c] = (uint32_t)t_len[k] - aln_shuffle_trim_of(spec->seed, stream[k], c, spec->max_trim);
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = up; ss->bytes[1] = sizeof(aln_signif_record) * n + (f ? 8 * total : 0);
+    seqset_done(ss, t0, up, sizeof(aln_signif_record) * n + (f ? 8 * total : 0));
     return ALN_OK;
 }
 
@@ -4393,13 +4422,7 @@ static int seqset_held_significance(aln_seqset *ss, const aln_params *params, co
 extern "C" int aln_seqset_held_significance(aln_seqset *ss, const aln_params *params, const aln_shuffle_spec *spec, const uint32_t *keep,
                                             uint64_t n_keep, aln_signif_record *records, double *f, uint32_t *lengths)
 {
-    try {
-        return seqset_held_significance(ss, params, spec, keep, n_keep, records, f, lengths);
-    } catch (const std::bad_alloc &) {
-        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(seqset_live(ss), seqset_held_significance(ss, params, spec, keep, n_keep, records, f, lengths))
 }
 
 // ---- reports of held hits: the columns of the held strings classed and counted on the device (aln_report.hip, aln_report_rules.h).
@@ -4419,6 +4442,57 @@ static int seqset_report_check(aln_seqset *ss, const aln_params *params, uint32_
     return ALN_OK;
 }
 
+// The steps of a call that has the held hits reported under a scheme, each once.  The check of a call whose filter is optional (with
+// one: params, flags and the bit table; without: only that hits are held) and of the filter's reserved word -- two checks, because a
+// caller's own refusals may stand between them; room for the table and n reports; the table's upload, which belongs before ev[0];
+// the launch over the listed hits, or with no list over all held hits, which belongs after it.
+static int seqset_filter_check(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, std::vector<uint32_t> &bits)
+{
+    return filter ? seqset_report_check(ss, params, flags, bits) : seqset_held_check(ss);
+}
+static int filter_reserved_check(const aln_hit_filter *filter)
+{
+    if (filter && filter->reserved != 0) { g_err = "the filter's reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    return ALN_OK;
+}
+static int seqset_reports_ensure(aln_seqset *ss, const std::vector<uint32_t> &bits, uint64_t n)
+{
+    const int st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false);
+    return st != ALN_OK ? st : dev_ensure(ss->reports, sizeof(aln_hit_report) * n, false);
+}
+static int seqset_bits_upload(aln_seqset *ss, const std::vector<uint32_t> &bits, hipStream_t q)
+{
+    HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
+    return ALN_OK;
+}
+static int seqset_report_queue(aln_seqset *ss, const aln_params *params, uint32_t flags, const uint32_t *list_d, uint64_t n, hipStream_t q)
+{
+    const HeldView v = held_view(ss->held_store);
+    aln_report_launch(v.info, v.res, v.tb, list_d, (uint32_t)n, (uint32_t)ss->hit_pair.size(), ss->rep_bits.as<uint32_t>(), params->rows, params->cols,
+                      params->blank_code, flags, ss->reports.as<aln_hit_report>(), q);
+    HIPCHK(hipGetLastError());
+    return ALN_OK;
+}
+static int seqset_report_all(aln_seqset *ss, const aln_params *params, uint32_t flags, hipStream_t q)
+{
+    return seqset_report_queue(ss, params, flags, nullptr, ss->hit_pair.size(), q);
+}
+// What cluster, profiles and the MSA plan send up of the held hits before ev[0]: the endpoints from the host's held list and, with a
+// filter (bits: its table, else null), the table; nothing when nothing is held.  And the bytes of that.
+static int seqset_endpoints_upload(aln_seqset *ss, uint32_t *d_q, uint32_t *d_t, const std::vector<uint32_t> *bits, hipStream_t q)
+{
+    const uint64_t held = ss->hit_pair.size();
+    if (!held) return ALN_OK;
+    HIPCHK(hipMemcpyAsync(d_q, ss->hit_q.data(), 4 * held, hipMemcpyHostToDevice, q));
+    HIPCHK(hipMemcpyAsync(d_t, ss->hit_t.data(), 4 * held, hipMemcpyHostToDevice, q));
+    return bits ? seqset_bits_upload(ss, *bits, q) : ALN_OK;
+}
+static uint64_t seqset_endpoints_bytes(const aln_seqset *ss, const std::vector<uint32_t> *bits)
+{
+    const uint64_t held = ss->hit_pair.size();
+    return 8ull * held + (bits && held ? 4ull * bits->size() : 0);
+}
+
 static int seqset_held_report(aln_seqset *ss, const aln_params *params, uint32_t flags, const uint32_t *keep, uint64_t n,
                               aln_hit_report *reports)
 {
@@ -4426,38 +4500,29 @@ static int seqset_held_report(aln_seqset *ss, const aln_params *params, uint32_t
     int st = seqset_report_check(ss, params, flags, bits);
     if (st != ALN_OK) return st;
     if (n && (!keep || !reports)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (n > 0x7FFFFFF0ull) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
-    const uint64_t held = ss->hit_pair.size();
-    for (uint64_t k = 0; k < n; ++k)
-        if (keep[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = held_list_check(keep, n, ss->hit_pair.size(), 0x7FFFFFF0ull)) != ALN_OK) return st;
     if (n == 0) return ALN_OK;
     HIPCHK(hipSetDevice(ss->ctx->device));
     hipStream_t q = ss->slot->stream;
     if ((st = dev_ensure(ss->held_store.list, 4ull * n, false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * n, false)) != ALN_OK) return st;
+    if ((st = seqset_reports_ensure(ss, bits, n)) != ALN_OK) return st;
     const auto t0 = std::chrono::steady_clock::now();
     // (the records land in a buffer of the call's own first: an error on the way leaves the caller's array as it was)
     std::vector<aln_hit_report> rep(n);
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    st = run_queued(q, [&]() -> int {
+        int e;
         HIPCHK(hipMemcpyAsync(ss->held_store.list.p, keep, 4ull * n, hipMemcpyHostToDevice, q));
-        HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
+        if ((e = seqset_bits_upload(ss, bits, q)) != ALN_OK) return e;
         HIPCHK(hipEventRecord(ss->ev[0], q));
-        aln_report_launch(ss->held_store.info.as<HeldEntry>(), ss->held_store.res.as<aln_pair_result>(), ss->held_store.tb.as<uint8_t>(), ss->held_store.list.as<uint32_t>(),
-                          (uint32_t)n, (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols, params->blank_code, flags,
-                          ss->reports.as<aln_hit_report>(), q);
-        HIPCHK(hipGetLastError());
+        if ((e = seqset_report_queue(ss, params, flags, ss->held_store.list.as<uint32_t>(), n, q)) != ALN_OK) return e;
         HIPCHK(hipEventRecord(ss->ev[1], q));
         HIPCHK(hipMemcpyAsync(rep.data(), ss->reports.p, sizeof(aln_hit_report) * n, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     memcpy(reports, rep.data(), sizeof(aln_hit_report) * n);
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 4ull * n + 4ull * bits.size(); ss->bytes[1] = sizeof(aln_hit_report) * n;
+    seqset_done(ss, t0, 4ull * n + 4ull * bits.size(), sizeof(aln_hit_report) * n);
     return ALN_OK;
 }
 
@@ -4468,7 +4533,7 @@ static int seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t
     int st = seqset_report_check(ss, params, flags, bits);
     if (st != ALN_OK) return st;
     if (!filter || !count || (capacity && !positions)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (filter->reserved != 0) { g_err = "the filter's reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = filter_reserved_check(filter)) != ALN_OK) return st;
     const uint64_t held = ss->hit_pair.size();        // (<= 0xFFFFFFF0: seqset_hold_list)
     if (held == 0) { *count = 0; return ALN_OK; }
     const uint64_t room = std::min<uint64_t>(capacity, held);
@@ -4476,8 +4541,7 @@ static int seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t
     hipStream_t q = ss->slot->stream;
     uint32_t *tile_count, *tile_off;
     if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(held), &tile_count, &tile_off)) != ALN_OK) return st;
-    if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
-    if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * held, false)) != ALN_OK) return st;
+    if ((st = seqset_reports_ensure(ss, bits, held)) != ALN_OK) return st;
     if ((st = dev_ensure(ss->rep_pos, 4ull * room, false)) != ALN_OK) return st;
     if (reports && (st = dev_ensure(ss->rep_out, sizeof(aln_hit_report) * room, false)) != ALN_OK) return st;
     const auto t0 = std::chrono::steady_clock::now();
@@ -4486,14 +4550,12 @@ static int seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t
     uint64_t wrote = 0;
     std::vector<uint32_t> pos;
     std::vector<aln_hit_report> rep;
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
-        HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
+    st = run_queued(q, [&]() -> int {
+        int e;
+        if ((e = seqset_bits_upload(ss, bits, q)) != ALN_OK) return e;
         HIPCHK(hipEventRecord(ss->ev[0], q));
-        aln_report_launch(ss->held_store.info.as<HeldEntry>(), ss->held_store.res.as<aln_pair_result>(), ss->held_store.tb.as<uint8_t>(), nullptr, (uint32_t)held,
-                          (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols, params->blank_code, flags,
-                          ss->reports.as<aln_hit_report>(), q);
-        HIPCHK(hipGetLastError());
-        aln_report_launch_filter(ss->reports.as<aln_hit_report>(), ss->held_store.info.as<HeldEntry>(), (uint32_t)held, filter, tile_count, tile_off,
+        if ((e = seqset_report_all(ss, params, flags, q)) != ALN_OK) return e;
+        aln_report_launch_filter(ss->reports.as<aln_hit_report>(), held_view(ss->held_store).info, (uint32_t)held, filter, tile_count, tile_off,
                                  d_count, room, ss->rep_pos.as<uint32_t>(), reports ? ss->rep_out.as<aln_hit_report>() : nullptr, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ss->ev[1], q));
@@ -4510,44 +4572,28 @@ static int seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t
             HIPCHK(hipStreamSynchronize(q));
         }
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     if (wrote) {
         memcpy(positions, pos.data(), 4ull * wrote);
         if (reports) memcpy(reports, rep.data(), sizeof(aln_hit_report) * wrote);
     }
     *count = kept;
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
     // (the 4-byte count aside: what comes down per kept hit)
-    ss->bytes[0] = 4ull * bits.size(); ss->bytes[1] = wrote * (4ull + (reports ? sizeof(aln_hit_report) : 0));
+    seqset_done(ss, t0, 4ull * bits.size(), wrote * (4ull + (reports ? sizeof(aln_hit_report) : 0)));
     return ALN_OK;
 }
 
-// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
 extern "C" int aln_seqset_held_report(aln_seqset *ss, const aln_params *params, uint32_t flags, const uint32_t *keep, uint64_t n_keep,
                                       aln_hit_report *reports)
 {
-    try {
-        return seqset_held_report(ss, params, flags, keep, n_keep, reports);
-    } catch (const std::bad_alloc &) {
-        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(seqset_live(ss), seqset_held_report(ss, params, flags, keep, n_keep, reports))
 }
 
 extern "C" int aln_seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter,
                                       uint32_t *positions, aln_hit_report *reports, uint64_t capacity, uint64_t *count)
 {
-    try {
-        return seqset_held_filter(ss, params, flags, filter, positions, reports, capacity, count);
-    } catch (const std::bad_alloc &) {
-        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(seqset_live(ss), seqset_held_filter(ss, params, flags, filter, positions, reports, capacity, count))
 }
 
 extern "C" int aln_seqset_stats(const aln_seqset *ss, double *ms, uint64_t *bytes)
@@ -4556,52 +4602,22 @@ extern "C" int aln_seqset_stats(const aln_seqset *ss, double *ms, uint64_t *byte
 }
 
 // ---------------------------------------------------------------- clusters of an edge list (aln_cluster.hip, aln_cluster_rules.h)
-// The tables of one call, carved out of one arena (every piece 256-aligned); base == nullptr only sizes it.
-struct ClusterBufs {
-    ClusterArgs a;
-    uint32_t *ea = nullptr, *eb = nullptr, *len = nullptr, *tile_count = nullptr, *tile_off = nullptr;
-    aln_cluster_record *rec = nullptr;
-};
-static size_t cluster_carve(uint8_t *base, uint32_t mode, uint64_t n, uint64_t m, uint64_t room, bool with_len, ClusterBufs *out)
+// What the kernels take of one call's arena (cluster_carve, aln_arena_rules.h).  len: the arena's own table, the set's, or null.
+static ClusterArgs cluster_args(const ClusterBufs &b, uint32_t mode, uint64_t n, uint64_t m, const aln_cluster_nodes &nodes, const uint32_t *len)
 {
-    size_t pos = 0;
-    auto take = [&](size_t bytes) -> uint8_t * {
-        uint8_t *p = base ? base + pos : nullptr;
-        pos += (size_t)align256(std::max<size_t>(bytes, 4));
-        return p;
-    };
-    const uint64_t tiles = aln_cluster_tiles(n);
-    ClusterBufs b;
-    b.a = ClusterArgs();
-    b.a.misc = reinterpret_cast<uint32_t *>(take(64));
-    b.a.label = reinterpret_cast<uint32_t *>(take(4 * n));
-    b.a.aux0 = reinterpret_cast<uint32_t *>(take(4 * n));
-    if (mode == ALN_CLUSTER_GREEDY) {
-        b.a.aux1 = reinterpret_cast<uint32_t *>(take(4 * n));
-        b.a.aux2 = reinterpret_cast<uint32_t *>(take(4 * n));
-    }
-    b.a.key = reinterpret_cast<uint64_t *>(take(8 * n));
-    b.a.size = reinterpret_cast<uint32_t *>(take(4 * n));
-    b.a.cedges = reinterpret_cast<uint32_t *>(take(4 * n));
-    b.ea = reinterpret_cast<uint32_t *>(take(4 * m));
-    b.eb = reinterpret_cast<uint32_t *>(take(4 * m));
-    if (with_len) b.len = reinterpret_cast<uint32_t *>(take(4 * n));
-    b.tile_off = reinterpret_cast<uint32_t *>(take(4 * tiles));
-    b.tile_count = reinterpret_cast<uint32_t *>(take(4 * tiles));
-    b.rec = reinterpret_cast<aln_cluster_record *>(take(sizeof(aln_cluster_record) * room));
-    b.a.mode = mode; b.a.n = n; b.a.m = m;
-    b.a.ea = b.ea; b.a.eb = b.eb; b.a.len = b.len;
-    if (out) *out = b;
-    return pos;
+    ClusterArgs a = ClusterArgs();
+    a.nodes = nodes; a.n = n; a.m = m; a.mode = mode;
+    a.len = len; a.ea = b.ea; a.eb = b.eb;
+    a.label = b.label; a.aux0 = b.aux0; a.aux1 = b.aux1; a.aux2 = b.aux2; a.key = b.key; a.size = b.size; a.cedges = b.cedges; a.misc = b.misc;
+    return a;
 }
 
 // The rounds and the finish, on a stream whose earlier work (the endpoints' upload, the held edges) is queued already.  The host reads
 // one 4-byte word per round: components the changed word, greedy the undecided count.  Labels, the first `room` records and the
 // summary land in the call's own host buffers.  On an error the caller waits for the stream.
-static int cluster_core(hipStream_t q, ClusterBufs &b, uint64_t room, std::vector<uint32_t> &label_h, std::vector<aln_cluster_record> &rec_h,
-                        aln_cluster_summary &sum, uint64_t *down)
+static int cluster_core(hipStream_t q, const ClusterArgs &a, const ClusterBufs &b, uint64_t room, std::vector<uint32_t> &label_h,
+                        std::vector<aln_cluster_record> &rec_h, aln_cluster_summary &sum, uint64_t *down)
 {
-    const ClusterArgs &a = b.a;
     const uint64_t nodes = aln_cluster_node_count(a.nodes);
     const uint64_t bound = a.n + 2;
     uint32_t rounds = 0, word = 0;
@@ -4676,24 +4692,24 @@ static int cluster_edges(aln_ctx *ctx, uint32_t mode, uint64_t n_nodes, const ui
     int st;
     if ((st = slot_init(s)) != ALN_OK) return st;
     // (the slot's shuffle table is a call's scratch: nothing outlives the call that wrote it)
-    if ((st = dev_ensure(s.shuffle, cluster_carve(nullptr, mode, n_nodes, n_edges, room, node_len != nullptr, nullptr), s.pooled)) != ALN_OK) return st;
+    const uint64_t tiles = aln_cluster_tiles(n_nodes);
+    if ((st = dev_ensure(s.shuffle, cluster_carve(nullptr, mode, n_nodes, n_edges, room, tiles, node_len != nullptr, nullptr), s.pooled)) != ALN_OK) return st;
     ClusterBufs b;
-    cluster_carve(s.shuffle.as<uint8_t>(), mode, n_nodes, n_edges, room, node_len != nullptr, &b);
-    b.a.nodes = aln_cluster_nodes_all(n_nodes);
+    cluster_carve(s.shuffle.as<uint8_t>(), mode, n_nodes, n_edges, room, tiles, node_len != nullptr, &b);
+    const ClusterArgs a = cluster_args(b, mode, n_nodes, n_edges, aln_cluster_nodes_all(n_nodes), b.len);
     hipStream_t q = s.stream;
     std::vector<uint32_t> label_h;
     std::vector<aln_cluster_record> rec_h;
     aln_cluster_summary sum;
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    st = run_queued(q, [&]() -> int {
         if (n_edges) {
             HIPCHK(hipMemcpyAsync(b.ea, edge_a, 4 * n_edges, hipMemcpyHostToDevice, q));
             HIPCHK(hipMemcpyAsync(b.eb, edge_b, 4 * n_edges, hipMemcpyHostToDevice, q));
         }
         if (node_len) HIPCHK(hipMemcpyAsync(b.len, node_len, 4 * n_nodes, hipMemcpyHostToDevice, q));
-        return cluster_core(q, b, room, label_h, rec_h, sum, nullptr);
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+        return cluster_core(q, a, b, room, label_h, rec_h, sum, nullptr);
+    });
+    if (st != ALN_OK) return st;
     // (everything landed in buffers of the call's own first: an error on the way left the caller's arrays as they were)
     memcpy(label, label_h.data(), 4 * n_nodes);
     if (!rec_h.empty()) memcpy(clusters, rec_h.data(), sizeof(aln_cluster_record) * rec_h.size());
@@ -4708,9 +4724,9 @@ static int seqset_held_cluster(aln_seqset *ss, const aln_params *params, uint32_
                                uint32_t *label, aln_cluster_record *clusters, uint64_t capacity, aln_cluster_summary *summary)
 {
     std::vector<uint32_t> bits;
-    int st = filter ? seqset_report_check(ss, params, flags, bits) : seqset_held_check(ss);
+    int st = seqset_filter_check(ss, params, flags, filter, bits);
     if (st != ALN_OK) return st;
-    if (filter && filter->reserved != 0) { g_err = "the filter's reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = filter_reserved_check(filter)) != ALN_OK) return st;
     if (mode != ALN_CLUSTER_COMPONENTS && mode != ALN_CLUSTER_GREEDY) { g_err = "unknown cluster mode"; return ALN_ERR_INVALID_ARGUMENT; }
     if (!summary || (ss->n && !label) || (capacity && !clusters)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     const uint64_t n = ss->n, held = ss->hit_pair.size();      // (n < 2^32 - 16 is checked below; held <= 0xFFFFFFF0: seqset_hold_list)
@@ -4718,110 +4734,92 @@ static int seqset_held_cluster(aln_seqset *ss, const aln_params *params, uint32_
     const uint64_t room = std::min<uint64_t>(capacity, n);
     HIPCHK(hipSetDevice(ss->ctx->device));
     hipStream_t q = ss->slot->stream;
-    if ((st = dev_ensure(ss->cluster, cluster_carve(nullptr, mode, n, held, room, false, nullptr), false)) != ALN_OK) return st;
-    if (filter && held) {
-        if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
-        if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * held, false)) != ALN_OK) return st;
-    }
+    const uint64_t tiles = aln_cluster_tiles(n);
+    if ((st = dev_ensure(ss->cluster, cluster_carve(nullptr, mode, n, held, room, tiles, false, nullptr), false)) != ALN_OK) return st;
+    if (filter && held && (st = seqset_reports_ensure(ss, bits, held)) != ALN_OK) return st;
     ClusterBufs b;
-    cluster_carve(ss->cluster.as<uint8_t>(), mode, n, held, room, false, &b);
-    b.a.nodes = aln_cluster_nodes_of_block(ss->held_block);
-    b.a.len = ss->d_len.as<uint32_t>();
+    cluster_carve(ss->cluster.as<uint8_t>(), mode, n, held, room, tiles, false, &b);
+    const ClusterArgs a = cluster_args(b, mode, n, held, aln_cluster_nodes_of_block(ss->held_block), ss->d_len.as<uint32_t>());
+    const std::vector<uint32_t> *up_bits = filter ? &bits : nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint32_t> label_h;
     std::vector<aln_cluster_record> rec_h;
     aln_cluster_summary sum;
     uint64_t down = 0;
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
-        if (held) {
-            HIPCHK(hipMemcpyAsync(b.ea, ss->hit_q.data(), 4 * held, hipMemcpyHostToDevice, q));
-            HIPCHK(hipMemcpyAsync(b.eb, ss->hit_t.data(), 4 * held, hipMemcpyHostToDevice, q));
-            if (filter) HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
-        }
+    st = run_queued(q, [&]() -> int {
+        int e;
+        if ((e = seqset_endpoints_upload(ss, b.ea, b.eb, up_bits, q)) != ALN_OK) return e;
         HIPCHK(hipEventRecord(ss->ev[0], q));
         if (held) {
-            if (filter) {
-                aln_report_launch(ss->held_store.info.as<HeldEntry>(), ss->held_store.res.as<aln_pair_result>(), ss->held_store.tb.as<uint8_t>(), nullptr,
-                                  (uint32_t)held, (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols, params->blank_code, flags,
-                                  ss->reports.as<aln_hit_report>(), q);
-                HIPCHK(hipGetLastError());
-            }
-            aln_cluster_launch_held_edges(ss->held_store.res.as<aln_pair_result>(), ss->reports.as<aln_hit_report>(), ss->held_store.info.as<HeldEntry>(),
-                                          filter, held, b.ea, b.eb, q);
+            if (filter && (e = seqset_report_all(ss, params, flags, q)) != ALN_OK) return e;
+            const HeldView v = held_view(ss->held_store);
+            aln_cluster_launch_held_edges(v.res, ss->reports.as<aln_hit_report>(), v.info, filter, held, b.ea, b.eb, q);
             HIPCHK(hipGetLastError());
         }
-        const int e = cluster_core(q, b, room, label_h, rec_h, sum, &down);
-        if (e != ALN_OK) return e;
+        if ((e = cluster_core(q, a, b, room, label_h, rec_h, sum, &down)) != ALN_OK) return e;
         HIPCHK(hipEventRecord(ss->ev[1], q));
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     if (n) memcpy(label, label_h.data(), 4 * n);
     if (!rec_h.empty()) memcpy(clusters, rec_h.data(), sizeof(aln_cluster_record) * rec_h.size());
     *summary = sum;
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 8ull * held + (filter && held ? 4ull * bits.size() : 0);
-    ss->bytes[1] = down;
+    seqset_done(ss, t0, seqset_endpoints_bytes(ss, up_bits), down);
     return ALN_OK;
 }
 
-// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
 extern "C" int aln_cluster_edges(aln_ctx *ctx, uint32_t mode, uint64_t n_nodes, const uint32_t *node_len, const uint32_t *edge_a,
                                  const uint32_t *edge_b, uint64_t n_edges, uint32_t *label, aln_cluster_record *clusters, uint64_t capacity,
                                  aln_cluster_summary *summary)
 {
-    try {
-        return cluster_edges(ctx, mode, n_nodes, node_len, edge_a, edge_b, n_edges, label, clusters, capacity, summary);
-    } catch (const std::bad_alloc &) {
-        if (ctx) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(ctx != nullptr, cluster_edges(ctx, mode, n_nodes, node_len, edge_a, edge_b, n_edges, label, clusters, capacity, summary))
 }
 
 extern "C" int aln_seqset_held_cluster(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, uint32_t mode,
                                        uint32_t *label, aln_cluster_record *clusters, uint64_t capacity, aln_cluster_summary *summary)
 {
-    try {
-        return seqset_held_cluster(ss, params, flags, filter, mode, label, clusters, capacity, summary);
-    } catch (const std::bad_alloc &) {
-        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(seqset_live(ss), seqset_held_cluster(ss, params, flags, filter, mode, label, clusters, capacity, summary))
 }
 
 // ---------------------------------------------------------------- profiles of a set's families (aln_profile.hip, aln_profile_rules.h)
-// The tables of one call, carved out of one arena (every piece 256-aligned); base == nullptr only sizes it.
-struct ProfileBufs {
-    unsigned long long *misc = nullptr;
-    uint32_t *hit_q = nullptr, *hit_t = nullptr, *label = nullptr, *slot_of = nullptr, *centers = nullptr, *out = nullptr;
-    uint64_t *off = nullptr;
-    aln_profile_record *rec = nullptr;
-};
-static size_t profile_carve(uint8_t *base, uint64_t n, uint64_t held, uint64_t n_centers, uint64_t total, ProfileBufs *out)
+// What profiles and the MSA plan do alike around their own kernels, on the pieces their arenas share (FamilyBufs, aln_arena_rules.h).
+// Up, before ev[0]: the endpoints and the filter's table, the labels, the centres and their offsets -- and the bytes of that.
+static int family_upload(aln_seqset *ss, const FamilyBufs &b, const std::vector<uint32_t> *bits, const uint32_t *label, const uint32_t *centers,
+                         uint64_t n_centers, const uint64_t *off, hipStream_t q)
 {
-    size_t pos = 0;
-    auto take = [&](size_t bytes) -> uint8_t * {
-        uint8_t *p = base ? base + pos : nullptr;
-        pos += (size_t)align256(std::max<size_t>(bytes, 4));
-        return p;
-    };
-    ProfileBufs b;
-    b.misc = reinterpret_cast<unsigned long long *>(take(8 * ALN_PROFILE_MISC_WORDS));
-    b.hit_q = reinterpret_cast<uint32_t *>(take(4 * held));
-    b.hit_t = reinterpret_cast<uint32_t *>(take(4 * held));
-    b.label = reinterpret_cast<uint32_t *>(take(4 * n));
-    b.slot_of = reinterpret_cast<uint32_t *>(take(4 * n));
-    b.centers = reinterpret_cast<uint32_t *>(take(4 * n_centers));
-    b.off = reinterpret_cast<uint64_t *>(take(8 * n_centers));
-    b.rec = reinterpret_cast<aln_profile_record *>(take(sizeof(aln_profile_record) * n_centers));
-    b.out = reinterpret_cast<uint32_t *>(take(4 * total));
-    if (out) *out = b;
-    return pos;
+    const int st = seqset_endpoints_upload(ss, b.hit_q, b.hit_t, bits, q);
+    if (st != ALN_OK) return st;
+    if (ss->n) HIPCHK(hipMemcpyAsync(b.label, label, 4 * ss->n, hipMemcpyHostToDevice, q));
+    if (n_centers) {
+        HIPCHK(hipMemcpyAsync(b.centers, centers, 4 * n_centers, hipMemcpyHostToDevice, q));
+        HIPCHK(hipMemcpyAsync(b.off, off, 8 * n_centers, hipMemcpyHostToDevice, q));
+    }
+    return ALN_OK;
+}
+static uint64_t family_upload_bytes(const aln_seqset *ss, const std::vector<uint32_t> *bits, uint64_t n_centers)
+{
+    return seqset_endpoints_bytes(ss, bits) + 4ull * ss->n + 12ull * n_centers;
+}
+// After ev[0]: the counters zero, no sequence a centre yet, the records (of either kind: rec_bytes in all) zero.
+static int family_clear(const aln_seqset *ss, const FamilyBufs &b, void *rec, size_t rec_bytes, hipStream_t q)
+{
+    HIPCHK(hipMemsetAsync(b.misc, 0, 8 * ALN_PROFILE_MISC_WORDS, q));
+    if (ss->n) HIPCHK(hipMemsetAsync(b.slot_of, 0xFF, 4 * ss->n, q));
+    if (rec_bytes) HIPCHK(hipMemsetAsync(rec, 0, rec_bytes, q));
+    return ALN_OK;
+}
+// The counters both summaries report (a 64-bit counter saturates into a 32-bit field); the rest of the summary is zero.
+static uint32_t sat32(unsigned long long v) { return (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull); }
+template <class Summary> static void family_summary(Summary *summary, uint64_t held, const unsigned long long *misc)
+{
+    memset(summary, 0, sizeof *summary);
+    summary->held = held;
+    summary->contributing = misc[ALN_PROFILE_COUNTS];
+    summary->self_pairs = sat32(misc[ALN_PROFILE_SELF]);
+    summary->between_members = sat32(misc[ALN_PROFILE_BETWEEN]);
+    summary->unlisted = sat32(misc[ALN_PROFILE_UNLISTED]);
+    summary->overflow = sat32(misc[ALN_PROFILE_MISC_OVERFLOW]);
 }
 
 // what both calls check of the centres and n_codes
@@ -4857,10 +4855,10 @@ static int seqset_held_profiles(aln_seqset *ss, const aln_params *params, uint32
     if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     if ((params != nullptr) != (filter != nullptr)) { g_err = "params and filter come together: the filter's reports are classed under params"; return ALN_ERR_INVALID_ARGUMENT; }
     std::vector<uint32_t> bits;
-    int st = filter ? seqset_report_check(ss, params, flags, bits) : seqset_held_check(ss);
+    int st = seqset_filter_check(ss, params, flags, filter, bits);
     if (st != ALN_OK) return st;
     if (flags & ~ALN_PROFILE_SKIP_SEED) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (filter && filter->reserved != 0) { g_err = "the filter's reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = filter_reserved_check(filter)) != ALN_OK) return st;
     if ((st = profile_layout_check(ss, centers, n_centers, n_codes)) != ALN_OK) return st;
     const uint64_t n = ss->n, held = ss->hit_pair.size();      // (n < 2^32: aln_seqset_create; held <= 0xFFFFFFF0: seqset_hold_list)
     if (!summary || (n && !label) || (n_centers && !records)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
@@ -4872,15 +4870,14 @@ static int seqset_held_profiles(aln_seqset *ss, const aln_params *params, uint32
     HIPCHK(hipSetDevice(ss->ctx->device));
     hipStream_t q = ss->slot->stream;
     if ((st = dev_ensure(ss->profile, profile_carve(nullptr, n, held, n_centers, total, nullptr), false)) != ALN_OK) return st;
-    if (filter && held) {
-        if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
-        if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * held, false)) != ALN_OK) return st;
-    }
+    if (filter && held && (st = seqset_reports_ensure(ss, bits, held)) != ALN_OK) return st;
     ProfileBufs b;
     profile_carve(ss->profile.as<uint8_t>(), n, held, n_centers, total, &b);
+    const HeldView v = held_view(ss->held_store);
+    const std::vector<uint32_t> *up_bits = filter ? &bits : nullptr;
     ProfileArgs a;
     memset(&a, 0, sizeof a);
-    a.held = ss->held_store.info.as<HeldEntry>(); a.res = ss->held_store.res.as<aln_pair_result>(); a.tb = ss->held_store.tb.as<uint8_t>();
+    a.held = v.info; a.res = v.res; a.tb = v.tb;
     a.rep = filter && held ? ss->reports.as<aln_hit_report>() : nullptr;
     if (filter) a.filter = *filter;
     a.hit_q = b.hit_q; a.hit_t = b.hit_t; a.label = b.label; a.len = ss->d_len.as<uint32_t>(); a.slot_of = b.slot_of; a.off = b.off;
@@ -4893,30 +4890,16 @@ static int seqset_held_profiles(aln_seqset *ss, const aln_params *params, uint32
     std::vector<uint32_t> out_h(total);
     std::vector<aln_profile_record> rec_h(n_centers);
     unsigned long long misc[ALN_PROFILE_MISC_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
-        if (held) {
-            HIPCHK(hipMemcpyAsync(b.hit_q, ss->hit_q.data(), 4 * held, hipMemcpyHostToDevice, q));
-            HIPCHK(hipMemcpyAsync(b.hit_t, ss->hit_t.data(), 4 * held, hipMemcpyHostToDevice, q));
-            if (filter) HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
-        }
-        if (n) HIPCHK(hipMemcpyAsync(b.label, label, 4 * n, hipMemcpyHostToDevice, q));
-        if (n_centers) {
-            HIPCHK(hipMemcpyAsync(b.centers, centers, 4 * n_centers, hipMemcpyHostToDevice, q));
-            HIPCHK(hipMemcpyAsync(b.off, off.data(), 8 * n_centers, hipMemcpyHostToDevice, q));
-        }
+    st = run_queued(q, [&]() -> int {
+        int e;
+        if ((e = family_upload(ss, b, up_bits, label, centers, n_centers, off.data(), q)) != ALN_OK) return e;
         HIPCHK(hipEventRecord(ss->ev[0], q));
-        HIPCHK(hipMemsetAsync(b.misc, 0, 8 * ALN_PROFILE_MISC_WORDS, q));
-        if (n) HIPCHK(hipMemsetAsync(b.slot_of, 0xFF, 4 * n, q));
-        if (n_centers) HIPCHK(hipMemsetAsync(b.rec, 0, sizeof(aln_profile_record) * n_centers, q));
+        if ((e = family_clear(ss, b, b.rec, sizeof(aln_profile_record) * n_centers, q)) != ALN_OK) return e;
         if (total) HIPCHK(hipMemsetAsync(b.out, 0, 4 * total, q));
         aln_profile_launch_slots(b.centers, (uint32_t)n_centers, (uint32_t)n, b.slot_of, b.rec, q);
         HIPCHK(hipGetLastError());
         if (held) {
-            if (filter) {
-                aln_report_launch(a.held, a.res, a.tb, nullptr, (uint32_t)held, (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols,
-                                  params->blank_code, flags, ss->reports.as<aln_hit_report>(), q);
-                HIPCHK(hipGetLastError());
-            }
+            if (filter && (e = seqset_report_all(ss, params, flags, q)) != ALN_OK) return e;
             aln_profile_launch(&a, q);
             HIPCHK(hipGetLastError());
         }
@@ -4926,104 +4909,31 @@ static int seqset_held_profiles(aln_seqset *ss, const aln_params *params, uint32
         if (total) HIPCHK(hipMemcpyAsync(out_h.data(), b.out, 4 * total, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     if (total) memcpy(out, out_h.data(), 4 * total);
     if (n_centers) memcpy(records, rec_h.data(), sizeof(aln_profile_record) * n_centers);
-    auto word = [](unsigned long long v) { return (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull); };
-    memset(summary, 0, sizeof *summary);
-    summary->held = held;
-    summary->contributing = misc[ALN_PROFILE_COUNTS];
-    summary->self_pairs = word(misc[ALN_PROFILE_SELF]);
-    summary->between_members = word(misc[ALN_PROFILE_BETWEEN]);
-    summary->unlisted = word(misc[ALN_PROFILE_UNLISTED]);
-    summary->overflow = word(misc[ALN_PROFILE_MISC_OVERFLOW]);
+    family_summary(summary, held, misc);
     summary->elements = total;
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 8ull * held + 4ull * n + 12ull * n_centers + (filter && held ? 4ull * bits.size() : 0);
-    ss->bytes[1] = 4ull * total + sizeof(aln_profile_record) * n_centers + 8ull * ALN_PROFILE_MISC_WORDS;
+    seqset_done(ss, t0, family_upload_bytes(ss, up_bits, n_centers), 4ull * total + sizeof(aln_profile_record) * n_centers + 8ull * ALN_PROFILE_MISC_WORDS);
     return ALN_OK;
 }
 
-// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
 extern "C" int aln_seqset_held_profiles(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, const uint32_t *label,
                                         const uint32_t *centers, uint64_t n_centers, uint32_t n_codes, uint32_t *out, uint64_t capacity,
                                         aln_profile_record *records, aln_profile_summary *summary)
 {
-    try {
-        return seqset_held_profiles(ss, params, flags, filter, label, centers, n_centers, n_codes, out, capacity, records, summary);
-    } catch (const std::bad_alloc &) {
-        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(seqset_live(ss), seqset_held_profiles(ss, params, flags, filter, label, centers, n_centers, n_codes, out, capacity, records, summary))
 }
 
 // ---------------------------------------------------------------- family alignments of a set (aln_msa.hip, aln_msa_rules.h)
-// The plan's tables, carved out of one arena (every piece 256-aligned); base == nullptr only sizes it.
-struct MsaPlanBufs {
-    unsigned long long *misc = nullptr;
-    uint32_t *hit_q = nullptr, *hit_t = nullptr, *label = nullptr, *slot_of = nullptr, *centers = nullptr, *mark = nullptr, *ins = nullptr, *col = nullptr;
-    uint64_t *ins_off = nullptr;
-    aln_msa_record *rec = nullptr;
-};
-static size_t msa_plan_carve(uint8_t *base, uint64_t n, uint64_t held, uint64_t n_centers, uint64_t n_ins, MsaPlanBufs *out)
-{
-    size_t pos = 0;
-    auto take = [&](size_t bytes) -> uint8_t * {
-        uint8_t *p = base ? base + pos : nullptr;
-        pos += (size_t)align256(std::max<size_t>(bytes, 4));
-        return p;
-    };
-    MsaPlanBufs b;
-    b.misc = reinterpret_cast<unsigned long long *>(take(8 * ALN_MSA_MISC_WORDS));
-    b.hit_q = reinterpret_cast<uint32_t *>(take(4 * held));
-    b.hit_t = reinterpret_cast<uint32_t *>(take(4 * held));
-    b.label = reinterpret_cast<uint32_t *>(take(4 * n));
-    b.slot_of = reinterpret_cast<uint32_t *>(take(4 * n));
-    b.centers = reinterpret_cast<uint32_t *>(take(4 * n_centers));
-    b.ins_off = reinterpret_cast<uint64_t *>(take(8 * n_centers));
-    b.rec = reinterpret_cast<aln_msa_record *>(take(sizeof(aln_msa_record) * n_centers));
-    b.mark = reinterpret_cast<uint32_t *>(take(4 * held));
-    b.ins = reinterpret_cast<uint32_t *>(take(4 * n_ins));
-    b.col = reinterpret_cast<uint32_t *>(take(4 * n_ins));
-    if (out) *out = b;
-    return pos;
-}
-// The fill's tables and its output, an arena of their own (sized when the plan's totals are known).
-struct MsaFillBufs {
-    uint64_t *byte_off = nullptr, *row_off = nullptr;
-    uint32_t *taken = nullptr, *list = nullptr, *hit_row = nullptr, *row_hit = nullptr;
-    uint8_t *out = nullptr;
-};
-static size_t msa_fill_carve(uint8_t *base, uint64_t held, uint64_t n_centers, uint64_t bytes, uint64_t total_rows, MsaFillBufs *out)
-{
-    size_t pos = 0;
-    auto take = [&](size_t room) -> uint8_t * {
-        uint8_t *p = base ? base + pos : nullptr;
-        pos += (size_t)align256(std::max<size_t>(room, 4));
-        return p;
-    };
-    MsaFillBufs b;
-    b.byte_off = reinterpret_cast<uint64_t *>(take(8 * n_centers));
-    b.row_off = reinterpret_cast<uint64_t *>(take(8 * n_centers));
-    b.taken = reinterpret_cast<uint32_t *>(take(4 * n_centers));
-    b.list = reinterpret_cast<uint32_t *>(take(4 * total_rows));
-    b.hit_row = reinterpret_cast<uint32_t *>(take(4 * held));
-    b.row_hit = reinterpret_cast<uint32_t *>(take(4 * total_rows));
-    b.out = take(bytes);
-    if (out) *out = b;
-    return pos;
-}
-
 // what both calls hand the kernels of the plan's arena
 static void msa_args(const aln_seqset *ss, const MsaPlanBufs &b, uint64_t n, uint64_t held, uint64_t n_centers, uint64_t n_ins, uint32_t blank, MsaArgs *a)
 {
     memset(a, 0, sizeof *a);
-    a->held = ss->held_store.info.as<HeldEntry>(); a->res = ss->held_store.res.as<aln_pair_result>(); a->tb = ss->held_store.tb.as<uint8_t>();
-    a->hit_q = b.hit_q; a->hit_t = b.hit_t; a->label = b.label; a->len = ss->d_len.as<uint32_t>(); a->slot_of = b.slot_of; a->ins_off = b.ins_off;
+    const HeldView v = held_view(ss->held_store);
+    a->held = v.info; a->res = v.res; a->tb = v.tb;
+    a->hit_q = b.hit_q; a->hit_t = b.hit_t; a->label = b.label; a->len = ss->d_len.as<uint32_t>(); a->slot_of = b.slot_of; a->ins_off = b.off;
     a->n_ins = n_ins;
     a->n_held = (uint32_t)held; a->n_seqs = (uint32_t)n; a->n_centers = (uint32_t)n_centers; a->blank = blank;
     a->ins = b.ins; a->col = b.col; a->mark = b.mark; a->rec = b.rec; a->misc = b.misc;
@@ -5046,9 +4956,9 @@ static int seqset_held_msa_plan(aln_seqset *ss, const aln_params *params, uint32
     }
     if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     std::vector<uint32_t> bits;
-    int st = filter ? seqset_report_check(ss, params, ALN_REPORT_SKIP_SEED, bits) : seqset_held_check(ss);
+    int st = seqset_filter_check(ss, params, ALN_REPORT_SKIP_SEED, filter, bits);
     if (st != ALN_OK) return st;
-    if (filter && filter->reserved != 0) { g_err = "the filter's reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = filter_reserved_check(filter)) != ALN_OK) return st;
     if (ss->destroyed) { g_err = "the set was destroyed"; return ALN_ERR_INVALID_ARGUMENT; }
     if (n_centers > ss->n || !aln_profile_centers_ok(centers, n_centers, ss->n)) {
         g_err = "the centres must be strictly ascending sequence numbers of the set";
@@ -5065,10 +4975,7 @@ static int seqset_held_msa_plan(aln_seqset *ss, const aln_params *params, uint32
     // (growing the arena drops the tables of the plan before: it is given up here, before anything else moves)
     if (ss->msa.cap < msa_plan_carve(nullptr, n, held, n_centers, n_ins, nullptr)) ss->msa_plan.valid = false;
     if ((st = dev_ensure(ss->msa, msa_plan_carve(nullptr, n, held, n_centers, n_ins, nullptr), false)) != ALN_OK) return st;
-    if (filter && held) {
-        if ((st = dev_ensure(ss->rep_bits, 4ull * bits.size(), false)) != ALN_OK) return st;
-        if ((st = dev_ensure(ss->reports, sizeof(aln_hit_report) * held, false)) != ALN_OK) return st;
-    }
+    if (filter && held && (st = seqset_reports_ensure(ss, bits, held)) != ALN_OK) return st;
     ss->msa_plan.valid = false;           // (the tables are rewritten from here on)
     MsaPlanBufs b;
     msa_plan_carve(ss->msa.as<uint8_t>(), n, held, n_centers, n_ins, &b);
@@ -5077,30 +4984,17 @@ static int seqset_held_msa_plan(aln_seqset *ss, const aln_params *params, uint32
     msa_args(ss, b, n, held, n_centers, n_ins, blank, &a);
     a.rep = filter && held ? ss->reports.as<aln_hit_report>() : nullptr;
     if (filter) a.filter = *filter;
+    const std::vector<uint32_t> *up_bits = filter ? &bits : nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<aln_msa_record> rec_h(n_centers);
     unsigned long long misc[ALN_MSA_MISC_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
-        if (held) {
-            HIPCHK(hipMemcpyAsync(b.hit_q, ss->hit_q.data(), 4 * held, hipMemcpyHostToDevice, q));
-            HIPCHK(hipMemcpyAsync(b.hit_t, ss->hit_t.data(), 4 * held, hipMemcpyHostToDevice, q));
-            if (filter) HIPCHK(hipMemcpyAsync(ss->rep_bits.p, bits.data(), 4ull * bits.size(), hipMemcpyHostToDevice, q));
-        }
-        if (n) HIPCHK(hipMemcpyAsync(b.label, label, 4 * n, hipMemcpyHostToDevice, q));
-        if (n_centers) {
-            HIPCHK(hipMemcpyAsync(b.centers, centers, 4 * n_centers, hipMemcpyHostToDevice, q));
-            HIPCHK(hipMemcpyAsync(b.ins_off, ins_off.data(), 8 * n_centers, hipMemcpyHostToDevice, q));
-        }
+    st = run_queued(q, [&]() -> int {
+        int e;
+        if ((e = family_upload(ss, b, up_bits, label, centers, n_centers, ins_off.data(), q)) != ALN_OK) return e;
         HIPCHK(hipEventRecord(ss->ev[0], q));
-        HIPCHK(hipMemsetAsync(b.misc, 0, 8 * ALN_MSA_MISC_WORDS, q));
-        if (n) HIPCHK(hipMemsetAsync(b.slot_of, 0xFF, 4 * n, q));
-        if (n_centers) HIPCHK(hipMemsetAsync(b.rec, 0, sizeof(aln_msa_record) * n_centers, q));
+        if ((e = family_clear(ss, b, b.rec, sizeof(aln_msa_record) * n_centers, q)) != ALN_OK) return e;
         if (n_ins) HIPCHK(hipMemsetAsync(b.ins, 0, 4 * n_ins, q));
-        if (held && filter) {
-            aln_report_launch(a.held, a.res, a.tb, nullptr, (uint32_t)held, (uint32_t)held, ss->rep_bits.as<uint32_t>(), params->rows, params->cols,
-                              params->blank_code, ALN_REPORT_SKIP_SEED, ss->reports.as<aln_hit_report>(), q);
-            HIPCHK(hipGetLastError());
-        }
+        if (held && filter && (e = seqset_report_all(ss, params, ALN_REPORT_SKIP_SEED, q)) != ALN_OK) return e;
         aln_msa_launch_plan(&a, b.centers, b.slot_of, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ss->ev[1], q));
@@ -5108,9 +5002,8 @@ static int seqset_held_msa_plan(aln_seqset *ss, const aln_params *params, uint32
         if (n_centers) HIPCHK(hipMemcpyAsync(rec_h.data(), b.rec, sizeof(aln_msa_record) * n_centers, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     if (misc[ALN_MSA_MISC_TOO_WIDE]) { g_err = "a family's width does not fit 32 bits"; return ALN_ERR_UNSUPPORTED; }
     aln_seqset::MsaPlan plan;
     plan.byte_off.resize(n_centers); plan.row_off.resize(n_centers);
@@ -5121,20 +5014,10 @@ static int seqset_held_msa_plan(aln_seqset *ss, const aln_params *params, uint32
     plan.valid = true; plan.passes = ss->held_passes; plan.n = n; plan.held = held; plan.n_centers = n_centers; plan.n_ins = n_ins; plan.blank = blank;
     ss->msa_plan = std::move(plan);
     if (n_centers) memcpy(records, rec_h.data(), sizeof(aln_msa_record) * n_centers);
-    auto word = [](unsigned long long v) { return (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull); };
-    memset(summary, 0, sizeof *summary);
-    summary->held = held;
-    summary->contributing = misc[ALN_PROFILE_COUNTS];
-    summary->self_pairs = word(misc[ALN_PROFILE_SELF]);
-    summary->between_members = word(misc[ALN_PROFILE_BETWEEN]);
-    summary->unlisted = word(misc[ALN_PROFILE_UNLISTED]);
-    summary->overflow = word(misc[ALN_PROFILE_MISC_OVERFLOW]);
+    family_summary(summary, held, misc);
     summary->bytes = ss->msa_plan.bytes;
     summary->total_rows = ss->msa_plan.total_rows;
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 8ull * held + 4ull * n + 12ull * n_centers + (filter && held ? 4ull * bits.size() : 0);
-    ss->bytes[1] = sizeof(aln_msa_record) * n_centers + 8ull * ALN_MSA_MISC_WORDS;
+    seqset_done(ss, t0, family_upload_bytes(ss, up_bits, n_centers), sizeof(aln_msa_record) * n_centers + 8ull * ALN_MSA_MISC_WORDS);
     return ALN_OK;
 }
 
@@ -5164,7 +5047,7 @@ static int seqset_held_msa_fill(aln_seqset *ss, uint8_t *out, uint64_t capacity_
     a.byte_off = f.byte_off; a.row_off = f.row_off; a.taken = f.taken; a.list = f.list; a.hit_row = f.hit_row; a.row_hit = f.row_hit; a.out = f.out;
     a.bytes = plan.bytes; a.total_rows = plan.total_rows;
     const auto t0 = std::chrono::steady_clock::now();
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    st = run_queued(q, [&]() -> int {
         if (n_centers) {
             HIPCHK(hipMemcpyAsync(f.byte_off, plan.byte_off.data(), 8 * n_centers, hipMemcpyHostToDevice, q));
             HIPCHK(hipMemcpyAsync(f.row_off, plan.row_off.data(), 8 * n_centers, hipMemcpyHostToDevice, q));
@@ -5181,72 +5064,30 @@ static int seqset_held_msa_fill(aln_seqset *ss, uint8_t *out, uint64_t capacity_
         if (plan.total_rows) HIPCHK(hipMemcpyAsync(row_hit, f.row_hit, 4 * plan.total_rows, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 16ull * n_centers;
-    ss->bytes[1] = plan.bytes + 4ull * plan.total_rows;
+    });
+    if (st != ALN_OK) return st;
+    seqset_done(ss, t0, 16ull * n_centers, plan.bytes + 4ull * plan.total_rows);
     return ALN_OK;
 }
 
-// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
 extern "C" int aln_seqset_held_msa_plan(aln_seqset *ss, const aln_params *params, uint32_t flags, const aln_hit_filter *filter, const uint32_t *label,
                                         const uint32_t *centers, uint64_t n_centers, aln_msa_record *records, aln_msa_summary *summary)
 {
-    try {
-        return seqset_held_msa_plan(ss, params, flags, filter, label, centers, n_centers, records, summary);
-    } catch (const std::bad_alloc &) {
-        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(seqset_live(ss), seqset_held_msa_plan(ss, params, flags, filter, label, centers, n_centers, records, summary))
 }
 
 extern "C" int aln_seqset_held_msa_fill(aln_seqset *ss, uint8_t *out, uint64_t capacity_bytes, uint32_t *row_hit, uint64_t capacity_rows)
 {
-    try {
-        return seqset_held_msa_fill(ss, out, capacity_bytes, row_hit, capacity_rows);
-    } catch (const std::bad_alloc &) {
-        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(seqset_live(ss), seqset_held_msa_fill(ss, out, capacity_bytes, row_hit, capacity_rows))
 }
 
 // ---------------------------------------------------------------- CIGARs of a set's held hits (aln_cigar.hip, aln_cigar_rules.h)
-// The plan's tables, carved out of one arena (every piece 256-aligned); base == nullptr only sizes it.
-struct CigarBufs {
-    unsigned long long *misc = nullptr;
-    uint32_t *list = nullptr;
-    aln_cigar_record *rec = nullptr;
-    uint64_t *off = nullptr, *tile_sum = nullptr, *tile_off = nullptr;
-};
-static size_t cigar_carve(uint8_t *base, uint64_t n, CigarBufs *out)
-{
-    size_t pos = 0;
-    auto take = [&](size_t bytes) -> uint8_t * {
-        uint8_t *p = base ? base + pos : nullptr;
-        pos += (size_t)align256(std::max<size_t>(bytes, 4));
-        return p;
-    };
-    CigarBufs b;
-    b.misc = reinterpret_cast<unsigned long long *>(take(8 * ALN_CIGAR_MISC_WORDS));
-    b.list = reinterpret_cast<uint32_t *>(take(4 * n));
-    b.rec = reinterpret_cast<aln_cigar_record *>(take(sizeof(aln_cigar_record) * n));
-    b.off = reinterpret_cast<uint64_t *>(take(8 * (n + 1)));
-    b.tile_sum = reinterpret_cast<uint64_t *>(take(8 * aln_cigar_tiles(n)));
-    b.tile_off = reinterpret_cast<uint64_t *>(take(8 * aln_cigar_tiles(n)));
-    if (out) *out = b;
-    return pos;
-}
-
 // what both calls hand the kernels of the plan's arena
 static void cigar_args(const aln_seqset *ss, const CigarBufs &b, uint64_t n, uint64_t held, uint32_t flags, uint32_t blank, CigarArgs *a)
 {
     memset(a, 0, sizeof *a);
-    a->held = ss->held_store.info.as<HeldEntry>(); a->res = ss->held_store.res.as<aln_pair_result>(); a->tb = ss->held_store.tb.as<uint8_t>();
+    const HeldView v = held_view(ss->held_store);
+    a->held = v.info; a->res = v.res; a->tb = v.tb;
     a->list = b.list; a->n_list = (uint32_t)n; a->n_held = (uint32_t)held; a->blank = blank; a->flags = flags; a->tiles = aln_cigar_tiles(n);
     a->rec = b.rec; a->off = b.off; a->tile_sum = b.tile_sum; a->tile_off = b.tile_off; a->misc = b.misc;
 }
@@ -5260,13 +5101,12 @@ static int seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t
     // (what needs no set comes first)
     if (!aln_cigar_flags_ok(flags)) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
     if (!summary || (n && (!which || !records))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (n > 0x7FFFFFF0ull) { g_err = "list too long"; return ALN_ERR_INVALID_ARGUMENT; }
-    int st = seqset_held_check(ss);
+    int st = held_length_check(n, 0x7FFFFFF0ull);
     if (st != ALN_OK) return st;
+    if ((st = seqset_held_check(ss)) != ALN_OK) return st;
     if (ss->destroyed) { g_err = "the set was destroyed"; return ALN_ERR_INVALID_ARGUMENT; }
     const uint64_t held = ss->hit_pair.size();        // (<= 0xFFFFFFF0: seqset_hold_list)
-    for (uint64_t k = 0; k < n; ++k)
-        if (which[k] >= held) { g_err = "a listed position is beyond the held hits"; return ALN_ERR_INVALID_ARGUMENT; }
+    if ((st = held_list_check(which, n, held, 0x7FFFFFF0ull)) != ALN_OK) return st;
     uint64_t longest = 0;
     for (uint64_t i = 0; i < ss->n; ++i) longest = std::max<uint64_t>(longest, ss->len[i]);
     if (!aln_cigar_supported(longest)) { g_err = "a run must fit 28 bits: some N + M + 2 of the set reaches 2^28"; return ALN_ERR_UNSUPPORTED; }
@@ -5285,7 +5125,7 @@ static int seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t
     // (the records land in a buffer of the call's own first: an error on the way leaves the caller's array as it was)
     std::vector<aln_cigar_record> rec_h(n);
     unsigned long long misc[ALN_CIGAR_MISC_WORDS] = {0, 0, 0, 0};
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    st = run_queued(q, [&]() -> int {
         if (n) HIPCHK(hipMemcpyAsync(b.list, which, 4 * n, hipMemcpyHostToDevice, q));
         HIPCHK(hipEventRecord(ss->ev[0], q));
         HIPCHK(hipMemsetAsync(b.misc, 0, 8 * ALN_CIGAR_MISC_WORDS, q));
@@ -5296,26 +5136,21 @@ static int seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t
         if (n) HIPCHK(hipMemcpyAsync(rec_h.data(), b.rec, sizeof(aln_cigar_record) * n, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
+    });
+    if (st != ALN_OK) return st;
     aln_seqset::CigarPlan plan;
     plan.valid = true; plan.passes = ss->held_passes; plan.n = n; plan.held = held; plan.total_ops = misc[ALN_CIGAR_MISC_TOTAL];
     plan.flags = flags; plan.blank = blank;
     ss->cigar_plan = plan;
     if (n) memcpy(records, rec_h.data(), sizeof(aln_cigar_record) * n);
-    auto word = [](unsigned long long v) { return (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull); };
     memset(summary, 0, sizeof *summary);
     summary->held = held;
     summary->listed = n;
     summary->total_ops = plan.total_ops;
-    summary->failed = word(misc[ALN_CIGAR_MISC_FAILED]);
-    summary->padded = word(misc[ALN_CIGAR_MISC_PADDED]);
-    summary->overflow = word(misc[ALN_CIGAR_MISC_OVERFLOW]);
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 4ull * n;
-    ss->bytes[1] = sizeof(aln_cigar_record) * n + 8ull * ALN_CIGAR_MISC_WORDS;
+    summary->failed = sat32(misc[ALN_CIGAR_MISC_FAILED]);
+    summary->padded = sat32(misc[ALN_CIGAR_MISC_PADDED]);
+    summary->overflow = sat32(misc[ALN_CIGAR_MISC_OVERFLOW]);
+    seqset_done(ss, t0, 4ull * n, sizeof(aln_cigar_record) * n + 8ull * ALN_CIGAR_MISC_WORDS);
     return ALN_OK;
 }
 
@@ -5343,7 +5178,7 @@ static int seqset_held_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capaci
     a.ops = ss->cigar_out.as<uint32_t>();
     a.total = plan.total_ops;
     const auto t0 = std::chrono::steady_clock::now();
-    auto run = [&]() -> int {          // (a HIPCHK in here leaves through the exit below, which waits for the stream)
+    st = run_queued(q, [&]() -> int {
         HIPCHK(hipEventRecord(ss->ev[0], q));
         if (plan.total_ops) HIPCHK(hipMemsetAsync(a.ops, 0, 4 * plan.total_ops, q));
         aln_cigar_launch_fill(&a, q);
@@ -5353,38 +5188,21 @@ static int seqset_held_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capaci
         if (offsets) HIPCHK(hipMemcpyAsync(offsets, b.off, 8 * (plan.n + 1), hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
         return ALN_OK;
-    };
-    st = run();
-    if (st != ALN_OK) { (void)hipStreamSynchronize(q); return st; }
-    ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]);
-    ss->ms[3] = wall_ms(t0);
-    ss->bytes[0] = 0;
-    ss->bytes[1] = 4ull * plan.total_ops + (offsets ? 8ull * (plan.n + 1) : 0);
+    });
+    if (st != ALN_OK) return st;
+    seqset_done(ss, t0, 0, 4ull * plan.total_ops + (offsets ? 8ull * (plan.n + 1) : 0));
     return ALN_OK;
 }
 
-// (host memory that cannot be had is ALN_ERR_OOM, not an exception through the C boundary)
 extern "C" int aln_seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t *which, uint64_t n, aln_cigar_record *records,
                                           aln_cigar_summary *summary)
 {
-    try {
-        return seqset_held_cigar_plan(ss, flags, which, n, records, summary);
-    } catch (const std::bad_alloc &) {
-        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(seqset_live(ss), seqset_held_cigar_plan(ss, flags, which, n, records, summary))
 }
 
 extern "C" int aln_seqset_held_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capacity_ops, uint64_t *offsets, uint64_t capacity_offsets)
 {
-    try {
-        return seqset_held_cigar_fill(ss, ops, capacity_ops, offsets, capacity_offsets);
-    } catch (const std::bad_alloc &) {
-        if (ss && ss->slot && ss->slot->stream) (void)hipDeviceSynchronize();
-        g_err = "out of host memory";
-        return ALN_ERR_OOM;
-    }
+    ALN_GUARDED(seqset_live(ss), seqset_held_cigar_fill(ss, ops, capacity_ops, offsets, capacity_offsets))
 }
 
 // ---------------------------------------------------------------- a pair set over a block of a sequence set, and the loop's step
