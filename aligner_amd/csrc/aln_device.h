@@ -29,29 +29,13 @@
 
 #include "../../include/aligner_hip.h"
 
-#ifndef ALN_FULL_R
-#define ALN_FULL_R 8             // rows per lane in a full strip of the batch kernels
-#endif
-#define ALN_STRIP_ROWS (64 * ALN_FULL_R)   // rows per full strip
+#include "aln_layout_rules.h"   // PairDesc, ALN_FULL_R, ALN_STRIP_ROWS and the size arithmetic of every region
+
 #define ALN_LAYOUT_SKEW 0u      // 512-row strips, R = 8 except the last strip (batch kernels)
 #define ALN_LAYOUT_ROWMAJOR 1u  // serial-order fallback
 #define ALN_LAYOUT_UNIFORM 2u   // every strip has 64*R rows, R in bits 8..15 (single-pair kernel; walked by the aln_tb_single_* kernels)
 #define ALN_LAYOUT_UBATCH 3u    // the same uniform-R strips written by the batch kernel (a cooperative re-fill, see CoopRec): walked by
                                 // the batch traceback like the skewed layout
-
-struct PairDesc {
-    uint64_t q_off, t_off;   // into seqs
-    uint32_t N, M;           // query / target length
-    uint64_t dir_off;        // into dirs, multiple of 256
-    uint64_t tb_off;         // into tb
-    uint64_t tag_off;        // into tags
-    uint64_t h_off;          // element offset into the optional H matrix buffer
-    int32_t status;          // pre-validation status; != 0 -> kernels skip the pair
-    uint32_t layout;         // written by the fill kernel
-};
-// pre-validation status "nothing to align, and the reference returns Ok": PWMAligner with an empty sequence (pwm/mod.rs:52-108:
-// the loops do not run, argmax is (0, 0), the traceback stops at once, f = 0).  The kernels skip the pair and report ALN_OK.
-#define ALN_PRE_EMPTY_OK (-1)
 
 // one pair of a shuffle call (aln_shuffle_*, aln_shuffle.hip): where its residues and its copies lie in the slot's residue buffer
 struct ShufflePair {
@@ -134,8 +118,6 @@ struct FillArgs {
     uint32_t f64_old;                // generic f64 kernels: 1 = run_strip's all-options loop instead of the lean f64 strip (ALN_F64_OLD, testing)
     uint32_t pair_matrices;          // lean f64 kernel (aln_pairset_run): 1 = `matrix` holds one rows x cols f64 matrix per descriptor, staged per wave
 };
-// aln_pairset_run: four waves' matrices of at most ALN_PAIRSET_MAX_ENTRIES doubles each
-__host__ __device__ inline uint32_t aln_pairset_lds_bytes(uint32_t rows, uint32_t cols) { return 4u * 8u * ((rows * cols + 1u) & ~1u); }
 
 // ---- cooperative passes of the fast batch kernel
 // One wave per pair leaves the tail of a small batch to whoever got the last large pair -- or a pair whose row-1 advice did not
@@ -156,7 +138,6 @@ __host__ __device__ inline uint32_t aln_pairset_lds_bytes(uint32_t rows, uint32_
 //                and read the same way (cdna_hip_programming.md, Guideline 16); the direction quads of such a kernel are
 //                stored write-through as well (FastIn::wt_dirs).
 // Every wait is bounded and raises the record's abort word; the owner then redoes the pass alone.
-#define ALN_COOP_MAX_NS 64u
 // Everything one wave hands to another is either inside a word that only atomic read-modify-writes touch (the claim word) or an
 // 8-byte GRANULE {value, tag}, stored and loaded whole (agent-scope atomics = write-through / past L1): the reader polls until the
 // tag is the one it expects, so neither the order in which stores become visible nor a copy of an older pass in some cache can be
@@ -168,6 +149,7 @@ struct CoopRec {
     unsigned long long pairg;                      // {pair, tag | 127}
     unsigned long long cand[ALN_COOP_MAX_NS][5];   // per strip {., tag | strip}: end-cell candidate bv, by, bx (T form), corner, status (1: gave up)
 };
+static_assert(sizeof(CoopRec) == ALN_COOP_REC_BYTES, "aln_layout_rules.h sizes the cooperative control block with ALN_COOP_REC_BYTES");
 __host__ __device__ inline uint32_t aln_coop_tag(uint32_t salt, uint32_t seq) { return 0x80000000u | ((salt & 0x3ffu) << 19) | ((seq & 0xfffu) << 7); }
 // claim word: bits 0..6 strips left, 7..13 strips, 14..15 kind (0: only the owner claims), 16 strip 0's bottom row keeps a row of
 // its own, 17..19 rows per lane of uniform strips (0: the skewed layout), 20..31 seq
@@ -186,7 +168,7 @@ __host__ __device__ inline uint32_t aln_coop_word(uint32_t seq, uint32_t R, uint
 #define ALN_COOP_ABORTS 6
 #define ALN_COOP_SCANS 7         // diagnostics: scans of the claim words
 #define ALN_COOP_ULOG 32         // .. 47: the waves (+ 1) that opened the last 16 urgent passes
-#define ALN_COOP_CTL_WORDS 256u   // (128 ..: diagnostics)
+// (ALN_COOP_CTL_WORDS control words in all, aln_layout_rules.h; 128 ..: diagnostics)
 
 // one large pair, one wave per strip, strips pipelined through granule rows in HBM/L2
 struct SingleArgs {
@@ -219,12 +201,8 @@ struct SingleArgs {
     uint32_t mode;            // 0 = a full pass (`pass`, gated by ctrl[1 + pass]); 1 = the repair run (gated by ctrl[8])
 };
 
-// strip 0 of a hazard pair checkpoints its lane state at steps max(16, one quad), then doubling, up to 1024 (r02: 512 -- enough for
-// BLOSUM62 11 / 2, whose bottom-row zeros sit next to the left border; under costlier gaps -- BLOSUM62 x 2 with 46 / 9, the integer
-// form of the dyadic scheme x 0.5 with 11.5 / 2.25 -- 41 % of C5's pairs flipped an advice bit beyond column 512 and were re-filled)
-#define ALN_CK_SLOTS 7
+// checkpoint steps of strip 0 of a hazard pair (ALN_CK_SLOTS of them, aln_layout_rules.h): the first and the last
 #define ALN_CK_LAST 1024u
-#define ALN_CASCADE_ROWS 3u
 #define ALN_CK_FIRST 16u
 
 struct TraceArgs {
@@ -267,24 +245,6 @@ struct WgArgs {
     void *hmat;               // optional: H dump, score type, (M+1)x(N+1) row-major per pair (desc.h_off elements in)
     uint32_t pwm;             // 1: position-weight-matrix scoring: S[t[y-1]][x-1], the column index instead of a query residue
 };
-#define ALN_WG_RING 256u      // entries of a hand-off ring (a strip's bottom row, by column & 255)
-__host__ __device__ inline uint32_t aln_wg_lds_bytes(uint32_t rows, uint32_t cols, uint32_t sc_size, uint32_t ns, uint32_t N)
-{
-    return ((rows * cols * sc_size + 15u) & ~15u) + ns * ALN_WG_RING * sc_size + 3u * ((N + 66u + 15u) & ~15u) + 64u * 4u + ns * 32u +
-           (N <= 2048u ? (((N + 66u) * sc_size + 15u) & ~15u) : 0u);      // row 1 of the pass: in LDS for short queries, else in the scratch
-}
-// LDS of the fast batch kernels (aln_fill_fast_kernel): [S][four waves' profiles][four waves' feed rings: query ring, boundary ring];
-// feed_bytes = 0 gives the offset of the rings.  PWM scoring (prof_stride == 0) has neither profiles nor rings.  C5 (24 x 24,
-// 12 KiB profiles): 51 456 + 1 856 = 53 312 bytes; three workgroups per CU fit up to 53 760 each (42 of the CU's 128 allocation
-// units of 1 280 bytes).
-#define ALN_QRING_BYTES 192u  // per wave: 128 query codes + the first 64 once more (aln_fast.h)
-#define ALN_BRING_BYTES 272u  // per wave: ints 1 .. 64 hold the 64 columns of the row above that the strip takes next
-#define ALN_FEED_BYTES (ALN_QRING_BYTES + ALN_BRING_BYTES)
-__host__ __device__ inline uint32_t aln_fast_lds_bytes(uint32_t rows, uint32_t cols, uint32_t prof_stride, uint32_t feed_bytes)
-{
-    const uint32_t s_bytes = (rows * cols * 4u + 15u) & ~15u;
-    return prof_stride == 0u ? s_bytes : s_bytes + 4u * prof_stride + 4u * feed_bytes;
-}
 
 // Parallel traceback of one large pair (uniform-R layout): per strip and entry column an "exit map", then a short
 // serial chain through the maps, then one walker per strip that writes its segment of the tag string.
@@ -303,7 +263,6 @@ struct TraceSingleArgs {
     uint32_t pwm;             // PWMAligner: no duplicated seed pair (pwm/mod.rs:76-108)
 };
 
-__host__ __device__ constexpr inline uint32_t aln_spb(uint32_t R) { return R >= 5 ? 2u : R >= 3 ? 4u : 16u / R; }
 // stored tag -> Direction discriminant (enums.rs:9-15: Top=0 Left=1 Diagonal=2 Beginning=3)
 __host__ __device__ inline int aln_tag_to_dir(int t) { return t == 3 ? 3 : 2 - t; }
 __host__ __device__ inline int aln_dir_to_tag(int d) { return d == 3 ? 3 : 2 - d; }
@@ -315,48 +274,9 @@ __host__ __device__ inline uint32_t aln_dir_bitpos(uint32_t k, uint32_t r, uint3
     const uint32_t e = bend < lend ? bend : lend;
     return 30u - 2u * ((e - k) * (uint32_t)R + ((uint32_t)R - 1u - r));
 }
-// rows handled per lane in the strip that starts `rem` rows before the end of the target: the smallest R with 64 R >= rem.
-// (A strip costs R cells of issue per step whatever its number of busy lanes; with R in {1,2,4,8} only, the last strips of C5
-// were rounded up by 8 % of the batch's work; every R in 1..8 leaves 3 %.)  Steps per direction word: aln_spb(R), the
-// largest power of two <= 16 / R (16, 8, 4, 4, 2, 2, 2, 2): the step arithmetic of fill and walk stays shifts and masks, and
-// the words of R = 3, 5, 6, 7 simply leave their low bits unused (12, 10, 12, 14 of 16 cell slots filled).
-__host__ __device__ inline int aln_pick_r(uint32_t rem)
-{
-    const int r = (int)((rem + 63u) / 64u);
-    return r > ALN_FULL_R ? ALN_FULL_R : (r < 1 ? 1 : r);
-}
-__host__ __device__ inline uint32_t aln_num_strips(uint32_t M) { return (M + ALN_STRIP_ROWS - 1) / ALN_STRIP_ROWS; }
-// blocks (of SPB steps) a strip of `nsteps` steps stores, padded to whole quads
-__host__ __device__ inline uint32_t aln_strip_blocks(uint32_t nsteps, uint32_t spb) { return (((nsteps + spb - 1) / spb) + 3u) & ~3u; }
 // word index of wave step k of lane `lane` inside its strip region
 __host__ __device__ inline uint64_t aln_dir_word_index(uint32_t k, uint32_t lane, uint32_t spb)
 {
     const uint32_t kb = k / spb;
     return ((uint64_t)(kb >> 2) * 64u + lane) * 4u + (kb & 3u);
-}
-// bytes of one full (R = 8) strip region: steps N+63, 2 steps per block, 256 B per block
-__host__ __device__ inline uint64_t aln_strip_bytes(uint32_t N) { return (uint64_t)aln_strip_blocks(N + 63, aln_spb(ALN_FULL_R)) * 256u; }
-// bytes of one strip of the uniform-R layout (single-pair kernel)
-__host__ __device__ inline uint64_t aln_uniform_strip_bytes(uint32_t N, uint32_t R) { return (uint64_t)aln_strip_blocks(N + 63, aln_spb(R)) * 256u; }
-__host__ __device__ inline uint64_t aln_rowmajor_bytes(uint32_t N, uint32_t M)
-{
-    return (uint64_t)(M + 1) * ((N + 4) / 4);
-}
-// rows per lane of a cooperative re-fill's uniform strips: at most eight strips up to 2048 rows; 0 = keep the skewed layout
-__host__ __device__ inline uint32_t aln_coop_uniform_r(uint32_t M)
-{
-    if (M <= 64u || M > 2048u) return 0u;
-    return M <= 512u ? 1u : M <= 1024u ? 2u : 4u;
-}
-__host__ __device__ inline uint64_t aln_dir_bytes(uint32_t N, uint32_t M)
-{
-    uint64_t a = (uint64_t)aln_num_strips(M) * aln_strip_bytes(N);
-    uint64_t b = aln_rowmajor_bytes(N, M);
-    uint64_t m = a > b ? a : b;
-    const uint32_t R = aln_coop_uniform_r(M);
-    if (R) {
-        const uint64_t c = (uint64_t)((M + 64u * R - 1u) / (64u * R)) * aln_uniform_strip_bytes(N, R);
-        m = c > m ? c : m;
-    }
-    return (m + 255) & ~(uint64_t)255;
 }

@@ -179,7 +179,7 @@ __device__ __forceinline__ uint32_t granule_load(const uint32_t *p)
 
 // LDS hand-off ring between two waves of a workgroup: T values (never zero) by column & (ALN_RING - 1); a slot is zeroed
 // by the consumer when it has taken it, and written by the producer only when it is zero.
-#define ALN_RING 4096u
+// (ALN_RING entries: aln_layout_rules.h, which sizes the kernel's LDS with it)
 
 // Everything a strip needs that is uniform over the pair.  Passed BY VALUE so that it lives in (scalar) registers.
 struct FastIn {

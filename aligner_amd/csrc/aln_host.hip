@@ -75,7 +75,6 @@ extern "C" void aln_launch_single(const SingleArgs *a, uint32_t N, int with_seri
 extern "C" void aln_launch_wgpipe(const WgArgs *a, int is_int, uint32_t lds_bytes, hipStream_t s);
 extern "C" void aln_launch_single_init(const SingleArgs *a, uint32_t n_bytes, hipStream_t s);
 extern "C" void aln_launch_single_repair(const SingleArgs *a, uint32_t N, hipStream_t s);
-extern "C" uint32_t aln_single_lds_bytes(uint32_t rows, uint32_t cols, uint32_t R, uint32_t N, uint32_t W);
 extern "C" void aln_launch_unpack(const uint8_t *dirs, const PairDesc *descs, uint32_t pair, int semantics, uint8_t *out,
                                   uint64_t cells, hipStream_t s);
 
@@ -394,14 +393,6 @@ struct Call {
     const double *pair_matrices = nullptr;   // aln_pairset_run: DEVICE array, one rows x cols matrix per pair of the call (lean f64 kernel only)
 };
 
-// bytes of the single-pair kernel's advice array and of its bottom-row record (one direction dword per block of the last
-// strip, at most (N + 63) / 2 + 4 blocks at R = 8), equal sizes, 256-aligned
-static inline uint64_t single_advice_bytes(uint64_t N)
-{
-    const uint64_t a = N + 128, z = 4 * ((N + 63) / 2 + 8);
-    return ((a > z ? a : z) + 255) & ~255ull;
-}
-
 static int call_init(Call &c, const aln_params *p, const uint64_t *q_len, const uint64_t *t_len, size_t n, bool want_h)
 {
     if (!p) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
@@ -465,55 +456,55 @@ static int call_init(Call &c, const aln_params *p, const uint64_t *q_len, const 
     return ALN_OK;
 }
 
-// ---------------------------------------------------------------- per chunk: descriptors, routing, layout
-struct Chunk {
-    size_t first = 0, n = 0;          // pairs [first, first + n) of the call
-    std::vector<PairDesc> descs;
-    std::vector<uint32_t> order;      // LPT order of the device work queue (pairs of the batch kernel)
-    std::vector<uint32_t> single_pairs, single_r;   // pairs routed to the single-pair (one wave per strip) kernel
-    std::vector<uint32_t> wg_pairs, wg_r;           // generic kernels: pairs filled by one workgroup each (aln_fill_wgpipe_kernel)
-    size_t n_small = 0;
-    uint64_t cells = 0, max_cells = 0, dir_bytes = 0, tb_bytes = 0, tag_bytes = 0, hmat_elems = 0;
-    uint32_t max_len = 1, grid = 1, zrow_bytes = 0, lds_bytes = 0, prof_stride = 0, tb_waves = 0, single_max_n = 0, cascade_rows = 1;
-    uint32_t duo_qo = 0;               // != 0: two short pairs per wave (aln_fill_duo_kernel): u16 entries of one staged query
-    uint64_t scratch_stride = 0, granule_bytes = 0, tbmap_entries = 0, granule_stride_max = 0;
-    size_t counter_bytes = 256;
-    bool overlap = false;             // walk waves beside the fill (in-kernel overlapped traceback)
-    // cooperative passes of the fast batch kernel (CoopRec, aln_device.h): hint ring capacities, bytes of the control block
-    bool coop = false, coop_linger = false;
-    bool coop_lean = false;           // the chunk would share, but so little that the kernel build without the machinery runs it (aln_coop_lean)
-    uint32_t coop_tail = 0;
-    uint64_t coop_bytes = 0;
-    // sequences: either one contiguous span of the caller's buffer, or gathered pair by pair into pinned staging
-    bool seq_direct = true;
-    uint64_t seq_lo = 0, seq_span = 0;
-    // a plan that is planned again keeps its arrays (6.4 MB of descriptors for 100 000 pairs: allocating and faulting them in afresh
-    // was 1 of the 2 ms the plan of a 100 000-window call took)
-    void reset()
-    {
-        std::vector<PairDesc> d = std::move(descs);
-        std::vector<uint32_t> o = std::move(order), sp = std::move(single_pairs), sr = std::move(single_r), wp = std::move(wg_pairs), wr = std::move(wg_r);
-        *this = Chunk();
-        d.clear(); o.clear(); sp.clear(); sr.clear(); wp.clear(); wr.clear();
-        descs = std::move(d); order = std::move(o); single_pairs = std::move(sp); single_r = std::move(sr); wg_pairs = std::move(wp); wg_r = std::move(wr);
-    }
-};
-
-// ALN_COOP_LEAN (read once): unset = aln_coop_lean_plan decides, 0 = the cooperative build wherever a chunk could share, 1 = the
-// lean build there.  Unlike ALN_NO_COOP (no cooperative passes at all, which also routes large pairs as if nothing could be shared)
-// it only picks the kernel build: routing, grid, claim runs and two pairs per wave are decided as without it.
-static int coop_lean_setting()
+// ---------------------------------------------------------------- per chunk: descriptors, routing, layout (aln_plan_rules.h)
+// the facts of a call that the plan reads
+static AlnPlanCall plan_call(const Call &c)
 {
-    static const int v = [] { const char *e = getenv("ALN_COOP_LEAN"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-    return v;
+    AlnPlanCall pc;
+    pc.pwm = c.pwm; pc.fast = c.fast; pc.is_int = c.is_int;
+    pc.want_h = c.want_h; pc.want_tb = c.want_tb; pc.store_dirs = c.store_dirs;
+    pc.semantics = c.semantics;
+    pc.hazard = c.semantics == ALN_CORE_LOCAL && c.p.del != c.p.ext;
+    pc.force_serial = c.p.force_serial != 0;
+    pc.pair_matrices = c.pair_matrices != nullptr;
+    pc.rows = c.rows; pc.cols = c.cols;
+    return pc;
 }
-// ALN_TRACE_PLAN=1 (read once): one stderr line per chunk that could share -- which build it runs, and the figures that decided it
-// ("aln plan:") -- and one per planned chunk, at the end of chunk_plan, that names its route ("aln route:": pairs of the batch
-// kernel, of the single-pair route, of the one-workgroup route, two pairs per wave, overlapped traceback, shared passes, kernel family)
+
+// The plan's settings (AlnPlanKnobs), read from the environment at every plan -- tests change them inside one process -- but for two:
+// ALN_COOP_LEAN (unset = aln_coop_lean_plan decides, 0 = the cooperative build wherever a chunk could share, 1 = the lean build
+// there.  Unlike ALN_NO_COOP -- no cooperative passes at all, which also routes large pairs as if nothing could be shared -- it only
+// picks the kernel build: routing, grid, claim runs and two pairs per wave are decided as without it) and
+// ALN_TRACE_PLAN (=1: one stderr line per chunk that could share -- which build it runs, and the figures that decided it, "aln plan:"
+// -- and one per planned chunk that names its route, "aln route:": pairs of the batch kernel, of the single-pair route, of the
+// one-workgroup route, two pairs per wave, overlapped traceback, shared passes, kernel family) are read once per process.
 static bool trace_plan()
 {
     static const bool v = getenv("ALN_TRACE_PLAN") != nullptr;
     return v;
+}
+static AlnPlanKnobs plan_knobs()
+{
+    static const int coop_lean = [] { const char *e = getenv("ALN_COOP_LEAN"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+    auto flag = [](const char *name) { return getenv(name) != nullptr; };
+    auto num = [](const char *name) { AlnKnob k; if (const char *e = getenv(name)) { k.set = true; k.v = atoi(e); } return k; };
+    AlnPlanKnobs kn;
+    kn.coop_lean = coop_lean;
+    kn.trace_plan = trace_plan();
+    kn.single_r = num("ALN_SINGLE_R");
+    kn.no_single = flag("ALN_NO_SINGLE");
+    kn.no_coop = flag("ALN_NO_COOP");
+    kn.big_to_single = num("ALN_BIG_TO_SINGLE");
+    kn.no_wgpipe = flag("ALN_NO_WGPIPE");
+    kn.wg_r = num("ALN_WG_R");
+    kn.tb_overlap = num("ALN_TB_OVERLAP");
+    kn.tb_overlap_any = flag("ALN_TB_OVERLAP_ANY");
+    if (const char *e = getenv("ALN_COOP_TAIL")) { kn.coop_tail.set = true; kn.coop_tail.v = (long long)strtoull(e, nullptr, 10); }
+    kn.chain_wgs = num("ALN_CHAIN_WGS");
+    kn.fill_wgs = num("ALN_FILL_WGS");
+    kn.no_duo = flag("ALN_NO_DUO");
+    if (const char *e = getenv("ALN_CHUNK_CELLS")) { kn.chunk_cells_set = true; kn.chunk_cells = atof(e); }
+    return kn;
 }
 
 // allow_overlap: the chunk has the device to itself (a single-chunk call, a staged batch).  many_chunks: one of more than four
@@ -521,321 +512,20 @@ static bool trace_plan()
 static int chunk_plan(const DevCtx *ctx, const Call &c, const uint64_t *q_off, const uint64_t *q_len, const uint64_t *t_off,
                       const uint64_t *t_len, size_t first, size_t n, bool allow_overlap, Chunk &k, bool many_chunks = false)
 {
-    k.first = first; k.n = n;
-    k.descs.assign(n, PairDesc{});
-    const bool pwm = c.pwm;
-    const uint32_t rows = c.rows, cols = c.cols;
-    const char *env_r = getenv("ALN_SINGLE_R");
-    const char *env_off = getenv("ALN_NO_SINGLE");
-    uint64_t seq_lo = ~0ull, seq_hi = 0, seq_sum = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const size_t g = first + i;
-        PairDesc &d = k.descs[i];
-        d.N = pwm ? cols : (uint32_t)q_len[g];                                 // PWM: the columns are the PWM positions
-        d.M = (uint32_t)t_len[g];
-        d.status = ALN_OK;
-        if (d.N == 0 || d.M == 0) d.status = (pwm && d.N != 0) ? ALN_PRE_EMPTY_OK : ALN_ERR_EMPTY_SEQUENCE;   // the reference panics
-        if (!pwm && q_len[g]) { seq_lo = std::min(seq_lo, q_off[g]); seq_hi = std::max(seq_hi, q_off[g] + q_len[g]); seq_sum += q_len[g]; }
-        if (t_len[g]) { seq_lo = std::min(seq_lo, t_off[g]); seq_hi = std::max(seq_hi, t_off[g] + t_len[g]); seq_sum += t_len[g]; }
-    }
-    if (seq_lo == ~0ull) { seq_lo = 0; seq_hi = 0; }
-    // the chunk's residues are one span of the caller's buffer unless the offsets are scattered far beyond what the chunk uses
-    k.seq_direct = (seq_hi - seq_lo) <= 2 * seq_sum + 65536;
-    k.seq_lo = seq_lo;
-    k.seq_span = k.seq_direct ? seq_hi - seq_lo : seq_sum;
-    uint64_t gpos = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const size_t g = first + i;
-        PairDesc &d = k.descs[i];
-        if (k.seq_direct) { d.q_off = pwm ? 0 : q_off[g] - (q_len[g] ? seq_lo : q_off[g]); d.t_off = t_len[g] ? t_off[g] - seq_lo : 0; }
-        else { d.q_off = gpos; gpos += pwm ? 0 : q_len[g]; d.t_off = gpos; gpos += t_len[g]; }
-    }
-
-    // ---- routing + HBM layout.  A pair goes to the single-pair kernel (one wave per strip, strips pipelined across
-    // CUs) when it is large, or when the chunk is too small to fill the chip with one wave per pair -- unless the chunk holds
-    // so many such pairs that the batch kernel, whose waves share the strips of a pair (cooperative passes), is through with all
-    // of them sooner than the single-pair route, which takes them one after the other.  Estimates (measured rates): the
-    // single-pair route fills at ~60 GCUPS plus ~0.2 ms of launches and traceback per pair; in the batch kernel a wave fills at
-    // ~0.85 GCUPS with the chip full (2.6 TCUPS at most), and the pipeline of a pair's strips takes (N + 63 + 170 (strips - 1))
-    // steps of ~0.55 us.
-    const bool coop_on = c.fast && !getenv("ALN_NO_COOP");
-    bool big_to_single = true;
-    if (coop_on && !pwm && !env_off) {
-        double t_single = 0, cells_all = 0, cells_small = 0, strips_all = 0, strips_small = 0, lat_all = 0, lat_small = 0;
-        size_t n_big = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const PairDesc &d = k.descs[i];
-            if (d.status != ALN_OK) continue;
-            const double pc = (double)d.N * d.M, st = (double)aln_num_strips(d.M);
-            const double lat = ((double)d.N + 63.0 + 170.0 * (st - 1.0)) * 0.55e-6;
-            const bool big = d.N >= 64 && d.M >= 128 && (pc >= (double)(1ull << 24) || (n <= 16 && pc >= (double)(1ull << 18)));
-            cells_all += pc; strips_all += st; lat_all = std::max(lat_all, lat);
-            if (big) { t_single += pc / 60e9 + 0.2e-3; ++n_big; }
-            else { cells_small += pc; strips_small += st; lat_small = std::max(lat_small, lat); }
-        }
-        const double waves = (double)ctx->cus * 12.0;
-        auto t_batch = [&](double cells, double strips, double lat) {
-            if (cells <= 0) return 0.0;
-            return std::max(std::max(cells / 2.6e12, lat), cells / (std::min(strips, waves) * 0.85e9));
-        };
-        if (n_big) big_to_single = t_single + t_batch(cells_small, strips_small, lat_small) <= t_batch(cells_all, strips_all, lat_all);
-        if (const char *e = getenv("ALN_BIG_TO_SINGLE")) big_to_single = atoi(e) != 0;
-    }
-    uint64_t dir_total = 0, tb_total = 0, tag_total = 0, hm_total = 0, cells = 0;
-    uint32_t max_len = 1;
-    for (size_t i = 0; i < n; ++i) {
-        PairDesc &d = k.descs[i];
-        // strings: cumulative 2 * cap per pair (PWM: 5 * cap, 4-aligned) -- the layout aln_align_batch documents for tb_buf
-        const uint64_t cap = (uint64_t)d.N + d.M + 2;
-        if (c.store_dirs) {
-            d.tb_off = tb_total;
-            tb_total += pwm ? ((5ull * cap + 3) & ~3ull) : 2ull * cap;
-            d.tag_off = tag_total;
-            tag_total += (cap + 3) & ~3ull;
-        }
-        if (d.status != ALN_OK) continue;
-        const uint64_t pc = (uint64_t)d.N * d.M;
-        cells += pc;
-        max_len = std::max(max_len, std::max(d.N, d.M));
-        bool single = c.fast && !pwm && !env_off && d.N >= 64 && d.M >= 128 && (pc >= (1ull << 24) || (n <= 16 && pc >= (1ull << 18))) &&
-                      (big_to_single || aln_num_strips(d.M) > ALN_COOP_MAX_NS);
-        uint64_t dbytes = aln_dir_bytes(d.N, d.M);
-        if (single) {
-            // rows per lane: two above ~2500 rows (measured, fill + traceback: 3000 x 3000 0.59 ms against 0.62 with one, 4000 x 4000
-            // 0.72 against 0.76; below, the traceback's longer strips cost more than the fill gains)
-            uint32_t R = env_r ? (uint32_t)atoi(env_r) : (d.M > 2560 ? 2u : 1u);
-            if (R != 1 && R != 2 && R != 4 && R != 8) R = 2;
-            while ((d.M + 64 * R - 1) / (64 * R) > 4096 && R < 8) R *= 2;      // keep every strip's wave resident
-            if ((d.M + 64 * R - 1) / (64 * R) > 4096) single = false;
-            // LDS: the whole query's profile offsets are staged (2 B per column) beside S and the waves' profiles; a workgroup may
-            // opt in to all 160 KiB of a CU (one wave per workgroup beyond ~43 000 columns, four below: aln_single_waves), which
-            // carries the route to ~77 000 columns.  Longer pairs take the batch kernel (one wave, slow but exact).
-            if (d.N > 100000u || aln_single_lds_bytes(rows, cols, R, d.N, 1) > 159u * 1024u) single = false;
-            if (single) {
-                const uint32_t ns = (d.M + 64 * R - 1) / (64 * R);
-                dbytes = std::max<uint64_t>(dbytes, (uint64_t)ns * aln_uniform_strip_bytes(d.N, R));
-                k.single_pairs.push_back((uint32_t)i);
-                k.single_r.push_back(R);
-                const uint64_t gstride = ((uint64_t)d.N + 64 + 63) & ~63ull;
-                k.granule_stride_max = std::max(k.granule_stride_max, gstride);
-                k.granule_bytes = std::max<uint64_t>(k.granule_bytes, std::max<uint64_t>((uint64_t)ns * gstride * 4, 4ull * (d.M + 2)));
-                k.single_max_n = std::max(k.single_max_n, std::max(d.N, ns));
-                k.tbmap_entries = std::max<uint64_t>(k.tbmap_entries, (uint64_t)ns * (d.N + 1) + ns + 64);
-            }
-        }
-        // Generic kernels (real-valued matrix, or an integer one outside the fast path's limits): a chunk of at most four pairs (their launches run one
-        // after the other; a larger chunk is better off with one wave per pair, all at once) gives each pair a whole workgroup, one wave per 64 R-row strip (<= 16 strips), instead of one wave -- the call HeuristicAligner makes
-        // once per iteration (heuristic/mod.rs:58-77).  Also with the H dump (AlignmentResult.alignment_matrix) and for PWM scoring (HeuristicPWMAligner).
-        if (!single && (!c.fast || c.want_h) && !c.pair_matrices && !c.p.force_serial && !getenv("ALN_NO_WGPIPE") && n <= 4 && pc >= (1ull << 14) &&
-            d.N >= 16 && d.N <= 8192 && d.M >= 65 && d.M <= 2048) {
-            // rows per lane: about eight strips = two waves per SIMD of the one CU (measured, 1000 x 1000 f64: R = 1 1.42 ms,
-            // R = 2 1.26, R = 4 1.28; 330 x 300: 0.43 / 0.43 / 0.50)
-            uint32_t R = d.M > 1024 ? 4u : d.M > 512 ? 2u : 1u;
-            if (const char *e = getenv("ALN_WG_R")) { const uint32_t v = (uint32_t)atoi(e); if ((v == 1 || v == 2 || v == 4) && (d.M + 64 * v - 1) / (64 * v) <= 16) R = v; }
-            const uint32_t ns = (d.M + 64 * R - 1) / (64 * R);
-            if (aln_wg_lds_bytes(c.rows, c.cols, c.is_int ? 4u : 8u, ns, d.N) <= 64u * 1024u) {
-                dbytes = std::max<uint64_t>(dbytes, (uint64_t)ns * aln_uniform_strip_bytes(d.N, R));
-                k.wg_pairs.push_back((uint32_t)i);
-                k.wg_r.push_back(R);
-                k.tbmap_entries = std::max<uint64_t>(k.tbmap_entries, (uint64_t)ns * (d.N + 1) + ns + 64);
-            }
-        }
-        d.dir_off = dir_total;
-        if (c.store_dirs) dir_total += dbytes;
-        if (c.want_h) { d.h_off = hm_total; hm_total += (uint64_t)(d.N + 1) * (d.M + 1); }
-    }
-    k.cells = cells; k.max_len = max_len;
-    k.dir_bytes = dir_total; k.tb_bytes = tb_total; k.tag_bytes = tag_total; k.hmat_elems = hm_total;
-
-    // ---- LPT order: longest pairs first into the device work queue.  "Longest" = the time one wave needs, not the cells: a strip of
-    // R rows per lane takes N + lanes - 1 steps of about 12 + 10.5 R instructions, so a 1900 x 270 pair (one strip of 5 rows per
-    // lane) keeps its wave as long as a 1000 x 1000 pair with twice the cells -- ordered by cells it was taken when the queue was
-    // almost dry and ended the 8-way shard's fill 0.9 ms after everybody else (tools/tail_timeline.py).
-    auto pair_cost = [](const PairDesc &d) -> uint64_t {
-        if (d.status != ALN_OK) return 0;
-        uint64_t cost = 0;
-        const uint32_t ns = aln_num_strips(d.M);
-        for (uint32_t st = 0; st < ns; ++st) {
-            const uint32_t rows = std::min<uint32_t>(d.M - st * ALN_STRIP_ROWS, ALN_STRIP_ROWS);
-            const uint32_t R = st + 1 == ns ? (uint32_t)aln_pick_r(rows) : (uint32_t)ALN_FULL_R, L = (rows + R - 1) / R;
-            cost += (uint64_t)(d.N + L - 1) * (24u + 21u * R);
-            if (cost >= (1ull << 40)) return (1ull << 40) - 1;
-        }
-        return cost;
-    };
-    k.order.clear();
-    k.order.reserve(n);
-    {
-        std::vector<char> is_single(n, 0);
-        for (uint32_t i : k.single_pairs) is_single[i] = 1;
-        for (uint32_t i : k.wg_pairs) is_single[i] = 1;
-        for (size_t i = 0; i < n; ++i) if (!is_single[i]) k.order.push_back((uint32_t)i);
-    }
-    k.n_small = k.order.size();
-    double cost_sum = 0;                  // pair_cost over the queue (aln_coop_lean)
-    {
-        // sort keys packed in one u64: cells descending, then index ascending (a stable order without a stable_sort)
-        std::vector<uint64_t> key(k.n_small);
-        bool packable = n < (1u << 24);
-        for (size_t j = 0; j < k.n_small && packable; ++j) {
-            const uint64_t pc = pair_cost(k.descs[k.order[j]]);
-            cost_sum += (double)pc;
-            key[j] = ((~pc & ((1ull << 40) - 1)) << 24) | k.order[j];
-        }
-        if (packable) {
-            // (equal pairs -- PWM windows, read pairs -- arrive sorted: the test costs one pass, the sort was 1 of the 1.7 ms the
-            // plan of 100 000 windows took)
-            if (!std::is_sorted(key.begin(), key.end())) {
-                // LSD radix sort on the bits of the cost that vary, 11 at a time (stable: equal costs keep the index order the keys
-                // were built in); std::sort was 0.35 of the 0.7 ms the plan of 12 500 pairs took
-                uint64_t lo = ~0ull, hi = 0;
-                for (uint64_t v : key) { lo = std::min(lo, v >> 24); hi = std::max(hi, v >> 24); }
-                const uint64_t range = hi - lo;                      // sort by (v >> 24) - lo
-                std::vector<uint64_t> tmp(key.size());
-                uint64_t *src = key.data(), *dst = tmp.data();
-                for (uint32_t shift = 0; shift < 40 && (range >> shift) != 0; shift += 11) {
-                    uint32_t cnt[2049] = {0};
-                    for (size_t j = 0; j < key.size(); ++j) ++cnt[((((src[j] >> 24) - lo) >> shift) & 2047u) + 1u];
-                    for (uint32_t d = 0; d < 2048; ++d) cnt[d + 1] += cnt[d];
-                    for (size_t j = 0; j < key.size(); ++j) dst[cnt[(((src[j] >> 24) - lo) >> shift) & 2047u]++] = src[j];
-                    std::swap(src, dst);
-                }
-                if (src != key.data()) memcpy(key.data(), src, key.size() * sizeof(uint64_t));
-            }
-            for (size_t j = 0; j < k.n_small; ++j) k.order[j] = (uint32_t)(key[j] & 0xffffffu);
-        } else {
-            std::stable_sort(k.order.begin(), k.order.end(), [&](uint32_t a, uint32_t b) { return pair_cost(k.descs[a]) > pair_cost(k.descs[b]); });
-            for (uint32_t i : k.order) cost_sum += (double)pair_cost(k.descs[i]);
-        }
-    }
-    k.max_cells = 0;
-    for (uint32_t i : k.order) if (k.descs[i].status == ALN_OK) k.max_cells = std::max(k.max_cells, (uint64_t)k.descs[i].N * k.descs[i].M);
-
-    // ---- grid: persistent waves, 4 per workgroup
-    const uint32_t wg_needed = (uint32_t)((k.n_small + 3) / 4);
-    k.grid = std::max(1u, std::min(wg_needed, (uint32_t)ctx->cus * 4u));
-    // Overlapped traceback: the walk kernel runs beside the fill.  The fast fill kernel is built for 160 VGPRs,
-    // three workgroups per CU, so that every SIMD keeps 32 registers free: exactly one wave of the walk kernel (32 VGPRs, no
-    // LDS).  ALN_TB_OVERLAP: unset = one walk wave per SIMD beside a full fill grid; 0 = off; n > 0 = the earlier scheme (the
-    // fill grid stops n workgroups short of residency and the walk waves crowd onto those CUs, 20 per slot).
-    {
-        const uint32_t resident = (uint32_t)ctx->cus * 3u;
-        const char *e = getenv("ALN_TB_OVERLAP");
-        const uint32_t reserve = e ? (uint32_t)atoi(e) : 0u;
-        const bool off = e && reserve == 0;
-        // (only where the fill is long enough to hide anything behind: the walk waves, their 30 us head start and the
-        // write-through stores cost a batch of 10 000 read pairs -- 0.3 ms of fill -- 40 % of its time)
-        k.overlap = allow_overlap && !off && c.fast && c.is_int && c.want_tb && c.store_dirs && reserve < resident &&
-                    k.n_small >= 4096 && wg_needed >= resident && (k.cells >= 2000000000ull || getenv("ALN_TB_OVERLAP_ANY"));
-        k.counter_bytes = 256;
-        if (k.overlap) {
-            k.grid = resident - reserve;
-            k.tb_waves = reserve ? reserve * 20u : (uint32_t)ctx->cus * 4u;
-            k.counter_bytes = 256 + 4ull * k.n_small;
-        }
-    }
-    // Cooperative passes: waves without a pair of their own take strips of other waves' pairs, so a batch with fewer pairs than
-    // resident waves still gets as many waves as it has strips
-    // (nothing to share in a batch whose pairs all have one strip -- read pairs, PWM windows, the p-value batch: the kernel then runs
-    // exactly as without the machinery)
-    uint64_t strips = 0, multi = 0;
-    for (size_t j = 0; j < k.n_small; ++j) {
-        const PairDesc &d = k.descs[k.order[j]];
-        // (a pair has something to share when its first pass has several strips, or when it may be re-filled -- core local with
-        // del != ext -- and is large enough for that re-fill to matter: a 330 x 300 window is through in 40 us either way)
-        if (d.status == ALN_OK) {
-            strips += aln_num_strips(d.M);
-            multi += (d.M > ALN_STRIP_ROWS || (c.semantics == ALN_CORE_LOCAL && c.p.del != c.p.ext && d.M > 64u && (uint64_t)d.N * d.M >= (1u << 18))) ? 1u : 0u;
-        }
-    }
-    // (one of many chunks of a pipelined call: its tail hides behind the chunks after it, and sharing re-fills only cost -- measured on
-    // C5 through aln_align_batch, eight chunks: 51.2 ms without, 52.0 with; three chunks of the 12 500-pair shard: 10.3 without, 9.3 with)
-    k.coop = coop_on && k.n_small != 0 && multi != 0 && !many_chunks;
-    // Many pairs per wave and a queue whose tail is short pairs: next to nothing would be shared -- the lean build (aln_plan_rules.h).
-    // (C5, 100 000 pairs: 33 per resident wave, the tail's longest re-fill 0.7 % of a wave's share)
-    // (k.grid as the kernel will run it: the overlapped traceback above has already cut it to the resident workgroups)
-    if (k.coop) {
-        const AlnLeanPlan lp = aln_coop_lean_plan(k.n_small, k.grid, (uint32_t)ctx->cus, cost_sum,
-                                                  [&](size_t j) { return pair_cost(k.descs[k.order[j]]); }, coop_lean_setting());
-        if (trace_plan())
+    const AlnPlanKnobs kn = plan_knobs();
+    AlnShareTrace tr;
+    aln_plan_chunk((uint32_t)ctx->cus, plan_call(c), kn, q_off, q_len, t_off, t_len, first, n, allow_overlap, many_chunks, k, &tr);
+    if (kn.trace_plan) {
+        const AlnLeanPlan &lp = tr.lp;
+        if (tr.could_share)
             fprintf(stderr, "aln plan: pairs %zu waves %llu resident %llu tail %llu share %.4g tail_cost %llu max_cost %llu build %s\n", k.n_small,
                     (unsigned long long)lp.waves, (unsigned long long)lp.resident, (unsigned long long)lp.tail, lp.share,
-                    (unsigned long long)pair_cost(k.descs[k.order[lp.tail]]), (unsigned long long)pair_cost(k.descs[k.order[0]]), lp.lean ? "lean" : "coop");
-        if (lp.lean) {
-            k.coop = false;
-            k.coop_lean = true;
-        }
-    }
-    if (k.coop) {
-        const uint32_t resident = (uint32_t)ctx->cus * 3u;
-        // (allow_overlap == false: a chunk of a pipelined call -- the chunks before and after it share the chip with this one, so its
-        // grid stays at one wave per pair, nobody lingers, and only re-fills are shared)
-        const bool alone = allow_overlap;
-        if (!k.overlap && alone) k.grid = std::max(k.grid, (uint32_t)std::min<uint64_t>(resident, (strips + 3) / 4));
-        // First passes give strips away only in batches of fewer than two pairs per resident wave -- there the pairs that are still
-        // running when the queue is dry are large, and idle waves are what fills the chip.  In a larger batch the last pairs are the
-        // shortest ones (measured on the 12 500-pair shard of C5: opening the first passes of its last 6000 pairs cost 0.15 ms of 6.8
-        // and shortened nothing); re-fills are always shared.  ALN_COOP_TAIL overrides (pairs from the end whose first pass is opened).
-        uint64_t tail = (alone && k.n_small < 2ull * resident * 4u) ? k.n_small : 0;
-        if (const char *e = getenv("ALN_COOP_TAIL")) tail = strtoull(e, nullptr, 10);
-        k.coop_tail = (uint32_t)(k.n_small > tail ? k.n_small - tail : 0);
-        // waves that find the queue dry stay around for strips only when they are what fills the chip: a batch with fewer pairs than
-        // resident waves (measured on the 12 500-pair shard: staying costs the waves that still work 0.2 ms of 7)
-        k.coop_linger = alone && k.n_small < (uint64_t)resident * 4u;
-        // Chains of strips (every first pass open, two or more strips per pair on average, no more pairs than resident waves) run
-        // with TWO waves per SIMD: a chain is as fast as its slowest strip, and the third wave of a SIMD is the one the arbiter
-        // leaves out (256 / 512 / 1024 pairs of 4200 x 4200, score only: 4.97 / 8.99 / 11.8 -> 4.47 / 7.82 / 10.6 ms; 3072 pairs
-        // 23.9 -> 22.8; 5000 pairs -- a wave per pair -- 32.8 -> 36.1: not there).  ALN_CHAIN_WGS=0: off.
-        if (alone && !k.overlap && tail >= k.n_small && k.n_small <= (uint64_t)resident * 4u && strips >= 2 * k.n_small && !(getenv("ALN_CHAIN_WGS") && atoi(getenv("ALN_CHAIN_WGS")) == 0))
-            k.grid = std::min(k.grid, (uint32_t)ctx->cus * 2u);
-    }
-    if (const char *e = getenv("ALN_FILL_WGS")) k.grid = std::max(1u, std::min(k.grid, (uint32_t)atoi(e)));   // experiments: fewer resident fill waves
-    if (k.coop) k.coop_bytes = 4ull * (ALN_COOP_CTL_WORDS + (((uint64_t)k.grid * 4 + 63) & ~63ull)) + (uint64_t)k.grid * 4 * sizeof(CoopRec);
-    const uint64_t sc_size = (c.is_int && !c.fast) ? 4 : 8;          // fast kernels: 8-byte granules {T value, tag}
-    const uint64_t brow_bytes = (((uint64_t)max_len + 66) * sc_size + 63) & ~63ull;
-    const uint64_t adv_bytes = ((uint64_t)max_len + 66 + 63) & ~63ull;
-    // fast path, core local with del != ext: strip 0's bottom row keeps a row of its own and strip 0 checkpoints its lane state
-    // (18 ints x 64 lanes per checkpoint): the localized repair of the row-1 hazard, do_pair_fast
-    // (fast kernels: a strip never writes the row it reads -- two rows; hazard pairs: strip 0's bottom row keeps one more to itself)
-    k.cascade_rows = (c.fast && c.semantics == ALN_CORE_LOCAL && c.p.del != c.p.ext) ? ALN_CASCADE_ROWS : (c.fast ? 2u : 1u);
-    const uint64_t ck_bytes = c.fast ? (uint64_t)ALN_CK_SLOTS * 18 * 64 * 4 : 0;
-    // bottom-row record: one byte per column (generic kernels) or one direction dword per block of the last strip (fast
-    // path: at most (max_len + 63) / 2 + 4 blocks)
-    const uint64_t zrow_bytes = std::max<uint64_t>(adv_bytes, ((c.fast ? 8ull : 4ull) * (((uint64_t)max_len + 63) / 2 + 8) + 63) & ~63ull);
-    k.zrow_bytes = (uint32_t)zrow_bytes;
-    // generic kernels: row 1 as the pass computed it (values + direction tags), for adopt_advice_checked
-    const uint64_t row1_bytes = c.fast ? 0 : brow_bytes + adv_bytes;
-    k.scratch_stride = (uint64_t)k.cascade_rows * brow_bytes + adv_bytes + zrow_bytes + ck_bytes + row1_bytes;
-    k.lds_bytes = c.pair_matrices ? aln_pairset_lds_bytes(rows, cols) : (uint32_t)(((uint64_t)rows * cols * (c.is_int ? 4 : 8) + 15) & ~15ull);
-    k.prof_stride = 0;
-    if (c.fast && !pwm) { k.prof_stride = cols * 64u * ALN_FULL_R; k.lds_bytes = aln_fast_lds_bytes(rows, cols, k.prof_stride, ALN_FEED_BYTES); }
-    // Two short pairs per wave (core global, read pairs: aln_fill_duo_kernel): every pair of the queue at most 256 rows and 1024
-    // columns, more pairs than resident waves (with fewer, a wave per pair is through sooner), nothing shared, no walk waves beside
-    // the fill, and the staged queries fit beside the profiles with three workgroups per CU.  ALN_NO_DUO=1: off.
-    k.duo_qo = 0;
-    if (c.fast && !pwm && c.semantics == ALN_CORE_GLOBAL && !k.coop && !k.coop_lean && !k.overlap && !getenv("ALN_NO_DUO") &&
-        k.n_small > (uint64_t)ctx->cus * 12u) {
-        uint32_t max_rows = 0, max_cols = 0;
-        for (size_t j = 0; j < k.n_small; ++j) { const PairDesc &d = k.descs[k.order[j]]; max_rows = std::max(max_rows, d.M); max_cols = std::max(max_cols, d.N); }
-        const uint32_t qo = (max_cols + 136u + 7u) & ~7u;
-        // (a wave's profile: R = ceil(rows / 32) bytes per lane and code, rounded up to 1 / 2 / 4 / 8 -- 20-letter alphabets fit with
-        // up to 128 rows)
-        const uint32_t rmax = (max_rows + 31u) / 32u, rp = rmax > 4u ? 8u : rmax > 2u ? 4u : std::max(rmax, 1u);
-        const uint32_t prof = cols * 64u * rp;
-        const uint32_t lds = (uint32_t)(((uint64_t)rows * cols * 4 + 15) & ~15ull) + 4u * (prof + 4u * qo);
-        if (max_rows <= 256u && max_cols <= 1024u && lds <= 52u * 1024u) {
-            k.duo_qo = qo;
-            k.prof_stride = prof;
-            k.lds_bytes = lds;
-            const uint32_t items = (uint32_t)((k.n_small + 1) / 2);
-            k.grid = std::max(1u, std::min((items + 3u) / 4u, (uint32_t)ctx->cus * 3u));
-        }
-    }
-    // ALN_TRACE_PLAN's second line, for every planned chunk: which route serves it (a score pass brings no flags word back)
-    if (trace_plan())
+                    (unsigned long long)aln_pair_cost(k.descs[k.order[lp.tail]]), (unsigned long long)aln_pair_cost(k.descs[k.order[0]]), lp.lean ? "lean" : "coop");
+        // for every planned chunk: which route serves it (a score pass brings no flags word back)
         fprintf(stderr, "aln route: pairs %zu small %zu single %zu wg %zu duo %d overlap %d share %s kernels %s\n", n, k.n_small,
                 k.single_pairs.size(), k.wg_pairs.size(), k.duo_qo ? 1 : 0, k.overlap ? 1 : 0, k.coop ? "coop" : k.coop_lean ? "lean" : "none",
                 c.fast ? "fast" : c.is_int ? "int" : "f64");
+    }
     return ALN_OK;
 }
 
@@ -848,15 +538,9 @@ static void chunk_resident(Chunk &k, const uint64_t *qo, const uint64_t *to, siz
     k.seq_direct = true; k.seq_lo = 0; k.seq_span = seq_span;
 }
 
-// upper bounds over the chunks of a pipelined call: a slot is sized for the largest chunk the first time it is touched, so no
-// buffer grows (hipFree + hipMalloc stall every stream) in the middle of the pipeline
-struct Need {
-    uint64_t seq_span = 0, n = 0, dir_bytes = 0, tb_bytes = 0, tag_bytes = 0, scratch = 0, coop = 0;
-};
-
 // device buffers of a slot for this chunk (grow-only; nothing happens once the pool is warm)
 // small_meta (window scans): the descriptors and the queue are built on the device, so the pinned staging holds the matrix only
-static int slot_ensure(Slot &s, const Call &c, const Chunk &k, const Need *need = nullptr, bool small_meta = false)
+static int slot_ensure(Slot &s, const Call &c, const Chunk &k, const AlnPlanBounds *need = nullptr, bool small_meta = false)
 {
     int st;
     const bool sl = s.pooled;
@@ -1248,56 +932,7 @@ static int slot_download(Slot &s, const Call &c, const Chunk &k, hipStream_t st,
     return ALN_OK;
 }
 
-// ---------------------------------------------------------------- chunking of a batch call
-// Chunks are ranges of the caller's pair order, between 5e9 and 1.6e10 cells each (1.4-4.6 GB of packed directions, 2-6 ms
-// of fill): small enough that the first upload and the last traceback + download -- the only stages nothing overlaps -- are a
-// few per cent of a large call, large enough that a chunk fills the chip and that its largest pairs (a 2000 x 2000 pair takes
-// ~3 ms on its wave whatever else runs) do not outlast it by much.  ALN_CHUNK_CELLS overrides.
-// Measured (profiles/r02_e2e_chunking.txt): C5 100 000 pairs (47.3 ms resident): 30 chunks 60 ms, 16 chunks 54 ms, 8 chunks 52 ms;
-// 25 000 pairs: 6 chunks 18.2 ms, 2-4 chunks 16.6-17.1, one chunk 21.1; 12 500 pairs: 7 chunks 15.6 ms, 3 chunks 9.7, one 10.7.
-static void make_chunks(const Call &c, const uint64_t *q_len, const uint64_t *t_len, size_t n, size_t ndev,
-                        std::vector<std::pair<size_t, size_t>> &out, double waves = 3072.0)
-{
-    out.clear();
-    double total = 0;
-    for (size_t i = 0; i < n; ++i) total += (double)(c.pwm ? c.cols : q_len[i]) * (double)t_len[i];
-    // (several devices: the same bounds per device -- each takes about three chunks or more from the common queue)
-    double target = std::min(1.6e10, std::max(5.0e9, total / (4.0 * (double)ndev)));
-    // The generic (f64 / off-fast-path) kernels take ~3 x as long per cell and have no cooperative passes: a chunk ends with its
-    // largest pairs alone on their waves for 10-30 ms, so what counts is pairs per wave, not overlap of the copies (r03, 20 000
-    // real-valued C5 pairs: four chunks 44.6 ms, one 40.7, resident 29.9).
-    if (!c.fast) target *= 3.0;
-    // Large pairs: what a chunk needs is pairs, not cells -- two or more per resident wave, or the whole batch, so that either every
-    // wave has pairs of its own or the chunk is alone on the chip and its waves share the strips of a pair (cooperative passes are
-    // for a kernel that has the chip to itself).  r03, 1024 pairs of 4200 x 4200, score only: four chunks of 284 pairs 31 ms (one
-    // wave per pair, 9 strips one after the other), one chunk 11.2 ms; 2000 pairs 31 -> 17.3 ms; 512 pairs 15.7 -> 8.9 ms.  Large
-    // pairs carry few bytes per cell, so the copies that chunking would overlap are small; the cap keeps a chunk's packed directions
-    // at 16 GB (four slots).
-    // (pairs of C5's size -- 1.2e6 cells on average -- keep the bounds above: they were measured on them)
-    if (n && total / (double)n >= 3.0e6) target = std::max(target, std::min(6.4e10, 2.0 * waves * (total / (double)n)));
-    bool forced = false;             // (a target set by hand also lifts the one-chunk floor below: tests cut small batches into chunks)
-    if (const char *e = getenv("ALN_CHUNK_CELLS")) { target = std::max(1.0, atof(e)); forced = true; }
-    // (one chunk up to 2e10 cells: a one-chunk call uploads its residues while it plans and its kernel has the chip to itself -- 12 500
-    // C5 pairs, 1.5e10 cells: 8.7 ms against 9.1-9.4 in three chunks; 25 000 pairs, 3e10: 17 against 15.5 in four)
-    // -- unless the strings it brings back are many: nothing overlaps that copy in a one-chunk call (100 000 PWM windows with both
-    // strings, 316 MB: 15.3 ms in one chunk, 13.2 in two)
-    double out_bytes = 0;
-    if (c.want_tb) for (size_t i = 0; i < n; ++i) out_bytes += (c.pwm ? 5.0 : 2.0) * ((double)(c.pwm ? c.cols : q_len[i]) + (double)t_len[i] + 2.0);
-    if (!forced && total <= std::max(1.5 * target, 2.0e10) && ndev == 1 && out_bytes <= 64.0e6) { out.emplace_back(0, n); return; }
-    if (total <= 1.5 * target) { out.emplace_back(0, n); return; }
-    size_t first = 0;
-    double acc = 0;
-    for (size_t i = 0; i < n; ++i) {
-        acc += (double)(c.pwm ? c.cols : q_len[i]) * (double)t_len[i];
-        if (acc >= target || i + 1 - first >= (1u << 22)) { out.emplace_back(first, i + 1 - first); first = i + 1; acc = 0; }
-    }
-    if (first < n) {
-        // a short tail joins the chunk before it
-        if (!out.empty() && acc < 0.25 * target) out.back().second += n - first;
-        else out.emplace_back(first, n - first);
-    }
-}
-
+// ---------------------------------------------------------------- chunking of a batch call (aln_make_chunks, aln_plan_rules.h)
 // The chunking aln_align_batch would use for these lengths on a context of n_devices GPUs: pure host arithmetic (no device is
 // touched), exported so that the sharding can be inspected and tested anywhere.  Returns the number of chunks; writes up to
 // `cap` (first pair, pair count) entries.
@@ -1313,7 +948,7 @@ extern "C" size_t aln_plan_chunks(const aln_params *params, const uint64_t *q_le
         c.fast = true;
     }
     std::vector<std::pair<size_t, size_t>> ranges;
-    if (n_pairs) make_chunks(c, q_len, t_len, n_pairs, (size_t)n_devices, ranges);
+    if (n_pairs) aln_make_chunks(plan_call(c), plan_knobs(), q_len, t_len, n_pairs, (size_t)n_devices, ranges);
     for (size_t i = 0; i < ranges.size() && i < cap; ++i) {
         if (first) first[i] = ranges[i].first;
         if (count) count[i] = ranges[i].second;
@@ -1330,7 +965,7 @@ struct BatchJob {
     uint8_t *tb_buf;
     const uint64_t *tb_off;
     const std::vector<std::pair<size_t, size_t>> *ranges;
-    Need need;
+    AlnPlanBounds need;            // upper bounds over the chunks: every slot is sized once (aln_plan_bounds)
     std::atomic<size_t> next{0};       // the chunk queue: devices take the next range when they have a free slot
     std::atomic<int> failed{0};
     std::mutex mu;
@@ -1404,20 +1039,17 @@ static void device_pipeline(DevCtx *dev, BatchJob &job)
         // one-chunk call); every later chunk is planned and uploaded while the chunks before it fill
         std::thread copier;
         hipError_t copy_err = hipSuccess;
-        uint64_t lo = ~0ull, hi = 0, sum = 0;
+        AlnSeqSpan span;
         bool early = false;
         if (li == 0 && !getenv("ALN_NO_EARLY_UPLOAD")) {
             const size_t f0 = (*job.ranges)[ci].first, f1 = f0 + (*job.ranges)[ci].second;
-            for (size_t i = f0; i < f1; ++i) {
-                if (!c.pwm && job.q_len[i]) { lo = std::min(lo, job.q_off[i]); hi = std::max(hi, job.q_off[i] + job.q_len[i]); sum += job.q_len[i]; }
-                if (job.t_len[i]) { lo = std::min(lo, job.t_off[i]); hi = std::max(hi, job.t_off[i] + job.t_len[i]); sum += job.t_len[i]; }
-            }
-            early = lo != ~0ull && (hi - lo) <= 2 * sum + 65536 && hi - lo >= (4u << 20) && hi - lo <= job.need.seq_span;
+            for (size_t i = f0; i < f1; ++i) span.add_pair(c.pwm, job.q_off[i], job.q_len[i], job.t_off[i], job.t_len[i]);
+            early = span.direct() && span.extent() >= (4u << 20) && span.extent() <= job.need.seq_span;
             if (early) {
                 if ((st = slot_init(s)) != ALN_OK || (st = dev_ensure(s.seqs, job.need.seq_span + 64, s.pooled)) != ALN_OK) break;
                 copier = std::thread([&] {
                     copy_err = hipSetDevice(dev->device);
-                    if (copy_err == hipSuccess) copy_err = hipMemcpyAsync(s.seqs.p, job.seqs + lo, hi - lo, hipMemcpyHostToDevice, s.stream);
+                    if (copy_err == hipSuccess) copy_err = hipMemcpyAsync(s.seqs.p, job.seqs + span.lo, span.extent(), hipMemcpyHostToDevice, s.stream);
                 });
             }
         }
@@ -1428,7 +1060,7 @@ static void device_pipeline(DevCtx *dev, BatchJob &job)
         if ((st = slot_ensure(s, c, k, &job.need)) != ALN_OK) break;
         if (copier.joinable()) copier.join();
         if (copy_err != hipSuccess) { st = fail(copy_err, "hipMemcpyAsync(residues)"); break; }
-        const bool seqs_there = early && k.seq_direct && k.seq_lo == lo && k.seq_span == hi - lo;
+        const bool seqs_there = early && k.seq_direct && k.seq_lo == span.lo && k.seq_span == span.extent();
         if ((st = slot_upload(s, c, k, job.seqs, job.q_off, job.q_len, job.t_off, job.t_len, s.stream, false, seqs_there)) != ALN_OK) break;
         // At most `depth` fills share the chip: chunk i's fill waits for the fill of chunk i - depth.  With every slot's fill
         // started at once the chunks run in lockstep -- they share the chip equally, reach their tails together (a chunk's
@@ -1464,7 +1096,7 @@ extern "C" int aln_align_batch(aln_ctx *ctx, const aln_params *params, const uin
     if (st != ALN_OK) return st;
     if (n_pairs == 0) return ALN_OK;
     std::vector<std::pair<size_t, size_t>> ranges;
-    make_chunks(c, q_len, t_len, n_pairs, ctx->devs.size(), ranges, 12.0 * (double)ctx->devs[0]->cus);
+    aln_make_chunks(plan_call(c), plan_knobs(), q_len, t_len, n_pairs, ctx->devs.size(), ranges, 12.0 * (double)ctx->devs[0]->cus);
     const size_t nc = ranges.size();
 
     if (nc == 1) {                                   // one chunk: everything on the caller's thread, on the next device in turn
@@ -1482,15 +1114,13 @@ extern "C" int aln_align_batch(aln_ctx *ctx, const aln_params *params, const uin
         auto now = [] { return std::chrono::steady_clock::now(); };
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         const auto t0 = now();
-        // The residues do not wait for the plan: where they lie is a min / max over the offsets (the same arithmetic as chunk_plan's),
+        // The residues do not wait for the plan: where they lie is a min / max over the offsets (AlnSeqSpan, as the plan's),
         // and copying pageable memory keeps the calling thread busy for its whole length (0.55 ms for the 27 MB of 12 500 C5 pairs,
         // beside 0.7 ms of planning) -- a helper thread copies while this one plans.
-        uint64_t lo = ~0ull, hi = 0, sum = 0;
-        for (size_t i = 0; i < n_pairs; ++i) {
-            if (!c.pwm && q_len[i]) { lo = std::min(lo, q_off[i]); hi = std::max(hi, q_off[i] + q_len[i]); sum += q_len[i]; }
-            if (t_len[i]) { lo = std::min(lo, t_off[i]); hi = std::max(hi, t_off[i] + t_len[i]); sum += t_len[i]; }
-        }
-        const bool early = lo != ~0ull && (hi - lo) <= 2 * sum + 65536 && hi - lo >= (4u << 20) && !getenv("ALN_NO_EARLY_UPLOAD");
+        AlnSeqSpan span;
+        for (size_t i = 0; i < n_pairs; ++i) span.add_pair(c.pwm, q_off[i], q_len[i], t_off[i], t_len[i]);
+        const uint64_t lo = span.lo, hi = span.hi;
+        const bool early = span.direct() && span.extent() >= (4u << 20) && !getenv("ALN_NO_EARLY_UPLOAD");
         std::thread copier;
         hipError_t copy_err = hipSuccess;
         if (early) {
@@ -1524,34 +1154,10 @@ extern "C" int aln_align_batch(aln_ctx *ctx, const aln_params *params, const uin
     job.c = &c; job.seqs = seqs; job.q_off = q_off; job.q_len = q_len; job.t_off = t_off; job.t_len = t_len;
     job.results = results; job.tb_buf = tb_buf; job.tb_off = tb_off; job.ranges = &ranges;
     {   // upper bounds over the chunks: every slot is sized once, before the pipeline runs
-        const uint64_t sc = (c.is_int && !c.fast) ? 4 : 8;       // fast kernels: 8-byte granules (chunk_plan)
         int max_cus = 0;
         for (const DevCtx *d : ctx->devs) max_cus = std::max(max_cus, d->cus);
-        Need &need = job.need;
-        for (const auto &r : ranges) {
-            uint64_t lo = ~0ull, hi = 0, sum = 0, dirs = 0, tb = 0, tags = 0, mlen = 1;
-            for (size_t i = r.first; i < r.first + r.second; ++i) {
-                const uint64_t N = c.pwm ? c.cols : q_len[i], M = t_len[i], cap = N + M + 2;
-                if (!c.pwm && N) { lo = std::min(lo, q_off[i]); hi = std::max(hi, q_off[i] + N); sum += N; }
-                if (M) { lo = std::min(lo, t_off[i]); hi = std::max(hi, t_off[i] + M); sum += M; }
-                if (c.store_dirs) { tb += c.pwm ? ((5 * cap + 3) & ~3ull) : 2 * cap; tags += (cap + 3) & ~3ull; }
-                if (N && M && c.store_dirs) dirs += aln_dir_bytes((uint32_t)N, (uint32_t)M);
-                if (N && M) mlen = std::max(mlen, std::max(N, M));
-            }
-            if (c.fast) need.coop = std::max<uint64_t>(need.coop, 4ull * (ALN_COOP_CTL_WORDS + (uint64_t)max_cus * 16 + 64) + (uint64_t)max_cus * 16 * sizeof(CoopRec));
-            const uint64_t span = hi > lo ? ((hi - lo) <= 2 * sum + 65536 ? hi - lo : sum) : 0;
-            need.seq_span = std::max(need.seq_span, span);
-            need.n = std::max<uint64_t>(need.n, r.second);
-            need.dir_bytes = std::max(need.dir_bytes, dirs);
-            need.tb_bytes = std::max(need.tb_bytes, tb);
-            need.tag_bytes = std::max(need.tag_bytes, tags);
-            // per wave: boundary row, advice, bottom-row record, checkpoints (chunk_plan)
-            const uint64_t nrows = (c.fast && c.semantics == ALN_CORE_LOCAL && c.p.del != c.p.ext) ? ALN_CASCADE_ROWS : (c.fast ? 2u : 1u);
-            const uint64_t stride = nrows * (((mlen + 66) * sc + 63) & ~63ull) + ((mlen + 66 + 63) & ~63ull) +
-                                    std::max<uint64_t>((mlen + 66 + 63) & ~63ull, ((c.fast ? 8 : 4) * ((mlen + 63) / 2 + 8) + 63) & ~63ull) +
-                                    (c.fast ? (uint64_t)ALN_CK_SLOTS * 18 * 64 * 4 : (((mlen + 66) * sc + 63) & ~63ull) + ((mlen + 66 + 63) & ~63ull));
-            need.scratch = std::max(need.scratch, (uint64_t)max_cus * 4 * 4 * stride);
-        }
+        const AlnPlanCall pc = plan_call(c);
+        for (const auto &r : ranges) job.need.raise(aln_plan_bounds((uint32_t)max_cus, pc, q_off, q_len, t_off, t_len, r.first, r.second));
     }
     // ---- the devices of the context take the chunks from one queue; device 0's pipeline runs on the caller's thread
     const size_t nd = std::min(ctx->devs.size(), nc);
@@ -1689,19 +1295,8 @@ extern "C" void *aln_batch_results_device(aln_batch *b) { return b ? b->slot->re
 extern "C" uint64_t aln_batch_direction_bytes(const aln_batch *b)
 {
     if (!b) return 0;
-    // bytes the fill kernel actually stores: per strip, ceil(steps / SPB) blocks of 256 B
     uint64_t total = 0;
-    for (const PairDesc &d : b->k.descs) {
-        if (d.status != ALN_OK) continue;
-        const uint32_t ns = aln_num_strips(d.M);
-        for (uint32_t s = 0; s < ns; ++s) {
-            const bool last = s + 1 == ns;
-            const uint32_t rem = d.M - s * ALN_STRIP_ROWS;
-            const int R = last ? aln_pick_r(rem) : ALN_FULL_R;
-            const uint32_t rows = std::min<uint32_t>(rem, 64u * R), L = (rows + R - 1) / R, spb = aln_spb((uint32_t)R);
-            total += (uint64_t)aln_strip_blocks(d.N + L - 1, spb) * 256u;
-        }
-    }
+    for (const PairDesc &d : b->k.descs) total += aln_pair_stored_dir_bytes(d);
     return total;
 }
 
@@ -1929,8 +1524,8 @@ static int scan_plan(aln_scan *sc, const Call &c, const aln_scan_geometry *g, ui
         }
         const uint64_t cap = (uint64_t)c.cols + wmax + 2;
         pl.dir_stride = (dmax + 255) & ~255ull;
-        pl.tb_stride = (5 * cap + 3) & ~3ull;
-        pl.tag_stride = (cap + 3) & ~3ull;
+        pl.tb_stride = aln_tb_bytes(true, cap);
+        pl.tag_stride = aln_tag_bytes(cap);
         pl.k.dir_bytes = hits * pl.dir_stride; pl.k.tb_bytes = hits * pl.tb_stride; pl.k.tag_bytes = hits * pl.tag_stride;
     }
     // The device writes the descriptors, and the queue as the window order.  Windows routed elsewhere (<= 4 windows, real-valued
@@ -2321,13 +1916,10 @@ struct ShuffleStage {
 static void shuffle_stage(const uint8_t *seqs, const uint64_t *q_off, const uint64_t *q_len, const uint64_t *t_off, const uint64_t *t_len,
                           size_t n, uint32_t per_pair, ShuffleStage &g)
 {
-    uint64_t lo = ~0ull, hi = 0, sum = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (q_len && q_len[i]) { lo = std::min(lo, q_off[i]); hi = std::max(hi, q_off[i] + q_len[i]); sum += q_len[i]; }
-        if (t_len[i]) { lo = std::min(lo, t_off[i]); hi = std::max(hi, t_off[i] + t_len[i]); sum += t_len[i]; }
-    }
-    if (lo == ~0ull) { lo = 0; hi = 0; }
-    g.direct = hi - lo <= 2 * sum + 65536;
+    AlnSeqSpan span;
+    for (size_t i = 0; i < n; ++i) { if (q_len) span.add(q_off[i], q_len[i]); span.add(t_off[i], t_len[i]); }
+    const uint64_t lo = span.empty() ? 0 : span.lo, sum = span.sum;
+    g.direct = span.direct();
     g.lo = lo;
     g.pairs.resize(n);
     if (!g.direct && seqs) g.packed.resize(sum);       // (no host residues: the caller copies the ranges on the device)
@@ -2350,11 +1942,11 @@ static void shuffle_stage(const uint8_t *seqs, const uint64_t *q_off, const uint
         P.out_off = out;
         out += (uint64_t)per_pair * P.t_len;
     }
-    g.bytes = g.direct ? hi - lo : pos;
+    g.bytes = g.direct ? span.extent() : pos;
 }
 
 // chunks of whole pairs: at most ALN_SHUFFLE_CHUNK_COPIES copies and ALN_SHUFFLE_CHUNK_BYTES shuffled residues (a single pair may
-// exceed the latter), and -- cells given -- cut once they reach `target` cells, as make_chunks cuts
+// exceed the latter), and -- cells given -- cut once they reach `target` cells, as aln_make_chunks cuts
 static void shuffle_chunks(const ShuffleStage &g, uint32_t per_pair, const std::vector<double> *cells, double target,
                            std::vector<std::pair<size_t, size_t>> &out)
 {
@@ -2446,10 +2038,7 @@ static int shuffle_job_plan(const DevCtx *dev, const aln_params *params, const a
 
     ShuffleStage &g = job.g;
     shuffle_stage(seqs, q_off, q_len, t_off, t_len, n_pairs, per, g);
-    // chunks: the cell bounds of make_chunks (1.6e10, three times that for the generic kernels; ALN_CHUNK_CELLS overrides)
-    double target = c.fast ? 1.6e10 : 4.8e10;
-    if (const char *e = getenv("ALN_CHUNK_CELLS")) target = std::max(1.0, atof(e));
-    shuffle_chunks(g, per, &cells, target, job.ranges);
+    shuffle_chunks(g, per, &cells, aln_chunk_cells_override(plan_knobs(), aln_shuffle_chunk_target(c.fast)), job.ranges);
     job.region = align256(g.bytes);
     // the plans of every chunk first: the copies' lengths and offsets in the residue buffer, routed and laid out by chunk_plan
     job.plans.resize(job.ranges.size());
@@ -2672,7 +2261,7 @@ static int held_refill(HeldStore &h, DevCtx *ctx, Slot &s, const Call &c, const 
         tb_total += 2ull * (ql[k] + tl[k] + 2);      // the chunks' own layout (chunk_plan), chunk after chunk
     }
     std::vector<std::pair<size_t, size_t>> ranges;
-    make_chunks(c, ql.data(), tl.data(), pairs, 1, ranges);
+    aln_make_chunks(plan_call(c), plan_knobs(), ql.data(), tl.data(), pairs, 1, ranges);
     Chunk k;
     bool timed = false;
     auto collect = [&]() {
@@ -3444,7 +3033,7 @@ struct PairSource {
         return st;
     }
     uint64_t positions() const { return list ? ss->cand_pair.size() : aln_seqset_block_pairs(ss->n, *b); }
-    // cells of all positions together (as a double, like make_chunks): a block's out of the length sums
+    // cells of all positions together (as a double, like aln_make_chunks): a block's out of the length sums
     double cells() const
     {
         if (list) {
@@ -3483,16 +3072,11 @@ struct PairSource {
     }
 };
 
-// the cells a chunk of a pass aims at (total cells over `pairs` pairs); *forced: ALN_CHUNK_CELLS said so.  Where the chunks are cut
-// is aln_seqset_cut's rule (aln_seqset_rules.h)
+// the cells a chunk of a pass aims at (total cells over `pairs` pairs, one device); *forced: ALN_CHUNK_CELLS said so.  Where the
+// chunks are cut is aln_seqset_cut's rule (aln_seqset_rules.h)
 static double seqset_chunk_target(const Call &c, double total, uint64_t pairs, bool *forced)
 {
-    double target = std::min(1.6e10, std::max(5.0e9, total / 4.0));
-    if (!c.fast) target *= 3.0;
-    if (total / (double)pairs >= 3.0e6) target = std::max(target, std::min(6.4e10, 2.0 * 3072.0 * (total / (double)pairs)));
-    *forced = false;
-    if (const char *e = getenv("ALN_CHUNK_CELLS")) { target = std::max(1.0, atof(e)); *forced = true; }
-    return target;
+    return aln_chunk_cells_override(plan_knobs(), aln_chunk_target(c.fast, total, pairs, 1, 3072.0), forced);
 }
 
 // what a chunk of n pairs needs of the set's buffers (the stream is idle: they may grow)
@@ -3512,7 +3096,7 @@ static int seqset_chunk_ensure(aln_seqset *ss, const Call &c, const Chunk &k, ui
     return ALN_OK;
 }
 
-// One pass over a source: its positions cut into chunks (aln_seqset_cut, by the cell bounds of make_chunks and the pair limit of a
+// One pass over a source: its positions cut into chunks (aln_seqset_cut, by the cell bounds of aln_make_chunks and the pair limit of a
 // chunk), every chunk expanded, filled and gathered on the set's stream.  f / status (optional): the caller's arrays, by position.
 // select: the POSITIONS of the chunk's pairs with status ALN_OK and f >= f_min are appended to ss->hit_pair (of a list, the caller
 // turns them into pair numbers), their f to hit_score.  *first_bad: the status of the first failed pair, ALN_OK if none failed.

@@ -3223,13 +3223,6 @@ extern "C" void aln_launch_fill(const FillArgs *a, int is_int, int fast, uint32_
 }
 #endif
 #if ALN_TU & ALN_PART_SINGLE
-// LDS bytes of the fill kernel for W waves per workgroup (rings + S + query offsets + per-wave profile and boundary ring)
-extern "C" uint32_t aln_single_lds_bytes(uint32_t rows, uint32_t cols, uint32_t R, uint32_t N, uint32_t W)
-{
-    const uint32_t s_bytes = (rows * cols * 4u + 15u) & ~15u, prof_bytes = (cols * 64u * R + 15u) & ~15u;
-    const uint32_t qo_bytes = ((N + 192u) * 2u + 15u) & ~15u;
-    return (W - 1u) * 4u * ALN_RING + s_bytes + qo_bytes + W * (prof_bytes + 512u) + 768u;      // + scratch words (aligned up)
-}
 // four strips per workgroup where the hand-written steady state exists and the LDS fits
 extern "C" uint32_t aln_single_waves(int semantics, uint32_t R, uint32_t rows, uint32_t cols, uint32_t N, uint32_t ns)
 {

@@ -5,9 +5,10 @@
   block indels of 5 .. 40; a second 600 ends in code 24, which no 24 x 24 matrix scores).  A block of a sequence set is two RANGES
   of sequence numbers, so the resident set lists the 92 shorts once and then, block by block, the members of every other block's
   ranges again (LAYOUT: 118 entries over the 102 sequences).
-* A table of blocks on that set (blocks()), one per route of chunk_plan (aln_host.hip), with the scheme that selects it.
+* A table of blocks on that set (blocks()), one per route of the batch plan (aln_plan_rules.h), with the scheme that selects it.
 * plan(): the routing of chunk_plan restated as arithmetic on lengths and counts, with the knobs the tests set -- what an
-  `aln route:` line (ALN_TRACE_PLAN) must say for a list of pairs.  Line numbers in the comments are aln_host.hip's.
+  `aln route:` line (ALN_TRACE_PLAN) must say for a list of pairs.  The comments name the steps of aln_plan_chunk
+  (aligner_amd/csrc/aln_plan_rules.h); tests/test_plan_rules_cpu.py checks plan() against those steps on every block.
 * The child processes of tests/test_set_routes_gpu.py: python route_cases.py MODE expected.npz report.json [block].
 """
 import hashlib
@@ -189,11 +190,11 @@ def plan(N, M, kind, local, dele, ext, traceback, env=(), alone=True):
     N, M = np.asarray(N, dtype=np.int64), np.asarray(M, dtype=np.int64)
     n, pc, fast = len(N), N * M, kind == "fast"
     assert n and (N > 0).all() and (M > 0).all() and max(N.max(), M.max()) <= 8192
-    # a large pair, or a sizeable one in a chunk of at most 16 (aln_host.hip:569, :598)
+    # a large pair, or a sizeable one in a chunk of at most 16 (aln_big_pair)
     big = (N >= 64) & (M >= 128) & ((pc >= 1 << 24) | ((n <= 16) & (pc >= 1 << 18)))
-    coop_on = fast and "ALN_NO_COOP" not in env                                            # :559
+    coop_on = fast and "ALN_NO_COOP" not in env                                            # aln_coop_on
     big_to_single = True
-    if coop_on and big.any():                                                              # the time rule, :561-580
+    if coop_on and big.any():                                                              # the time rule, aln_big_to_single
         lat = (N + 63.0 + 170.0 * (strips(M) - 1.0)) * 0.55e-6
         waves = CUS * 12.0
 
@@ -206,23 +207,23 @@ def plan(N, M, kind, local, dele, ext, traceback, env=(), alone=True):
         big_to_single = t_single + rest <= t_batch(float(pc.sum()), float(strips(M).sum()), float(lat.max()))
         if "ALN_BIG_TO_SINGLE" in env:
             big_to_single = int(env["ALN_BIG_TO_SINGLE"]) != 0
-    single = big & fast & (big_to_single | (strips(M) > 64))                               # :598 (N <= 8192: the LDS bound of :611 is far)
-    # generic kernels, a chunk of at most four pairs: one workgroup per pair (:627; aln_wg_lds_bytes is far below 64 KiB here)
+    single = big & fast & (big_to_single | (strips(M) > 64))                               # aln_plan_routes (N <= 8192: the LDS bound of aln_single_route_r is far)
+    # generic kernels, a chunk of at most four pairs: one workgroup per pair (aln_wg_route_r; aln_wg_lds_bytes is far below 64 KiB here)
     wg = ~single & (not fast) & ("ALN_NO_WGPIPE" not in env) & (n <= 4) & (pc >= 1 << 14) & (N >= 16) & (N <= 8192) & (M >= 65) & (M <= 2048)
     small = ~single & ~wg
     n_small = int(small.sum())
     r = dict(pairs=n, small=n_small, single=int(single.sum()), wg=int(wg.sum()), kernels=kind, single_mask=single, wg_mask=wg)
-    # walk waves beside the fill (:726): a held pass of at least 4096 pairs that fill the chip, integer fast kernels
+    # walk waves beside the fill (aln_plan_grid): a held pass of at least 4096 pairs that fill the chip, integer fast kernels
     wg_needed = (n_small + 3) // 4
     r["overlap"] = int(alone and env.get("ALN_TB_OVERLAP") != "0" and fast and traceback and n_small >= 4096 and wg_needed >= 3 * CUS and
                        (int(pc.sum()) >= 2000000000 or "ALN_TB_OVERLAP_ANY" in env))
-    # something to share (:746): several strips, or a re-fill of a core-local pair with del != ext that is large enough to matter
+    # something to share (aln_plan_share): several strips, or a re-fill of a core-local pair with del != ext that is large enough to matter
     multi = (M[small] > STRIP_ROWS) | (bool(local and dele != ext) & (M[small] > 64) & (pc[small] >= 1 << 18))
-    coop = bool(coop_on and n_small and multi.any())                                       # :751 (one chunk, or at most four)
+    coop = bool(coop_on and n_small and multi.any())                                       # aln_plan_share (one chunk, or at most four)
     # the lean build needs 16 pairs per kernel wave (aln_plan_rules.h); the grid is at least one workgroup of four
     assert not (coop and n_small >= 64), "a block that could run the lean build: restate aln_coop_lean_plan"
     r["share"] = "coop" if coop else "none"
-    # two pairs per wave (:814): core global, nothing shared, no walk waves, more pairs than 12 per CU, short pairs, LDS (24 x 24)
+    # two pairs per wave (aln_plan_duo): core global, nothing shared, no walk waves, more pairs than 12 per CU, short pairs, LDS (24 x 24)
     duo = fast and not local and not coop and not r["overlap"] and "ALN_NO_DUO" not in env and n_small > CUS * 12
     if duo:
         rows, cols = int(M[small].max()), int(N[small].max())

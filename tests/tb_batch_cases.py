@@ -444,7 +444,7 @@ def ubatch_mode(case):
 
 def duo_halves(pairs):
     """Which half of a wave (0: lanes 0 .. 31, 1: lanes 32 .. 63) fills each pair of a two-pairs-per-wave batch: the work queue is the
-    pairs by falling cost, equal costs by rising position (chunk_plan's pair_cost and sort keys, aln_host.hip), and item i of the queue
+    pairs by falling cost, equal costs by rising position (aln_pair_cost and aln_plan_order's sort keys, aln_plan_rules.h), and item i of the queue
     takes its positions 2 i and 2 i + 1 (aln_fill_duo_kernel).  Every pair here has one strip."""
     def cost(q, t):
         N, M = len(q), len(t)

@@ -1,7 +1,7 @@
 """Which build of the fast batch kernel a chunk that could share strips runs (aln_coop_lean_plan, aligner_amd/csrc/aln_plan_rules.h;
 no GPU): the lean build (no cooperative machinery) for C5's 100 000 pairs, the cooperative one where sharing pays -- the 12 500-pair
 shard, batches of large pairs, a batch of short pairs with a few long ones -- and the ALN_COOP_LEAN setting overriding either way.
-The queue costs are modelled here with aln_host.hip's pair_cost; tests/test_coop_lean_gpu.py checks the figures the library itself
+The queue costs are modelled here with aln_plan_rules.h's aln_pair_cost (tests/test_plan_rules_cpu.py checks the restatement); tests/test_coop_lean_gpu.py checks the figures the library itself
 plans with (ALN_TRACE_PLAN)."""
 import os
 import shutil
@@ -63,7 +63,7 @@ def rule(tmp_path_factory):
 
 
 def pair_cost(N, M):
-    """aln_host.hip's pair_cost: steps x (24 + 21 R) over the pair's strips (512 rows; the last picks R by its rows)."""
+    """aln_plan_rules.h's aln_pair_cost: steps x (24 + 21 R) over the pair's strips (512 rows; the last picks R by its rows)."""
     c = 0
     ns = (M + 511) // 512
     for s in range(ns):
