@@ -74,6 +74,9 @@ MSA_EXPORTS = ["aln_seqset_held_msa_fill", "aln_seqset_held_msa_plan"]
 CIGAR_EXPORTS = ["aln_seqset_held_cigar_fill", "aln_seqset_held_cigar_plan"]
 CIGAR_EXTENDED = 1              # ALN_CIGAR_EXTENDED
 CIGAR_CLIPS = 2                 # ALN_CIGAR_CLIPS
+# every symbol the companion header include/aligner_hip_strand.h declares (the same library, as above)
+STRAND_EXPORTS = ["aln_seqset_create_stranded", "aln_seqset_held_strand_cigar_fill", "aln_seqset_held_strand_cigar_plan",
+                  "aln_seqset_strand_records", "aln_seqset_strand_residues"]
 PAIRSET_MAX_ENTRIES = 1024      # ALN_PAIRSET_MAX_ENTRIES
 TRANSFORM_NO_ROOT = 1           # ALN_TRANSFORM_NO_ROOT
 # aln_pairset_loop_step's causes (aligner_amd/csrc/aln_loop_rules.h)
@@ -198,6 +201,15 @@ class CigarSummary(C.Structure):
 
 
 assert C.sizeof(CigarRecord) == 32 and C.sizeof(CigarSummary) == 48
+
+
+class StrandRecord(C.Structure):
+    """aln_strand_record: which original records and which strand a listed hit of a stranded set is on (aligner_amd/csrc/aln_strand_rules.h)."""
+    _fields_ = [("q_rec", C.c_uint32), ("t_rec", C.c_uint32), ("strand", C.c_uint8), ("q_mirror", C.c_uint8), ("t_mirror", C.c_uint8),
+                ("reserved", C.c_uint8), ("reserved2", C.c_uint32)]
+
+
+assert C.sizeof(StrandRecord) == 16
 
 
 class PrefilterSpec(C.Structure):
@@ -401,6 +413,16 @@ def load():
     lib.aln_seqset_held_cigar_plan.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, C.POINTER(CigarSummary)]
     lib.aln_seqset_held_cigar_fill.restype = i
     lib.aln_seqset_held_cigar_fill.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+    lib.aln_seqset_create_stranded.restype = vp
+    lib.aln_seqset_create_stranded.argtypes = [vp, vp, u64p, u64p, C.c_size_t, vp, C.POINTER(C.c_int)]
+    lib.aln_seqset_strand_records.restype = C.c_uint64
+    lib.aln_seqset_strand_records.argtypes = [vp]
+    lib.aln_seqset_strand_residues.restype = i
+    lib.aln_seqset_strand_residues.argtypes = [vp, C.c_uint64, C.c_uint64, u64p, vp]
+    lib.aln_seqset_held_strand_cigar_plan.restype = i
+    lib.aln_seqset_held_strand_cigar_plan.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.POINTER(CigarSummary)]
+    lib.aln_seqset_held_strand_cigar_fill.restype = i
+    lib.aln_seqset_held_strand_cigar_fill.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
     _lib = lib
     return lib
 

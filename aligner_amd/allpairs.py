@@ -65,6 +65,15 @@ With --kmer K --word-join the same candidates come from a sorted word index inst
 and the records that carry a word name the pairs that share it, so the work follows what is shared and A^K may be as large as 2^32
 (proteins: K up to 7).  --min-shared defaults to 1 here and may not be 0: a join sees only pairs that share a word.  Everything that
 combines with --kmer combines with --kmer --word-join; where both routes apply they print the same rows.
+
+With --dna --both-strands every record is also held as its reverse complement, made on the device behind the records, and every pass is
+one rectangle: each record as the query against every record on both strands.  Every row gains a `strand` column after t_head -- `+`, or
+`-` where the partner matches as its reverse complement; t_head is the original record's header.  A pair (i, j) is computed from both
+sides; the rows of all pairs, of --f-min and of --kmer print it once per strand, from the record that comes first in the file (a block
+shape for "i < j across strands" is not built), so a record against its own reverse complement is not among them; --best and
+--best-candidates print per record as always, a record's own reverse complement included, and may name a partner on both strands.
+--paf writes the strand, the coordinates on the original records and the CIGAR along the forward target.  --report, --min-* and
+--shuffles work unchanged.  --cluster, --profiles, --msa and --heuristic over both strands are not built.
 """
 import argparse
 import sys
@@ -75,7 +84,7 @@ from . import _ffi
 from .enums import DNA, Protein
 from .fasta import encode_records, read_fasta
 from .matrices import get_blosum62, nucleotide_matrix
-from .seqset import SeqSet, rectangle
+from .seqset import SeqSet, both, rectangle
 
 
 MAX_TRIM = 6          # tail residues a shuffled copy may lose (statistics/mod.rs:312-314)
@@ -113,7 +122,14 @@ def main(argv=None):
     ap.add_argument("--best-candidates", type=int, default=None, metavar="N",
                     help="with --kmer: per record its N best partners (1 .. %d) among its candidates on the full square; self pairs are aligned, then skipped" % _ffi.SEQSET_BEST_MAX)
     ap.add_argument("--word-join", action="store_true", help="with --kmer: the candidates by a join over a sorted word index; A^K up to 2^32, --min-shared at least 1 (default 1)")
+    ap.add_argument("--both-strands", action="store_true", help="with --dna: also match every record as its reverse complement; rows gain a strand column")
     a = ap.parse_args(argv)
+    if a.both_strands:
+        if not a.dna:
+            ap.error("--both-strands is the reverse complement of nucleotide records: give --dna")
+        for given, name in ((a.cluster is not None, "--cluster"), (a.profiles is not None, "--profiles"), (a.msa is not None, "--msa"), (a.heuristic, "--heuristic")):
+            if given:
+                ap.error("--both-strands with %s is not built" % name)
     if a.word_join and a.kmer is None:
         ap.error("--word-join is a route of the prefilter: give --kmer K")
     if a.best_candidates is not None:
@@ -188,6 +204,24 @@ def main(argv=None):
     sem = _ffi.CORE_GLOBAL if a.global_ else _ffi.CORE_LOCAL
     heads = [r.head.decode("utf-8", "replace") for r in records]
     out = sys.stdout
+    n_rec = len(records)
+
+    def make_set(codes):
+        return SeqSet.stranded(codes, alphabet, device=a.device) if a.both_strands else SeqSet(codes, alphabet, device=a.device)
+
+    def square(ss):
+        """every record as the query against every resident record: with --both-strands the mirrors too"""
+        return both(rectangle(0, n_rec, 0, n_rec), n_rec) if a.both_strands else rectangle(0, len(ss), 0, len(ss))
+
+    def t_cols(t):
+        """the row's t_head, and with --both-strands the strand column behind it"""
+        t = int(t)
+        return "%s,%s" % (heads[t % n_rec], "-" if t >= n_rec else "+") if a.both_strands else heads[t]
+
+    def once(q, t):
+        """--both-strands, rows that are not per record: which of the rectangle's pairs are printed -- each pair and strand from the
+        record that comes first"""
+        return np.asarray(q, dtype=np.int64) < np.asarray(t, dtype=np.int64) % n_rec
 
     def kept(held):
         """positions of the held list that are printed (None: all) and their reports (None without --report)"""
@@ -226,11 +260,11 @@ def main(argv=None):
     def write_paf(held, order):
         """--paf: one line per printed hit, `order` their held positions in the rows' order"""
         order = np.asarray(order, dtype=np.uint32)
-        got = held.cigars(keep=order, extended=a.eqx)
+        got = held.cigars(keep=order, extended=a.eqx, stranded=a.both_strands)
         length = held.owner.len
         with open(a.paf, "w") as fh:
             for i, h in enumerate(order.tolist()):
-                q, t = int(held.q[h]), int(held.t[h])
+                q, t = (int(got.q_rec[i]), int(got.t_rec[i])) if a.both_strands else (int(held.q[h]), int(held.t[h]))
                 fh.write(got.paf(i, heads[q], length[q], heads[t], length[t], held.f[h]) + "\n")
 
     def tail(held, pos=None, reports=None):
@@ -266,11 +300,11 @@ def main(argv=None):
         if a.best is not None and not 1 <= a.best <= _ffi.SEQSET_BEST_MAX:
             ap.error("--best: K must lie in 1 .. %d" % _ffi.SEQSET_BEST_MAX)
         floor = float("-inf") if a.f_min is None else a.f_min
-        with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
+        with make_set(encode_records(records, alphabet)) as ss:
             if a.best is not None:
-                held = ss.best(matrix, a.del_, a.ext, a.best, f_min=floor, skip_self=True, semantics=sem)
+                held = ss.best(matrix, a.del_, a.ext, a.best, f_min=floor, block=square(ss), skip_self=True, semantics=sem)
             else:
-                cand = candidates(ss, rectangle(0, len(ss), 0, len(ss)))
+                cand = candidates(ss, square(ss))
                 held = cand.best(matrix, a.del_, a.ext, a.best_candidates, f_min=floor, skip_self=True, semantics=sem)
             if a.cluster is not None:
                 clustered(held)
@@ -281,7 +315,7 @@ def main(argv=None):
             printed = []
             for q, pos in held.by_query():
                 for p in pos[show[pos]]:
-                    out.write("%s,%d,%s,%r%s\n" % (heads[q], int(held.rank[p]) + 1, heads[int(held.t[p])], float(held.f[p]), more[p]))
+                    out.write("%s,%d,%s,%r%s\n" % (heads[q], int(held.rank[p]) + 1, t_cols(held.t[p]), float(held.f[p]), more[p]))
                     printed.append(int(p))
             if a.paf is not None:
                 write_paf(held, printed)
@@ -307,14 +341,21 @@ def main(argv=None):
             for _, q, t, r in align_set(ss, a.del_, a.ext, matrix, Heuristics(kd=a.kd, r_squared=a.r_squared, frequencies=freq)):
                 out.write("%s,%s,%s\n" % (heads[q], heads[t], repr(float(r.alignment.f)) if not isinstance(r, Exception) else "panic: %s" % r))
         return 0
-    with SeqSet(encode_records(records, alphabet), alphabet, device=a.device) as ss:
+    with make_set(encode_records(records, alphabet)) as ss:
         if a.kmer is not None:
-            cand = candidates(ss, None)
+            cand = candidates(ss, square(ss) if a.both_strands else None)
         if a.kmer is not None and a.f_min is None:
             f, status = cand.score(matrix, a.del_, a.ext, semantics=sem)
-            for c in range(len(cand)):
-                out.write("%s,%s,%s,%d\n" % (heads[int(cand.q[c])], heads[int(cand.t[c])],
+            for c in (np.flatnonzero(once(cand.q, cand.t)) if a.both_strands else range(len(cand))):
+                out.write("%s,%s,%s,%d\n" % (heads[int(cand.q[c])], t_cols(cand.t[c]),
                                              repr(float(f[c])) if status[c] == _ffi.OK else _ffi.STATUS_NAMES[int(status[c])], int(cand.shared[c])))
+        elif a.f_min is None and a.both_strands:
+            f, status = ss.score(matrix, a.del_, a.ext, square(ss), semantics=sem)
+            for i in range(n_rec):
+                for t in range(2 * n_rec):
+                    if i < t % n_rec:
+                        k = i * 2 * n_rec + t
+                        out.write("%s,%s,%s\n" % (heads[i], t_cols(t), repr(float(f[k])) if status[k] == _ffi.OK else _ffi.STATUS_NAMES[int(status[k])]))
         elif a.f_min is None:
             f, status = ss.score(matrix, a.del_, a.ext, None, semantics=sem)
             k = 0
@@ -323,14 +364,19 @@ def main(argv=None):
                     out.write("%s,%s,%s\n" % (heads[i], heads[j], repr(float(f[k])) if status[k] == _ffi.OK else _ffi.STATUS_NAMES[int(status[k])]))
                     k += 1
         else:
-            held = cand.hits(matrix, a.del_, a.ext, a.f_min, semantics=sem) if a.kmer is not None else ss.hits(matrix, a.del_, a.ext, a.f_min, None, semantics=sem)
+            held = cand.hits(matrix, a.del_, a.ext, a.f_min, semantics=sem) if a.kmer is not None else \
+                ss.hits(matrix, a.del_, a.ext, a.f_min, square(ss) if a.both_strands else None, semantics=sem)
             if a.cluster is not None:
                 clustered(held)
                 return 0
             pos_kept, reports = kept(held)
+            if a.both_strands:                        # the rectangle holds every pair from both sides: the rows are one side's
+                pos_kept = np.arange(len(held), dtype=np.uint32) if pos_kept is None else np.asarray(pos_kept, dtype=np.uint32)
+                side = once(held.q[pos_kept], held.t[pos_kept])
+                pos_kept, reports = pos_kept[side], (None if reports is None else reports[side])
             more = tail(held, pos_kept, reports)
             for h in (range(len(held)) if pos_kept is None else pos_kept):
-                out.write("%s,%s,%r%s\n" % (heads[int(held.q[h])], heads[int(held.t[h])], float(held.f[h]), more[int(h)]))
+                out.write("%s,%s,%r%s\n" % (heads[int(held.q[h])], t_cols(held.t[h]), float(held.f[h]), more[int(h)]))
             if a.paf is not None:
                 write_paf(held, np.arange(len(held)) if pos_kept is None else pos_kept)
     return 0

@@ -15,6 +15,10 @@ RECORD_DTYPE = np.dtype([("n_ops", "<u4"), ("q_start", "<u4"), ("q_end", "<u4"),
 assert RECORD_DTYPE.itemsize == 32
 CIGAR_RECORD_DTYPE = RECORD_DTYPE
 SUMMARY_KEYS = ("held", "listed", "total_ops", "failed", "padded", "overflow")
+# aln_strand_record (include/aligner_hip_strand.h): strand is ord("+") or ord("-")
+STRAND_DTYPE = np.dtype([("q_rec", "<u4"), ("t_rec", "<u4"), ("strand", "u1"), ("q_mirror", "u1"), ("t_mirror", "u1"), ("reserved", "u1"),
+                         ("reserved2", "<u4")])
+assert STRAND_DTYPE.itemsize == 16
 EXTENDED, CLIPS = _ffi.CIGAR_EXTENDED, _ffi.CIGAR_CLIPS
 M, I, D, S, P, EQ, X = 0, 1, 2, 4, 6, 7, 8
 OP_CHARS = "MIDNSHP=X"
@@ -74,13 +78,22 @@ def encode(query_str, target_str, blank=98, flags=0, start_x=0, start_y=0, q_len
     return rec, np.array(words, dtype=np.uint32), pads, overflow
 
 
-def decode(ops, q_residues, t_residues, q_start, t_start, blank=98):
+def mirror(residues, table):
+    """The mirror of a record as a stranded set holds it: table[residues[::-1]]."""
+    return np.asarray(table, dtype=np.uint8)[np.asarray(residues, dtype=np.uint8)[::-1]]
+
+
+def decode(ops, q_residues, t_residues, q_start, t_start, blank=98, reversed_target=False):
     """The two aligned strings (uint8, without the seed column) the words stand for over the two sequences: the inverse of encode.
-    Clips stand for residues outside the strings and move nothing; a P column is blank in both."""
+    Clips stand for residues outside the strings and move nothing; a P column is blank in both.  reversed_target: the words are those
+    of a stranded plan's hit on a mirrored target (StrandRecord.t_mirror), which stand in reverse order; the residues and the starts
+    are still those of the records that were aligned -- mirror() of an original record, N - q_end and M - t_end of the stranded
+    coordinates where a side is mirrored."""
     q_residues = np.asarray(q_residues, dtype=np.uint8)
     t_residues = np.asarray(t_residues, dtype=np.uint8)
     qs, ts, q, t = [], [], int(q_start), int(t_start)
-    for w in np.asarray(ops, dtype=np.uint32).tolist():
+    words = np.asarray(ops, dtype=np.uint32)
+    for w in (words[::-1] if reversed_target else words).tolist():
         n, op = w >> 4, w & 15
         if op == S:
             continue
@@ -107,10 +120,15 @@ def decode(ops, q_residues, t_residues, q_start, t_start, blank=98):
 class Cigars:
     """.records: RECORD_DTYPE, one per listed hit (n_ops, q_start, q_end, t_start, t_end, matches, block, status); .summary: dict of
     held, listed, total_ops, failed, padded, overflow; .offsets: uint64, len + 1 word offsets; .words: every hit's words, uint32;
-    .which: the listed held positions."""
+    .which: the listed held positions.  Of a stranded plan (HeldHits.cigars(stranded=True)) also .strands (STRAND_DTYPE) and its
+    columns .q_rec, .t_rec (the original records) and .strand ("+" / "-" as uint8 codes); None otherwise."""
 
-    def __init__(self, which, records, summary, offsets, words, flags=0):
+    def __init__(self, which, records, summary, offsets, words, flags=0, strands=None):
         self.which, self.records, self.summary, self.offsets, self.words, self.flags = which, records, summary, offsets, words, int(flags)
+        self.strands = strands
+        self.q_rec = None if strands is None else strands["q_rec"]
+        self.t_rec = None if strands is None else strands["t_rec"]
+        self.strand = None if strands is None else strands["strand"]
 
     def __len__(self):
         return len(self.records)
@@ -123,8 +141,10 @@ class Cigars:
         return text_of(self.ops(i))
 
     def paf(self, i, q_name, q_len, t_name, t_len, f):
-        """Listed hit i as a PAF line (no newline): the 12 standard columns -- strand +, mapping quality 255 -- then af:f: and cg:Z:."""
+        """Listed hit i as a PAF line (no newline): the 12 standard columns -- the strand it holds, + when it holds none, mapping quality
+        255 -- then af:f: and cg:Z:.  Of a stranded plan the names and lengths are those of records q_rec[i] and t_rec[i]."""
         r = self.records[i]
-        return "\t".join([str(q_name), str(int(q_len)), str(int(r["q_start"])), str(int(r["q_end"])), "+", str(t_name), str(int(t_len)),
+        strand = "+" if self.strand is None else chr(int(self.strand[i]))
+        return "\t".join([str(q_name), str(int(q_len)), str(int(r["q_start"])), str(int(r["q_end"])), strand, str(t_name), str(int(t_len)),
                           str(int(r["t_start"])), str(int(r["t_end"])), str(int(r["matches"])), str(int(r["block"])), "255",
                           "af:f:%r" % float(f), "cg:Z:%s" % self.text(i)])

@@ -17,7 +17,9 @@
 //             for lane 63 from one look-ahead load of column j + 1, guarded by j + 1 < n, so the seed column is never read.  The run's
 //             index is the run starts at or below the column (this round's ballot plus a count carried across rounds) minus one; its
 //             length is j - s + 1, s the highest run-start bit at or below the lane, else a second carried value: the start of the run
-//             that was open when the round began, so a run across one or more rounds is one word.  Lane 0 writes the clips
+//             that was open when the round began, so a run across one or more rounds is one word.  Lane 0 writes the clips.
+//             A stranded plan (aln_seqset_held_strand_cigar_plan) marks the listed hits whose target is a mirror: their word r goes
+//             to place n_ops - 1 - r of the hit's words, clips included; nothing else differs and a plain plan has no marks
 //
 // Bounds: a column index stays below aln_len clipped to N + M + 2, the room of one string in the held store (the look-ahead load too);
 // a listed position is compared with n_held before it indexes; a word index is compared with off[k + 1] and with the plan's total
@@ -29,6 +31,7 @@
 #include "aln_device.h"
 #include "aln_launch.h"
 #include "aln_select.h"
+#include "aln_strand_rules.h"
 
 #define ALN_CIGAR_WAVES 4u
 static_assert(ALN_CIGAR_TILE == ALN_SELECT_THREADS, "a tile is one value per thread of the block scan");
@@ -161,7 +164,9 @@ __global__ __launch_bounds__(64 * ALN_CIGAR_WAVES) void aln_cigar_write_kernel(C
     const CigarHit m = aln_cigar_hit(a, k);
     if (m.status != ALN_OK) return;
     const uint64_t first = a.off[k], end = a.off[k + 1u];
+    const bool reversed = a.rev && a.rev[k];          // (a stranded plan's hit on a mirrored target: aln_strand_rules.h)
     auto put = [&](uint64_t w, uint64_t length, uint32_t op) {
+        if (reversed) w = first + aln_strand_word_pos(w - first, rec.n_ops, true);
         if (w >= first && w < end && w < a.total) a.ops[w] = aln_cigar_word(length, op);
     };
     const uint32_t lead = aln_cigar_lead(rec.q_start, a.flags), trail = aln_cigar_trail(rec.q_end, m.N, a.flags);

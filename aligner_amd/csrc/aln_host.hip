@@ -54,6 +54,7 @@
 #include "aln_prefilter_rules.h"
 #include "../../include/aligner_hip_prefilter.h"
 #include "aln_wordjoin_rules.h"
+#include "aln_strand_rules.h"
 #include "../../include/aligner_hip_wordjoin.h"
 
 #define ALN_TIMING_SLOTS 256u
@@ -2866,9 +2867,14 @@ struct aln_seqset : CallStats {
     DevBuf cigar, cigar_out;
     struct CigarPlan {
         bool valid = false;
+        bool stranded = false;        // a plan of aln_seqset_held_strand_cigar_plan: cigar_rev marks the listed hits on a mirrored target
         uint64_t passes = 0, n = 0, held = 0, total_ops = 0;
         uint32_t flags = 0, blank = 0;
     } cigar_plan;
+    // aln_seqset_create_stranded (aln_strand_rules.h): the caller's records, 0 for a plain set -- n is twice that, records strand_n + i
+    // the mirrors; the byte table the mirror kernel read; a stranded plan's marks, one byte per listed hit
+    uint64_t strand_n = 0;
+    DevBuf strand_map, cigar_rev;
     // the k-mer prefilter (aln_prefilter_rules.h).  The index: one bitmap row of kmer_stride elements and one word count per
     // sequence, resident until the next aln_seqset_kmer_index (kmer_k == 0: none built)
     uint32_t kmer_k = 0, kmer_alphabet = 0, kmer_stride = 0;
@@ -2916,7 +2922,7 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
                    &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster, &ss->kmer_bits, &ss->kmer_n,
                    &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first, &ss->profile, &ss->msa, &ss->msa_out, &ss->cigar,
-                   &ss->cigar_out, &ss->word_e, &ss->word_n, &ss->wj_first, &ss->wj_len, &ss->wj_off, &ss->wj_occ, &ss->wj_a, &ss->wj_b, &ss->wj_temp};
+                   &ss->cigar_out, &ss->strand_map, &ss->cigar_rev, &ss->word_e, &ss->word_n, &ss->wj_first, &ss->wj_len, &ss->wj_off, &ss->wj_occ, &ss->wj_a, &ss->wj_b, &ss->wj_temp};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
@@ -2926,12 +2932,16 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     delete ss;
 }
 
-extern "C" aln_seqset *aln_seqset_create(aln_ctx *ctx, const uint8_t *seqs, const uint64_t *off, const uint64_t *len, size_t n_seqs, int *status)
+// map: null for a plain set (aln_seqset_create); else the set is stranded (aln_seqset_create_stranded, aln_strand_rules.h): the n_seqs
+// records go up as they do for a plain set and the mirror kernel writes n_seqs more behind them
+static aln_seqset *seqset_create(aln_ctx *ctx, const uint8_t *seqs, const uint64_t *off, const uint64_t *len, size_t n_seqs, const uint8_t *map,
+                                 bool stranded, int *status)
 {
     int st = ALN_OK;
     aln_seqset *ss = nullptr;
     uint64_t total = 0;
-    if (!ctx || (n_seqs && (!off || !len))) { g_err = "null argument"; st = ALN_ERR_INVALID_ARGUMENT; }
+    if (!ctx || (n_seqs && (!off || !len)) || (stranded && !map)) { g_err = "null argument"; st = ALN_ERR_INVALID_ARGUMENT; }
+    else if (stranded && !aln_strand_count_ok(n_seqs)) { g_err = "a stranded sequence set holds fewer than 2^31 records: twice as many are resident"; st = ALN_ERR_INVALID_ARGUMENT; }
     else if ((uint64_t)n_seqs >= (1ull << 32)) { g_err = "a sequence set holds fewer than 2^32 sequences"; st = ALN_ERR_INVALID_ARGUMENT; }
     else {
         for (size_t i = 0; i < n_seqs && st == ALN_OK; ++i) {
@@ -2943,11 +2953,13 @@ extern "C" aln_seqset *aln_seqset_create(aln_ctx *ctx, const uint8_t *seqs, cons
     if (st == ALN_OK) {
         ss = new aln_seqset();
         ss->ctx = ctx->devs[0];
-        ss->n = n_seqs;
-        ss->total = total;
+        const size_t resident = stranded ? 2 * n_seqs : n_seqs;
+        ss->n = resident;
+        ss->total = stranded ? 2 * total : total;
+        ss->strand_n = stranded ? n_seqs : 0;
         ss->slot = new Slot();
         ss->slot->pooled = false;
-        ss->off.resize(n_seqs); ss->len.resize(n_seqs);
+        ss->off.resize(resident); ss->len.resize(resident);
         // every sequence once, packed in set order: the buffer never moves afterwards
         std::vector<uint8_t> packed(total);
         uint64_t pos = 0;
@@ -2956,11 +2968,13 @@ extern "C" aln_seqset *aln_seqset_create(aln_ctx *ctx, const uint8_t *seqs, cons
             if (len[i]) memcpy(packed.data() + pos, seqs + off[i], len[i]);
             pos += len[i];
         }
+        for (size_t i = 0; stranded && i < n_seqs; ++i) { ss->off[n_seqs + i] = aln_strand_mirror_off(total, ss->off[i]); ss->len[n_seqs + i] = ss->len[i]; }
         hipError_t e = hipSetDevice(ss->ctx->device);
         if (e != hipSuccess) st = fail(e, "hipSetDevice");
-        if (st == ALN_OK) st = dev_ensure(ss->slot->seqs, total + 256, false);
-        if (st == ALN_OK) st = dev_ensure(ss->d_off, 8ull * n_seqs, false);
-        if (st == ALN_OK) st = dev_ensure(ss->d_len, 4ull * n_seqs, false);
+        if (st == ALN_OK) st = dev_ensure(ss->slot->seqs, stranded ? aln_strand_buffer_bytes(total) : total + 256, false);
+        if (st == ALN_OK) st = dev_ensure(ss->d_off, 8ull * resident, false);
+        if (st == ALN_OK) st = dev_ensure(ss->d_len, 4ull * resident, false);
+        if (st == ALN_OK && stranded) st = dev_ensure(ss->strand_map, 256, false);
         if (st == ALN_OK) st = dev_ensure(ss->misc, 256, false);
         if (st == ALN_OK) st = slot_init(*ss->slot);
         for (int i = 0; i < 6 && st == ALN_OK; ++i) { e = hipEventCreate(&ss->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
@@ -2968,16 +2982,71 @@ extern "C" aln_seqset *aln_seqset_create(aln_ctx *ctx, const uint8_t *seqs, cons
             hipStream_t q = ss->slot->stream;
             e = hipSuccess;
             if (total) e = hipMemcpyAsync(ss->slot->seqs.p, packed.data(), total, hipMemcpyHostToDevice, q);
-            if (e == hipSuccess && n_seqs) e = hipMemcpyAsync(ss->d_off.p, ss->off.data(), 8ull * n_seqs, hipMemcpyHostToDevice, q);
-            if (e == hipSuccess && n_seqs) e = hipMemcpyAsync(ss->d_len.p, ss->len.data(), 4ull * n_seqs, hipMemcpyHostToDevice, q);
+            if (e == hipSuccess && n_seqs) e = hipMemcpyAsync(ss->d_off.p, ss->off.data(), 8ull * resident, hipMemcpyHostToDevice, q);
+            if (e == hipSuccess && n_seqs) e = hipMemcpyAsync(ss->d_len.p, ss->len.data(), 4ull * resident, hipMemcpyHostToDevice, q);
+            if (e == hipSuccess && stranded) {        // the mirrors: behind the uploads on the set's stream
+                const auto t0 = std::chrono::steady_clock::now();
+                e = hipMemcpyAsync(ss->strand_map.p, map, 256, hipMemcpyHostToDevice, q);
+                if (e == hipSuccess) e = hipEventRecord(ss->ev[0], q);
+                if (e == hipSuccess) {
+                    aln_strand_launch_mirror(ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), n_seqs, total,
+                                             ss->strand_map.as<uint8_t>(), q);
+                    e = hipGetLastError();
+                }
+                if (e == hipSuccess) e = hipEventRecord(ss->ev[1], q);
+                if (e == hipSuccess) e = hipStreamSynchronize(q);
+                if (e == hipSuccess) { ss->ms[2] = ev_ms(ss->ev[0], ss->ev[1]); ss->ms[3] = wall_ms(t0); }
+            }
             if (e == hipSuccess) e = hipStreamSynchronize(q);
             if (e != hipSuccess) st = fail(e, "upload");
         }
-        ss->bytes[0] = total + 12ull * n_seqs;
+        ss->bytes[0] = total + 12ull * resident + (stranded ? 256u : 0u);
         if (st != ALN_OK) { aln_seqset_destroy(ss); ss = nullptr; }
     }
     if (status) *status = st;
     return ss;
+}
+
+extern "C" aln_seqset *aln_seqset_create(aln_ctx *ctx, const uint8_t *seqs, const uint64_t *off, const uint64_t *len, size_t n_seqs, int *status)
+{
+    return seqset_create(ctx, seqs, off, len, n_seqs, nullptr, false, status);
+}
+
+extern "C" aln_seqset *aln_seqset_create_stranded(aln_ctx *ctx, const uint8_t *seqs, const uint64_t *off, const uint64_t *len, size_t n_seqs,
+                                                  const uint8_t map[256], int *status)
+{
+    return seqset_create(ctx, seqs, off, len, n_seqs, map, true, status);
+}
+
+extern "C" uint64_t aln_seqset_strand_records(const aln_seqset *ss)
+{
+    return ss ? ss->strand_n : 0;
+}
+
+// Resident records first .. first + count - 1 as they lie in the residue buffer, record first + k to out + out_off[k]
+extern "C" int aln_seqset_strand_residues(aln_seqset *ss, uint64_t first, uint64_t count, const uint64_t *out_off, uint8_t *out)
+{
+    if (!ss || (count && !out_off)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ss->destroyed || !ss->slot) { g_err = "the set was destroyed"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (first > ss->n || count > ss->n - first) { g_err = "a record beyond the set"; return ALN_ERR_INVALID_ARGUMENT; }
+    uint64_t bytes = 0;
+    for (uint64_t k = 0; k < count; ++k) bytes += ss->len[first + k];
+    if (bytes && !out) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int st = run_queued(q, [&]() -> int {
+        for (uint64_t k = 0; k < count; ++k) {
+            const uint64_t i = first + k;
+            if (ss->len[i]) HIPCHK(hipMemcpyAsync(out + out_off[k], ss->slot->seqs.as<uint8_t>() + ss->off[i], ss->len[i], hipMemcpyDeviceToHost, q));
+        }
+        HIPCHK(hipStreamSynchronize(q));
+        return ALN_OK;
+    });
+    if (st != ALN_OK) return st;
+    ss->ms[2] = 0.0; ss->ms[3] = wall_ms(t0);
+    ss->bytes[0] = 0; ss->bytes[1] = bytes;
+    return ALN_OK;
 }
 
 extern "C" uint64_t aln_seqset_pairs(const aln_seqset *ss, const aln_seqset_block *b)
@@ -4679,16 +4748,19 @@ static void cigar_args(const aln_seqset *ss, const CigarBufs &b, uint64_t n, uin
 // Every listed hit counted and classed, the offsets of their words.  Up go the listed positions; down come the records and the
 // counters.  The held store is only read.  A refusal leaves the plan before it as it was; once the tables are being rewritten there is
 // no plan until this one has gone well.
+// stranded: the plan of aln_seqset_held_strand_cigar_plan (aln_strand_rules.h) -- the same kernels and tables; the listed hits on a
+// mirrored target are marked for the fill, one byte each, and the caller's records get their coordinates on the original records
 static int seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t *which, uint64_t n, aln_cigar_record *records,
-                                  aln_cigar_summary *summary)
+                                  aln_cigar_summary *summary, bool stranded = false, aln_strand_record *strands = nullptr)
 {
     // (what needs no set comes first)
     if (!aln_cigar_flags_ok(flags)) { g_err = "unknown flag bits"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (!summary || (n && (!which || !records))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!summary || (n && (!which || !records || (stranded && !strands)))) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     int st = held_length_check(n, 0x7FFFFFF0ull);
     if (st != ALN_OK) return st;
     if ((st = seqset_held_check(ss)) != ALN_OK) return st;
     if (ss->destroyed) { g_err = "the set was destroyed"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (stranded && !ss->strand_n) { g_err = "not a stranded set: aln_seqset_create_stranded made none of its records"; return ALN_ERR_INVALID_ARGUMENT; }
     const uint64_t held = ss->hit_pair.size();        // (<= 0xFFFFFFF0: seqset_hold_list)
     if ((st = held_list_check(which, n, held, 0x7FFFFFF0ull)) != ALN_OK) return st;
     uint64_t longest = 0;
@@ -4700,6 +4772,16 @@ static int seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t
     if (ss->cigar.cap < cigar_carve(nullptr, n, nullptr)) ss->cigar_plan.valid = false;
     if ((st = dev_ensure(ss->cigar, cigar_carve(nullptr, n, nullptr), false)) != ALN_OK) return st;
     ss->cigar_plan.valid = false;         // (the tables are rewritten from here on)
+    std::vector<uint8_t> rev_h;
+    std::vector<aln_strand_record> strand_h;
+    if (stranded) {
+        if ((st = dev_ensure(ss->cigar_rev, std::max<uint64_t>(n, 1), false)) != ALN_OK) return st;
+        rev_h.resize(n); strand_h.resize(n);
+        for (uint64_t k = 0; k < n; ++k) {
+            strand_h[k] = aln_strand_classify(ss->hit_q[which[k]], ss->hit_t[which[k]], (uint32_t)ss->strand_n);
+            rev_h[k] = strand_h[k].t_mirror;
+        }
+    }
     CigarBufs b;
     cigar_carve(ss->cigar.as<uint8_t>(), n, &b);
     const uint32_t blank = ss->held_blank;
@@ -4711,6 +4793,7 @@ static int seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t
     unsigned long long misc[ALN_CIGAR_MISC_WORDS] = {0, 0, 0, 0};
     st = run_queued(q, [&]() -> int {
         if (n) HIPCHK(hipMemcpyAsync(b.list, which, 4 * n, hipMemcpyHostToDevice, q));
+        if (n && stranded) HIPCHK(hipMemcpyAsync(ss->cigar_rev.p, rev_h.data(), n, hipMemcpyHostToDevice, q));
         HIPCHK(hipEventRecord(ss->ev[0], q));
         HIPCHK(hipMemsetAsync(b.misc, 0, 8 * ALN_CIGAR_MISC_WORDS, q));
         aln_cigar_launch_plan(&a, q);
@@ -4724,9 +4807,12 @@ static int seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t
     if (st != ALN_OK) return st;
     aln_seqset::CigarPlan plan;
     plan.valid = true; plan.passes = ss->held_passes; plan.n = n; plan.held = held; plan.total_ops = misc[ALN_CIGAR_MISC_TOTAL];
-    plan.flags = flags; plan.blank = blank;
+    plan.flags = flags; plan.blank = blank; plan.stranded = stranded;
     ss->cigar_plan = plan;
+    for (uint64_t k = 0; stranded && k < n; ++k)      // (the device keeps the plain records: the fill's clips are decided from them)
+        rec_h[k] = aln_strand_record_of(rec_h[k], strand_h[k], ss->len[ss->hit_q[which[k]]], ss->len[ss->hit_t[which[k]]]);
     if (n) memcpy(records, rec_h.data(), sizeof(aln_cigar_record) * n);
+    if (n && stranded) memcpy(strands, strand_h.data(), sizeof(aln_strand_record) * n);
     memset(summary, 0, sizeof *summary);
     summary->held = held;
     summary->listed = n;
@@ -4734,18 +4820,20 @@ static int seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t
     summary->failed = sat32(misc[ALN_CIGAR_MISC_FAILED]);
     summary->padded = sat32(misc[ALN_CIGAR_MISC_PADDED]);
     summary->overflow = sat32(misc[ALN_CIGAR_MISC_OVERFLOW]);
-    seqset_done(ss, t0, 4ull * n, sizeof(aln_cigar_record) * n + 8ull * ALN_CIGAR_MISC_WORDS);
+    seqset_done(ss, t0, (stranded ? 5ull : 4ull) * n, sizeof(aln_cigar_record) * n + 8ull * ALN_CIGAR_MISC_WORDS);
     return ALN_OK;
 }
 
 // The words of the last plan, and its offsets when asked for.  Nothing is decided again: the listed positions, the records and the
 // offsets are the plan's, resident.
-static int seqset_held_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capacity_ops, uint64_t *offsets, uint64_t capacity_offsets)
+static int seqset_held_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capacity_ops, uint64_t *offsets, uint64_t capacity_offsets,
+                                  bool stranded = false)
 {
     int st = seqset_held_check(ss);
     if (st != ALN_OK) return st;
     const aln_seqset::CigarPlan plan = ss->cigar_plan;
     if (!plan.valid) { g_err = "no plan: aln_seqset_held_cigar_plan has not run on this set"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (plan.stranded != stranded) { g_err = "no plan of this family: the set's last plan is the other's (plain or stranded)"; return ALN_ERR_INVALID_ARGUMENT; }
     if (plan.passes != ss->held_passes || plan.held != ss->hit_pair.size()) {
         g_err = "the plan is of held hits that another pass has replaced";
         return ALN_ERR_INVALID_ARGUMENT;
@@ -4761,6 +4849,7 @@ static int seqset_held_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capaci
     cigar_args(ss, b, plan.n, plan.held, plan.flags, plan.blank, &a);
     a.ops = ss->cigar_out.as<uint32_t>();
     a.total = plan.total_ops;
+    a.rev = plan.stranded ? ss->cigar_rev.as<uint8_t>() : nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     st = run_queued(q, [&]() -> int {
         HIPCHK(hipEventRecord(ss->ev[0], q));
@@ -4787,6 +4876,17 @@ extern "C" int aln_seqset_held_cigar_plan(aln_seqset *ss, uint32_t flags, const 
 extern "C" int aln_seqset_held_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capacity_ops, uint64_t *offsets, uint64_t capacity_offsets)
 {
     ALN_GUARDED(seqset_live(ss), seqset_held_cigar_fill(ss, ops, capacity_ops, offsets, capacity_offsets))
+}
+
+extern "C" int aln_seqset_held_strand_cigar_plan(aln_seqset *ss, uint32_t flags, const uint32_t *which, uint64_t n, aln_cigar_record *records,
+                                                 aln_strand_record *strands, aln_cigar_summary *summary)
+{
+    ALN_GUARDED(seqset_live(ss), seqset_held_cigar_plan(ss, flags, which, n, records, summary, true, strands))
+}
+
+extern "C" int aln_seqset_held_strand_cigar_fill(aln_seqset *ss, uint32_t *ops, uint64_t capacity_ops, uint64_t *offsets, uint64_t capacity_offsets)
+{
+    ALN_GUARDED(seqset_live(ss), seqset_held_cigar_fill(ss, ops, capacity_ops, offsets, capacity_offsets, true))
 }
 
 // ---------------------------------------------------------------- a pair set over a block of a sequence set, and the loop's step

@@ -1,4 +1,4 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip, aln_msa.hip, aln_cigar.hip and aln_wordjoin.hip define
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip, aln_msa.hip, aln_cigar.hip, aln_wordjoin.hip and aln_strand.hip define
 // and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
 #pragma once
@@ -78,6 +78,7 @@ struct CigarArgs {
     // the fill
     uint32_t *ops;                   // total words
     uint64_t total;
+    const uint8_t *rev;              // n_list, or null: not 0 where a listed hit's words go in reverse order (aln_strand_rules.h)
 };
 
 static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
@@ -246,5 +247,9 @@ void aln_wordjoin_launch_expand(const uint64_t *entries, const uint32_t *piece_f
 void aln_wordjoin_launch_append(const uint64_t *sorted, uint64_t n, const aln_seqset_block *block, uint64_t pairs, const uint32_t *n_words,
                                 uint64_t n_seqs, uint32_t min_shared, uint32_t min_per_1024, uint32_t *shared, uint8_t *keep, uint32_t *tile_count,
                                 uint32_t *tile_off, uint32_t *count, uint64_t room, uint64_t *out_k, uint32_t *out_shared, hipStream_t s);
+
+// ---- aln_strand.hip: the mirrors of a stranded sequence set (aln_strand_rules.h)
+// seqs: 2 * total + 256 bytes, the first `total` the n records packed in order; off, len: theirs; map: 256 bytes
+void aln_strand_launch_mirror(uint8_t *seqs, const uint64_t *off, const uint32_t *len, uint64_t n, uint64_t total, const uint8_t *map, hipStream_t s);
 
 }

@@ -187,3 +187,10 @@ class DNA(_Alphabet):
     letters = "ATCG"                       # codes 0..3 in A,T,C,G order, enums.rs:139-143
     name = "DNA"
     from_u8_skips_unknown = True
+
+    @classmethod
+    def complement_map(cls):
+        """The 256-byte table of SeqSet.stranded: A <-> T and C <-> G are code ^ 1 for the codes 0..3, every other byte is itself."""
+        table = np.arange(256, dtype=np.uint8)
+        table[:4] ^= 1
+        return table

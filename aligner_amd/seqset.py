@@ -91,6 +91,21 @@ def rectangle(q_first, q_count, t_first, t_count):
     return _ffi.SeqsetBlock(int(q_first), int(q_count), int(t_first), int(t_count), 0, 0)
 
 
+def minus(block, n):
+    """The same rectangle of a stranded set of n records on the minus strand: the targets shifted onto their mirrors."""
+    if block.upper:
+        raise ValueError("seqset.minus: a rectangle, not an upper block")
+    return _ffi.SeqsetBlock(block.q_first, block.q_count, block.t_first + int(n), block.t_count, 0, 0)
+
+
+def both(block, n):
+    """The rectangle of a stranded set of n records that holds every query of `block` against all its targets on both strands: the
+    target range widened to 0 .. 2n - 1 when it is the whole 0 .. n - 1 (only then is the union one rectangle)."""
+    if block.upper or block.t_first != 0 or block.t_count != int(n):
+        raise ValueError("seqset.both: a rectangle whose targets are all n records")
+    return _ffi.SeqsetBlock(block.q_first, block.q_count, 0, 2 * int(n), 0, 0)
+
+
 def window(block, first, n):
     """(q, t) uint64 arrays: the sequence numbers of pairs first .. first + n - 1 of a valid block, in the numbering of
     aligner_amd/csrc/aln_seqset_rules.h, with numpy on whole arrays (exact: integers below 2^63)."""
@@ -105,7 +120,7 @@ def window(block, first, n):
 
 
 class SeqSet:
-    def __init__(self, seqs, alphabet=Protein, device=None):
+    def __init__(self, seqs, alphabet=Protein, device=None, _map=None):
         """seqs: residue code arrays (or strings, encoded with alphabet.str_to_vec)."""
         self.lib = _ffi.load()
         self.alphabet = alphabet
@@ -116,12 +131,66 @@ class SeqSet:
             self.off[1:] = np.cumsum(self.len)[:-1]
         self.seqs = np.concatenate(codes) if codes else np.zeros(0, dtype=np.uint8)
         st = C.c_int(0)
-        self.handle = self.lib.aln_seqset_create(runtime.context(device), self.seqs.ctypes.data, self.off.ctypes.data, self.len.ctypes.data,
-                                                 len(codes), C.byref(st))
+        self.records = len(codes)              # the caller's records: of a stranded set half of len()
+        self.map = None
+        if _map is None:
+            self.handle = self.lib.aln_seqset_create(runtime.context(device), self.seqs.ctypes.data, self.off.ctypes.data, self.len.ctypes.data,
+                                                     len(codes), C.byref(st))
+        else:
+            # the host's view of the 2n resident records: lengths and offsets as the device lays them out; only the n forward records
+            # go up, and .seqs gains the mirrors, made here in numpy, when it is first asked for
+            self.map = np.ascontiguousarray(_map, dtype=np.uint8)
+            if self.map.shape != (256,):
+                raise ValueError("SeqSet.stranded: map is a table of 256 bytes")
+            self.handle = self.lib.aln_seqset_create_stranded(runtime.context(device), self.seqs.ctypes.data, self.off.ctypes.data,
+                                                              self.len.ctypes.data, len(codes), self.map.ctypes.data, C.byref(st))
+            total = len(self._seqs)
+            self._forward, self._seqs = codes, None
+            self.off = np.concatenate([self.off, self.off + np.uint64(total)]).astype(np.uint64)
+            self.len = np.concatenate([self.len, self.len])
         if not self.handle:
-            runtime.raise_for_status(st.value, "aln_seqset_create")
+            runtime.raise_for_status(st.value, "aln_seqset_create_stranded" if _map is not None else "aln_seqset_create")
             raise RuntimeError("aln_seqset_create returned NULL")
         self._word = None          # the (k, alphabet_size) of the word index this object built (word_index), if any
+
+    @classmethod
+    def stranded(cls, seqs, alphabet=None, device=None, map=None):
+        """aln_seqset_create_stranded: the n records and, made on the device behind them, their n mirrors -- record n + i is
+        map[record i reversed] -- as one set of 2n resident records that every other call takes as ordinary records.  map: 256 bytes
+        (default: alphabet.complement_map(), alphabet DNA unless given).  .records is n, len() is 2n; minus() and both() shift and
+        widen a rectangle onto the mirrors."""
+        from .enums import DNA
+        alphabet = DNA if alphabet is None else alphabet
+        return cls(seqs, alphabet, device=device, _map=alphabet.complement_map() if map is None else map)
+
+    @property
+    def is_stranded(self):
+        return self.map is not None
+
+    @property
+    def seqs(self):
+        """The residues of every resident record, packed as the device holds them (of a stranded set the mirrors are made on the host
+        the first time this is read; residues() brings down what the device made)."""
+        if self._seqs is None:
+            self._seqs = np.concatenate(self._forward + [self.map[c[::-1]] for c in self._forward]) if self._forward else np.zeros(0, dtype=np.uint8)
+        return self._seqs
+
+    @seqs.setter
+    def seqs(self, value):
+        self._seqs = value
+
+    def residues(self, first=0, count=None):
+        """aln_seqset_strand_residues: resident records first .. first + count - 1 (default: to the last) as the device holds them, a
+        list of uint8 arrays."""
+        count = len(self) - int(first) if count is None else int(count)
+        lens = self.len[int(first):int(first) + count]
+        off = np.zeros(count, dtype=np.uint64)
+        if count > 1:
+            off[1:] = np.cumsum(lens)[:-1]
+        out = np.zeros(max(int(lens.sum()), 1), dtype=np.uint8)
+        st = self.lib.aln_seqset_strand_residues(self.handle, int(first), count, off.ctypes.data, out.ctypes.data)
+        runtime.raise_for_status(st, "aln_seqset_strand_residues")
+        return [out[int(a):int(a) + int(n)].copy() for a, n in zip(off, lens)]
 
     def __len__(self):
         return len(self.len)
@@ -534,26 +603,36 @@ class HeldHits:
         # (without a matrix the device used the held pass's blank code: the one the pass was given)
         return _msa.FamilyAlignments(cen, rec, _msa.summary_dict(summ), out, row_hit, self.q, self.t, o.alphabet, blank)
 
-    def cigars(self, keep=None, extended=False, clips=False):
+    def cigars(self, keep=None, extended=False, clips=False, stranded=False):
         """aln_seqset_held_cigar_plan + aln_seqset_held_cigar_fill: the alignments of the listed positions of the held list (default:
         all) as CIGARs, run-length encoded on the device from the held strings -- per hit a few 32-bit words in BAM's encoding and a
         32-byte record (coordinates, matches, block length); the strings stay where they are.  extended: `=` / `X` in place of `M`;
-        clips: soft clips for the query's residues outside the alignment.  Returns a cigar.Cigars."""
+        clips: soft clips for the query's residues outside the alignment.  stranded (a SeqSet.stranded only):
+        aln_seqset_held_strand_cigar_plan / _fill -- the coordinates on the original records, the words along the forward target, and
+        .q_rec, .t_rec, .strand beside them.  Returns a cigar.Cigars."""
         from . import cigar as _cigar
         o = self.owner
         w = self._keep(keep)
         flags = (_ffi.CIGAR_EXTENDED if extended else 0) | (_ffi.CIGAR_CLIPS if clips else 0)
         rec = np.zeros(len(w), dtype=_cigar.RECORD_DTYPE)
         summ = _ffi.CigarSummary()
-        st = o.lib.aln_seqset_held_cigar_plan(o.handle, flags, w.ctypes.data if len(w) else None, len(w), rec.ctypes.data if len(w) else None,
-                                              C.byref(summ))
-        runtime.raise_for_status(st, "aln_seqset_held_cigar_plan")
+        strands = None
+        if stranded:
+            strands = np.zeros(len(w), dtype=_cigar.STRAND_DTYPE)
+            st = o.lib.aln_seqset_held_strand_cigar_plan(o.handle, flags, w.ctypes.data if len(w) else None, len(w), rec.ctypes.data if len(w) else None,
+                                                         strands.ctypes.data if len(w) else None, C.byref(summ))
+            runtime.raise_for_status(st, "aln_seqset_held_strand_cigar_plan")
+        else:
+            st = o.lib.aln_seqset_held_cigar_plan(o.handle, flags, w.ctypes.data if len(w) else None, len(w), rec.ctypes.data if len(w) else None,
+                                                  C.byref(summ))
+            runtime.raise_for_status(st, "aln_seqset_held_cigar_plan")
         self.last_cigar_plan_stats = o.stats()
         words = np.zeros(int(summ.total_ops), dtype=np.uint32)
         offsets = np.zeros(len(w) + 1, dtype=np.uint64)
-        st = o.lib.aln_seqset_held_cigar_fill(o.handle, words.ctypes.data if len(words) else None, len(words), offsets.ctypes.data, len(offsets))
-        runtime.raise_for_status(st, "aln_seqset_held_cigar_fill")
-        return _cigar.Cigars(w, rec, _cigar.summary_dict(summ), offsets, words, flags)
+        fill = o.lib.aln_seqset_held_strand_cigar_fill if stranded else o.lib.aln_seqset_held_cigar_fill
+        st = fill(o.handle, words.ctypes.data if len(words) else None, len(words), offsets.ctypes.data, len(offsets))
+        runtime.raise_for_status(st, "aln_seqset_held_strand_cigar_fill" if stranded else "aln_seqset_held_cigar_fill")
+        return _cigar.Cigars(w, rec, _cigar.summary_dict(summ), offsets, words, flags, strands)
 
     def fractions(self, reports, keep=None):
         """report_fractions of records that belong to the listed positions (default: all)."""
