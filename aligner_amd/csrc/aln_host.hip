@@ -2835,6 +2835,19 @@ struct aln_seqset : CallStats {
     DevBuf d_off, d_len;              // the same tables on the device (the expansion reads them)
     // a chunk's gathered output: f | status; tile counts | offsets; the chunk's hits (pair number, f); [0] hit count, [2..3] first failure
     DevBuf fbuf, stbuf, tiles, hit_k, hit_f, misc;
+    // misc: 256 bytes of counters, 64 32-bit words.  Every call family's words, in one place:
+    //   words 0 .. 3   (bytes 0 .. 15)   a pass's chunk (seqset_pass_chunks): word 0 the chunk's hit count (the threshold selection),
+    //                                    bytes 8 .. 15 the first failed status (the gather).  Zeroed per chunk, read per chunk.
+    //   words 8, 9     (bytes 32 .. 39)  the k best: the rows' total (seqset_best_finish), 64 bits.  Written by the count kernel.
+    //   word 16        (byte 64)         the kept count of ONE compaction: a sharing chunk of aln_seqset_prefilter, and the selection of
+    //                                    aln_seqset_held_filter.  Both are written by the compaction's offsets step, which writes its
+    //                                    total whatever it is (aln_select.h: for n == 0 too), and both are read back by the call that
+    //                                    queued the kernel, behind a synchronize, before that call queues anything else or returns.  A
+    //                                    handle's calls run one at a time on the set's one stream, so the two users are never live
+    //                                    together and neither reads what the other left: no zeroing, no second word.
+    //   words 20 .. 22 (bytes 80 .. 91)  the word index: word 20 the distinct entries (written by its compaction); the word join, per
+    //                                    chunk: [20] kept pairs, [21] positions without a pair, [22] occurrences scanned, zeroed per chunk.
+    // The other words are unused.  The arenas (cluster, profile, msa, cigar) carry their own counters and zero them per call.
     PinBuf h_out;                     // a chunk's f | status | misc on their way to the caller
     // held hits (aln_seqset_hits): the list lives on the host (it is what the re-fill was planned from); hit h is entry h of the
     // store -- until the next pass on this set
