@@ -62,6 +62,10 @@ PREFILTER_MAX_CANDIDATES = 0xFFFFFFF0
 WORDJOIN_EXPORTS = ["aln_seqset_word_index", "aln_seqset_word_join"]
 WORDJOIN_MAX_K, WORDJOIN_MAX_WORDS = 8, 1 << 32             # aligner_amd/csrc/aln_wordjoin_rules.h
 WORDJOIN_CHUNK_OCCURRENCES, WORDJOIN_MAX_CHUNK_OCCURRENCES = 1 << 24, 1 << 26
+# every symbol the companion header include/aligner_hip_seedjoin.h declares (the same library, as above)
+SEEDJOIN_EXPORTS = ["aln_seqset_candidate_diags", "aln_seqset_seed_index", "aln_seqset_seed_join"]
+SEEDJOIN_MAX_K, SEEDJOIN_MAX_WORDS, SEEDJOIN_MAX_BAND = 16, 1 << 32, (1 << 31) - 1        # aligner_amd/csrc/aln_seedjoin_rules.h
+SEEDJOIN_CHUNK_SEEDS, SEEDJOIN_MAX_CHUNK_SEEDS = 1 << 24, 1 << 26
 # every symbol the companion header include/aligner_hip_search.h declares (the same library, as above)
 SEARCH_EXPORTS = ["aln_seqset_candidate_best"]
 # every symbol the companion header include/aligner_hip_profile.h declares (the same library, as above)
@@ -230,6 +234,20 @@ class WordjoinSpec(C.Structure):
 assert C.sizeof(WordjoinSpec) == 32
 
 
+class SeedjoinSpec(C.Structure):
+    """aln_seedjoin_spec: the seed index a join expects, its thresholds and its band (include/aligner_hip_seedjoin.h)."""
+    _fields_ = [("k", C.c_uint32), ("alphabet", C.c_uint32), ("min_seeds", C.c_uint32), ("band", C.c_uint32), ("max_occ", C.c_uint32),
+                ("chunk_seeds", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SeedjoinSummary(C.Structure):
+    """aln_seedjoin_summary: the counts of one seed join."""
+    _fields_ = [("seeds", C.c_uint64), ("pairs_with_seed", C.c_uint64), ("words_dropped", C.c_uint64), ("chunks", C.c_uint64)]
+
+
+assert C.sizeof(SeedjoinSpec) == 32 and C.sizeof(SeedjoinSummary) == 32
+
+
 class SeqsetBlock(C.Structure):
     _fields_ = [("q_first", C.c_uint64), ("q_count", C.c_uint64), ("t_first", C.c_uint64), ("t_count", C.c_uint64),
                 ("upper", C.c_uint32), ("reserved", C.c_uint32)]
@@ -392,6 +410,12 @@ def load():
     lib.aln_seqset_word_index.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
     lib.aln_seqset_word_join.restype = i
     lib.aln_seqset_word_join.argtypes = [vp, C.POINTER(WordjoinSpec), bp, C.POINTER(C.c_uint64)]
+    lib.aln_seqset_seed_index.restype = i
+    lib.aln_seqset_seed_index.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.aln_seqset_seed_join.restype = i
+    lib.aln_seqset_seed_join.argtypes = [vp, C.POINTER(SeedjoinSpec), bp, C.POINTER(SeedjoinSummary), C.POINTER(C.c_uint64)]
+    lib.aln_seqset_candidate_diags.restype = i
+    lib.aln_seqset_candidate_diags.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
     lib.aln_seqset_candidates.restype = i
     lib.aln_seqset_candidates.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
     lib.aln_seqset_candidate_scores.restype = i

@@ -66,6 +66,15 @@ and the records that carry a word name the pairs that share it, so the work foll
 (proteins: K up to 7).  --min-shared defaults to 1 here and may not be 0: a join sees only pairs that share a word.  Everything that
 combines with --kmer combines with --kmer --word-join; where both routes apply they print the same rows.
 
+With --kmer K --seed-join the candidates come from word hits that lie on a common diagonal: every occurrence of a word keeps its
+position, a seed is a word at position pq of the first record and pt of the second, its diagonal pt - pq, and a pair is a candidate
+if some band of diagonals d0 .. d0 + B (--band B, default 0) holds at least --min-seeds N seeds (default 1).  Words with more than
+--max-occ C occurrences in the whole set make no seed (default 0: none is dropped).  K goes up to 16 on this route (A^K up to 2^32).
+Not with --word-join, --min-shared or --min-shared-per-1024.  Rows without --f-min are `q_head,t_head,f,seeds,diag`: the seeds of the
+best band and its least diagonal.  Everything that combines with --kmer --word-join combines with --kmer --seed-join, --both-strands
+and --best-candidates included; against a reverse-complement partner the diagonal is in the mirror's coordinates (position p of the
+mirror is position length - 1 - p of the record).
+
 With --dna --both-strands every record is also held as its reverse complement, made on the device behind the records, and every pass is
 one rectangle: each record as the query against every record on both strands.  Every row gains a `strand` column after t_head -- `+`, or
 `-` where the partner matches as its reverse complement; t_head is the original record's header.  A pair (i, j) is computed from both
@@ -122,6 +131,11 @@ def main(argv=None):
     ap.add_argument("--best-candidates", type=int, default=None, metavar="N",
                     help="with --kmer: per record its N best partners (1 .. %d) among its candidates on the full square; self pairs are aligned, then skipped" % _ffi.SEQSET_BEST_MAX)
     ap.add_argument("--word-join", action="store_true", help="with --kmer: the candidates by a join over a sorted word index; A^K up to 2^32, --min-shared at least 1 (default 1)")
+    ap.add_argument("--seed-join", action="store_true",
+                    help="with --kmer: the candidates by word hits on a common diagonal; K up to %d, A^K up to 2^32; rows gain seeds,diag (on a reverse-complement partner diag is in the mirror's coordinates)" % _ffi.SEEDJOIN_MAX_K)
+    ap.add_argument("--min-seeds", type=int, default=None, metavar="N", help="with --seed-join: candidates have at least N seeds within one band of diagonals (default 1)")
+    ap.add_argument("--band", type=int, default=None, metavar="B", help="with --seed-join: a band holds the diagonals d0 .. d0 + B (default 0)")
+    ap.add_argument("--max-occ", type=int, default=None, metavar="C", help="with --seed-join: words with more than C occurrences in the whole set make no seed (default 0: none is dropped)")
     ap.add_argument("--both-strands", action="store_true", help="with --dna: also match every record as its reverse complement; rows gain a strand column")
     a = ap.parse_args(argv)
     if a.both_strands:
@@ -132,6 +146,15 @@ def main(argv=None):
                 ap.error("--both-strands with %s is not built" % name)
     if a.word_join and a.kmer is None:
         ap.error("--word-join is a route of the prefilter: give --kmer K")
+    if a.seed_join:
+        if a.kmer is None:
+            ap.error("--seed-join is a route of the prefilter: give --kmer K")
+        if a.word_join:
+            ap.error("--seed-join with --word-join: both name the route to the candidates; give one")
+        if a.min_shared is not None or a.min_shared_per_1024 is not None:
+            ap.error("--min-shared / --min-shared-per-1024 count distinct shared words: --seed-join counts seeds, its thresholds are --min-seeds, --band and --max-occ")
+    elif a.min_seeds is not None or a.band is not None or a.max_occ is not None:
+        ap.error("--min-seeds / --band / --max-occ are the thresholds of --seed-join: give --kmer K --seed-join")
     if a.best_candidates is not None:
         if a.kmer is None:
             ap.error("--best-candidates selects among the prefilter's candidates: give --kmer K")
@@ -150,7 +173,16 @@ def main(argv=None):
         if a.heuristic:
             ap.error("--kmer with --heuristic: the matrix loop over a sparse candidate list is not built")
         kmer_alphabet = a.kmer_alphabet if a.kmer_alphabet is not None else (4 if a.dna else 20)
-        if a.word_join:
+        if a.seed_join:
+            if not 1 <= a.kmer <= _ffi.SEEDJOIN_MAX_K or kmer_alphabet < 1 or kmer_alphabet ** a.kmer > _ffi.SEEDJOIN_MAX_WORDS:
+                ap.error("--kmer with --seed-join: K must lie in 1 .. %d and A^K may not exceed 2^32" % _ffi.SEEDJOIN_MAX_K)
+            if a.min_seeds is not None and not 1 <= a.min_seeds < 2 ** 32:
+                ap.error("--min-seeds: N must lie in 1 .. 2^32 - 1, a join sees only pairs that have a seed")
+            if a.band is not None and not 0 <= a.band <= _ffi.SEEDJOIN_MAX_BAND:
+                ap.error("--band: B must lie in 0 .. 2^31 - 1")
+            if a.max_occ is not None and not 0 <= a.max_occ < 2 ** 32:
+                ap.error("--max-occ: C must lie in 0 .. 2^32 - 1")
+        elif a.word_join:
             if not 1 <= a.kmer <= _ffi.WORDJOIN_MAX_K or kmer_alphabet < 1 or kmer_alphabet ** a.kmer > _ffi.WORDJOIN_MAX_WORDS:
                 ap.error("--kmer with --word-join: K must lie in 1 .. %d and A^K may not exceed 2^32" % _ffi.WORDJOIN_MAX_K)
             if a.min_shared is not None and a.min_shared < 1:
@@ -288,7 +320,11 @@ def main(argv=None):
         return rows
 
     def candidates(ss, block):
-        """the candidate list of --kmer over the block, by the bitmaps or, with --word-join, by the sorted word index"""
+        """the candidate list of --kmer over the block, by the bitmaps or, with --word-join, by the sorted word index or, with
+        --seed-join, by the seeds on a common diagonal"""
+        if a.seed_join:
+            return ss.seed_join(a.kmer, kmer_alphabet, min_seeds=1 if a.min_seeds is None else a.min_seeds, band=a.band or 0, max_occ=a.max_occ or 0,
+                                block=block)
         if a.word_join:
             return ss.word_join(a.kmer, kmer_alphabet, min_shared=1 if a.min_shared is None else a.min_shared,
                                 min_per_1024=a.min_shared_per_1024 or 0, block=block)
@@ -347,8 +383,9 @@ def main(argv=None):
         if a.kmer is not None and a.f_min is None:
             f, status = cand.score(matrix, a.del_, a.ext, semantics=sem)
             for c in (np.flatnonzero(once(cand.q, cand.t)) if a.both_strands else range(len(cand))):
-                out.write("%s,%s,%s,%d\n" % (heads[int(cand.q[c])], t_cols(cand.t[c]),
-                                             repr(float(f[c])) if status[c] == _ffi.OK else _ffi.STATUS_NAMES[int(status[c])], int(cand.shared[c])))
+                out.write("%s,%s,%s,%d%s\n" % (heads[int(cand.q[c])], t_cols(cand.t[c]),
+                                               repr(float(f[c])) if status[c] == _ffi.OK else _ffi.STATUS_NAMES[int(status[c])], int(cand.shared[c]),
+                                               ",%d" % int(cand.diag[c]) if a.seed_join else ""))
         elif a.f_min is None and a.both_strands:
             f, status = ss.score(matrix, a.del_, a.ext, square(ss), semantics=sem)
             for i in range(n_rec):

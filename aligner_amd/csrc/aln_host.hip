@@ -56,6 +56,8 @@
 #include "aln_wordjoin_rules.h"
 #include "aln_strand_rules.h"
 #include "../../include/aligner_hip_wordjoin.h"
+#include "aln_seedjoin_rules.h"
+#include "../../include/aligner_hip_seedjoin.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -302,7 +304,7 @@ static void warm_context(aln_ctx *c)
         if (hipSetDevice(c->devs[d]->device) != hipSuccess) continue;
         (void)aln_warm_single(); (void)aln_warm_tb(); (void)aln_warm_generic();
         (void)aln_warm_fast_cl(); (void)aln_warm_fast_cl_solo(); (void)aln_warm_fast_rest(); (void)aln_warm_fast_rest_solo();
-        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile(); (void)aln_warm_msa(); (void)aln_warm_cigar(); (void)aln_warm_wordjoin();
+        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile(); (void)aln_warm_msa(); (void)aln_warm_cigar(); (void)aln_warm_wordjoin(); (void)aln_warm_seedjoin();
         aln_pair_result r;
         (void)aln_align_pair(c, &p, q.data(), L, t.data(), L, &r, qa.data(), ta.data(), nullptr, nullptr);   // devices in turn
     }
@@ -2847,6 +2849,9 @@ struct aln_seqset : CallStats {
     //                                    together and neither reads what the other left: no zeroing, no second word.
     //   words 20 .. 22 (bytes 80 .. 91)  the word index: word 20 the distinct entries (written by its compaction); the word join, per
     //                                    chunk: [20] kept pairs, [21] positions without a pair, [22] occurrences scanned, zeroed per chunk.
+    //   words 24 .. 28 (bytes 96 .. 115) the seed index: word 24 the occurrences (zeroed, then written by its count kernel); the seed join:
+    //                                    [24] kept pairs, [25] keys without a pair, [26] seeds scanned, [27] pairs with a seed, zeroed per
+    //                                    chunk, and [28] the dropped words, zeroed with the others before the plan.
     // The other words are unused.  The arenas (cluster, profile, msa, cigar) carry their own counters and zero them per call.
     PinBuf h_out;                     // a chunk's f | status | misc on their way to the caller
     // held hits (aln_seqset_hits): the list lives on the host (it is what the re-fill was planned from); hit h is entry h of the
@@ -2906,6 +2911,15 @@ struct aln_seqset : CallStats {
     uint32_t word_k = 0, word_alphabet = 0;
     uint64_t word_entries = 0;
     DevBuf word_e, word_n, wj_first, wj_len, wj_off, wj_occ, wj_a, wj_b, wj_temp;
+    // the positional word index (aln_seedjoin_rules.h): every occurrence's key and position, ascending by (word, sequence),
+    // resident until the next aln_seqset_seed_index (seed_k == 0: none built); beside the other two indexes.  A seed join plans and
+    // sorts in the word join's wj_* buffers and brings sj_diag, a chunk's compacted diagonals.  cand_diag: the diagonals of a candidate
+    // list that aln_seqset_seed_join made (cand_has_diag), on the host beside cand_shared
+    uint32_t seed_k = 0, seed_alphabet = 0;
+    uint64_t seed_entries = 0;
+    DevBuf seed_key, seed_pos, sj_diag;
+    bool cand_has_diag = false;
+    std::vector<int32_t> cand_diag;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a chunk's launches; 4, 5: the best selection
     // pair sets made by aln_pairset_create_from_set read the residue buffer: a destroy with some of them alive releases everything
     // else, moves the buffer here and leaves the rest to the last of them
@@ -2935,13 +2949,13 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
                    &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster, &ss->kmer_bits, &ss->kmer_n,
                    &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first, &ss->profile, &ss->msa, &ss->msa_out, &ss->cigar,
-                   &ss->cigar_out, &ss->strand_map, &ss->cigar_rev, &ss->word_e, &ss->word_n, &ss->wj_first, &ss->wj_len, &ss->wj_off, &ss->wj_occ, &ss->wj_a, &ss->wj_b, &ss->wj_temp};
+                   &ss->cigar_out, &ss->strand_map, &ss->cigar_rev, &ss->word_e, &ss->word_n, &ss->wj_first, &ss->wj_len, &ss->wj_off, &ss->wj_occ, &ss->wj_a, &ss->wj_b, &ss->wj_temp, &ss->seed_key, &ss->seed_pos, &ss->sj_diag};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
     slot_destroy(ss->slot);
     ss->slot = nullptr;
-    if (ss->derived) { ss->destroyed = true; ss->held = false; ss->cand = false; ss->kmer_k = 0; ss->word_k = 0; return; }      // the residues go with the last derived pair set
+    if (ss->derived) { ss->destroyed = true; ss->held = false; ss->cand = false; ss->kmer_k = 0; ss->word_k = 0; ss->seed_k = 0; return; }      // the residues go with the last derived pair set
     delete ss;
 }
 
@@ -3546,6 +3560,8 @@ static void seqset_drop_candidates(aln_seqset *ss)
 {
     ss->cand = false;
     ss->cand_pair.clear(); ss->cand_qs.clear(); ss->cand_ts.clear(); ss->cand_shared.clear();
+    ss->cand_has_diag = false;
+    ss->cand_diag.clear();
 }
 
 static int seqset_kmer_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
@@ -3596,6 +3612,50 @@ static int seqset_cand_room(aln_seqset *ss, uint64_t used, uint64_t entries)
     }
     dev_free(ss->cand_k);
     ss->cand_k = bigger;
+    return ALN_OK;
+}
+
+// What the three routes to the candidate list (prefilter, word join, seed join) do alike.
+// A chunk's `got` kept pairs, compacted behind the `total` that are there, come down with their shared counts (pf_out): the host
+// indexes its tables with this list, so it must be pairs k_lo .. k_end - 1 of the block, ascending (the stream is idle)
+static int seqset_cand_take(aln_seqset *ss, uint64_t total, uint64_t got, uint64_t k_lo, uint64_t k_end)
+{
+    if (!got) return ALN_OK;
+    ss->cand_pair.resize(total + got); ss->cand_shared.resize(total + got);
+    HIPCHK(hipMemcpy(ss->cand_pair.data() + total, ss->cand_k.as<uint64_t>() + total, 8ull * got, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ss->cand_shared.data() + total, ss->pf_out.p, 4ull * got, hipMemcpyDeviceToHost));
+    for (uint64_t i = total; i < total + got; ++i)
+        if (ss->cand_pair[i] < k_lo || ss->cand_pair[i] >= k_end || (i > total && ss->cand_pair[i] <= ss->cand_pair[i - 1])) { g_err = "the candidate list is not an ascending list of the chunk's pairs"; return ALN_ERR_DEVICE; }
+    return ALN_OK;
+}
+
+// the list is complete: its sequence numbers, and the state the candidate calls read
+static void seqset_cand_finish(aln_seqset *ss, const aln_seqset_block *b, uint64_t total, uint64_t *count)
+{
+    ss->cand_qs.resize(total); ss->cand_ts.resize(total);
+    for (uint64_t i = 0; i < total; ++i) {
+        uint64_t sq, tq;
+        aln_seqset_unrank(*b, ss->cand_pair[i], &sq, &tq);
+        ss->cand_qs[i] = (uint32_t)sq; ss->cand_ts[i] = (uint32_t)tq;
+    }
+    ss->cand = true;
+    ss->cand_block = *b;
+    *count = total;
+}
+
+// the query rows of a join cut into chunks: cut(first) gives the rows of the chunk that starts at row `first`, 0 if that row alone is
+// above the cap (ALN_ERR_CAPACITY with `over`); a run of rows without anything to expand is no chunk
+template <class Cut> static int seqset_cut_rows(const std::vector<uint64_t> &per_row, Cut cut, const char *over, std::vector<uint64_t> &chunk_first,
+                                                std::vector<uint64_t> &chunk_rows, std::vector<uint64_t> &chunk_sum)
+{
+    for (uint64_t first = 0; first < per_row.size();) {
+        const uint64_t n = cut(first);
+        if (!n) { g_err = over; return ALN_ERR_CAPACITY; }
+        uint64_t sum = 0;
+        for (uint64_t r = first; r < first + n; ++r) sum += per_row[r];
+        if (sum) { chunk_first.push_back(first); chunk_rows.push_back(n); chunk_sum.push_back(sum); }
+        first += n;
+    }
     return ALN_OK;
 }
 
@@ -3651,29 +3711,14 @@ static int seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *sp, const 
             down += 8;
             if (got > n) { g_err = "the compaction kept more pairs than the chunk holds"; return ALN_ERR_DEVICE; }
             if (total + got > 0xFFFFFFF0ull) { g_err = "too many candidates"; return ALN_ERR_UNSUPPORTED; }
-            if (got) {
-                ss->cand_pair.resize(total + got); ss->cand_shared.resize(total + got);
-                HIPCHK(hipMemcpy(ss->cand_pair.data() + total, ss->cand_k.as<uint64_t>() + total, 8ull * got, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(ss->cand_shared.data() + total, ss->pf_out.p, 4ull * got, hipMemcpyDeviceToHost));
-                down += 12ull * got;
-                // the host indexes its tables with this list: pairs of the chunk, ascending
-                for (uint64_t h = total; h < total + got; ++h)
-                    if (ss->cand_pair[h] < k0 || ss->cand_pair[h] - k0 >= n || (h > total && ss->cand_pair[h] <= ss->cand_pair[h - 1])) { g_err = "the candidate list is not an ascending list of the chunk's pairs"; return ALN_ERR_DEVICE; }
-            }
+            if ((st = seqset_cand_take(ss, total, got, k0, k0 + n)) != ALN_OK) return st;
+            down += 12ull * got;
             total += got;
         }
         return ALN_OK;
     });
     if (st != ALN_OK) { seqset_drop_candidates(ss); return st; }
-    ss->cand_qs.resize(total); ss->cand_ts.resize(total);
-    for (uint64_t h = 0; h < total; ++h) {
-        uint64_t sq, tq;
-        aln_seqset_unrank(*b, ss->cand_pair[h], &sq, &tq);
-        ss->cand_qs[h] = (uint32_t)sq; ss->cand_ts[h] = (uint32_t)tq;
-    }
-    ss->cand = true;
-    ss->cand_block = *b;
-    *count = total;
+    seqset_cand_finish(ss, b, total, count);
     seqset_done(ss, t0, 0, down, kernels);          // 12 bytes per candidate and the 8 of a chunk's count
     return ALN_OK;
 }
@@ -3827,15 +3872,8 @@ static int seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *sp, const a
         HIPCHK(hipStreamSynchronize(q));
         kernels += ev_ms(ss->ev[0], ss->ev[1]);
         down += 8 * rows;
-        for (uint64_t first = 0; first < rows;) {
-            const uint64_t n = aln_wordjoin_cut(occ.data(), rows, first, cap);
-            if (!n) { g_err = "one query row of the block has more occurrences than chunk_occurrences allows"; return ALN_ERR_CAPACITY; }
-            uint64_t sum = 0;
-            for (uint64_t r = first; r < first + n; ++r) sum += occ[r];
-            if (sum) { chunk_first.push_back(first); chunk_rows.push_back(n); chunk_occ.push_back(sum); }
-            first += n;
-        }
-        return ALN_OK;
+        return seqset_cut_rows(occ, [&](uint64_t first) { return aln_wordjoin_cut(occ.data(), rows, first, cap); },
+                               "one query row of the block has more occurrences than chunk_occurrences allows", chunk_first, chunk_rows, chunk_occ);
     });
     if (st != ALN_OK) return st;
     seqset_drop_candidates(ss);
@@ -3883,29 +3921,14 @@ static int seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *sp, const a
             if (h[1]) { g_err = "an occurrence of the join names no pair of the block"; return ALN_ERR_DEVICE; }
             if (got > room) { g_err = "the join kept more pairs than the chunk's rows hold"; return ALN_ERR_DEVICE; }
             if (total + got > 0xFFFFFFF0ull) { g_err = "too many candidates"; return ALN_ERR_UNSUPPORTED; }
-            if (got) {
-                ss->cand_pair.resize(total + got); ss->cand_shared.resize(total + got);
-                HIPCHK(hipMemcpy(ss->cand_pair.data() + total, ss->cand_k.as<uint64_t>() + total, 8ull * got, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(ss->cand_shared.data() + total, ss->pf_out.p, 4ull * got, hipMemcpyDeviceToHost));
-                down += 12ull * got;
-                // the host indexes its tables with this list: pairs of the chunk's rows, ascending
-                for (uint64_t i = total; i < total + got; ++i)
-                    if (ss->cand_pair[i] < k_lo || ss->cand_pair[i] >= k_end || (i > total && ss->cand_pair[i] <= ss->cand_pair[i - 1])) { g_err = "the candidate list is not an ascending list of the chunk's pairs"; return ALN_ERR_DEVICE; }
-            }
+            if ((st = seqset_cand_take(ss, total, got, k_lo, k_end)) != ALN_OK) return st;
+            down += 12ull * got;
             total += got;
         }
         return ALN_OK;
     });
     if (st != ALN_OK) { seqset_drop_candidates(ss); return st; }
-    ss->cand_qs.resize(total); ss->cand_ts.resize(total);
-    for (uint64_t i = 0; i < total; ++i) {
-        uint64_t sq, tq;
-        aln_seqset_unrank(*b, ss->cand_pair[i], &sq, &tq);
-        ss->cand_qs[i] = (uint32_t)sq; ss->cand_ts[i] = (uint32_t)tq;
-    }
-    ss->cand = true;
-    ss->cand_block = *b;
-    *count = total;
+    seqset_cand_finish(ss, b, total, count);
     seqset_done(ss, t0, 0, down, kernels);          // 8 bytes per query row, 12 per chunk and 12 per candidate
     return ALN_OK;
 }
@@ -3918,6 +3941,213 @@ extern "C" int aln_seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphab
 extern "C" int aln_seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *spec, const aln_seqset_block *b, uint64_t *count)
 {
     ALN_GUARDED(seqset_live(ss), seqset_word_join(ss, spec, b, count))
+}
+
+// ---------------------------------------------------------------- the positional word index and the seed join (include/aligner_hip_seedjoin.h)
+// A third road to the candidate state above: every occurrence of a word keeps its position, and a pair is judged by the most seeds it has
+// within one band of diagonals.  What is left behind is the prefilter's list with `shared` holding seeds, and the diagonals beside it.
+static const char *const SEEDJOIN_RANGE = "k must lie in 1 .. 16, the alphabet size be at least 1 and alphabet^k at most 2^32";
+
+static int seqset_seed_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint64_t *occurrences)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t words = aln_seedjoin_words(k, alphabet);
+    if (!words) { g_err = SEEDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ss->total > 0x7FFFFFFFull) { g_err = "a seed index holds fewer than 2^31 residue positions"; return ALN_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t total = ss->total;
+    uint32_t seq_end, word_end;
+    aln_wordjoin_sort_bits(words, ss->n, &seq_end, &word_end);
+    // everything new first: a failure leaves the old index and the candidate list as they were
+    DevBuf keys_a, keys_b, pos_a, pos_b, temp, keys, pos;
+    uint32_t got = 0;
+    const int st = run_queued(q, [&]() -> int {
+        int st;
+        size_t temp_bytes = 0;
+        HIPCHK((hipError_t)aln_seedjoin_sort_pairs_temp_bytes(total, &temp_bytes));
+        if ((st = dev_ensure(keys_a, 8 * total, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(keys_b, 8 * total, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(pos_a, 4 * total, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(pos_b, 4 * total, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(temp, temp_bytes, false)) != ALN_OK) return st;
+        uint32_t *d_count = ss->misc.as<uint32_t>() + 24;
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        HIPCHK(hipMemsetAsync(d_count, 0, 4, q));
+        aln_seedjoin_launch_keys(ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), ss->n, total, k, alphabet,
+                                 keys_a.as<uint64_t>(), pos_a.as<uint32_t>(), q);
+        HIPCHK(hipGetLastError());
+        // the word join's two ranges, or the whole key in one pass where the word field reaches bit 64 (aln_wordjoin_sort_bits)
+        if (word_end == 64u) {
+            HIPCHK((hipError_t)aln_seedjoin_launch_sort_pairs(temp.p, temp.cap, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), pos_a.as<uint32_t>(),
+                                                              pos_b.as<uint32_t>(), total, 0, 64, q));
+            std::swap(keys_a, keys_b); std::swap(pos_a, pos_b);
+        } else {
+            HIPCHK((hipError_t)aln_seedjoin_launch_sort_pairs(temp.p, temp.cap, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), pos_a.as<uint32_t>(),
+                                                              pos_b.as<uint32_t>(), total, 0, seq_end, q));
+            HIPCHK((hipError_t)aln_seedjoin_launch_sort_pairs(temp.p, temp.cap, keys_b.as<uint64_t>(), keys_a.as<uint64_t>(), pos_b.as<uint32_t>(),
+                                                              pos_a.as<uint32_t>(), total, 32, word_end, q));
+        }
+        if (total) aln_seedjoin_launch_count(keys_a.as<uint64_t>(), total, d_count, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(&got, d_count, 4, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        if (got > total) { g_err = "the seed index holds more occurrences than the set has windows"; return ALN_ERR_DEVICE; }
+        // the resident list at its own size; the sort's buffers go
+        if ((st = dev_ensure(keys, 8ull * got, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(pos, 4ull * got, false)) != ALN_OK) return st;
+        if (got) HIPCHK(hipMemcpy(keys.p, keys_a.p, 8ull * got, hipMemcpyDeviceToDevice));
+        if (got) HIPCHK(hipMemcpy(pos.p, pos_a.p, 4ull * got, hipMemcpyDeviceToDevice));
+        return ALN_OK;
+    });
+    dev_free(keys_a); dev_free(keys_b); dev_free(pos_a); dev_free(pos_b); dev_free(temp);
+    if (st != ALN_OK) { dev_free(keys); dev_free(pos); return st; }
+    dev_free(ss->seed_key); dev_free(ss->seed_pos);
+    ss->seed_key = keys; ss->seed_pos = pos;
+    ss->seed_k = k; ss->seed_alphabet = alphabet; ss->seed_entries = got;
+    seqset_drop_candidates(ss);
+    if (occurrences) *occurrences = got;
+    seqset_done(ss, t0, 0, 4);
+    return ALN_OK;
+}
+
+static int seqset_seed_join(aln_seqset *ss, const aln_seedjoin_spec *sp, const aln_seqset_block *b, aln_seedjoin_summary *summary, uint64_t *count)
+{
+    if (!ss || !sp || !b || !count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!aln_seedjoin_words(sp->k, sp->alphabet)) { g_err = SEEDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ss->seed_k || sp->k != ss->seed_k || sp->alphabet != ss->seed_alphabet) { g_err = "no seed index of this k and alphabet: aln_seqset_seed_index builds it"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->min_seeds == 0u) { g_err = "min_seeds must be at least 1: a join sees only the pairs that have a seed"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->band > ALN_SEEDJOIN_MAX_BAND) { g_err = "band must lie in 0 .. 2^31 - 1"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->flags != 0u || sp->reserved != 0u) { g_err = "the spec's flags and reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->chunk_seeds > ALN_SEEDJOIN_MAX_CHUNK_SEEDS) { g_err = "chunk_seeds must lie in 0 .. 2^26"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t pairs = aln_seqset_block_pairs(ss->n, *b);
+    if (pairs == 0) { g_err = "block: a range beyond the set, unequal ranges of an upper block, a reserved word, or no pairs"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t cap = sp->chunk_seeds ? sp->chunk_seeds : ALN_SEEDJOIN_CHUNK_SEEDS;
+    const uint64_t n_p = ss->seed_entries, rows = b->q_count;
+    uint64_t total = 0, down = 0, seeds_all = 0, pairs_seen = 0;
+    uint32_t dropped = 0;
+    double kernels = 0;
+    int st;
+    uint32_t *d_words = ss->misc.as<uint32_t>() + 24;        // [0] kept pairs, [1] keys without a pair, [2] seeds scanned, [3] pairs with a seed, [4] dropped words
+    // ---- the plan: nothing of the set's state is touched before the rows are cut
+    std::vector<uint64_t> row_seeds(rows, 0);
+    std::vector<uint64_t> chunk_first, chunk_rows, chunk_seeds;
+    st = run_queued(q, [&]() -> int {
+        if ((st = dev_ensure(ss->wj_first, 4 * n_p, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->wj_len, 4 * n_p, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->wj_off, 4 * n_p, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->wj_occ, 8 * rows, false)) != ALN_OK) return st;
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        HIPCHK(hipMemsetAsync(ss->wj_occ.p, 0, 8 * rows, q));
+        HIPCHK(hipMemsetAsync(d_words, 0, 20, q));
+        aln_seedjoin_launch_plan(ss->seed_key.as<uint64_t>(), n_p, b, sp->max_occ, ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(),
+                                 ss->wj_occ.as<uint64_t>(), d_words + 4, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(row_seeds.data(), ss->wj_occ.p, 8 * rows, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(&dropped, d_words + 4, 4, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        kernels += ev_ms(ss->ev[0], ss->ev[1]);
+        down += 8 * rows + 4;
+        return seqset_cut_rows(row_seeds, [&](uint64_t first) { return aln_seedjoin_cut(row_seeds.data(), *b, first, cap); },
+                               "one query row of the block has more seeds than chunk_seeds allows: max_occ drops the words that occur too often",
+                               chunk_first, chunk_rows, chunk_seeds);
+    });
+    if (st != ALN_OK) return st;
+    seqset_drop_candidates(ss);
+    st = run_queued(q, [&]() -> int {
+        if ((st = seqset_cand_room(ss, 0, 1)) != ALN_OK) return st;      // (an empty list is resident too, as the prefilter's is)
+        for (size_t c = 0; c < chunk_first.size(); ++c) {
+            const uint64_t m = chunk_seeds[c], q_lo = b->q_first + chunk_first[c], q_rows = chunk_rows[c];
+            // the chunk's pairs: the pair numbers of its rows, at most 2^32 of them (aln_seedjoin_cut)
+            const uint64_t k_lo = b->upper ? aln_seqset_row_start(rows, chunk_first[c]) : chunk_first[c] * b->t_count;
+            const uint64_t k_end = k_lo + aln_seedjoin_row_pairs(*b, chunk_first[c], q_rows);
+            const uint64_t room = std::min(m, k_end - k_lo);
+            const uint32_t key_bits = 32u + std::max<uint32_t>(aln_wordjoin_bits_needed(k_end - k_lo), 1u);
+            size_t temp_bytes = 0;
+            HIPCHK((hipError_t)aln_wordjoin_sort_temp_bytes(m, &temp_bytes));
+            uint32_t *tile_count = nullptr, *tile_off = nullptr;
+            if ((st = dev_ensure(ss->wj_a, 8 * m, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->wj_b, 8 * m, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->wj_temp, temp_bytes, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->pf_out, 4 * room, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->sj_diag, 4 * room, false)) != ALN_OK) return st;
+            if ((st = tiles_ensure(ss->tiles, std::max(aln_seqset_tiles(n_p), aln_seqset_tiles(m)), &tile_count, &tile_off)) != ALN_OK) return st;
+            if ((st = seqset_cand_room(ss, total, total + room)) != ALN_OK) return st;
+            HIPCHK(hipEventRecord(ss->ev[0], q));
+            HIPCHK(hipMemsetAsync(d_words, 0, 16, q));
+            aln_wordjoin_launch_offsets(ss->seed_key.as<uint64_t>(), ss->wj_len.as<uint32_t>(), n_p, q_lo, q_rows, tile_count, tile_off, d_words + 2,
+                                        ss->wj_off.as<uint32_t>(), q);
+            HIPCHK(hipGetLastError());
+            aln_seedjoin_launch_expand(ss->seed_key.as<uint64_t>(), ss->seed_pos.as<uint32_t>(), ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(),
+                                       ss->wj_off.as<uint32_t>(), n_p, m, b, k_lo, k_end, q_lo, q_rows, ss->wj_a.as<uint64_t>(), d_words + 1, q);
+            HIPCHK(hipGetLastError());
+            HIPCHK((hipError_t)aln_wordjoin_launch_sort(ss->wj_temp.p, ss->wj_temp.cap, ss->wj_a.as<uint64_t>(), ss->wj_b.as<uint64_t>(), m, 0, key_bits, q));
+            // the unsorted keys have been read: their buffer holds the pairs' slots now
+            HIPCHK(hipMemsetAsync(ss->wj_a.p, 0, 8 * m, q));
+            aln_seedjoin_launch_append(ss->wj_b.as<uint64_t>(), m, k_lo, k_end - k_lo, sp->band, sp->min_seeds, ss->wj_a.as<uint64_t>(), d_words + 1,
+                                       tile_count, tile_off, d_words + 3, d_words, room, ss->cand_k.as<uint64_t>() + total, ss->pf_out.as<uint32_t>(),
+                                       ss->sj_diag.as<int32_t>(), q);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ss->ev[1], q));
+            uint32_t h[4] = {0, 0, 0, 0};
+            HIPCHK(hipMemcpyAsync(h, d_words, 16, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipStreamSynchronize(q));
+            kernels += ev_ms(ss->ev[0], ss->ev[1]);
+            down += 16;
+            const uint64_t got = h[0];
+            if (h[2] != m) { g_err = "a chunk's seeds differ from the plan's"; return ALN_ERR_DEVICE; }
+            if (h[1]) { g_err = "a seed of the join names no pair of the block"; return ALN_ERR_DEVICE; }
+            if (got > room || got > h[3] || h[3] > room) { g_err = "the join kept more pairs than the chunk's rows hold"; return ALN_ERR_DEVICE; }
+            if (total + got > 0xFFFFFFF0ull) { g_err = "too many candidates"; return ALN_ERR_UNSUPPORTED; }
+            if ((st = seqset_cand_take(ss, total, got, k_lo, k_end)) != ALN_OK) return st;
+            if (got) {
+                ss->cand_diag.resize(total + got);
+                HIPCHK(hipMemcpy(ss->cand_diag.data() + total, ss->sj_diag.p, 4ull * got, hipMemcpyDeviceToHost));
+            }
+            down += 16ull * got;
+            total += got;
+            seeds_all += m;
+            pairs_seen += h[3];
+        }
+        return ALN_OK;
+    });
+    if (st != ALN_OK) { seqset_drop_candidates(ss); return st; }
+    seqset_cand_finish(ss, b, total, count);
+    ss->cand_has_diag = true;
+    if (summary) { summary->seeds = seeds_all; summary->pairs_with_seed = pairs_seen; summary->words_dropped = dropped; summary->chunks = chunk_first.size(); }
+    seqset_done(ss, t0, 0, down, kernels);          // 8 bytes per query row and 4, 16 per chunk and 16 per candidate
+    return ALN_OK;
+}
+
+extern "C" int aln_seqset_seed_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint64_t *occurrences)
+{
+    ALN_GUARDED(seqset_live(ss), seqset_seed_index(ss, k, alphabet, occurrences))
+}
+
+extern "C" int aln_seqset_seed_join(aln_seqset *ss, const aln_seedjoin_spec *spec, const aln_seqset_block *b, aln_seedjoin_summary *summary,
+                                    uint64_t *count)
+{
+    ALN_GUARDED(seqset_live(ss), seqset_seed_join(ss, spec, b, summary, count))
+}
+
+extern "C" int aln_seqset_candidate_diags(aln_seqset *ss, uint64_t first, uint64_t n, int32_t *diag)
+{
+    const int st = seqset_cand_check(ss);
+    if (st != ALN_OK) return st;
+    if (!ss->cand_has_diag) { g_err = "the candidate list has no diagonals: aln_seqset_seed_join makes the lists that have"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t have = ss->cand_diag.size();
+    if (first > have || n > have - first) { g_err = "range beyond the candidate list"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && !diag) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    for (uint64_t i = 0; i < n; ++i) diag[i] = ss->cand_diag[first + i];
+    return ALN_OK;                       // (no byte moves and no kernel runs: the stats stay as they are)
 }
 
 static int seqset_held_check(aln_seqset *ss)

@@ -1,4 +1,4 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip, aln_msa.hip, aln_cigar.hip, aln_wordjoin.hip and aln_strand.hip define
+// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip, aln_msa.hip, aln_cigar.hip, aln_wordjoin.hip, aln_seedjoin.hip and aln_strand.hip define
 // and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
 #pragma once
@@ -247,6 +247,33 @@ void aln_wordjoin_launch_expand(const uint64_t *entries, const uint32_t *piece_f
 void aln_wordjoin_launch_append(const uint64_t *sorted, uint64_t n, const aln_seqset_block *block, uint64_t pairs, const uint32_t *n_words,
                                 uint64_t n_seqs, uint32_t min_shared, uint32_t min_per_1024, uint32_t *shared, uint8_t *keep, uint32_t *tile_count,
                                 uint32_t *tile_off, uint32_t *count, uint64_t room, uint64_t *out_k, uint32_t *out_shared, hipStream_t s);
+
+// ---- aln_seedjoin.hip: the positional word index of a sequence set and the seed join over it (aln_seedjoin_rules.h)
+int aln_warm_seedjoin(void);
+// rocPRIM's device radix sort of n (64-bit key, 32-bit value) pairs, stable, under the rules of aln_wordjoin_launch_sort
+int aln_seedjoin_sort_pairs_temp_bytes(uint64_t n, size_t *bytes);
+int aln_seedjoin_launch_sort_pairs(void *temp, size_t temp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in,
+                                   uint32_t *vals_out, uint64_t n, uint32_t begin_bit, uint32_t end_bit, hipStream_t s);
+// keys, pos: `total` entries each, one per residue position of the packed set
+void aln_seedjoin_launch_keys(const uint8_t *seqs, const uint64_t *seq_off, const uint32_t *seq_len, uint64_t n_seqs, uint64_t total, uint32_t k,
+                              uint32_t alphabet, uint64_t *keys, uint32_t *pos, hipStream_t s);
+// sorted: n keys ascending -> count[0]: the keys that are words
+void aln_seedjoin_launch_count(const uint64_t *sorted, uint64_t n, uint32_t *count, hipStream_t s);
+// keys: the n occurrences of the index, ascending.  piece_first / piece_len: n each; row_seeds: block->q_count totals, zeroed before;
+// counters[0], zeroed before: the distinct words with more than max_occ occurrences (max_occ == 0: none)
+void aln_seedjoin_launch_plan(const uint64_t *keys, uint64_t n, const aln_seqset_block *block, uint32_t max_occ, uint32_t *piece_first,
+                              uint32_t *piece_len, uint64_t *row_seeds, uint32_t *counters, hipStream_t s);
+// out: the sort keys of the n_out seeds of query rows q_lo .. q_lo + q_rows - 1, whose pairs are numbers k_lo .. k_end - 1 of the
+// block (offsets: aln_wordjoin_launch_offsets over keys and piece_len); errors[0] counts the seeds that name no such pair
+void aln_seedjoin_launch_expand(const uint64_t *keys, const uint32_t *pos, const uint32_t *piece_first, const uint32_t *piece_len,
+                                const uint32_t *offsets, uint64_t n, uint64_t n_out, const aln_seqset_block *block, uint64_t k_lo, uint64_t k_end,
+                                uint64_t q_lo, uint64_t q_rows, uint64_t *out, uint32_t *errors, hipStream_t s);
+// sorted: n sort keys ascending -> the kept (k_lo + pair, seeds, diag) appended in order: out_k, out_seeds and out_diag, `room` entries
+// each; count[0]: how many; pairs_seen[0]: the pairs with a seed.  slots: n 64-bit words, zeroed before; errors[0] counts the keys
+// beyond chunk_pairs.  tile_count / tile_off: aln_select_tiles(n) words each
+void aln_seedjoin_launch_append(const uint64_t *sorted, uint64_t n, uint64_t k_lo, uint64_t chunk_pairs, uint32_t band, uint32_t min_seeds,
+                                uint64_t *slots, uint32_t *errors, uint32_t *tile_count, uint32_t *tile_off, uint32_t *pairs_seen, uint32_t *count,
+                                uint64_t room, uint64_t *out_k, uint32_t *out_seeds, int32_t *out_diag, hipStream_t s);
 
 // ---- aln_strand.hip: the mirrors of a stranded sequence set (aln_strand_rules.h)
 // seqs: 2 * total + 256 bytes, the first `total` the n records packed in order; off, len: theirs; map: 256 bytes

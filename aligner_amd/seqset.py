@@ -306,6 +306,34 @@ class SeqSet:
         runtime.raise_for_status(st, "aln_seqset_word_join")
         return Candidates(self, int(count.value))
 
+    def seed_index(self, k, alphabet_size):
+        """aln_seqset_seed_index: builds (or replaces) the resident list of every occurrence (word, sequence, position) of the set --
+        words of k residues, k up to 16, with every code below alphabet_size, alphabet_size ** k <= 2 ** 32 -- and returns how many
+        there are.  Any candidate list is dropped; the bitmaps of kmer_index and the list of word_index stay."""
+        occurrences = C.c_uint64(0)
+        st = self.lib.aln_seqset_seed_index(self.handle, int(k), int(alphabet_size), C.byref(occurrences))
+        runtime.raise_for_status(st, "aln_seqset_seed_index")
+        self._seed = (int(k), int(alphabet_size))
+        return int(occurrences.value)
+
+    def seed_join(self, k, alphabet_size, min_seeds=1, band=0, max_occ=0, block=None, chunk_seeds=0):
+        """aln_seqset_seed_join: the pairs of the block with at least min_seeds seeds -- word hits (pq, pt), diagonal pt - pq -- on
+        diagonals d0 .. d0 + band for some d0, words with more than max_occ occurrences in the whole set left out (0: none).  Builds
+        the seed index if none of this (k, alphabet_size) is there.  Returns a Candidates whose .shared holds the seeds of the best
+        band, .diag its least diagonal d0 and .summary the call's counts; on a mirrored record of a stranded set the diagonal is in the
+        mirror's coordinates."""
+        b, n = self._checked(block)
+        if getattr(self, "_seed", None) != (int(k), int(alphabet_size)):
+            self.seed_index(k, alphabet_size)
+        spec = _ffi.SeedjoinSpec(int(k), int(alphabet_size), int(min_seeds), int(band), int(max_occ), int(chunk_seeds), 0, 0)
+        summ = _ffi.SeedjoinSummary()
+        count = C.c_uint64(0)
+        st = self.lib.aln_seqset_seed_join(self.handle, C.byref(spec), C.byref(b), C.byref(summ), C.byref(count))
+        runtime.raise_for_status(st, "aln_seqset_seed_join")
+        return Candidates(self, int(count.value), diags=True,
+                          summary=dict(seeds=int(summ.seeds), pairs_with_seed=int(summ.pairs_with_seed), words_dropped=int(summ.words_dropped),
+                                       chunks=int(summ.chunks)))
+
     def stats(self):
         """(after best, fetch_kernel_ms is the selection kernels' time until a held fetch overwrites it; after kmer_index and
         prefilter it is the index and sharing kernels' time)"""
@@ -317,10 +345,18 @@ class SeqSet:
 class Candidates:
     """The candidate list of SeqSet.prefilter: .index (pair numbers in the block), .q, .t (sequence numbers) and .shared (distinct
     words both sequences hold) in ascending pair order.  .score(...) aligns the candidates only, .hits(...) holds those at or above
-    a threshold as SeqSet.hits would, .best(...) the k best of every query's candidates as SeqSet.best would."""
+    a threshold as SeqSet.hits would, .best(...) the k best of every query's candidates as SeqSet.best would.  A list of
+    SeqSet.seed_join holds the seeds of the pair's best band in .shared, and has .diag (int32, the band's least diagonal) and .summary;
+    on the other routes both are None."""
 
-    def __init__(self, owner, count):
+    def __init__(self, owner, count, diags=False, summary=None):
         self.owner, self.count = owner, count
+        self.diag, self.summary = None, summary
+        if diags:
+            self.diag = np.zeros(count, dtype=np.int32)
+            if count:
+                st = owner.lib.aln_seqset_candidate_diags(owner.handle, 0, count, self.diag.ctypes.data)
+                runtime.raise_for_status(st, "aln_seqset_candidate_diags")
         self.index = np.zeros(count, dtype=np.uint64)
         self.q = np.zeros(count, dtype=np.uint32)
         self.t = np.zeros(count, dtype=np.uint32)
