@@ -15,7 +15,7 @@ SOURCES = ["aln_kernels.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip",
 # aln_kernels.hip is compiled as several translation units side by side (-DALN_TU=<mask of its ALN_PART_* families>): the fast
 # core-local batch kernel alone is half of the compile time
 KERNEL_UNITS = [("generic", 1), ("fast_cl", 2), ("fast_rest", 4), ("single", 8), ("tb", 16), ("fast_cl_solo", 32), ("fast_rest_solo", 64)]
-HEADERS = ["aln_arena_rules.h", "aln_best_rules.h", "aln_cigar_rules.h", "aln_cluster_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_layout_rules.h", "aln_loop_rules.h", "aln_msa_rules.h", "aln_plan_rules.h", "aln_prefilter_rules.h", "aln_profile_rules.h", "aln_report_rules.h", "aln_scheme_rules.h", "aln_search_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_signif_rules.h", "aln_strand_rules.h", "aln_transform_rules.h", "aln_wordjoin_rules.h", "aln_seedjoin_rules.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h"),
+HEADERS = ["aln_arena_rules.h", "aln_best_rules.h", "aln_cigar_rules.h", "aln_cluster_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_layout_rules.h", "aln_loop_rules.h", "aln_msa_rules.h", "aln_plan_rules.h", "aln_prefilter_rules.h", "aln_profile_rules.h", "aln_report_rules.h", "aln_scheme_rules.h", "aln_search_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_signif_rules.h", "aln_strand_rules.h", "aln_transform_rules.h", "aln_wordjoin_rules.h", "aln_seedjoin_rules.h", "aln_postings.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h"),
            os.path.join("..", "..", "include", "aligner_hip_cluster.h"), os.path.join("..", "..", "include", "aligner_hip_prefilter.h"),
            os.path.join("..", "..", "include", "aligner_hip_search.h"), os.path.join("..", "..", "include", "aligner_hip_profile.h"),
            os.path.join("..", "..", "include", "aligner_hip_msa.h"), os.path.join("..", "..", "include", "aligner_hip_cigar.h"),

@@ -2827,6 +2827,21 @@ struct BestPass { uint32_t slots; uint32_t flags; double f_min; };
 
 #define ALN_SEQSET_CHUNK_PAIRS (1ull << 22)        // per chunk: the pair limit of a chunk of aln_align_batch
 
+// the host's copy of a set's candidate list: pair numbers of `block`, ascending, with their sequence numbers and shared counts (a seed
+// join: seeds, and the diagonals beside them).  live: there is a list
+struct CandList {
+    bool live = false, has_diag = false;
+    aln_seqset_block block = {0, 0, 0, 0, 0, 0};
+    std::vector<uint64_t> pair;
+    std::vector<uint32_t> qs, ts, shared;
+    std::vector<int32_t> diag;
+    void clear()
+    {
+        live = has_diag = false;
+        pair.clear(); qs.clear(); ts.clear(); shared.clear(); diag.clear();
+    }
+};
+
 struct aln_seqset : CallStats {
     DevCtx *ctx = nullptr;            // one device: the context's first (as a staged batch)
     Slot *slot = nullptr;             // private slot; slot->seqs holds every sequence once, packed in set order
@@ -2837,22 +2852,7 @@ struct aln_seqset : CallStats {
     DevBuf d_off, d_len;              // the same tables on the device (the expansion reads them)
     // a chunk's gathered output: f | status; tile counts | offsets; the chunk's hits (pair number, f); [0] hit count, [2..3] first failure
     DevBuf fbuf, stbuf, tiles, hit_k, hit_f, misc;
-    // misc: 256 bytes of counters, 64 32-bit words.  Every call family's words, in one place:
-    //   words 0 .. 3   (bytes 0 .. 15)   a pass's chunk (seqset_pass_chunks): word 0 the chunk's hit count (the threshold selection),
-    //                                    bytes 8 .. 15 the first failed status (the gather).  Zeroed per chunk, read per chunk.
-    //   words 8, 9     (bytes 32 .. 39)  the k best: the rows' total (seqset_best_finish), 64 bits.  Written by the count kernel.
-    //   word 16        (byte 64)         the kept count of ONE compaction: a sharing chunk of aln_seqset_prefilter, and the selection of
-    //                                    aln_seqset_held_filter.  Both are written by the compaction's offsets step, which writes its
-    //                                    total whatever it is (aln_select.h: for n == 0 too), and both are read back by the call that
-    //                                    queued the kernel, behind a synchronize, before that call queues anything else or returns.  A
-    //                                    handle's calls run one at a time on the set's one stream, so the two users are never live
-    //                                    together and neither reads what the other left: no zeroing, no second word.
-    //   words 20 .. 22 (bytes 80 .. 91)  the word index: word 20 the distinct entries (written by its compaction); the word join, per
-    //                                    chunk: [20] kept pairs, [21] positions without a pair, [22] occurrences scanned, zeroed per chunk.
-    //   words 24 .. 28 (bytes 96 .. 115) the seed index: word 24 the occurrences (zeroed, then written by its count kernel); the seed join:
-    //                                    [24] kept pairs, [25] keys without a pair, [26] seeds scanned, [27] pairs with a seed, zeroed per
-    //                                    chunk, and [28] the dropped words, zeroed with the others before the plan.
-    // The other words are unused.  The arenas (cluster, profile, msa, cigar) carry their own counters and zero them per call.
+    // misc: ALN_SEQSET_MISC_WORDS counter words; which call family owns which word is aln_seqset_rules.h's ALN_SEQSET_MISC_*
     PinBuf h_out;                     // a chunk's f | status | misc on their way to the caller
     // held hits (aln_seqset_hits): the list lives on the host (it is what the re-fill was planned from); hit h is entry h of the
     // store -- until the next pass on this set
@@ -2897,13 +2897,11 @@ struct aln_seqset : CallStats {
     // sequence, resident until the next aln_seqset_kmer_index (kmer_k == 0: none built)
     uint32_t kmer_k = 0, kmer_alphabet = 0, kmer_stride = 0;
     DevBuf kmer_bits, kmer_n;
-    // the candidate list of aln_seqset_prefilter: the block's pair numbers resident (cand_k) and, with shared and the sequence numbers,
-    // on the host (the later passes are planned from this copy).  Separate from the held hits: until the next index, prefilter, destroy
-    bool cand = false;
-    aln_seqset_block cand_block = {0, 0, 0, 0, 0, 0};
+    // the candidate list of aln_seqset_prefilter or of a join: the block's pair numbers resident (cand_k) and the whole list on the
+    // host (cands: the later passes are planned from this copy).  Separate from the held hits: until the next index, prefilter,
+    // join, destroy
+    CandList cands;
     DevBuf cand_k, pf_shared, pf_keep, pf_out;      // pf_*: a sharing chunk's shared | keep flags | compacted shared
-    std::vector<uint64_t> cand_pair;
-    std::vector<uint32_t> cand_qs, cand_ts, cand_shared;
     // the sorted word index (aln_wordjoin_rules.h): the distinct (word, sequence) keys ascending and the word count per sequence,
     // resident until the next aln_seqset_word_index (word_k == 0: none built); beside the bitmap index, not in its place.  wj_*: what
     // a join plans with (where each entry's piece starts | its length | its offset in a chunk | the occurrences per query row) and a
@@ -2913,13 +2911,10 @@ struct aln_seqset : CallStats {
     DevBuf word_e, word_n, wj_first, wj_len, wj_off, wj_occ, wj_a, wj_b, wj_temp;
     // the positional word index (aln_seedjoin_rules.h): every occurrence's key and position, ascending by (word, sequence),
     // resident until the next aln_seqset_seed_index (seed_k == 0: none built); beside the other two indexes.  A seed join plans and
-    // sorts in the word join's wj_* buffers and brings sj_diag, a chunk's compacted diagonals.  cand_diag: the diagonals of a candidate
-    // list that aln_seqset_seed_join made (cand_has_diag), on the host beside cand_shared
+    // sorts in the word join's wj_* buffers and brings sj_diag, a chunk's compacted diagonals
     uint32_t seed_k = 0, seed_alphabet = 0;
     uint64_t seed_entries = 0;
     DevBuf seed_key, seed_pos, sj_diag;
-    bool cand_has_diag = false;
-    std::vector<int32_t> cand_diag;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a chunk's launches; 4, 5: the best selection
     // pair sets made by aln_pairset_create_from_set read the residue buffer: a destroy with some of them alive releases everything
     // else, moves the buffer here and leaves the rest to the last of them
@@ -2955,7 +2950,7 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
     slot_destroy(ss->slot);
     ss->slot = nullptr;
-    if (ss->derived) { ss->destroyed = true; ss->held = false; ss->cand = false; ss->kmer_k = 0; ss->word_k = 0; ss->seed_k = 0; return; }      // the residues go with the last derived pair set
+    if (ss->derived) { ss->destroyed = true; ss->held = false; ss->cands.clear(); ss->kmer_k = 0; ss->word_k = 0; ss->seed_k = 0; return; }      // the residues go with the last derived pair set
     delete ss;
 }
 
@@ -3002,7 +2997,7 @@ static aln_seqset *seqset_create(aln_ctx *ctx, const uint8_t *seqs, const uint64
         if (st == ALN_OK) st = dev_ensure(ss->d_off, 8ull * resident, false);
         if (st == ALN_OK) st = dev_ensure(ss->d_len, 4ull * resident, false);
         if (st == ALN_OK && stranded) st = dev_ensure(ss->strand_map, 256, false);
-        if (st == ALN_OK) st = dev_ensure(ss->misc, 256, false);
+        if (st == ALN_OK) st = dev_ensure(ss->misc, 4 * ALN_SEQSET_MISC_WORDS, false);
         if (st == ALN_OK) st = slot_init(*ss->slot);
         for (int i = 0; i < 6 && st == ALN_OK; ++i) { e = hipEventCreate(&ss->ev[i]); if (e != hipSuccess) st = fail(e, "hipEventCreate"); }
         if (st == ALN_OK) {
@@ -3107,7 +3102,7 @@ static int seqset_call(aln_seqset *ss, const aln_params *params, const aln_seqse
 static int seqset_cand_check(aln_seqset *ss)
 {
     if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (!ss->cand) { g_err = "no candidate list: aln_seqset_prefilter has not run, or a new k-mer index has replaced it"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ss->cands.live) { g_err = "no candidate list: aln_seqset_prefilter has not run, or a new k-mer index has replaced it"; return ALN_ERR_INVALID_ARGUMENT; }
     return ALN_OK;
 }
 
@@ -3125,16 +3120,16 @@ struct PairSource {
     {
         if (!list) return ALN_OK;
         const int st = seqset_cand_check(ss);
-        if (st == ALN_OK) b = &ss->cand_block;
+        if (st == ALN_OK) b = &ss->cands.block;
         return st;
     }
-    uint64_t positions() const { return list ? ss->cand_pair.size() : aln_seqset_block_pairs(ss->n, *b); }
+    uint64_t positions() const { return list ? ss->cands.pair.size() : aln_seqset_block_pairs(ss->n, *b); }
     // cells of all positions together (as a double, like aln_make_chunks): a block's out of the length sums
     double cells() const
     {
         if (list) {
             double sum = 0;
-            for (size_t h = 0; h < ss->cand_pair.size(); ++h) sum += (double)ss->len[ss->cand_qs[h]] * (double)ss->len[ss->cand_ts[h]];
+            for (size_t h = 0; h < ss->cands.pair.size(); ++h) sum += (double)ss->len[ss->cands.qs[h]] * (double)ss->len[ss->cands.ts[h]];
             return sum;
         }
         double sq = 0, st = 0, s2 = 0;
@@ -3151,7 +3146,7 @@ struct PairSource {
     // the sequence numbers of position `at`, and on to the next
     void step(uint64_t *q, uint64_t *t)
     {
-        if (list) { *q = ss->cand_qs[at]; *t = ss->cand_ts[at]; }
+        if (list) { *q = ss->cands.qs[at]; *t = ss->cands.ts[at]; }
         else { *q = cq; *t = ct; aln_seqset_next(*b, &cq, &ct); }
         ++at;
     }
@@ -3293,7 +3288,7 @@ static int seqset_pass_chunks(aln_seqset *ss, const Call &c, PairSource &src, do
             HIPCHK(hipEventRecord(ss->ev[4], q));
             if (src.list) {                            // the rows the chunk's candidates lie in
                 const uint64_t t_count = src.b->t_count;
-                const uint64_t row0 = aln_search_row(ss->cand_pair[k0], t_count), row1 = aln_search_row(ss->cand_pair[k0 + n - 1], t_count);
+                const uint64_t row0 = aln_search_row(ss->cands.pair[k0], t_count), row1 = aln_search_row(ss->cands.pair[k0 + n - 1], t_count);
                 aln_search_launch_chunk(ss->cand_k.as<uint64_t>(), ss->row_first.as<uint32_t>(), ss->fbuf.as<double>(), ss->stbuf.as<int32_t>(), k0, n, row0,
                                         row1 - row0 + 1, src.b, best->f_min, best->flags, best->slots, ss->cand_key.as<uint64_t>(),
                                         ss->cand_t.as<uint32_t>(), ss->run_key.as<uint64_t>(), ss->run_t.as<uint32_t>(), ss->run_n.as<uint32_t>(), q);
@@ -3416,8 +3411,8 @@ static int seqset_run_hits(PairSource src, const aln_params *params, double f_mi
     // the selection numbered a list's candidates by list position: the held list speaks of pairs of the block
     if (src.list)
         for (uint64_t &p : ss->hit_pair) {
-            if (p >= ss->cand_pair.size()) { g_err = "the selection's list leaves the candidate list"; seqset_begin(ss); return ALN_ERR_DEVICE; }
-            p = ss->cand_pair[p];
+            if (p >= ss->cands.pair.size()) { g_err = "the selection's list leaves the candidate list"; seqset_begin(ss); return ALN_ERR_DEVICE; }
+            p = ss->cands.pair[p];
         }
     if ((st = seqset_hold_list(ss, ct, b)) != ALN_OK) { seqset_begin(ss); return st; }
     ss->ms[3] = wall_ms(t0);
@@ -3556,13 +3551,11 @@ extern "C" int aln_seqset_best(aln_seqset *ss, const aln_params *params, const a
 // Words first, the dynamic programme on the candidates only.  The index and the candidate list are state of their own beside the held
 // hits; the candidate passes are the passes of score, hits and best over a PairSource that names the list: their chunks are runs of
 // consecutive list positions.
-static void seqset_drop_candidates(aln_seqset *ss)
-{
-    ss->cand = false;
-    ss->cand_pair.clear(); ss->cand_qs.clear(); ss->cand_ts.clear(); ss->cand_shared.clear();
-    ss->cand_has_diag = false;
-    ss->cand_diag.clear();
-}
+static void seqset_drop_candidates(aln_seqset *ss) { ss->cands.clear(); }
+
+// the refusals that every route to the candidate list words alike
+static const char *const CAND_SPEC_WORDS = "the spec's flags and reserved word must be 0";
+static const char *const CAND_BLOCK = "block: a range beyond the set, unequal ranges of an upper block, a reserved word, or no pairs";
 
 static int seqset_kmer_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
 {
@@ -3616,30 +3609,35 @@ static int seqset_cand_room(aln_seqset *ss, uint64_t used, uint64_t entries)
 }
 
 // What the three routes to the candidate list (prefilter, word join, seed join) do alike.
-// A chunk's `got` kept pairs, compacted behind the `total` that are there, come down with their shared counts (pf_out): the host
-// indexes its tables with this list, so it must be pairs k_lo .. k_end - 1 of the block, ascending (the stream is idle)
-static int seqset_cand_take(aln_seqset *ss, uint64_t total, uint64_t got, uint64_t k_lo, uint64_t k_end)
+// A chunk's `got` kept pairs, compacted behind the `total` that are there, come down with their shared counts (pf_out), 12 bytes per
+// pair: at most `room` of them (`more` says so), and the host indexes its tables with this list, so it must be pairs
+// k_lo .. k_end - 1 of the block, ascending (the stream is idle)
+static int seqset_cand_append(aln_seqset *ss, uint64_t total, uint64_t got, uint64_t room, const char *more, uint64_t k_lo, uint64_t k_end,
+                              uint64_t *down)
 {
+    if (got > room) { g_err = more; return ALN_ERR_DEVICE; }
+    if (total + got > 0xFFFFFFF0ull) { g_err = "too many candidates"; return ALN_ERR_UNSUPPORTED; }
+    *down += 12ull * got;
     if (!got) return ALN_OK;
-    ss->cand_pair.resize(total + got); ss->cand_shared.resize(total + got);
-    HIPCHK(hipMemcpy(ss->cand_pair.data() + total, ss->cand_k.as<uint64_t>() + total, 8ull * got, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ss->cand_shared.data() + total, ss->pf_out.p, 4ull * got, hipMemcpyDeviceToHost));
+    ss->cands.pair.resize(total + got); ss->cands.shared.resize(total + got);
+    HIPCHK(hipMemcpy(ss->cands.pair.data() + total, ss->cand_k.as<uint64_t>() + total, 8ull * got, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ss->cands.shared.data() + total, ss->pf_out.p, 4ull * got, hipMemcpyDeviceToHost));
     for (uint64_t i = total; i < total + got; ++i)
-        if (ss->cand_pair[i] < k_lo || ss->cand_pair[i] >= k_end || (i > total && ss->cand_pair[i] <= ss->cand_pair[i - 1])) { g_err = "the candidate list is not an ascending list of the chunk's pairs"; return ALN_ERR_DEVICE; }
+        if (ss->cands.pair[i] < k_lo || ss->cands.pair[i] >= k_end || (i > total && ss->cands.pair[i] <= ss->cands.pair[i - 1])) { g_err = "the candidate list is not an ascending list of the chunk's pairs"; return ALN_ERR_DEVICE; }
     return ALN_OK;
 }
 
 // the list is complete: its sequence numbers, and the state the candidate calls read
 static void seqset_cand_finish(aln_seqset *ss, const aln_seqset_block *b, uint64_t total, uint64_t *count)
 {
-    ss->cand_qs.resize(total); ss->cand_ts.resize(total);
+    ss->cands.qs.resize(total); ss->cands.ts.resize(total);
     for (uint64_t i = 0; i < total; ++i) {
         uint64_t sq, tq;
-        aln_seqset_unrank(*b, ss->cand_pair[i], &sq, &tq);
-        ss->cand_qs[i] = (uint32_t)sq; ss->cand_ts[i] = (uint32_t)tq;
+        aln_seqset_unrank(*b, ss->cands.pair[i], &sq, &tq);
+        ss->cands.qs[i] = (uint32_t)sq; ss->cands.ts[i] = (uint32_t)tq;
     }
-    ss->cand = true;
-    ss->cand_block = *b;
+    ss->cands.live = true;
+    ss->cands.block = *b;
     *count = total;
 }
 
@@ -3665,10 +3663,10 @@ static int seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *sp, const 
     if (!aln_prefilter_bits(sp->k, sp->alphabet)) { g_err = "k must lie in 1 .. 8, the alphabet size be at least 1 and alphabet^k at most 2^18"; return ALN_ERR_INVALID_ARGUMENT; }
     if (!ss->kmer_k || sp->k != ss->kmer_k || sp->alphabet != ss->kmer_alphabet) { g_err = "no k-mer index of this k and alphabet: aln_seqset_kmer_index builds it"; return ALN_ERR_INVALID_ARGUMENT; }
     if (sp->min_per_1024 > ALN_PREFILTER_MAX_PER_1024) { g_err = "min_per_1024 must lie in 0 .. 1024"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (sp->flags != 0u || sp->reserved != 0u) { g_err = "the spec's flags and reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->flags != 0u || sp->reserved != 0u) { g_err = CAND_SPEC_WORDS; return ALN_ERR_INVALID_ARGUMENT; }
     if (sp->chunk_pairs > ALN_PREFILTER_CHUNK_PAIRS) { g_err = "chunk_pairs must lie in 0 .. 2^22"; return ALN_ERR_INVALID_ARGUMENT; }
     const uint64_t pairs = aln_seqset_block_pairs(ss->n, *b);
-    if (pairs == 0) { g_err = "block: a range beyond the set, unequal ranges of an upper block, a reserved word, or no pairs"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (pairs == 0) { g_err = CAND_BLOCK; return ALN_ERR_INVALID_ARGUMENT; }
     HIPCHK(hipSetDevice(ss->ctx->device));
     hipStream_t q = ss->slot->stream;
     HIPCHK(hipStreamSynchronize(q));
@@ -3695,7 +3693,7 @@ static int seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *sp, const 
             if ((st = dev_ensure(ss->pf_out, 4 * n, false)) != ALN_OK) return st;
             if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(n), &tile_count, &tile_off)) != ALN_OK) return st;
             if ((st = seqset_cand_room(ss, total, total + n)) != ALN_OK) return st;
-            uint32_t *d_count = ss->misc.as<uint32_t>() + 16;          // (words 0 .. 9 belong to the passes and to best)
+            uint32_t *d_count = ss->misc.as<uint32_t>() + ALN_SEQSET_MISC_COMPACT;
             HIPCHK(hipEventRecord(ss->ev[0], q));
             aln_prefilter_launch_share(ss->kmer_bits.as<uint32_t>(), ss->kmer_n.as<uint32_t>(), ss->kmer_stride, b, k0, n, q_lo, q_hi - q_lo + 1, t_lo,
                                        t_count, sp->min_shared, sp->min_per_1024, ss->pf_shared.as<uint32_t>(), ss->pf_keep.as<uint8_t>(), q);
@@ -3709,10 +3707,7 @@ static int seqset_prefilter(aln_seqset *ss, const aln_prefilter_spec *sp, const 
             HIPCHK(hipStreamSynchronize(q));
             kernels += ev_ms(ss->ev[0], ss->ev[1]);
             down += 8;
-            if (got > n) { g_err = "the compaction kept more pairs than the chunk holds"; return ALN_ERR_DEVICE; }
-            if (total + got > 0xFFFFFFF0ull) { g_err = "too many candidates"; return ALN_ERR_UNSUPPORTED; }
-            if ((st = seqset_cand_take(ss, total, got, k0, k0 + n)) != ALN_OK) return st;
-            down += 12ull * got;
+            if ((st = seqset_cand_append(ss, total, got, n, "the compaction kept more pairs than the chunk holds", k0, k0 + n, &down)) != ALN_OK) return st;
             total += got;
         }
         return ALN_OK;
@@ -3738,12 +3733,12 @@ extern "C" int aln_seqset_candidates(aln_seqset *ss, uint64_t first, uint64_t n,
 {
     int st = seqset_cand_check(ss);
     if (st != ALN_OK) return st;
-    const uint64_t have = ss->cand_pair.size();
+    const uint64_t have = ss->cands.pair.size();
     if (first > have || n > have - first) { g_err = "range beyond the candidate list"; return ALN_ERR_INVALID_ARGUMENT; }
     if (n && (!pair_index || !q_seq || !t_seq || !shared)) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     for (uint64_t i = 0; i < n; ++i) {
-        pair_index[i] = ss->cand_pair[first + i]; q_seq[i] = ss->cand_qs[first + i]; t_seq[i] = ss->cand_ts[first + i];
-        shared[i] = ss->cand_shared[first + i];
+        pair_index[i] = ss->cands.pair[first + i]; q_seq[i] = ss->cands.qs[first + i]; t_seq[i] = ss->cands.ts[first + i];
+        shared[i] = ss->cands.shared[first + i];
     }
     return ALN_OK;                       // (no byte moves and no kernel runs: the stats stay as they are)
 }
@@ -3763,17 +3758,19 @@ extern "C" int aln_seqset_candidate_best(aln_seqset *ss, const aln_params *param
     ALN_GUARDED(seqset_live(ss), seqset_run_best(PairSource{ss, true, nullptr}, params, k, f_min, flags, count))
 }
 
-// ---------------------------------------------------------------- the sorted word index and its join (include/aligner_hip_wordjoin.h)
-// The prefilter's candidate list by another road: every (word, sequence) sorted once, the pairs named by the posting lists.  What it
-// leaves behind is the candidate state above, so the candidate passes, aln_seqset_candidates and the held calls know no difference.
+// ---------------------------------------------------------------- the posting-list routes: the sorted word index and its join
+// (include/aligner_hip_wordjoin.h), the positional word index and the seed join (include/aligner_hip_seedjoin.h)
+// The prefilter's candidate list by two more roads.  The word index holds every (word, sequence) once, sorted, and its join names the
+// pairs by the posting lists; the seed index keeps every occurrence with its position, and its join judges a pair by the most seeds
+// it has within one band of diagonals.  What either leaves behind is the candidate state above (`shared` holds seeds after a seed
+// join, the diagonals lie beside it), so the candidate passes, aln_seqset_candidates and the held calls know no difference.
 static const char *const WORDJOIN_RANGE = "k must lie in 1 .. 8, the alphabet size be at least 1 and alphabet^k at most 2^32";
+static const char *const SEEDJOIN_RANGE = "k must lie in 1 .. 16, the alphabet size be at least 1 and alphabet^k at most 2^32";
 
-static int seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
+// ---- both index builds: the key of every residue position, sorted by (word, seq); then the word index keeps the distinct keys and
+// n(s), the seed index (seed) every occurrence with its position.  *entries: how many it holds
+static int seqset_posting_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint64_t words, bool seed, uint32_t *n_words, uint32_t *entries)
 {
-    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    const uint64_t words = aln_wordjoin_words(k, alphabet);
-    if (!words) { g_err = WORDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
-    if (ss->total > 0x7FFFFFFFull) { g_err = "a word index holds fewer than 2^31 residue positions"; return ALN_ERR_UNSUPPORTED; }
     HIPCHK(hipSetDevice(ss->ctx->device));
     hipStream_t q = ss->slot->stream;
     HIPCHK(hipStreamSynchronize(q));
@@ -3781,58 +3778,228 @@ static int seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint
     const uint64_t total = ss->total;
     uint32_t seq_end, word_end;
     aln_wordjoin_sort_bits(words, ss->n, &seq_end, &word_end);
-    // everything new first: a failure leaves the old index and the candidate list as they were
-    DevBuf keys_a, keys_b, temp, entries, counts;
+    // everything new first: a failure leaves the old index and the candidate list as they were.  a | b: the keys before | after a
+    // pass of the sort, pos_*: their positions; keep: the resident list; aux: n(s), or the resident positions
+    DevBuf a, b, pos_a, pos_b, temp, keep, aux;
     std::vector<uint32_t> counts_h(n_words ? ss->n : 0);
     uint32_t got = 0;
+    uint32_t *d_count = ss->misc.as<uint32_t>() + (seed ? ALN_SEQSET_MISC_SEED : ALN_SEQSET_MISC_WORD) + ALN_JOIN_MISC_KEPT;
+    auto pass = [&](uint32_t begin, uint32_t end) -> int {      // a -> b over bits begin .. end - 1, then the names change places
+        if (seed) HIPCHK((hipError_t)aln_seedjoin_launch_sort_pairs(temp.p, temp.cap, a.as<uint64_t>(), b.as<uint64_t>(), pos_a.as<uint32_t>(), pos_b.as<uint32_t>(), total, begin, end, q));
+        else HIPCHK((hipError_t)aln_wordjoin_launch_sort(temp.p, temp.cap, a.as<uint64_t>(), b.as<uint64_t>(), total, begin, end, q));
+        std::swap(a, b); std::swap(pos_a, pos_b);
+        return ALN_OK;
+    };
     const int st = run_queued(q, [&]() -> int {
         int st;
         size_t temp_bytes = 0;
-        HIPCHK((hipError_t)aln_wordjoin_sort_temp_bytes(total, &temp_bytes));
-        if ((st = dev_ensure(keys_a, 8 * total, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(keys_b, 8 * total, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(temp, temp_bytes, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(counts, 4ull * ss->n, false)) != ALN_OK) return st;
         uint32_t *tile_count = nullptr, *tile_off = nullptr;
-        if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(total), &tile_count, &tile_off)) != ALN_OK) return st;
-        uint32_t *d_count = ss->misc.as<uint32_t>() + 20;
+        if (seed) HIPCHK((hipError_t)aln_seedjoin_sort_pairs_temp_bytes(total, &temp_bytes));
+        else HIPCHK((hipError_t)aln_wordjoin_sort_temp_bytes(total, &temp_bytes));
+        if ((st = dev_ensure(a, 8 * total, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(b, 8 * total, false)) != ALN_OK) return st;
+        if (seed && (st = dev_ensure(pos_a, 4 * total, false)) != ALN_OK) return st;
+        if (seed && (st = dev_ensure(pos_b, 4 * total, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(temp, temp_bytes, false)) != ALN_OK) return st;
+        if (!seed && (st = dev_ensure(aux, 4ull * ss->n, false)) != ALN_OK) return st;
+        if (!seed && (st = tiles_ensure(ss->tiles, aln_seqset_tiles(total), &tile_count, &tile_off)) != ALN_OK) return st;
         HIPCHK(hipEventRecord(ss->ev[0], q));
-        HIPCHK(hipMemsetAsync(counts.p, 0, std::max<size_t>(4ull * ss->n, 4), q));
-        aln_wordjoin_launch_keys(ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), ss->n, total, k, alphabet,
-                                 keys_a.as<uint64_t>(), q);
-        HIPCHK(hipGetLastError());
-        // a full word field is sorted as the whole key in one pass (what the launcher asks of a range that ends at bit 64): the bits
-        // between the fields are zero in every word's key, so the order is that of the two passes
-        if (word_end == 64u) {
-            HIPCHK((hipError_t)aln_wordjoin_launch_sort(temp.p, temp.cap, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), total, 0, 64, q));
-            std::swap(keys_a, keys_b);
+        if (seed) {
+            HIPCHK(hipMemsetAsync(d_count, 0, 4, q));
+            aln_seedjoin_launch_keys(ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), ss->n, total, k, alphabet,
+                                     a.as<uint64_t>(), pos_a.as<uint32_t>(), q);
         } else {
-            HIPCHK((hipError_t)aln_wordjoin_launch_sort(temp.p, temp.cap, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), total, 0, seq_end, q));
-            HIPCHK((hipError_t)aln_wordjoin_launch_sort(temp.p, temp.cap, keys_b.as<uint64_t>(), keys_a.as<uint64_t>(), total, 32, word_end, q));
+            HIPCHK(hipMemsetAsync(aux.p, 0, std::max<size_t>(4ull * ss->n, 4), q));
+            aln_wordjoin_launch_keys(ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), ss->n, total, k, alphabet,
+                                     a.as<uint64_t>(), q);
         }
-        aln_wordjoin_launch_distinct(keys_a.as<uint64_t>(), total, tile_count, tile_off, d_count, total, keys_b.as<uint64_t>(), ss->n,
-                                     counts.as<uint32_t>(), q);
+        HIPCHK(hipGetLastError());
+        // the sequence's bits, then the word's.  A full word field is sorted as the whole key in one pass (what the launcher asks of a
+        // range that ends at bit 64): the bits between the fields are zero in every word's key, so the order is that of the two passes
+        if (word_end == 64u) st = pass(0, 64);
+        else if ((st = pass(0, seq_end)) == ALN_OK) st = pass(32, word_end);
+        if (st != ALN_OK) return st;
+        // a is sorted: the occurrences are the keys in front of the all-ones keys; the entries are the distinct ones, compacted into b
+        if (!seed) aln_wordjoin_launch_distinct(a.as<uint64_t>(), total, tile_count, tile_off, d_count, total, b.as<uint64_t>(), ss->n, aux.as<uint32_t>(), q);
+        else if (total) aln_seedjoin_launch_count(a.as<uint64_t>(), total, d_count, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ss->ev[1], q));
         HIPCHK(hipMemcpyAsync(&got, d_count, 4, hipMemcpyDeviceToHost, q));
-        if (n_words && ss->n) HIPCHK(hipMemcpyAsync(counts_h.data(), counts.p, 4ull * ss->n, hipMemcpyDeviceToHost, q));
+        if (n_words && ss->n) HIPCHK(hipMemcpyAsync(counts_h.data(), aux.p, 4ull * ss->n, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
-        if (got > total) { g_err = "the word index holds more entries than the set has windows"; return ALN_ERR_DEVICE; }
+        if (got > total) {
+            g_err = seed ? "the seed index holds more occurrences than the set has windows" : "the word index holds more entries than the set has windows";
+            return ALN_ERR_DEVICE;
+        }
         // the resident list at its own size; the sort's buffers go
-        if ((st = dev_ensure(entries, 8ull * got, false)) != ALN_OK) return st;
-        if (got) HIPCHK(hipMemcpy(entries.p, keys_b.p, 8ull * got, hipMemcpyDeviceToDevice));
+        if ((st = dev_ensure(keep, 8ull * got, false)) != ALN_OK) return st;
+        if (seed && (st = dev_ensure(aux, 4ull * got, false)) != ALN_OK) return st;
+        if (got) HIPCHK(hipMemcpy(keep.p, seed ? a.p : b.p, 8ull * got, hipMemcpyDeviceToDevice));
+        if (seed && got) HIPCHK(hipMemcpy(aux.p, pos_a.p, 4ull * got, hipMemcpyDeviceToDevice));
         return ALN_OK;
     });
-    dev_free(keys_a); dev_free(keys_b); dev_free(temp);
-    if (st != ALN_OK) { dev_free(entries); dev_free(counts); return st; }
-    dev_free(ss->word_e); dev_free(ss->word_n);
-    ss->word_e = entries; ss->word_n = counts;
-    ss->word_k = k; ss->word_alphabet = alphabet; ss->word_entries = got;
+    for (DevBuf *d : {&a, &b, &pos_a, &pos_b, &temp}) dev_free(*d);
+    if (st != ALN_OK) { dev_free(keep); dev_free(aux); return st; }
+    DevBuf &list = seed ? ss->seed_key : ss->word_e, &beside = seed ? ss->seed_pos : ss->word_n;
+    dev_free(list); dev_free(beside);
+    list = keep; beside = aux;
+    (seed ? ss->seed_k : ss->word_k) = k; (seed ? ss->seed_alphabet : ss->word_alphabet) = alphabet; (seed ? ss->seed_entries : ss->word_entries) = got;
     seqset_drop_candidates(ss);
     if (n_words && ss->n) memcpy(n_words, counts_h.data(), 4ull * ss->n);
+    *entries = got;
     seqset_done(ss, t0, 0, 4 + (n_words ? 4ull * ss->n : 0));
     return ALN_OK;
 }
+
+static int seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint32_t *n_words)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t words = aln_wordjoin_words(k, alphabet);
+    if (!words) { g_err = WORDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ss->total > 0x7FFFFFFFull) { g_err = "a word index holds fewer than 2^31 residue positions"; return ALN_ERR_UNSUPPORTED; }
+    uint32_t entries;
+    return seqset_posting_index(ss, k, alphabet, words, false, n_words, &entries);
+}
+
+static int seqset_seed_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint64_t *occurrences)
+{
+    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t words = aln_seedjoin_words(k, alphabet);
+    if (!words) { g_err = SEEDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
+    if (ss->total > 0x7FFFFFFFull) { g_err = "a seed index holds fewer than 2^31 residue positions"; return ALN_ERR_UNSUPPORTED; }
+    uint32_t entries;
+    const int st = seqset_posting_index(ss, k, alphabet, words, true, nullptr, &entries);
+    if (st == ALN_OK && occurrences) *occurrences = entries;
+    return st;
+}
+
+// ---- both joins over an index of n keys.  A Route names the index, its block of the set's counter words (misc: a chunk zeroes and
+// reads WORDS of them; the plan's PLAN_WORDS lie behind those and come down into plan_h) and its messages, and adds:
+//   plan(q)                      the plan launch into wj_first / wj_len / wj_occ
+//   cut(per_row, first)          the rows of the chunk that starts at row `first`; 0: that row alone is above the cap (OVER)
+//   ensure(k)                    the chunk's buffers beside wj_a / wj_b / wj_temp
+//   queue(q, k, tiles, out_k)    expand -> sort -> append, between the chunk's two events
+//   sound(h, k)                  what else must hold of the chunk's counter words h
+//   take(h, k, at, got, down)    what comes down per kept pair beside the 12 bytes of seqset_cand_append
+struct JoinChunk { uint64_t m, q_lo, q_rows, k_lo, k_end, room; };      // m occurrences; the rows; their pairs; the most it can keep
+
+template <class Route> static int seqset_join(aln_seqset *ss, const aln_seqset_block *b, Route &r, uint64_t *chunks, uint64_t *count)
+{
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t rows = b->q_count;
+    uint64_t total = 0, down = 0;
+    double kernels = 0;
+    int st;
+    // ---- the plan: nothing of the set's state is touched before the rows are cut
+    std::vector<uint64_t> per_row(rows, 0), chunk_first, chunk_rows, chunk_sum;
+    st = run_queued(q, [&]() -> int {
+        if ((st = dev_ensure(ss->wj_first, 4 * r.n, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->wj_len, 4 * r.n, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->wj_off, 4 * r.n, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->wj_occ, 8 * rows, false)) != ALN_OK) return st;
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        HIPCHK(hipMemsetAsync(ss->wj_occ.p, 0, 8 * rows, q));
+        if ((st = r.plan(q)) != ALN_OK) return st;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(per_row.data(), ss->wj_occ.p, 8 * rows, hipMemcpyDeviceToHost, q));
+        if constexpr (Route::PLAN_WORDS != 0) HIPCHK(hipMemcpyAsync(r.plan_h, r.misc + Route::WORDS, 4 * Route::PLAN_WORDS, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        kernels += ev_ms(ss->ev[0], ss->ev[1]);
+        down += 8 * rows + 4 * Route::PLAN_WORDS;
+        return seqset_cut_rows(per_row, [&](uint64_t first) { return r.cut(per_row.data(), first); }, Route::OVER, chunk_first, chunk_rows, chunk_sum);
+    });
+    if (st != ALN_OK) return st;
+    seqset_drop_candidates(ss);
+    st = run_queued(q, [&]() -> int {
+        if ((st = seqset_cand_room(ss, 0, 1)) != ALN_OK) return st;      // (an empty list is resident too, as the prefilter's is)
+        for (size_t c = 0; c < chunk_first.size(); ++c) {
+            // the chunk's pairs: the pair numbers of its rows
+            const uint64_t first = chunk_first[c], end = first + chunk_rows[c];
+            const uint64_t k_lo = b->upper ? aln_seqset_row_start(rows, first) : first * b->t_count;
+            const uint64_t k_end = b->upper ? aln_seqset_row_start(rows, end) : end * b->t_count;
+            const JoinChunk k = {chunk_sum[c], b->q_first + first, chunk_rows[c], k_lo, k_end, std::min(chunk_sum[c], k_end - k_lo)};
+            size_t temp_bytes = 0;
+            HIPCHK((hipError_t)aln_wordjoin_sort_temp_bytes(k.m, &temp_bytes));
+            uint32_t *tile_count = nullptr, *tile_off = nullptr;
+            if ((st = dev_ensure(ss->wj_a, 8 * k.m, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->wj_b, 8 * k.m, false)) != ALN_OK) return st;
+            if ((st = dev_ensure(ss->wj_temp, temp_bytes, false)) != ALN_OK) return st;
+            if ((st = r.ensure(k)) != ALN_OK) return st;
+            if ((st = tiles_ensure(ss->tiles, std::max(aln_seqset_tiles(r.n), aln_seqset_tiles(k.m)), &tile_count, &tile_off)) != ALN_OK) return st;
+            if ((st = seqset_cand_room(ss, total, total + k.room)) != ALN_OK) return st;
+            HIPCHK(hipEventRecord(ss->ev[0], q));
+            HIPCHK(hipMemsetAsync(r.misc, 0, 4 * Route::WORDS, q));
+            aln_wordjoin_launch_offsets(r.keys, ss->wj_len.as<uint32_t>(), r.n, k.q_lo, k.q_rows, tile_count, tile_off, r.misc + ALN_JOIN_MISC_SCANNED,
+                                        ss->wj_off.as<uint32_t>(), q);
+            HIPCHK(hipGetLastError());
+            if ((st = r.queue(q, k, tile_count, tile_off, ss->cand_k.as<uint64_t>() + total)) != ALN_OK) return st;
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ss->ev[1], q));
+            uint32_t h[Route::WORDS] = {};
+            HIPCHK(hipMemcpyAsync(h, r.misc, 4 * Route::WORDS, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipStreamSynchronize(q));
+            kernels += ev_ms(ss->ev[0], ss->ev[1]);
+            down += 4 * Route::WORDS;
+            const uint64_t got = h[ALN_JOIN_MISC_KEPT];
+            if (h[ALN_JOIN_MISC_SCANNED] != k.m) { g_err = Route::SCANNED; return ALN_ERR_DEVICE; }
+            if (h[ALN_JOIN_MISC_NO_PAIR]) { g_err = Route::NO_PAIR; return ALN_ERR_DEVICE; }
+            const char *const more = "the join kept more pairs than the chunk's rows hold";
+            if (!r.sound(h, k)) { g_err = more; return ALN_ERR_DEVICE; }
+            if ((st = seqset_cand_append(ss, total, got, k.room, more, k.k_lo, k.k_end, &down)) != ALN_OK) return st;
+            if ((st = r.take(h, k, total, got, &down)) != ALN_OK) return st;
+            total += got;
+        }
+        return ALN_OK;
+    });
+    if (st != ALN_OK) { seqset_drop_candidates(ss); return st; }
+    seqset_cand_finish(ss, b, total, count);
+    *chunks = chunk_first.size();
+    seqset_done(ss, t0, 0, down, kernels);
+    return ALN_OK;
+}
+
+// bytes down: 8 per query row, 12 per chunk and 12 per candidate
+struct WordJoinRoute {
+    aln_seqset *ss;
+    const aln_wordjoin_spec *sp;
+    const aln_seqset_block *b;
+    uint64_t pairs, cap, n = ss->word_entries;
+    const uint64_t *keys = ss->word_e.as<uint64_t>();
+    uint32_t *misc = ss->misc.as<uint32_t>() + ALN_SEQSET_MISC_WORD;
+    static constexpr uint32_t WORDS = ALN_SEQSET_MISC_WORD_WORDS, PLAN_WORDS = 0;
+    static constexpr const char *OVER = "one query row of the block has more occurrences than chunk_occurrences allows";
+    static constexpr const char *SCANNED = "a chunk's occurrences differ from the plan's", *NO_PAIR = "an occurrence of the join names no pair of the block";
+    int plan(hipStream_t q)
+    {
+        aln_wordjoin_launch_plan(keys, n, b, ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(), ss->wj_occ.as<uint64_t>(), q);
+        return ALN_OK;
+    }
+    uint64_t cut(const uint64_t *occ, uint64_t first) const { return aln_wordjoin_cut(occ, b->q_count, first, cap); }
+    int ensure(const JoinChunk &k)
+    {
+        int st;
+        if ((st = dev_ensure(ss->pf_shared, 4 * k.m, false)) != ALN_OK || (st = dev_ensure(ss->pf_keep, k.m, false)) != ALN_OK) return st;
+        return dev_ensure(ss->pf_out, 4 * k.room, false);
+    }
+    int queue(hipStream_t q, const JoinChunk &k, uint32_t *tile_count, uint32_t *tile_off, uint64_t *out_k)
+    {
+        aln_wordjoin_launch_expand(keys, ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(), ss->wj_off.as<uint32_t>(), n, k.m, b, pairs, k.q_lo,
+                                   k.q_rows, ss->wj_a.as<uint64_t>(), misc + ALN_JOIN_MISC_NO_PAIR, q);
+        HIPCHK(hipGetLastError());
+        const uint32_t pair_bits = std::max<uint32_t>(aln_wordjoin_bits_needed(pairs), 1u);
+        HIPCHK((hipError_t)aln_wordjoin_launch_sort(ss->wj_temp.p, ss->wj_temp.cap, ss->wj_a.as<uint64_t>(), ss->wj_b.as<uint64_t>(), k.m, 0, pair_bits, q));
+        aln_wordjoin_launch_append(ss->wj_b.as<uint64_t>(), k.m, b, pairs, ss->word_n.as<uint32_t>(), ss->n, sp->min_shared, sp->min_per_1024,
+                                   ss->pf_shared.as<uint32_t>(), ss->pf_keep.as<uint8_t>(), tile_count, tile_off, misc + ALN_JOIN_MISC_KEPT, k.room, out_k,
+                                   ss->pf_out.as<uint32_t>(), q);
+        return ALN_OK;
+    }
+    bool sound(const uint32_t *, const JoinChunk &) const { return true; }
+    int take(const uint32_t *, const JoinChunk &, uint64_t, uint64_t, uint64_t *) { return ALN_OK; }
+};
 
 static int seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *sp, const aln_seqset_block *b, uint64_t *count)
 {
@@ -3841,95 +4008,86 @@ static int seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *sp, const a
     if (!ss->word_k || sp->k != ss->word_k || sp->alphabet != ss->word_alphabet) { g_err = "no word index of this k and alphabet: aln_seqset_word_index builds it"; return ALN_ERR_INVALID_ARGUMENT; }
     if (sp->min_shared == 0u) { g_err = "min_shared must be at least 1: a join sees only the pairs that share a word"; return ALN_ERR_INVALID_ARGUMENT; }
     if (sp->min_per_1024 > ALN_PREFILTER_MAX_PER_1024) { g_err = "min_per_1024 must lie in 0 .. 1024"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (sp->flags != 0u || sp->reserved != 0u) { g_err = "the spec's flags and reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->flags != 0u || sp->reserved != 0u) { g_err = CAND_SPEC_WORDS; return ALN_ERR_INVALID_ARGUMENT; }
     if (sp->chunk_occurrences > ALN_WORDJOIN_MAX_CHUNK_OCCURRENCES) { g_err = "chunk_occurrences must lie in 0 .. 2^26"; return ALN_ERR_INVALID_ARGUMENT; }
     const uint64_t pairs = aln_seqset_block_pairs(ss->n, *b);
-    if (pairs == 0) { g_err = "block: a range beyond the set, unequal ranges of an upper block, a reserved word, or no pairs"; return ALN_ERR_INVALID_ARGUMENT; }
-    HIPCHK(hipSetDevice(ss->ctx->device));
-    hipStream_t q = ss->slot->stream;
-    HIPCHK(hipStreamSynchronize(q));
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t cap = sp->chunk_occurrences ? sp->chunk_occurrences : ALN_WORDJOIN_CHUNK_OCCURRENCES;
-    const uint64_t n_e = ss->word_entries, rows = b->q_count;
-    const uint32_t pair_bits = std::max<uint32_t>(aln_wordjoin_bits_needed(pairs), 1u);
-    uint64_t total = 0, down = 0;
-    double kernels = 0;
-    int st;
-    // ---- the plan: nothing of the set's state is touched before the rows are cut
-    std::vector<uint64_t> occ(rows, 0);
-    std::vector<uint64_t> chunk_first, chunk_rows, chunk_occ;
-    st = run_queued(q, [&]() -> int {
-        if ((st = dev_ensure(ss->wj_first, 4 * n_e, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(ss->wj_len, 4 * n_e, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(ss->wj_off, 4 * n_e, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(ss->wj_occ, 8 * rows, false)) != ALN_OK) return st;
-        HIPCHK(hipEventRecord(ss->ev[0], q));
-        HIPCHK(hipMemsetAsync(ss->wj_occ.p, 0, 8 * rows, q));
-        aln_wordjoin_launch_plan(ss->word_e.as<uint64_t>(), n_e, b, ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(), ss->wj_occ.as<uint64_t>(), q);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ss->ev[1], q));
-        HIPCHK(hipMemcpyAsync(occ.data(), ss->wj_occ.p, 8 * rows, hipMemcpyDeviceToHost, q));
-        HIPCHK(hipStreamSynchronize(q));
-        kernels += ev_ms(ss->ev[0], ss->ev[1]);
-        down += 8 * rows;
-        return seqset_cut_rows(occ, [&](uint64_t first) { return aln_wordjoin_cut(occ.data(), rows, first, cap); },
-                               "one query row of the block has more occurrences than chunk_occurrences allows", chunk_first, chunk_rows, chunk_occ);
-    });
-    if (st != ALN_OK) return st;
-    seqset_drop_candidates(ss);
-    st = run_queued(q, [&]() -> int {
-        if ((st = seqset_cand_room(ss, 0, 1)) != ALN_OK) return st;      // (an empty list is resident too, as the prefilter's is)
-        for (size_t c = 0; c < chunk_first.size(); ++c) {
-            const uint64_t m = chunk_occ[c], q_lo = b->q_first + chunk_first[c], q_rows = chunk_rows[c];
-            // the chunk's pairs: the pair numbers of its rows
-            const uint64_t k_lo = b->upper ? aln_seqset_row_start(rows, chunk_first[c]) : chunk_first[c] * b->t_count;
-            const uint64_t k_end = b->upper ? aln_seqset_row_start(rows, chunk_first[c] + q_rows) : (chunk_first[c] + q_rows) * b->t_count;
-            const uint64_t room = std::min(m, k_end - k_lo);
-            size_t temp_bytes = 0;
-            HIPCHK((hipError_t)aln_wordjoin_sort_temp_bytes(m, &temp_bytes));
-            uint32_t *tile_count = nullptr, *tile_off = nullptr;
-            if ((st = dev_ensure(ss->wj_a, 8 * m, false)) != ALN_OK) return st;
-            if ((st = dev_ensure(ss->wj_b, 8 * m, false)) != ALN_OK) return st;
-            if ((st = dev_ensure(ss->wj_temp, temp_bytes, false)) != ALN_OK) return st;
-            if ((st = dev_ensure(ss->pf_shared, 4 * m, false)) != ALN_OK) return st;
-            if ((st = dev_ensure(ss->pf_keep, m, false)) != ALN_OK) return st;
-            if ((st = dev_ensure(ss->pf_out, 4 * room, false)) != ALN_OK) return st;
-            if ((st = tiles_ensure(ss->tiles, std::max(aln_seqset_tiles(n_e), aln_seqset_tiles(m)), &tile_count, &tile_off)) != ALN_OK) return st;
-            if ((st = seqset_cand_room(ss, total, total + room)) != ALN_OK) return st;
-            uint32_t *d_words = ss->misc.as<uint32_t>() + 20;          // [0] kept pairs, [1] positions without a pair, [2] occurrences scanned
-            HIPCHK(hipEventRecord(ss->ev[0], q));
-            HIPCHK(hipMemsetAsync(d_words, 0, 12, q));
-            aln_wordjoin_launch_offsets(ss->word_e.as<uint64_t>(), ss->wj_len.as<uint32_t>(), n_e, q_lo, q_rows, tile_count, tile_off, d_words + 2,
-                                        ss->wj_off.as<uint32_t>(), q);
-            HIPCHK(hipGetLastError());
-            aln_wordjoin_launch_expand(ss->word_e.as<uint64_t>(), ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(), ss->wj_off.as<uint32_t>(), n_e, m,
-                                       b, pairs, q_lo, q_rows, ss->wj_a.as<uint64_t>(), d_words + 1, q);
-            HIPCHK(hipGetLastError());
-            HIPCHK((hipError_t)aln_wordjoin_launch_sort(ss->wj_temp.p, ss->wj_temp.cap, ss->wj_a.as<uint64_t>(), ss->wj_b.as<uint64_t>(), m, 0, pair_bits, q));
-            aln_wordjoin_launch_append(ss->wj_b.as<uint64_t>(), m, b, pairs, ss->word_n.as<uint32_t>(), ss->n, sp->min_shared, sp->min_per_1024,
-                                       ss->pf_shared.as<uint32_t>(), ss->pf_keep.as<uint8_t>(), tile_count, tile_off, d_words, room,
-                                       ss->cand_k.as<uint64_t>() + total, ss->pf_out.as<uint32_t>(), q);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(ss->ev[1], q));
-            uint32_t h[3] = {0, 0, 0};
-            HIPCHK(hipMemcpyAsync(h, d_words, 12, hipMemcpyDeviceToHost, q));
-            HIPCHK(hipStreamSynchronize(q));
-            kernels += ev_ms(ss->ev[0], ss->ev[1]);
-            down += 12;
-            const uint64_t got = h[0];
-            if (h[2] != m) { g_err = "a chunk's occurrences differ from the plan's"; return ALN_ERR_DEVICE; }
-            if (h[1]) { g_err = "an occurrence of the join names no pair of the block"; return ALN_ERR_DEVICE; }
-            if (got > room) { g_err = "the join kept more pairs than the chunk's rows hold"; return ALN_ERR_DEVICE; }
-            if (total + got > 0xFFFFFFF0ull) { g_err = "too many candidates"; return ALN_ERR_UNSUPPORTED; }
-            if ((st = seqset_cand_take(ss, total, got, k_lo, k_end)) != ALN_OK) return st;
-            down += 12ull * got;
-            total += got;
-        }
+    if (pairs == 0) { g_err = CAND_BLOCK; return ALN_ERR_INVALID_ARGUMENT; }
+    WordJoinRoute r{ss, sp, b, pairs, sp->chunk_occurrences ? sp->chunk_occurrences : ALN_WORDJOIN_CHUNK_OCCURRENCES};
+    uint64_t chunks;
+    return seqset_join(ss, b, r, &chunks, count);
+}
+
+// bytes down: 8 per query row and 4, 16 per chunk and 16 per candidate
+struct SeedJoinRoute {
+    aln_seqset *ss;
+    const aln_seedjoin_spec *sp;
+    const aln_seqset_block *b;
+    uint64_t cap, n = ss->seed_entries;
+    const uint64_t *keys = ss->seed_key.as<uint64_t>();
+    uint32_t *misc = ss->misc.as<uint32_t>() + ALN_SEQSET_MISC_SEED;
+    uint32_t plan_h[1] = {0};                          // the words max_occ dropped
+    uint64_t seeds_all = 0, pairs_seen = 0;
+    static constexpr uint32_t WORDS = ALN_SEQSET_MISC_SEED_WORDS - 1u, PLAN_WORDS = 1;
+    static constexpr const char *OVER = "one query row of the block has more seeds than chunk_seeds allows: max_occ drops the words that occur too often";
+    static constexpr const char *SCANNED = "a chunk's seeds differ from the plan's", *NO_PAIR = "a seed of the join names no pair of the block";
+    int plan(hipStream_t q)
+    {
+        HIPCHK(hipMemsetAsync(misc, 0, 4 * ALN_SEQSET_MISC_SEED_WORDS, q));
+        aln_seedjoin_launch_plan(keys, n, b, sp->max_occ, ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(), ss->wj_occ.as<uint64_t>(),
+                                 misc + ALN_JOIN_MISC_DROPPED, q);
         return ALN_OK;
-    });
-    if (st != ALN_OK) { seqset_drop_candidates(ss); return st; }
-    seqset_cand_finish(ss, b, total, count);
-    seqset_done(ss, t0, 0, down, kernels);          // 8 bytes per query row, 12 per chunk and 12 per candidate
+    }
+    uint64_t cut(const uint64_t *seeds, uint64_t first) const { return aln_seedjoin_cut(seeds, *b, first, cap); }
+    int ensure(const JoinChunk &k)
+    {
+        const int st = dev_ensure(ss->pf_out, 4 * k.room, false);
+        return st != ALN_OK ? st : dev_ensure(ss->sj_diag, 4 * k.room, false);
+    }
+    int queue(hipStream_t q, const JoinChunk &k, uint32_t *tile_count, uint32_t *tile_off, uint64_t *out_k)
+    {
+        // the chunk's pairs are at most 2^32 (aln_seedjoin_cut): their number in the chunk fits the key's high half
+        aln_seedjoin_launch_expand(keys, ss->seed_pos.as<uint32_t>(), ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(), ss->wj_off.as<uint32_t>(), n,
+                                   k.m, b, k.k_lo, k.k_end, k.q_lo, k.q_rows, ss->wj_a.as<uint64_t>(), misc + ALN_JOIN_MISC_NO_PAIR, q);
+        HIPCHK(hipGetLastError());
+        const uint32_t key_bits = 32u + std::max<uint32_t>(aln_wordjoin_bits_needed(k.k_end - k.k_lo), 1u);
+        HIPCHK((hipError_t)aln_wordjoin_launch_sort(ss->wj_temp.p, ss->wj_temp.cap, ss->wj_a.as<uint64_t>(), ss->wj_b.as<uint64_t>(), k.m, 0, key_bits, q));
+        // the unsorted keys have been read: their buffer holds the pairs' slots now
+        HIPCHK(hipMemsetAsync(ss->wj_a.p, 0, 8 * k.m, q));
+        aln_seedjoin_launch_append(ss->wj_b.as<uint64_t>(), k.m, k.k_lo, k.k_end - k.k_lo, sp->band, sp->min_seeds, ss->wj_a.as<uint64_t>(),
+                                   misc + ALN_JOIN_MISC_NO_PAIR, tile_count, tile_off, misc + ALN_JOIN_MISC_PAIRS_SEEN, misc + ALN_JOIN_MISC_KEPT, k.room,
+                                   out_k, ss->pf_out.as<uint32_t>(), ss->sj_diag.as<int32_t>(), q);
+        return ALN_OK;
+    }
+    bool sound(const uint32_t *h, const JoinChunk &k) const { return h[ALN_JOIN_MISC_KEPT] <= h[ALN_JOIN_MISC_PAIRS_SEEN] && h[ALN_JOIN_MISC_PAIRS_SEEN] <= k.room; }
+    int take(const uint32_t *h, const JoinChunk &k, uint64_t at, uint64_t got, uint64_t *down)      // the diagonals beside the list
+    {
+        if (got) {
+            ss->cands.diag.resize(at + got);
+            HIPCHK(hipMemcpy(ss->cands.diag.data() + at, ss->sj_diag.p, 4ull * got, hipMemcpyDeviceToHost));
+        }
+        *down += 4ull * got;
+        seeds_all += k.m;
+        pairs_seen += h[ALN_JOIN_MISC_PAIRS_SEEN];
+        return ALN_OK;
+    }
+};
+
+static int seqset_seed_join(aln_seqset *ss, const aln_seedjoin_spec *sp, const aln_seqset_block *b, aln_seedjoin_summary *summary, uint64_t *count)
+{
+    if (!ss || !sp || !b || !count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!aln_seedjoin_words(sp->k, sp->alphabet)) { g_err = SEEDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ss->seed_k || sp->k != ss->seed_k || sp->alphabet != ss->seed_alphabet) { g_err = "no seed index of this k and alphabet: aln_seqset_seed_index builds it"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->min_seeds == 0u) { g_err = "min_seeds must be at least 1: a join sees only the pairs that have a seed"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->band > ALN_SEEDJOIN_MAX_BAND) { g_err = "band must lie in 0 .. 2^31 - 1"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->flags != 0u || sp->reserved != 0u) { g_err = CAND_SPEC_WORDS; return ALN_ERR_INVALID_ARGUMENT; }
+    if (sp->chunk_seeds > ALN_SEEDJOIN_MAX_CHUNK_SEEDS) { g_err = "chunk_seeds must lie in 0 .. 2^26"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (aln_seqset_block_pairs(ss->n, *b) == 0) { g_err = CAND_BLOCK; return ALN_ERR_INVALID_ARGUMENT; }
+    SeedJoinRoute r{ss, sp, b, sp->chunk_seeds ? sp->chunk_seeds : ALN_SEEDJOIN_CHUNK_SEEDS};
+    uint64_t chunks;
+    const int st = seqset_join(ss, b, r, &chunks, count);
+    if (st != ALN_OK) return st;
+    ss->cands.has_diag = true;
+    if (summary) { summary->seeds = r.seeds_all; summary->pairs_with_seed = r.pairs_seen; summary->words_dropped = r.plan_h[0]; summary->chunks = chunks; }
     return ALN_OK;
 }
 
@@ -3941,190 +4099,6 @@ extern "C" int aln_seqset_word_index(aln_seqset *ss, uint32_t k, uint32_t alphab
 extern "C" int aln_seqset_word_join(aln_seqset *ss, const aln_wordjoin_spec *spec, const aln_seqset_block *b, uint64_t *count)
 {
     ALN_GUARDED(seqset_live(ss), seqset_word_join(ss, spec, b, count))
-}
-
-// ---------------------------------------------------------------- the positional word index and the seed join (include/aligner_hip_seedjoin.h)
-// A third road to the candidate state above: every occurrence of a word keeps its position, and a pair is judged by the most seeds it has
-// within one band of diagonals.  What is left behind is the prefilter's list with `shared` holding seeds, and the diagonals beside it.
-static const char *const SEEDJOIN_RANGE = "k must lie in 1 .. 16, the alphabet size be at least 1 and alphabet^k at most 2^32";
-
-static int seqset_seed_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint64_t *occurrences)
-{
-    if (!ss) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    const uint64_t words = aln_seedjoin_words(k, alphabet);
-    if (!words) { g_err = SEEDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
-    if (ss->total > 0x7FFFFFFFull) { g_err = "a seed index holds fewer than 2^31 residue positions"; return ALN_ERR_UNSUPPORTED; }
-    HIPCHK(hipSetDevice(ss->ctx->device));
-    hipStream_t q = ss->slot->stream;
-    HIPCHK(hipStreamSynchronize(q));
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t total = ss->total;
-    uint32_t seq_end, word_end;
-    aln_wordjoin_sort_bits(words, ss->n, &seq_end, &word_end);
-    // everything new first: a failure leaves the old index and the candidate list as they were
-    DevBuf keys_a, keys_b, pos_a, pos_b, temp, keys, pos;
-    uint32_t got = 0;
-    const int st = run_queued(q, [&]() -> int {
-        int st;
-        size_t temp_bytes = 0;
-        HIPCHK((hipError_t)aln_seedjoin_sort_pairs_temp_bytes(total, &temp_bytes));
-        if ((st = dev_ensure(keys_a, 8 * total, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(keys_b, 8 * total, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(pos_a, 4 * total, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(pos_b, 4 * total, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(temp, temp_bytes, false)) != ALN_OK) return st;
-        uint32_t *d_count = ss->misc.as<uint32_t>() + 24;
-        HIPCHK(hipEventRecord(ss->ev[0], q));
-        HIPCHK(hipMemsetAsync(d_count, 0, 4, q));
-        aln_seedjoin_launch_keys(ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), ss->n, total, k, alphabet,
-                                 keys_a.as<uint64_t>(), pos_a.as<uint32_t>(), q);
-        HIPCHK(hipGetLastError());
-        // the word join's two ranges, or the whole key in one pass where the word field reaches bit 64 (aln_wordjoin_sort_bits)
-        if (word_end == 64u) {
-            HIPCHK((hipError_t)aln_seedjoin_launch_sort_pairs(temp.p, temp.cap, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), pos_a.as<uint32_t>(),
-                                                              pos_b.as<uint32_t>(), total, 0, 64, q));
-            std::swap(keys_a, keys_b); std::swap(pos_a, pos_b);
-        } else {
-            HIPCHK((hipError_t)aln_seedjoin_launch_sort_pairs(temp.p, temp.cap, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), pos_a.as<uint32_t>(),
-                                                              pos_b.as<uint32_t>(), total, 0, seq_end, q));
-            HIPCHK((hipError_t)aln_seedjoin_launch_sort_pairs(temp.p, temp.cap, keys_b.as<uint64_t>(), keys_a.as<uint64_t>(), pos_b.as<uint32_t>(),
-                                                              pos_a.as<uint32_t>(), total, 32, word_end, q));
-        }
-        if (total) aln_seedjoin_launch_count(keys_a.as<uint64_t>(), total, d_count, q);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ss->ev[1], q));
-        HIPCHK(hipMemcpyAsync(&got, d_count, 4, hipMemcpyDeviceToHost, q));
-        HIPCHK(hipStreamSynchronize(q));
-        if (got > total) { g_err = "the seed index holds more occurrences than the set has windows"; return ALN_ERR_DEVICE; }
-        // the resident list at its own size; the sort's buffers go
-        if ((st = dev_ensure(keys, 8ull * got, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(pos, 4ull * got, false)) != ALN_OK) return st;
-        if (got) HIPCHK(hipMemcpy(keys.p, keys_a.p, 8ull * got, hipMemcpyDeviceToDevice));
-        if (got) HIPCHK(hipMemcpy(pos.p, pos_a.p, 4ull * got, hipMemcpyDeviceToDevice));
-        return ALN_OK;
-    });
-    dev_free(keys_a); dev_free(keys_b); dev_free(pos_a); dev_free(pos_b); dev_free(temp);
-    if (st != ALN_OK) { dev_free(keys); dev_free(pos); return st; }
-    dev_free(ss->seed_key); dev_free(ss->seed_pos);
-    ss->seed_key = keys; ss->seed_pos = pos;
-    ss->seed_k = k; ss->seed_alphabet = alphabet; ss->seed_entries = got;
-    seqset_drop_candidates(ss);
-    if (occurrences) *occurrences = got;
-    seqset_done(ss, t0, 0, 4);
-    return ALN_OK;
-}
-
-static int seqset_seed_join(aln_seqset *ss, const aln_seedjoin_spec *sp, const aln_seqset_block *b, aln_seedjoin_summary *summary, uint64_t *count)
-{
-    if (!ss || !sp || !b || !count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (!aln_seedjoin_words(sp->k, sp->alphabet)) { g_err = SEEDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
-    if (!ss->seed_k || sp->k != ss->seed_k || sp->alphabet != ss->seed_alphabet) { g_err = "no seed index of this k and alphabet: aln_seqset_seed_index builds it"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (sp->min_seeds == 0u) { g_err = "min_seeds must be at least 1: a join sees only the pairs that have a seed"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (sp->band > ALN_SEEDJOIN_MAX_BAND) { g_err = "band must lie in 0 .. 2^31 - 1"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (sp->flags != 0u || sp->reserved != 0u) { g_err = "the spec's flags and reserved word must be 0"; return ALN_ERR_INVALID_ARGUMENT; }
-    if (sp->chunk_seeds > ALN_SEEDJOIN_MAX_CHUNK_SEEDS) { g_err = "chunk_seeds must lie in 0 .. 2^26"; return ALN_ERR_INVALID_ARGUMENT; }
-    const uint64_t pairs = aln_seqset_block_pairs(ss->n, *b);
-    if (pairs == 0) { g_err = "block: a range beyond the set, unequal ranges of an upper block, a reserved word, or no pairs"; return ALN_ERR_INVALID_ARGUMENT; }
-    HIPCHK(hipSetDevice(ss->ctx->device));
-    hipStream_t q = ss->slot->stream;
-    HIPCHK(hipStreamSynchronize(q));
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t cap = sp->chunk_seeds ? sp->chunk_seeds : ALN_SEEDJOIN_CHUNK_SEEDS;
-    const uint64_t n_p = ss->seed_entries, rows = b->q_count;
-    uint64_t total = 0, down = 0, seeds_all = 0, pairs_seen = 0;
-    uint32_t dropped = 0;
-    double kernels = 0;
-    int st;
-    uint32_t *d_words = ss->misc.as<uint32_t>() + 24;        // [0] kept pairs, [1] keys without a pair, [2] seeds scanned, [3] pairs with a seed, [4] dropped words
-    // ---- the plan: nothing of the set's state is touched before the rows are cut
-    std::vector<uint64_t> row_seeds(rows, 0);
-    std::vector<uint64_t> chunk_first, chunk_rows, chunk_seeds;
-    st = run_queued(q, [&]() -> int {
-        if ((st = dev_ensure(ss->wj_first, 4 * n_p, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(ss->wj_len, 4 * n_p, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(ss->wj_off, 4 * n_p, false)) != ALN_OK) return st;
-        if ((st = dev_ensure(ss->wj_occ, 8 * rows, false)) != ALN_OK) return st;
-        HIPCHK(hipEventRecord(ss->ev[0], q));
-        HIPCHK(hipMemsetAsync(ss->wj_occ.p, 0, 8 * rows, q));
-        HIPCHK(hipMemsetAsync(d_words, 0, 20, q));
-        aln_seedjoin_launch_plan(ss->seed_key.as<uint64_t>(), n_p, b, sp->max_occ, ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(),
-                                 ss->wj_occ.as<uint64_t>(), d_words + 4, q);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ss->ev[1], q));
-        HIPCHK(hipMemcpyAsync(row_seeds.data(), ss->wj_occ.p, 8 * rows, hipMemcpyDeviceToHost, q));
-        HIPCHK(hipMemcpyAsync(&dropped, d_words + 4, 4, hipMemcpyDeviceToHost, q));
-        HIPCHK(hipStreamSynchronize(q));
-        kernels += ev_ms(ss->ev[0], ss->ev[1]);
-        down += 8 * rows + 4;
-        return seqset_cut_rows(row_seeds, [&](uint64_t first) { return aln_seedjoin_cut(row_seeds.data(), *b, first, cap); },
-                               "one query row of the block has more seeds than chunk_seeds allows: max_occ drops the words that occur too often",
-                               chunk_first, chunk_rows, chunk_seeds);
-    });
-    if (st != ALN_OK) return st;
-    seqset_drop_candidates(ss);
-    st = run_queued(q, [&]() -> int {
-        if ((st = seqset_cand_room(ss, 0, 1)) != ALN_OK) return st;      // (an empty list is resident too, as the prefilter's is)
-        for (size_t c = 0; c < chunk_first.size(); ++c) {
-            const uint64_t m = chunk_seeds[c], q_lo = b->q_first + chunk_first[c], q_rows = chunk_rows[c];
-            // the chunk's pairs: the pair numbers of its rows, at most 2^32 of them (aln_seedjoin_cut)
-            const uint64_t k_lo = b->upper ? aln_seqset_row_start(rows, chunk_first[c]) : chunk_first[c] * b->t_count;
-            const uint64_t k_end = k_lo + aln_seedjoin_row_pairs(*b, chunk_first[c], q_rows);
-            const uint64_t room = std::min(m, k_end - k_lo);
-            const uint32_t key_bits = 32u + std::max<uint32_t>(aln_wordjoin_bits_needed(k_end - k_lo), 1u);
-            size_t temp_bytes = 0;
-            HIPCHK((hipError_t)aln_wordjoin_sort_temp_bytes(m, &temp_bytes));
-            uint32_t *tile_count = nullptr, *tile_off = nullptr;
-            if ((st = dev_ensure(ss->wj_a, 8 * m, false)) != ALN_OK) return st;
-            if ((st = dev_ensure(ss->wj_b, 8 * m, false)) != ALN_OK) return st;
-            if ((st = dev_ensure(ss->wj_temp, temp_bytes, false)) != ALN_OK) return st;
-            if ((st = dev_ensure(ss->pf_out, 4 * room, false)) != ALN_OK) return st;
-            if ((st = dev_ensure(ss->sj_diag, 4 * room, false)) != ALN_OK) return st;
-            if ((st = tiles_ensure(ss->tiles, std::max(aln_seqset_tiles(n_p), aln_seqset_tiles(m)), &tile_count, &tile_off)) != ALN_OK) return st;
-            if ((st = seqset_cand_room(ss, total, total + room)) != ALN_OK) return st;
-            HIPCHK(hipEventRecord(ss->ev[0], q));
-            HIPCHK(hipMemsetAsync(d_words, 0, 16, q));
-            aln_wordjoin_launch_offsets(ss->seed_key.as<uint64_t>(), ss->wj_len.as<uint32_t>(), n_p, q_lo, q_rows, tile_count, tile_off, d_words + 2,
-                                        ss->wj_off.as<uint32_t>(), q);
-            HIPCHK(hipGetLastError());
-            aln_seedjoin_launch_expand(ss->seed_key.as<uint64_t>(), ss->seed_pos.as<uint32_t>(), ss->wj_first.as<uint32_t>(), ss->wj_len.as<uint32_t>(),
-                                       ss->wj_off.as<uint32_t>(), n_p, m, b, k_lo, k_end, q_lo, q_rows, ss->wj_a.as<uint64_t>(), d_words + 1, q);
-            HIPCHK(hipGetLastError());
-            HIPCHK((hipError_t)aln_wordjoin_launch_sort(ss->wj_temp.p, ss->wj_temp.cap, ss->wj_a.as<uint64_t>(), ss->wj_b.as<uint64_t>(), m, 0, key_bits, q));
-            // the unsorted keys have been read: their buffer holds the pairs' slots now
-            HIPCHK(hipMemsetAsync(ss->wj_a.p, 0, 8 * m, q));
-            aln_seedjoin_launch_append(ss->wj_b.as<uint64_t>(), m, k_lo, k_end - k_lo, sp->band, sp->min_seeds, ss->wj_a.as<uint64_t>(), d_words + 1,
-                                       tile_count, tile_off, d_words + 3, d_words, room, ss->cand_k.as<uint64_t>() + total, ss->pf_out.as<uint32_t>(),
-                                       ss->sj_diag.as<int32_t>(), q);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(ss->ev[1], q));
-            uint32_t h[4] = {0, 0, 0, 0};
-            HIPCHK(hipMemcpyAsync(h, d_words, 16, hipMemcpyDeviceToHost, q));
-            HIPCHK(hipStreamSynchronize(q));
-            kernels += ev_ms(ss->ev[0], ss->ev[1]);
-            down += 16;
-            const uint64_t got = h[0];
-            if (h[2] != m) { g_err = "a chunk's seeds differ from the plan's"; return ALN_ERR_DEVICE; }
-            if (h[1]) { g_err = "a seed of the join names no pair of the block"; return ALN_ERR_DEVICE; }
-            if (got > room || got > h[3] || h[3] > room) { g_err = "the join kept more pairs than the chunk's rows hold"; return ALN_ERR_DEVICE; }
-            if (total + got > 0xFFFFFFF0ull) { g_err = "too many candidates"; return ALN_ERR_UNSUPPORTED; }
-            if ((st = seqset_cand_take(ss, total, got, k_lo, k_end)) != ALN_OK) return st;
-            if (got) {
-                ss->cand_diag.resize(total + got);
-                HIPCHK(hipMemcpy(ss->cand_diag.data() + total, ss->sj_diag.p, 4ull * got, hipMemcpyDeviceToHost));
-            }
-            down += 16ull * got;
-            total += got;
-            seeds_all += m;
-            pairs_seen += h[3];
-        }
-        return ALN_OK;
-    });
-    if (st != ALN_OK) { seqset_drop_candidates(ss); return st; }
-    seqset_cand_finish(ss, b, total, count);
-    ss->cand_has_diag = true;
-    if (summary) { summary->seeds = seeds_all; summary->pairs_with_seed = pairs_seen; summary->words_dropped = dropped; summary->chunks = chunk_first.size(); }
-    seqset_done(ss, t0, 0, down, kernels);          // 8 bytes per query row and 4, 16 per chunk and 16 per candidate
-    return ALN_OK;
 }
 
 extern "C" int aln_seqset_seed_index(aln_seqset *ss, uint32_t k, uint32_t alphabet, uint64_t *occurrences)
@@ -4142,11 +4116,11 @@ extern "C" int aln_seqset_candidate_diags(aln_seqset *ss, uint64_t first, uint64
 {
     const int st = seqset_cand_check(ss);
     if (st != ALN_OK) return st;
-    if (!ss->cand_has_diag) { g_err = "the candidate list has no diagonals: aln_seqset_seed_join makes the lists that have"; return ALN_ERR_INVALID_ARGUMENT; }
-    const uint64_t have = ss->cand_diag.size();
+    if (!ss->cands.has_diag) { g_err = "the candidate list has no diagonals: aln_seqset_seed_join makes the lists that have"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t have = ss->cands.diag.size();
     if (first > have || n > have - first) { g_err = "range beyond the candidate list"; return ALN_ERR_INVALID_ARGUMENT; }
     if (n && !diag) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
-    for (uint64_t i = 0; i < n; ++i) diag[i] = ss->cand_diag[first + i];
+    for (uint64_t i = 0; i < n; ++i) diag[i] = ss->cands.diag[first + i];
     return ALN_OK;                       // (no byte moves and no kernel runs: the stats stay as they are)
 }
 
@@ -4441,7 +4415,7 @@ static int seqset_held_filter(aln_seqset *ss, const aln_params *params, uint32_t
     if ((st = dev_ensure(ss->rep_pos, 4ull * room, false)) != ALN_OK) return st;
     if (reports && (st = dev_ensure(ss->rep_out, sizeof(aln_hit_report) * room, false)) != ALN_OK) return st;
     const auto t0 = std::chrono::steady_clock::now();
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(ss->misc.as<uint8_t>() + 64);
+    uint32_t *d_count = ss->misc.as<uint32_t>() + ALN_SEQSET_MISC_COMPACT;
     uint32_t kept = 0;
     uint64_t wrote = 0;
     std::vector<uint32_t> pos;

@@ -218,6 +218,7 @@ void aln_cigar_launch_plan(const CigarArgs *a, hipStream_t s);
 void aln_cigar_launch_fill(const CigarArgs *a, hipStream_t s);
 
 // ---- aln_wordjoin.hip: the sorted word index of a sequence set and the join over its posting lists (aln_wordjoin_rules.h)
+// (keys, plan, expand and the sort's argument rules are aln_postings.h's, which aln_seedjoin.hip instantiates too; offsets serves both)
 int aln_warm_wordjoin(void);
 // rocPRIM's device radix sort of n 64-bit numbers over bits begin_bit .. end_bit - 1, in -> out; the host owns the temporary storage,
 // whose size for n numbers the first call gives.  Both return a hipError_t; n < 2^31; a range that ends at bit 64 begins at bit 0
@@ -250,7 +251,7 @@ void aln_wordjoin_launch_append(const uint64_t *sorted, uint64_t n, const aln_se
 
 // ---- aln_seedjoin.hip: the positional word index of a sequence set and the seed join over it (aln_seedjoin_rules.h)
 int aln_warm_seedjoin(void);
-// rocPRIM's device radix sort of n (64-bit key, 32-bit value) pairs, stable, under the rules of aln_wordjoin_launch_sort
+// rocPRIM's device radix sort of n (64-bit key, 32-bit value) pairs, stable, under the rules of aln_wordjoin_launch_sort (aln_postings.h)
 int aln_seedjoin_sort_pairs_temp_bytes(uint64_t n, size_t *bytes);
 int aln_seedjoin_launch_sort_pairs(void *temp, size_t temp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in,
                                    uint32_t *vals_out, uint64_t n, uint32_t begin_bit, uint32_t end_bit, hipStream_t s);

@@ -30,16 +30,7 @@
 #define ALN_SEEDJOIN_MAX_CHUNK_PAIRS (1ull << 32)          // what the key's pair field numbers
 
 // A^k, or 0 where (k, A) is refused: k outside 1 .. 16, A == 0, A^k beyond 2^32
-ALN_HD inline uint64_t aln_seedjoin_words(uint32_t k, uint32_t alphabet)
-{
-    if (k < 1u || k > ALN_SEEDJOIN_MAX_K || alphabet < 1u) return 0;
-    uint64_t words = 1;
-    for (uint32_t j = 0; j < k; ++j) {
-        words *= alphabet;                                 // (below 2^32 * 2^32 before the check: the product before was <= 2^32)
-        if (words > ALN_SEEDJOIN_MAX_WORDS) return 0;
-    }
-    return words;
-}
+ALN_HD inline uint64_t aln_seedjoin_words(uint32_t k, uint32_t alphabet) { return aln_postings_words(k, alphabet, ALN_SEEDJOIN_MAX_K); }
 
 // d + 2^31 as 32 bits: ascending in d over the whole of int32_t
 ALN_HD inline uint32_t aln_seedjoin_bias(int32_t d) { return (uint32_t)d ^ 0x80000000u; }
@@ -69,18 +60,6 @@ ALN_HD inline uint64_t aln_seedjoin_pack(uint32_t count, uint32_t position) { re
 ALN_HD inline uint32_t aln_seedjoin_packed_count(uint64_t packed) { return (uint32_t)(packed >> 32); }
 ALN_HD inline uint32_t aln_seedjoin_packed_position(uint64_t packed) { return ~(uint32_t)packed; }
 
-// the first index in [0, n) whose key is > x (n if none): at most 64 trips
-ALN_HD inline uint64_t aln_seedjoin_upper_bound(const uint64_t *a, uint64_t n, uint64_t x)
-{
-    uint64_t lo = 0, hi = n;
-    for (uint32_t trip = 0; trip < 64u && lo < hi; ++trip) {
-        const uint64_t mid = lo + (hi - lo) / 2u;
-        if (a[mid] <= x) lo = mid + 1u;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // One pair's seeds as n ascending keys of one pair: seeds and diag of the rule.  What the kernels compute with one thread per window
 // start and an integer atomicMax per pair, as one loop (the CPU driver's; n >= 1)
 ALN_HD inline void aln_seedjoin_best_window(const uint64_t *keys, uint64_t n, uint32_t band, uint64_t *seeds, int32_t *diag)
@@ -88,7 +67,7 @@ ALN_HD inline void aln_seedjoin_best_window(const uint64_t *keys, uint64_t n, ui
     uint64_t best = 0;
     for (uint64_t p = 0; p < n; ++p) {
         if (p && keys[p - 1u] == keys[p]) continue;        // a window starts where a diagonal starts
-        const uint64_t c = aln_seedjoin_upper_bound(keys, n, aln_seedjoin_band_last(keys[p], band)) - p;
+        const uint64_t c = aln_postings_upper_bound(keys, n, aln_seedjoin_band_last(keys[p], band)) - p;
         const uint64_t packed = aln_seedjoin_pack((uint32_t)c, (uint32_t)p);
         if (packed > best) best = packed;
     }

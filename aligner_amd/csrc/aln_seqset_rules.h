@@ -23,6 +23,32 @@
 #define ALN_HD
 #endif
 
+// The set's `misc` buffer: 64 32-bit counter words on the device, every call family's words in one place.  A handle's calls run one
+// at a time on the set's one stream, and every user reads its words back, behind a synchronize, before its call queues anything else
+// or returns; so users of the same word are never live together.  The arenas (cluster, profile, msa, cigar) carry their own counters.
+//   words 0 .. 3   a pass's chunk (seqset_pass_chunks): word 0 the chunk's hit count (the threshold selection), bytes 8 .. 15 the
+//                  first failed status (the gather).  Zeroed per chunk, read per chunk
+//   words 8, 9     the k best: the rows' total (seqset_best_finish), 64 bits, written by the count kernel
+//   the rest       the named words below; the other words are unused
+#define ALN_SEQSET_MISC_WORDS 64u
+// the kept count of ONE compaction: a sharing chunk of aln_seqset_prefilter, and the selection of aln_seqset_held_filter.  Written by
+// the compaction's offsets step, which writes its total whatever it is (aln_select.h: for n == 0 too): no zeroing, no second word
+#define ALN_SEQSET_MISC_COMPACT 16u
+// the word index and the word join: ALN_SEQSET_MISC_WORD + ...  The index: KEPT holds the distinct entries (written by its compaction).
+// The join zeroes the three per chunk
+#define ALN_SEQSET_MISC_WORD 20u
+#define ALN_SEQSET_MISC_WORD_WORDS 3u
+// the seed index and the seed join: ALN_SEQSET_MISC_SEED + ...  The index: KEPT holds the occurrences (zeroed, then written by its
+// count kernel).  The join zeroes the first four per chunk, and all five before the plan
+#define ALN_SEQSET_MISC_SEED 24u
+#define ALN_SEQSET_MISC_SEED_WORDS 5u
+// the offsets of both joins' blocks (a chunk's words are read back from KEPT on: 3 for the word join, 4 for the seed join)
+#define ALN_JOIN_MISC_KEPT 0u          // the pairs a chunk kept
+#define ALN_JOIN_MISC_NO_PAIR 1u       // output positions that named no pair of the block
+#define ALN_JOIN_MISC_SCANNED 2u       // occurrences (seeds) the chunk's offsets summed
+#define ALN_JOIN_MISC_PAIRS_SEEN 3u    // seed join: the chunk's pairs with a seed
+#define ALN_JOIN_MISC_DROPPED 4u       // seed join: the words max_occ dropped, counted by the plan
+
 // pairs of a block over a set of n_seqs sequences; 0 for an invalid block (a range past the set, upper with unequal ranges, a
 // reserved word that is not 0, no pairs)
 ALN_HD inline uint64_t aln_seqset_block_pairs(uint64_t n_seqs, const aln_seqset_block &b)

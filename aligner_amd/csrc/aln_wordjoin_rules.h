@@ -24,16 +24,40 @@
 #define ALN_WORDJOIN_MAX_CHUNK_OCCURRENCES (1u << 26)
 #define ALN_WORDJOIN_NO_KEY 0xFFFFFFFFFFFFFFFFull
 
-// A^k, or 0 where (k, A) is refused: k outside 1 .. 8, A == 0, A^k beyond 2^32
-ALN_HD inline uint64_t aln_wordjoin_words(uint32_t k, uint32_t alphabet)
+// A^k, or 0 where (k, A) is refused: k outside 1 .. max_k, A == 0, A^k beyond 2^32.  Both joins' cap
+ALN_HD inline uint64_t aln_postings_words(uint32_t k, uint32_t alphabet, uint32_t max_k)
 {
-    if (k < 1u || k > ALN_WORDJOIN_MAX_K || alphabet < 1u) return 0;
+    if (k < 1u || k > max_k || alphabet < 1u) return 0;
     uint64_t words = 1;
     for (uint32_t j = 0; j < k; ++j) {
         words *= alphabet;                                 // (below 2^32 * 2^32 before the check: the product before was <= 2^32)
         if (words > ALN_WORDJOIN_MAX_WORDS) return 0;
     }
     return words;
+}
+ALN_HD inline uint64_t aln_wordjoin_words(uint32_t k, uint32_t alphabet) { return aln_postings_words(k, alphabet, ALN_WORDJOIN_MAX_K); }
+
+// the first index in [0, n) of the ascending a[] whose key is >= x (lower) or > x (upper), n if none: at most 64 trips.  Every search
+// of the two joins' kernels in a sorted list (64-bit keys, 32-bit offsets) is one of these
+template <class T> ALN_HD inline uint64_t aln_postings_lower_bound(const T *a, uint64_t n, uint64_t x)
+{
+    uint64_t lo = 0, hi = n;
+    for (uint32_t trip = 0; trip < 64u && lo < hi; ++trip) {
+        const uint64_t mid = lo + (hi - lo) / 2u;
+        if (a[mid] < x) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+template <class T> ALN_HD inline uint64_t aln_postings_upper_bound(const T *a, uint64_t n, uint64_t x)
+{
+    uint64_t lo = 0, hi = n;
+    for (uint32_t trip = 0; trip < 64u && lo < hi; ++trip) {
+        const uint64_t mid = lo + (hi - lo) / 2u;
+        if (a[mid] <= x) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
 }
 
 // the least b with 2^b >= n; 0 for n <= 1, 64 for n > 2^63

@@ -82,6 +82,33 @@ int main(int argc, char **argv)
         }
         return 0;
     }
+    if (!strcmp(argv[1], "pwords")) {         // lines `k A max_k` -> A^k or 0
+        uint32_t k, a, max_k;
+        while (scanf("%" SCNu32 " %" SCNu32 " %" SCNu32, &k, &a, &max_k) == 3) printf("%" PRIu64 "\n", aln_postings_words(k, a, max_k));
+        return 0;
+    }
+    if (!strcmp(argv[1], "bounds")) {         // lines `x n a0 .. a(n-1)` (ascending) -> lower upper, over 64-bit and over 32-bit elements
+        uint64_t x, n;
+        while (scanf("%" SCNu64 " %" SCNu64, &x, &n) == 2) {
+            std::vector<uint64_t> a(n);
+            for (uint64_t i = 0; i < n; ++i) if (scanf("%" SCNu64, &a[i]) != 1) return 2;
+            printf("%" PRIu64 " %" PRIu64, aln_postings_lower_bound(a.data(), n, x), aln_postings_upper_bound(a.data(), n, x));
+            bool narrow = true;
+            for (uint64_t v : a) narrow = narrow && v <= 0xFFFFFFFFull;
+            if (narrow) {
+                std::vector<uint32_t> b(a.begin(), a.end());
+                printf(" %" PRIu64 " %" PRIu64, aln_postings_lower_bound(b.data(), n, x), aln_postings_upper_bound(b.data(), n, x));
+            }
+            printf("\n");
+        }
+        return 0;
+    }
+    if (!strcmp(argv[1], "misc")) {           // -> `name first words` of every named range of the set's counter words, then the total
+        printf("compact %u 1\nword %u %u\nseed %u %u\ntotal %u\n", ALN_SEQSET_MISC_COMPACT, ALN_SEQSET_MISC_WORD, ALN_SEQSET_MISC_WORD_WORDS,
+               ALN_SEQSET_MISC_SEED, ALN_SEQSET_MISC_SEED_WORDS, ALN_SEQSET_MISC_WORDS);
+        printf("offsets %u %u %u %u %u\n", ALN_JOIN_MISC_KEPT, ALN_JOIN_MISC_NO_PAIR, ALN_JOIN_MISC_SCANNED, ALN_JOIN_MISC_PAIRS_SEEN, ALN_JOIN_MISC_DROPPED);
+        return 0;
+    }
     return 2;
 }
 """
@@ -199,6 +226,50 @@ def test_chunk_cutting(drivers):
         seen_equal += any(sum(occ[f:f + n]) == cap for f, n in got)
         seen_empty += any(v == 0 for v in occ)
     assert seen_over > 10 and seen_equal > 10 and seen_empty > 10
+
+
+# ---------------------------------------------------------------- what the word join and the seed join share
+def test_the_shared_cap_at_max_k_8_and_16(drivers):
+    cases = [(k, a, max_k) for max_k in (8, 16) for k in range(0, 19) for a in (0, 1, 2, 3, 4, 5, 16, 17, 20, 256, 257, 65536, 65537, 2 ** 32 - 1)]
+    out = run(drivers, "pwords", ["%d %d %d" % c for c in cases])
+    assert len(out) == len(cases)
+    for (k, a, max_k), line in zip(cases, out):
+        want = a ** k if 1 <= k <= max_k and a >= 1 and a ** k <= 2 ** 32 else 0
+        assert int(line) == want, (k, a, max_k)
+    assert (9, 4, 8) in cases and (9, 4, 16) in cases and (16, 4, 16) in cases and (17, 1, 16) in cases      # k between and beyond the two caps
+
+
+def test_lower_and_upper_bound(drivers):
+    import bisect
+    top = 2 ** 64 - 1
+    cases = [(5, []), (0, []), (top, []),                                        # n = 0
+             (4, [5]), (5, [5]), (6, [5]), (top, [5]), (top, [top]), (0, [0]),   # one element
+             (7, [7] * 9), (6, [7] * 9), (8, [7] * 9), (top, [top] * 3),         # all equal
+             (0, [1, 3, 3, 9]), (10, [1, 3, 3, 9]), (top, [1, 3, 3, 9]),         # below the first, above the last
+             (9, [1, 3, 9, 9, 9]), (3, [1, 3, 3]), (top, [1, top, top]),         # a run that ends at n
+             (2 ** 32, [1, 2 ** 32 - 1]), (2 ** 32 - 1, [1, 2 ** 32 - 1]), (2 ** 40, [2 ** 40 - 1, 2 ** 40, 2 ** 40, 2 ** 63, top])]
+    rng = random.Random(64)
+    for _ in range(200):
+        span = rng.choice([4, 50, 2 ** 32, 2 ** 64])
+        a = sorted(rng.randrange(span) for _ in range(rng.randrange(0, 70)))
+        cases.append((rng.choice(a + [rng.randrange(span)]), a))
+    out = run(drivers, "bounds", ["%d %d %s" % (x, len(a), " ".join(map(str, a))) for x, a in cases])
+    assert len(out) == len(cases)
+    for (x, a), line in zip(cases, out):
+        got = [int(v) for v in line.split()]
+        want = [bisect.bisect_left(a, x), bisect.bisect_right(a, x)]
+        assert got == want * (2 if all(v < 2 ** 32 for v in a) else 1), (x, a)
+
+
+def test_the_sets_counter_words_do_not_overlap(drivers):
+    out = run(drivers, "misc", [])
+    ranges = {l.split()[0]: (int(l.split()[1]), int(l.split()[2])) for l in out[:3]}
+    total = int(out[3].split()[1])
+    assert ranges == {"compact": (16, 1), "word": (20, 3), "seed": (24, 5)} and total == 64
+    used = [w for first, n in list(ranges.values()) + [(0, 4), (8, 2)] for w in range(first, first + n)]      # (the passes' and the k best's words)
+    assert len(used) == len(set(used)) and max(used) < total
+    offsets = [int(v) for v in out[4].split()[1:]]
+    assert offsets == [0, 1, 2, 3, 4] and max(offsets) < ranges["seed"][1] and max(offsets[:3]) < ranges["word"][1]
 
 
 # ---------------------------------------------------------------- the companion header and its mirrors
