@@ -195,11 +195,11 @@ def case_line(c, facts, tables_path, lists_path="-"):
     """The driver's line for a case; facts: the call's facts as the fixture holds them (FACTS)."""
     env, n_total = c["env"], len(lengths(c["spec"])[0])
     assert not set(env) - {"ALN_SINGLE_R", "ALN_NO_SINGLE", "ALN_NO_COOP", "ALN_BIG_TO_SINGLE", "ALN_NO_WGPIPE", "ALN_WG_R", "ALN_TB_OVERLAP",
-                           "ALN_TB_OVERLAP_ANY", "ALN_COOP_TAIL", "ALN_CHAIN_WGS", "ALN_FILL_WGS", "ALN_NO_DUO", "ALN_CHUNK_CELLS"}
+                           "ALN_TB_OVERLAP_ANY", "ALN_COOP_TAIL", "ALN_CHAIN_WGS", "ALN_FILL_WGS", "ALN_NO_DUO", "ALN_CHUNK_CELLS", "ALN_COOP_LEAN"}
     words = [c["name"], str(tables_path), n_total, c["first"], n_total - c["first"] if c["n"] is None else c["n"], int(c["allow"]), int(c["many"]), CUS]
     words += [int(facts[k]) for k in FACTS]
     words += [_knob(env, "ALN_SINGLE_R"), int("ALN_NO_SINGLE" in env), int("ALN_NO_COOP" in env), _knob(env, "ALN_BIG_TO_SINGLE"),
-              int("ALN_NO_WGPIPE" in env), _knob(env, "ALN_WG_R"), _knob(env, "ALN_TB_OVERLAP"), int("ALN_TB_OVERLAP_ANY" in env), -1,
+              int("ALN_NO_WGPIPE" in env), _knob(env, "ALN_WG_R"), _knob(env, "ALN_TB_OVERLAP"), int("ALN_TB_OVERLAP_ANY" in env), int(env.get("ALN_COOP_LEAN", -1)),
               _knob(env, "ALN_COOP_TAIL"), _knob(env, "ALN_CHAIN_WGS"), _knob(env, "ALN_FILL_WGS"), int("ALN_NO_DUO" in env),
               "1 %s" % env["ALN_CHUNK_CELLS"] if "ALN_CHUNK_CELLS" in env else "0 0", str(lists_path)]
     return " ".join(str(w) for w in words)

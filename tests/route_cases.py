@@ -220,9 +220,16 @@ def plan(N, M, kind, local, dele, ext, traceback, env=(), alone=True):
     # something to share (aln_plan_share): several strips, or a re-fill of a core-local pair with del != ext that is large enough to matter
     multi = (M[small] > STRIP_ROWS) | (bool(local and dele != ext) & (M[small] > 64) & (pc[small] >= 1 << 18))
     coop = bool(coop_on and n_small and multi.any())                                       # aln_plan_share (one chunk, or at most four)
-    # the lean build needs 16 pairs per kernel wave (aln_plan_rules.h); the grid is at least one workgroup of four
-    assert not (coop and n_small >= 64), "a block that could run the lean build: restate aln_coop_lean_plan"
-    r["share"] = "coop" if coop else "none"
+    # the lean build needs 16 pairs per kernel wave (aln_plan_rules.h); the grid is at least one workgroup of four.  ALN_COOP_LEAN
+    # decides by itself (aln_coop_lean_plan's setting: 0 never lean, > 0 always lean)
+    lean = False
+    if coop and "ALN_COOP_LEAN" in env:
+        lean = int(env["ALN_COOP_LEAN"]) > 0
+        coop = not lean
+    else:
+        assert not (coop and n_small >= 64), "a block that could run the lean build: restate aln_coop_lean_plan"
+    r["share"] = "coop" if coop else "lean" if lean else "none"
+    coop = coop or lean                                                                    # (aln_plan_duo: neither build)
     # two pairs per wave (aln_plan_duo): core global, nothing shared, no walk waves, more pairs than 12 per CU, short pairs, LDS (24 x 24)
     duo = fast and not local and not coop and not r["overlap"] and "ALN_NO_DUO" not in env and n_small > CUS * 12
     if duo:
