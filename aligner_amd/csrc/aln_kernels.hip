@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "aln_device.h"
+#include "aln_launch.h"
 
 // The file is compiled as several translation units in parallel (aligner_amd/build.py: -DALN_TU=<mask>), each instantiating one
 // family of kernels together with the launch helpers that name them; the templates themselves are seen by every unit.
@@ -2915,14 +2916,8 @@ extern "C" __global__ void aln_unpack_directions_kernel(const uint8_t *dirs, con
 #endif   // ALN_PART_TB
 
 // ---------------------------------------------------------------- launch helpers used by aln_host.hip
-// (beyond 64 KiB of dynamic LDS -- S, the profiles and the rings of a 30-letter alphabet -- a kernel has to be told once)
-#define ALN_FAST_GO(...)                                                                                                   \
-    do {                                                                                                                   \
-        auto kern = &__VA_ARGS__;                                                                                          \
-        if (lds_bytes > 64u * 1024u)                                                                                       \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-        hipLaunchKernelGGL(kern, g, b, lds_bytes, s, *a);                                                                  \
-    } while (0)
+// (beyond 64 KiB of dynamic LDS -- S, the profiles and the rings of a 30-letter alphabet -- a kernel has to be told: aln_launch_lds)
+#define ALN_FAST_GO(...) aln_launch_lds(&__VA_ARGS__, g, b, lds_bytes, s, *a)
 #define ALN_FAST_REST_LAUNCH(COOPV)                                                                                        \
     switch (a->semantics) {                                                                                                \
     case ALN_CORE_GLOBAL: ALN_FAST_GO(aln_fill_fast_kernel<ALN_CORE_GLOBAL, false, COOPV>); break; \
@@ -3236,13 +3231,7 @@ extern "C" void aln_launch_single(const SingleArgs *a, uint32_t N, int with_seri
     const uint32_t lds_bytes = aln_single_lds_bytes(a->rows, a->cols, a->R, N, W);
     const dim3 g((a->ns + W - 1) / W), b(64 * W);
     const uint32_t serial_lds = (a->rows * a->cols * 4u + 15u) & ~15u;
-#define ALN_SINGLE_LAUNCH(SEM, RR, WW)                                                                         \
-    do {                                                                                                       \
-        auto kern = aln_fill_single_kernel<SEM, RR, WW>;                                                       \
-        if (lds_bytes > 64u * 1024u)                                                                           \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-        hipLaunchKernelGGL(kern, g, b, lds_bytes, s, *a);                                                      \
-    } while (0)
+#define ALN_SINGLE_LAUNCH(SEM, RR, WW) aln_launch_lds(&aln_fill_single_kernel<SEM, RR, WW>, g, b, lds_bytes, s, *a)
 #define ALN_SINGLE(SEM)                                                                                        \
     do {                                                                                                       \
         if (a->R == 1) ALN_SINGLE_LAUNCH(SEM, 1, 1);                                                           \
@@ -3314,13 +3303,7 @@ extern "C" void aln_launch_single_repair(const SingleArgs *a0, uint32_t N, hipSt
     const uint32_t W = aln_single_waves(a.semantics, a.R, a.rows, a.cols, N, a.ns);
     const uint32_t lds_bytes = aln_single_lds_bytes(a.rows, a.cols, a.R, N, W);
     const dim3 g((a.rep_S + W - 1) / W), b(64 * W);
-#define ALN_REPAIR_LAUNCH(RR, WW)                                                                              \
-    do {                                                                                                       \
-        auto kern = aln_fill_single_kernel<ALN_CORE_LOCAL, RR, WW>;                                            \
-        if (lds_bytes > 64u * 1024u)                                                                           \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-        hipLaunchKernelGGL(kern, g, b, lds_bytes, s, a);                                                       \
-    } while (0)
+#define ALN_REPAIR_LAUNCH(RR, WW) aln_launch_lds(&aln_fill_single_kernel<ALN_CORE_LOCAL, RR, WW>, g, b, lds_bytes, s, a)
     if (W == 4) { if (a.R == 1) ALN_REPAIR_LAUNCH(1, 4); else ALN_REPAIR_LAUNCH(2, 4); }
     else if (a.R == 1) ALN_REPAIR_LAUNCH(1, 1);
     else if (a.R == 2) ALN_REPAIR_LAUNCH(2, 1);

@@ -4,6 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "aln_device.h"
 #include "aln_cluster_rules.h"
 #include "aln_profile_rules.h"
@@ -82,6 +86,34 @@ struct CigarArgs {
 };
 
 static inline uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+
+// Beyond 64 KiB of dynamic LDS a kernel has to be told (hipFuncAttributeMaxDynamicSharedMemorySize).  The attribute belongs to the
+// kernel on a device, not to a stream or a thread, and callers on several threads launch one kernel with different sizes: so it only
+// ever goes up -- the highest size asked for so far, per (device, kernel), raised under a lock before the launch that needs it.  A
+// launch can then never find the attribute below its own size, whatever another thread set in between.  (One definition for the
+// whole library: an inline function's statics are shared by every translation unit.)
+inline hipError_t aln_lds_opt_in(const void *kern, uint32_t lds_bytes)
+{
+    if (lds_bytes <= 64u * 1024u) return hipSuccess;
+    static std::mutex lock;
+    static std::map<std::pair<int, const void *>, uint32_t> highest;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> hold(lock);
+    uint32_t &high = highest[std::make_pair(dev, kern)];
+    if (lds_bytes <= high) return hipSuccess;
+    e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e == hipSuccess) high = lds_bytes;
+    return e;
+}
+// the launch of a kernel that may need the opt-in (the launch's own error stays with the stream's next check, as for every launch)
+template <typename... P, typename... A>
+static inline void aln_launch_lds(void (*kern)(P...), dim3 g, dim3 b, uint32_t lds_bytes, hipStream_t s, A &&...args)
+{
+    (void)aln_lds_opt_in(reinterpret_cast<const void *>(kern), lds_bytes);
+    hipLaunchKernelGGL(kern, g, b, lds_bytes, s, std::forward<A>(args)...);
+}
 
 extern "C" {
 

@@ -95,10 +95,8 @@ static void shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair 
 {
     if (!n) return;
     const uint32_t lds = slot * ALN_SHUFFLE_THREADS;
-    if (lds > 64u * 1024u)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(aln_shuffle_kernel<TABLE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(aln_shuffle_kernel<TABLE>, dim3(blocks_of(n, ALN_SHUFFLE_THREADS)), dim3(ALN_SHUFFLE_THREADS), lds, s, seqs, out, pairs, p0, n,
-                       per_pair, seed, pair_base, max_trim, out_base, slot, stream);
+    aln_launch_lds(&aln_shuffle_kernel<TABLE>, dim3(blocks_of(n, ALN_SHUFFLE_THREADS)), dim3(ALN_SHUFFLE_THREADS), lds, s, seqs, out, pairs, p0, n, per_pair,
+                   seed, pair_base, max_trim, out_base, slot, stream);
 }
 
 extern "C" void aln_shuffle_launch(const uint8_t *seqs, uint8_t *out, const ShufflePair *pairs, uint32_t p0, uint64_t n, uint32_t per_pair,

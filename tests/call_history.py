@@ -13,6 +13,7 @@
 import ctypes as C
 import os
 import sys
+import threading
 
 import numpy as np
 
@@ -259,7 +260,14 @@ def _shuffle_entry(name, seed):
     return Entry(name, run, expected, [], shape=dict(kind="shuffle", pairs=len(pairs), per_pair=per_pair))
 
 
-_scan = {}
+_scan = threading.local()           # .scan: the calling thread's scan (one handle is one thread's: tests/concurrent_cases.py)
+
+
+def close_scan():
+    """destroys the calling thread's scan of scan_hits_held_list, if it has one"""
+    scan = _scan.__dict__.pop("scan", None)
+    if scan is not None:
+        scan.close()
 
 
 def _scan_entry(name, seed):
@@ -276,9 +284,9 @@ def _scan_entry(name, seed):
     mean, sd, z_min = 10.0, 4.0, 5.0                                 # hits: f >= 30
 
     def run():
-        if "scan" not in _scan:                                      # one scan per process: its private slot is reused as well
-            _scan["scan"] = HeldGpuScan(seq)
-        h = _scan["scan"].hits(pwm, 3, 1, 0, step, width, mean, sd, z_min)
+        if not hasattr(_scan, "scan"):                               # one scan per thread: its private slot is reused as well
+            _scan.scan = HeldGpuScan(seq)
+        h = _scan.scan.hits(pwm, 3, 1, 0, step, width, mean, sd, z_min)
         alns = h.alignments(np.arange(len(h)))
         return dict(idx=h.idx, f=h.f, numbered=np.concatenate([a.numbered for a in alns] + [np.zeros(0, np.uint32)]),
                     strings=np.concatenate([a.query for a in alns] + [np.zeros(0, np.uint8)]),
