@@ -11,10 +11,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libaligner_hip.so")
-SOURCES = ["aln_kernels.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip", "aln_signif.hip", "aln_pairset.hip", "aln_seqset.hip", "aln_loop.hip", "aln_best.hip", "aln_report.hip", "aln_cluster.hip", "aln_prefilter.hip", "aln_search.hip", "aln_profile.hip", "aln_msa.hip", "aln_cigar.hip", "aln_wordjoin.hip", "aln_strand.hip", "aln_seedjoin.hip"]
-# aln_kernels.hip is compiled as several translation units side by side (-DALN_TU=<mask of its ALN_PART_* families>): the fast
-# core-local batch kernel alone is half of the compile time
-KERNEL_UNITS = [("generic", 1), ("fast_cl", 2), ("fast_rest", 4), ("single", 8), ("tb", 16), ("fast_cl_solo", 32), ("fast_rest_solo", 64)]
+SOURCES = ["aln_kernels.hip", "aln_traceback.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip", "aln_signif.hip", "aln_pairset.hip", "aln_seqset.hip", "aln_loop.hip", "aln_best.hip", "aln_report.hip", "aln_cluster.hip", "aln_prefilter.hip", "aln_search.hip", "aln_profile.hip", "aln_msa.hip", "aln_cigar.hip", "aln_wordjoin.hip", "aln_strand.hip", "aln_seedjoin.hip"]
+# aln_kernels.hip (the fills) is compiled as several translation units side by side (-DALN_TU=<mask of its ALN_PART_* families>): the
+# fast core-local batch kernel alone is half of the compile time.  fast_rest_solo also holds the two-pairs-per-wave kernel
+# (ALN_PART_DUO, 128).  Every other source, aln_traceback.hip included, is one unit.
+KERNEL_UNITS = [("generic", 1), ("fast_cl", 2), ("fast_rest", 4), ("single", 8), ("fast_cl_solo", 32), ("fast_rest_solo", 64 | 128)]
 HEADERS = ["aln_arena_rules.h", "aln_best_rules.h", "aln_cigar_rules.h", "aln_cluster_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_layout_rules.h", "aln_loop_rules.h", "aln_msa_rules.h", "aln_plan_rules.h", "aln_prefilter_rules.h", "aln_profile_rules.h", "aln_report_rules.h", "aln_scheme_rules.h", "aln_search_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_signif_rules.h", "aln_strand_rules.h", "aln_transform_rules.h", "aln_wordjoin_rules.h", "aln_seedjoin_rules.h", "aln_postings.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h"),
            os.path.join("..", "..", "include", "aligner_hip_cluster.h"), os.path.join("..", "..", "include", "aligner_hip_prefilter.h"),
            os.path.join("..", "..", "include", "aligner_hip_search.h"), os.path.join("..", "..", "include", "aligner_hip_profile.h"),
@@ -176,7 +177,7 @@ def _build_lib(force=False, remarks=False):
     os.makedirs(objdir, exist_ok=True)
     jobs = [(base + ["-DALN_TU=%d" % mask, "-c", os.path.join(CSRC, "aln_kernels.hip"), "-o", os.path.join(objdir, "aln_kernels_%s.o" % name)])
             for name, mask in KERNEL_UNITS]
-    jobs += [base + ["-c", os.path.join(CSRC, src), "-o", os.path.join(objdir, src.replace(".hip", ".o"))] for src in SOURCES[1:]]
+    jobs += [base + ["-c", os.path.join(CSRC, src), "-o", os.path.join(objdir, src.replace(".hip", ".o"))] for src in SOURCES if src != "aln_kernels.hip"]
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as pool:
         for rc, cmd in zip(pool.map(subprocess.call, jobs), jobs):

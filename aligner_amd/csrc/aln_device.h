@@ -264,6 +264,7 @@ struct TraceSingleArgs {
 };
 
 // stored tag -> Direction discriminant (enums.rs:9-15: Top=0 Left=1 Diagonal=2 Beginning=3)
+constexpr int D_TOP = 0, D_LEFT = 1, D_DIAG = 2, D_BEG = 3;
 __host__ __device__ inline int aln_tag_to_dir(int t) { return t == 3 ? 3 : 2 - t; }
 __host__ __device__ inline int aln_dir_to_tag(int d) { return d == 3 ? 3 : 2 - d; }
 // bit position of cell (row r of the lane, wave step k) inside its packed word; lane l is active for steps l .. l+N-1

@@ -64,23 +64,6 @@
 // queue and wait for each other (measured: 6 slots 67 ms, 4 slots 57 ms for the C5 batch)
 #define ALN_POOL_SLOTS 4
 
-extern "C" void aln_launch_fill(const FillArgs *a, int is_int, int fast, uint32_t grid, uint32_t lds_bytes, hipStream_t s);
-extern "C" void aln_launch_validate(const uint8_t *seqs, PairDesc *descs, uint32_t n_pairs, uint32_t rows, uint32_t cols, int pwm,
-                                    hipStream_t s);
-extern "C" void aln_launch_traceback(const TraceArgs *a, hipStream_t s);
-extern "C" void aln_launch_traceback_wave(const TraceArgs *a, hipStream_t s);
-extern "C" void aln_launch_scale_results(aln_pair_result *results, uint32_t n, double factor, hipStream_t s);
-extern "C" void aln_launch_traceback_overlap(const TraceArgs *a, uint32_t waves, hipStream_t s);
-extern "C" void aln_launch_traceback_expand(const TraceArgs *a, hipStream_t s);
-extern "C" void aln_launch_traceback_single(const TraceSingleArgs *a, uint32_t N, hipStream_t s);
-extern "C" void aln_launch_traceback_expand_single(const TraceArgs *a, uint32_t pair, hipStream_t s);
-extern "C" void aln_launch_single(const SingleArgs *a, uint32_t N, int with_serial, hipStream_t s);
-extern "C" void aln_launch_wgpipe(const WgArgs *a, int is_int, uint32_t lds_bytes, hipStream_t s);
-extern "C" void aln_launch_single_init(const SingleArgs *a, uint32_t n_bytes, hipStream_t s);
-extern "C" void aln_launch_single_repair(const SingleArgs *a, uint32_t N, hipStream_t s);
-extern "C" void aln_launch_unpack(const uint8_t *dirs, const PairDesc *descs, uint32_t pair, int semantics, uint8_t *out,
-                                  uint64_t cells, hipStream_t s);
-
 static thread_local std::string g_err;
 
 // HIP multiplexes the streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4).  A pipelined batch call keeps
@@ -275,13 +258,6 @@ extern "C" int aln_abi_version(void) { return ALN_ABI_VERSION; }
 // events and staging, the buffers of the single-pair route at the size of the usual pair, the first launch of every kernel on
 // that route.  ALN_NO_WARMUP=1 leaves all of it to the first call as before.  A failure here is not an error of aln_create: the
 // first real call meets the same condition and reports it.
-extern "C" int aln_warm_fast_cl(void);
-extern "C" int aln_warm_fast_cl_solo(void);
-extern "C" int aln_warm_fast_rest(void);
-extern "C" int aln_warm_fast_rest_solo(void);
-extern "C" int aln_warm_generic(void);
-extern "C" int aln_warm_single(void);
-extern "C" int aln_warm_tb(void);
 static void warm_context(aln_ctx *c)
 {
     if (getenv("ALN_NO_WARMUP")) return;

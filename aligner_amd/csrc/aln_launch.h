@@ -1,6 +1,8 @@
-// aln_launch.h -- the launchers that aln_scan.hip, aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip, aln_search.hip, aln_profile.hip, aln_msa.hip, aln_cigar.hip, aln_wordjoin.hip, aln_seedjoin.hip and aln_strand.hip define
-// and aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
-// declaration the host compiles against.  (The launchers of aln_kernels.hip are declared at the top of aln_host.hip.)
+// aln_launch.h -- the launchers and code-object warm-ups that the kernel files (aln_kernels.hip, aln_traceback.hip, aln_scan.hip,
+// aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip,
+// aln_search.hip, aln_profile.hip, aln_msa.hip, aln_cigar.hip, aln_wordjoin.hip, aln_seedjoin.hip and aln_strand.hip) define and
+// aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
+// declaration the host compiles against: they are extern "C", and a signature that drifted would still link.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -116,6 +118,39 @@ static inline void aln_launch_lds(void (*kern)(P...), dim3 g, dim3 b, uint32_t l
 }
 
 extern "C" {
+
+// ---- aln_kernels.hip: the fills.  One code object per kernel unit (aligner_amd/build.py, KERNEL_UNITS), each with its warm-up
+int aln_warm_generic(void);
+int aln_warm_fast_cl(void);
+int aln_warm_fast_rest(void);
+int aln_warm_single(void);
+int aln_warm_fast_cl_solo(void);
+int aln_warm_fast_rest_solo(void);
+// the batch fill: picks the kernel (generic unit) and, for the fast integer path, hands on to the unit that holds it
+void aln_launch_fill(const FillArgs *a, int is_int, int fast, uint32_t grid, uint32_t lds_bytes, hipStream_t s);
+void aln_launch_fill_fast_cl(const FillArgs *a, uint32_t grid, uint32_t lds_bytes, hipStream_t s);
+void aln_launch_fill_fast_rest(const FillArgs *a, uint32_t grid, uint32_t lds_bytes, hipStream_t s);
+void aln_launch_fill_fast_cl_solo(const FillArgs *a, uint32_t grid, uint32_t lds_bytes, hipStream_t s);
+void aln_launch_fill_fast_rest_solo(const FillArgs *a, uint32_t grid, uint32_t lds_bytes, hipStream_t s);
+void aln_launch_fill_duo(const FillArgs *a, uint32_t grid, uint32_t lds_bytes, hipStream_t s);
+void aln_launch_wgpipe(const WgArgs *a, int is_int, uint32_t lds_bytes, hipStream_t s);
+void aln_launch_validate(const uint8_t *seqs, PairDesc *descs, uint32_t n_pairs, uint32_t rows, uint32_t cols, int pwm, hipStream_t s);
+// the single-pair route; aln_single_waves: strips per workgroup of its fill
+uint32_t aln_single_waves(int semantics, uint32_t R, uint32_t rows, uint32_t cols, uint32_t N, uint32_t ns);
+void aln_launch_single_init(const SingleArgs *a, uint32_t n_bytes, hipStream_t s);
+void aln_launch_single(const SingleArgs *a, uint32_t N, int with_serial, hipStream_t s);
+void aln_launch_single_repair(const SingleArgs *a, uint32_t N, hipStream_t s);
+
+// ---- aln_traceback.hip: the walks over the direction store, the aligned strings, the direction unpack, the dyadic rescaling
+int aln_warm_tb(void);
+void aln_launch_traceback(const TraceArgs *a, hipStream_t s);
+void aln_launch_traceback_wave(const TraceArgs *a, hipStream_t s);
+void aln_launch_traceback_overlap(const TraceArgs *a, uint32_t waves, hipStream_t s);
+void aln_launch_traceback_expand(const TraceArgs *a, hipStream_t s);
+void aln_launch_traceback_single(const TraceSingleArgs *a, uint32_t N, hipStream_t s);
+void aln_launch_traceback_expand_single(const TraceArgs *a, uint32_t pair, hipStream_t s);
+void aln_launch_unpack(const uint8_t *dirs, const PairDesc *descs, uint32_t pair, int semantics, uint8_t *out, uint64_t cells, hipStream_t s);
+void aln_launch_scale_results(aln_pair_result *results, uint32_t n, double factor, hipStream_t s);
 
 // ---- aln_scan.hip: the window scan
 void aln_scan_launch_expand(PairDesc *descs, uint32_t *order, uint64_t n, uint64_t first, uint64_t step, uint64_t width, uint64_t len,

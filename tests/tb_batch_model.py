@@ -1,4 +1,4 @@
-"""The batch traceback (tb_walk_pair, tb_walk_pair_wave, aln_traceback_expand_kernel: aln_kernels.hip) and the direction store
+"""The batch traceback (tb_walk_pair, tb_walk_pair_wave, aln_traceback_expand_kernel: aln_traceback.hip) and the direction store
 they read (aln_device.h), restated on the CPU.  Not a test module.
 
 `pack` turns the ORACLE's direction matrix into the words of a strip region; `lane_walk` and `wave_walk` then take the steps the

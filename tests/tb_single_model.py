@@ -15,14 +15,14 @@ at the end cell (core, PWM) or at its diagonal predecessor (legacy: aligner_core
 The band on the row `cy` a strip is entered on: the slope-1 line through the walk's first cell (ey, ex) is at column
 ex - (ey - cy), clamped at 0; the band starts BAND/2 columns left of it, clamped at 0, and holds BAND columns, clamped at N.
 
-Constants restated from aligner_amd/csrc/aln_kernels.hip (by the names and lines they have there):
-  BAND    1024  `#define TB_BAND 1024u` (l. 2650), used by tb_band (l. 2651-2659)
-  cap     2 rows + 64 steps: the last arguments of walk_in_strip in aln_tb_single_maps_kernel (l. 2695); the loop's test is
-          `n < n_stop` (l. 2625), `gave_up` is "still inside after the loop" (l. 2627)
-  window  min(12 R, 48) quads: tb_window_quads (l. 2644); a quad is 4 blocks of 16 / R wave steps (stage_window, l. 2568-2594:
+Constants restated from aligner_amd/csrc/aln_traceback.hip (by the names and lines they have there):
+  BAND    1024  `#define TB_BAND 1024u` (l. 414), used by tb_band (l. 415-423)
+  cap     2 rows + 64 steps: the last arguments of walk_in_strip in aln_tb_single_maps_kernel (l. 459); the loop's test is
+          `n < n_stop` (l. 389), `gave_up` is "still inside after the loop" (l. 391)
+  window  min(12 R, 48) quads: tb_window_quads (l. 408); a quad is 4 blocks of 16 / R wave steps (stage_window, l. 332-358:
           the window ends with the quad of wave step k_hi)
-  BLOCK   256 columns per workgroup of the maps kernel: `__launch_bounds__(256)` (l. 2662), grid TB_BAND / 256 (l. 3377)
-A wave step is k = x - 1 + lane, lane = (y - 1 - y0) / R (walk_in_strip, l. 2614-2616).
+  BLOCK   256 columns per workgroup of the maps kernel: `__launch_bounds__(256)` (l. 426), grid TB_BAND / 256 (l. 713)
+A wave step is k = x - 1 + lane, lane = (y - 1 - y0) / R (walk_in_strip, l. 378-380).
 """
 BAND = 1024
 BLOCK = 256

@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import tb_batch_cases as tc  # noqa: E402
 import tb_batch_model as bm  # noqa: E402
+from aligner_amd import build as native_build  # noqa: E402
 
 _refs = {}
 
@@ -195,3 +196,4 @@ def test_multiply_shift_is_the_division():
         rinv = (65535 + R) // R
         assert all((iy * rinv) >> 16 == iy // R for iy in range(512)), R
     assert [bm.spb(R) for R in range(1, 9)] == [16, 8, 4, 4, 2, 2, 2, 2]
+    assert "aln_traceback.hip" in native_build.SOURCES and "aln_launch.h" in native_build.HEADERS     # where the walks restated here live
