@@ -66,6 +66,11 @@ WORDJOIN_CHUNK_OCCURRENCES, WORDJOIN_MAX_CHUNK_OCCURRENCES = 1 << 24, 1 << 26
 SEEDJOIN_EXPORTS = ["aln_seqset_candidate_diags", "aln_seqset_seed_index", "aln_seqset_seed_join"]
 SEEDJOIN_MAX_K, SEEDJOIN_MAX_WORDS, SEEDJOIN_MAX_BAND = 16, 1 << 32, (1 << 31) - 1        # aligner_amd/csrc/aln_seedjoin_rules.h
 SEEDJOIN_CHUNK_SEEDS, SEEDJOIN_MAX_CHUNK_SEEDS = 1 << 24, 1 << 26
+# every symbol the companion header include/aligner_hip_seedchain.h declares (the same library, as above)
+SEEDCHAIN_EXPORTS = ["aln_seqset_candidate_chain_filter", "aln_seqset_candidate_chain_records", "aln_seqset_candidate_chains"]
+SEEDCHAIN_MAX_GAP, SEEDCHAIN_MAX_SKEW, SEEDCHAIN_MAX_GAP_SCALE = (1 << 31) - 1, (1 << 31) - 1, 255        # aligner_amd/csrc/aln_seedchain_rules.h
+SEEDCHAIN_PAIR_SEEDS, SEEDCHAIN_MAX_PAIR_SEEDS, SEEDCHAIN_CHUNK_ANCHORS, SEEDCHAIN_MAX_CHUNK_ANCHORS = 1 << 16, 1 << 20, 1 << 24, 1 << 26
+CHAIN_OVERFLOW = 1
 # every symbol the companion header include/aligner_hip_search.h declares (the same library, as above)
 SEARCH_EXPORTS = ["aln_seqset_candidate_best"]
 # every symbol the companion header include/aligner_hip_profile.h declares (the same library, as above)
@@ -238,6 +243,24 @@ class SeedjoinSpec(C.Structure):
     """aln_seedjoin_spec: the seed index a join expects, its thresholds and its band (include/aligner_hip_seedjoin.h)."""
     _fields_ = [("k", C.c_uint32), ("alphabet", C.c_uint32), ("min_seeds", C.c_uint32), ("band", C.c_uint32), ("max_occ", C.c_uint32),
                 ("chunk_seeds", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SeedchainSpec(C.Structure):
+    """aln_seedchain_spec: the seed index a chaining call expects and the chain's parameters (include/aligner_hip_seedchain.h)."""
+    _fields_ = [("k", C.c_uint32), ("alphabet", C.c_uint32), ("max_occ", C.c_uint32), ("max_gap", C.c_uint32), ("max_skew", C.c_uint32),
+                ("gap_scale", C.c_uint32), ("max_pair_seeds", C.c_uint32), ("chunk_anchors", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class ChainRecord(C.Structure):
+    """aln_chain_record: one candidate's chain."""
+    _fields_ = [("score", C.c_int32), ("anchors", C.c_uint32), ("q_start", C.c_uint32), ("q_end", C.c_uint32), ("t_start", C.c_uint32),
+                ("t_end", C.c_uint32), ("seeds", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SeedchainSummary(C.Structure):
+    """aln_seedchain_summary: the counts of one chaining call."""
+    _fields_ = [("anchors", C.c_uint64), ("with_anchor", C.c_uint64), ("overflowed", C.c_uint64), ("chunks", C.c_uint64)]
 
 
 class SeedjoinSummary(C.Structure):
@@ -416,6 +439,12 @@ def load():
     lib.aln_seqset_seed_join.argtypes = [vp, C.POINTER(SeedjoinSpec), bp, C.POINTER(SeedjoinSummary), C.POINTER(C.c_uint64)]
     lib.aln_seqset_candidate_diags.restype = i
     lib.aln_seqset_candidate_diags.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
+    lib.aln_seqset_candidate_chains.restype = i
+    lib.aln_seqset_candidate_chains.argtypes = [vp, C.POINTER(SeedchainSpec), C.c_uint64, C.c_uint64, vp, C.POINTER(SeedchainSummary)]
+    lib.aln_seqset_candidate_chain_filter.restype = i
+    lib.aln_seqset_candidate_chain_filter.argtypes = [vp, C.POINTER(SeedchainSpec), C.c_int32, C.c_uint32, C.POINTER(SeedchainSummary), C.POINTER(C.c_uint64)]
+    lib.aln_seqset_candidate_chain_records.restype = i
+    lib.aln_seqset_candidate_chain_records.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
     lib.aln_seqset_candidates.restype = i
     lib.aln_seqset_candidates.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
     lib.aln_seqset_candidate_scores.restype = i

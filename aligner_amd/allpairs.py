@@ -75,6 +75,19 @@ best band and its least diagonal.  Everything that combines with --kmer --word-j
 and --best-candidates included; against a reverse-complement partner the diagonal is in the mirror's coordinates (position p of the
 mirror is position length - 1 - p of the record).
 
+With --kmer K --seed-join --chain (or --word-join --chain) the candidates are filtered, before any pass, by the colinear chain over ALL
+their seeds (anchors: every (pq, pt) with the same, not dropped, word at both), chained on the device from the seed index alone: an
+anchor may follow another that lies before it on both records, within --max-gap G on either (default 1000) and within --max-skew B of
+diagonal drift (default 200); a link gains min(the two distances, K) and costs drift / 8; a chain's score is K plus its links'.  A
+candidate is kept if its best chain scores at least --min-chain-score S (default 0) and spans at least --min-chain-span L residues on
+both records (default 0), or if it has more than 2^16 anchors and is not chained at all (never lost for being expensive; its chain
+columns are 0).  Rows without --f-min gain `chain_score,anchors,q_start,q_end,t_start,t_end` (after `diag` with --seed-join): the
+chain's score, its anchors, and where it starts and ends (0-based, end exclusive) on the two records; against a reverse-complement
+partner the target positions are in the mirror's coordinates, as diag is.  --chain-paf FILE writes one approximate PAF line per printed
+candidate WITHOUT any fill: the 12 columns with residue matches = anchors * K capped at the shorter span and block length = the longer
+span, mapping quality 255, then `cs:i:<score>` and `cn:i:<anchors>`, no `cg`; with --both-strands strand `-` and the coordinates on the
+original records, converted as --paf converts them.  Every option that combines with --seed-join combines with --chain unchanged.
+
 With --dna --both-strands every record is also held as its reverse complement, made on the device behind the records, and every pass is
 one rectangle: each record as the query against every record on both strands.  Every row gains a `strand` column after t_head -- `+`, or
 `-` where the partner matches as its reverse complement; t_head is the original record's header.  A pair (i, j) is computed from both
@@ -136,6 +149,12 @@ def main(argv=None):
     ap.add_argument("--min-seeds", type=int, default=None, metavar="N", help="with --seed-join: candidates have at least N seeds within one band of diagonals (default 1)")
     ap.add_argument("--band", type=int, default=None, metavar="B", help="with --seed-join: a band holds the diagonals d0 .. d0 + B (default 0)")
     ap.add_argument("--max-occ", type=int, default=None, metavar="C", help="with --seed-join: words with more than C occurrences in the whole set make no seed (default 0: none is dropped)")
+    ap.add_argument("--chain", action="store_true", help="with --seed-join or --word-join: keep the candidates by the colinear chain over their seeds; rows gain chain_score,anchors,q_start,q_end,t_start,t_end")
+    ap.add_argument("--max-gap", type=int, default=None, metavar="G", help="with --chain: chained seeds lie within G residues of each other on either record (default 1000)")
+    ap.add_argument("--max-skew", type=int, default=None, metavar="B", help="with --chain: chained seeds drift at most B diagonals apart (default 200)")
+    ap.add_argument("--min-chain-score", type=int, default=None, metavar="S", help="with --chain: keep the candidates whose chain scores at least S (default 0)")
+    ap.add_argument("--min-chain-span", type=int, default=None, metavar="L", help="with --chain: keep the candidates whose chain spans at least L residues on both records (default 0)")
+    ap.add_argument("--chain-paf", default=None, metavar="FILE", help="with --chain: write one approximate PAF line per printed candidate to FILE, without any fill")
     ap.add_argument("--both-strands", action="store_true", help="with --dna: also match every record as its reverse complement; rows gain a strand column")
     a = ap.parse_args(argv)
     if a.both_strands:
@@ -155,6 +174,13 @@ def main(argv=None):
             ap.error("--min-shared / --min-shared-per-1024 count distinct shared words: --seed-join counts seeds, its thresholds are --min-seeds, --band and --max-occ")
     elif a.min_seeds is not None or a.band is not None or a.max_occ is not None:
         ap.error("--min-seeds / --band / --max-occ are the thresholds of --seed-join: give --kmer K --seed-join")
+    if a.chain_paf is not None and not a.chain:
+        ap.error("--chain-paf writes the chains of --chain: give --chain")
+    if a.chain:
+        if a.kmer is None or not (a.seed_join or a.word_join):
+            ap.error("--chain chains the seeds of a join's candidates: give --kmer K with --seed-join or --word-join")
+    elif a.max_gap is not None or a.max_skew is not None or a.min_chain_score is not None or a.min_chain_span is not None:
+        ap.error("--max-gap / --max-skew / --min-chain-score / --min-chain-span are the parameters of --chain: give --chain")
     if a.best_candidates is not None:
         if a.kmer is None:
             ap.error("--best-candidates selects among the prefilter's candidates: give --kmer K")
@@ -189,6 +215,15 @@ def main(argv=None):
                 ap.error("--min-shared with --word-join: N must be at least 1, a join sees only pairs that share a word")
         elif not 1 <= a.kmer <= _ffi.PREFILTER_MAX_K or kmer_alphabet < 1 or kmer_alphabet ** a.kmer > _ffi.PREFILTER_MAX_BITS:
             ap.error("--kmer: K must lie in 1 .. %d and A^K may not exceed 2^18" % _ffi.PREFILTER_MAX_K)
+        if a.chain:
+            if a.max_gap is not None and not 1 <= a.max_gap <= _ffi.SEEDCHAIN_MAX_GAP:
+                ap.error("--max-gap: G must lie in 1 .. 2^31 - 1")
+            if a.max_skew is not None and not 0 <= a.max_skew <= _ffi.SEEDCHAIN_MAX_SKEW:
+                ap.error("--max-skew: B must lie in 0 .. 2^31 - 1")
+            if a.min_chain_score is not None and not -(2 ** 31) <= a.min_chain_score < 2 ** 31:
+                ap.error("--min-chain-score: S must fit 32 signed bits")
+            if a.min_chain_span is not None and not 0 <= a.min_chain_span < 2 ** 32:
+                ap.error("--min-chain-span: L must lie in 0 .. 2^32 - 1")
         if a.min_shared is not None and not 0 <= a.min_shared < 2 ** 32:
             ap.error("--min-shared: N must lie in 0 .. 2^32 - 1")
         if a.min_shared_per_1024 is not None and not 0 <= a.min_shared_per_1024 <= 1024:
@@ -319,9 +354,37 @@ def main(argv=None):
                                                             float(x["t_cover"]), int(x["gap_opens"]), int(x["gaps"]))
         return rows
 
+    def chain_paf(cand):
+        """--chain-paf: one approximate line per printed candidate, from its chain record alone"""
+        length = cand.owner.len
+        shown = np.flatnonzero(once(cand.q, cand.t)) if a.both_strands else range(len(cand))
+        with open(a.chain_paf, "w") as fh:
+            for c in shown:
+                r, q, t = cand.chain[c], int(cand.q[c]), int(cand.t[c])
+                minus = a.both_strands and t >= n_rec
+                t_len, ts, te = int(length[t]), int(r["t_start"]), int(r["t_end"])
+                if minus:
+                    ts, te = t_len - te, t_len - ts
+                sq, st = int(r["q_end"]) - int(r["q_start"]), te - ts
+                fh.write("%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tcs:i:%d\tcn:i:%d\n" % (
+                    heads[q], int(length[q]), int(r["q_start"]), int(r["q_end"]), "-" if minus else "+", heads[t % n_rec], t_len, ts, te,
+                    min(int(r["anchors"]) * a.kmer, sq, st), max(sq, st), int(r["score"]), int(r["anchors"])))
+
     def candidates(ss, block):
         """the candidate list of --kmer over the block, by the bitmaps or, with --word-join, by the sorted word index or, with
-        --seed-join, by the seeds on a common diagonal"""
+        --seed-join, by the seeds on a common diagonal; with --chain, filtered by the chain over their seeds"""
+        if not a.chain:
+            return joined(ss, block)
+        if not a.seed_join:
+            ss.seed_index(a.kmer, kmer_alphabet)       # before the list is made: a new index drops it
+        cand = joined(ss, block).chain_filter(a.min_chain_score or 0, a.min_chain_span or 0, max_gap=1000 if a.max_gap is None else a.max_gap,
+                                              max_skew=200 if a.max_skew is None else a.max_skew, max_occ=a.max_occ or 0, k=a.kmer,
+                                              alphabet_size=kmer_alphabet)
+        if a.chain_paf is not None:
+            chain_paf(cand)
+        return cand
+
+    def joined(ss, block):
         if a.seed_join:
             return ss.seed_join(a.kmer, kmer_alphabet, min_seeds=1 if a.min_seeds is None else a.min_seeds, band=a.band or 0, max_occ=a.max_occ or 0,
                                 block=block)
@@ -385,7 +448,9 @@ def main(argv=None):
             for c in (np.flatnonzero(once(cand.q, cand.t)) if a.both_strands else range(len(cand))):
                 out.write("%s,%s,%s,%d%s\n" % (heads[int(cand.q[c])], t_cols(cand.t[c]),
                                                repr(float(f[c])) if status[c] == _ffi.OK else _ffi.STATUS_NAMES[int(status[c])], int(cand.shared[c]),
-                                               ",%d" % int(cand.diag[c]) if a.seed_join else ""))
+                                               (",%d" % int(cand.diag[c]) if a.seed_join else "") +
+                                               (",%d,%d,%d,%d,%d,%d" % tuple(int(cand.chain[c][n]) for n in ("score", "anchors", "q_start", "q_end", "t_start", "t_end"))
+                                                if a.chain else "")))
         elif a.f_min is None and a.both_strands:
             f, status = ss.score(matrix, a.del_, a.ext, square(ss), semantics=sem)
             for i in range(n_rec):

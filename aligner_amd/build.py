@@ -11,17 +11,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libaligner_hip.so")
-SOURCES = ["aln_kernels.hip", "aln_traceback.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip", "aln_signif.hip", "aln_pairset.hip", "aln_seqset.hip", "aln_loop.hip", "aln_best.hip", "aln_report.hip", "aln_cluster.hip", "aln_prefilter.hip", "aln_search.hip", "aln_profile.hip", "aln_msa.hip", "aln_cigar.hip", "aln_wordjoin.hip", "aln_strand.hip", "aln_seedjoin.hip"]
+SOURCES = ["aln_kernels.hip", "aln_traceback.hip", "aln_host.hip", "aln_scan.hip", "aln_shuffle.hip", "aln_signif.hip", "aln_pairset.hip", "aln_seqset.hip", "aln_loop.hip", "aln_best.hip", "aln_report.hip", "aln_cluster.hip", "aln_prefilter.hip", "aln_search.hip", "aln_profile.hip", "aln_msa.hip", "aln_cigar.hip", "aln_wordjoin.hip", "aln_strand.hip", "aln_seedjoin.hip", "aln_seedchain.hip"]
 # aln_kernels.hip (the fills) is compiled as several translation units side by side (-DALN_TU=<mask of its ALN_PART_* families>): the
 # fast core-local batch kernel alone is half of the compile time.  fast_rest_solo also holds the two-pairs-per-wave kernel
 # (ALN_PART_DUO, 128).  Every other source, aln_traceback.hip included, is one unit.
 KERNEL_UNITS = [("generic", 1), ("fast_cl", 2), ("fast_rest", 4), ("single", 8), ("fast_cl_solo", 32), ("fast_rest_solo", 64 | 128)]
-HEADERS = ["aln_arena_rules.h", "aln_best_rules.h", "aln_cigar_rules.h", "aln_cluster_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_layout_rules.h", "aln_loop_rules.h", "aln_msa_rules.h", "aln_plan_rules.h", "aln_prefilter_rules.h", "aln_profile_rules.h", "aln_report_rules.h", "aln_scheme_rules.h", "aln_search_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_signif_rules.h", "aln_strand_rules.h", "aln_transform_rules.h", "aln_wordjoin_rules.h", "aln_seedjoin_rules.h", "aln_postings.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h"),
+HEADERS = ["aln_arena_rules.h", "aln_best_rules.h", "aln_cigar_rules.h", "aln_cluster_rules.h", "aln_device.h", "aln_fast.h", "aln_launch.h", "aln_layout_rules.h", "aln_loop_rules.h", "aln_msa_rules.h", "aln_plan_rules.h", "aln_prefilter_rules.h", "aln_profile_rules.h", "aln_report_rules.h", "aln_scheme_rules.h", "aln_search_rules.h", "aln_select.h", "aln_seqset_rules.h", "aln_shuffle_rules.h", "aln_signif_rules.h", "aln_strand_rules.h", "aln_transform_rules.h", "aln_wordjoin_rules.h", "aln_seedjoin_rules.h", "aln_seedchain_rules.h", "aln_postings.h", "aln_single_unit.inc", os.path.join("..", "..", "include", "aligner_hip.h"),
            os.path.join("..", "..", "include", "aligner_hip_cluster.h"), os.path.join("..", "..", "include", "aligner_hip_prefilter.h"),
            os.path.join("..", "..", "include", "aligner_hip_search.h"), os.path.join("..", "..", "include", "aligner_hip_profile.h"),
            os.path.join("..", "..", "include", "aligner_hip_msa.h"), os.path.join("..", "..", "include", "aligner_hip_cigar.h"),
            os.path.join("..", "..", "include", "aligner_hip_wordjoin.h"), os.path.join("..", "..", "include", "aligner_hip_strand.h"),
-           os.path.join("..", "..", "include", "aligner_hip_seedjoin.h")]
+           os.path.join("..", "..", "include", "aligner_hip_seedjoin.h"), os.path.join("..", "..", "include", "aligner_hip_seedchain.h")]
 # host-only helper of the synthetic workloads (splitmix64 residues; aligner_amd/workloads.py only LOADS it)
 SYNTH_LIB = os.path.join(LIBDIR, "libaln_synth.so")
 SYNTH_SRC = os.path.join(CSRC, "aln_synth.c")
@@ -90,6 +90,10 @@ STRAND = os.path.join(HERE, "..", "tests", "bin", "abi_strand")
 # tests/test_seedjoin_gpu.py)
 SEEDJOIN_SRC = os.path.join(HERE, "..", "tests", "abi_seedjoin.c")
 SEEDJOIN = os.path.join(HERE, "..", "tests", "bin", "abi_seedjoin")
+# tests/abi_seedchain.c: the same for the companion header include/aligner_hip_seedchain.h (tests/test_seedchain_rules_cpu.py,
+# tests/test_seedchain_gpu.py)
+SEEDCHAIN_SRC = os.path.join(HERE, "..", "tests", "abi_seedchain.c")
+SEEDCHAIN = os.path.join(HERE, "..", "tests", "bin", "abi_seedchain")
 
 
 def build_harness(force=False):
@@ -136,9 +140,13 @@ def build_seedjoin_harness(force=False):
     return _build_c_program(SEEDJOIN_SRC, SEEDJOIN, force)
 
 
+def build_seedchain_harness(force=False):
+    return _build_c_program(SEEDCHAIN_SRC, SEEDCHAIN, force)
+
+
 def _build_c_program(src, out, force=False):
     src, out = os.path.abspath(src), os.path.abspath(out)
-    hdrs = [os.path.join(HERE, "..", "include", h) for h in ("aligner_hip.h", "aligner_hip_cluster.h", "aligner_hip_prefilter.h", "aligner_hip_search.h", "aligner_hip_profile.h", "aligner_hip_msa.h", "aligner_hip_cigar.h", "aligner_hip_wordjoin.h", "aligner_hip_strand.h", "aligner_hip_seedjoin.h")]
+    hdrs = [os.path.join(HERE, "..", "include", h) for h in ("aligner_hip.h", "aligner_hip_cluster.h", "aligner_hip_prefilter.h", "aligner_hip_search.h", "aligner_hip_profile.h", "aligner_hip_msa.h", "aligner_hip_cigar.h", "aligner_hip_wordjoin.h", "aligner_hip_strand.h", "aligner_hip_seedjoin.h", "aligner_hip_seedchain.h")]
     if force or not os.path.exists(out) or max([os.path.getmtime(f) for f in [src, LIB] + hdrs]) > os.path.getmtime(out):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         tmp = out + ".tmp%d" % os.getpid()
@@ -161,6 +169,7 @@ def build(force=False, remarks=False):
     build_wordjoin_harness(force)
     build_strand_harness(force)
     build_seedjoin_harness(force)
+    build_seedchain_harness(force)
     return lib
 
 

@@ -58,6 +58,7 @@
 #include "../../include/aligner_hip_wordjoin.h"
 #include "aln_seedjoin_rules.h"
 #include "../../include/aligner_hip_seedjoin.h"
+#include "aln_seedchain_rules.h"
 
 #define ALN_TIMING_SLOTS 256u
 // HIP multiplexes streams onto 4 hardware queues by default (GPU_MAX_HW_QUEUES): with more slots than that two chunks share a
@@ -280,7 +281,7 @@ static void warm_context(aln_ctx *c)
         if (hipSetDevice(c->devs[d]->device) != hipSuccess) continue;
         (void)aln_warm_single(); (void)aln_warm_tb(); (void)aln_warm_generic();
         (void)aln_warm_fast_cl(); (void)aln_warm_fast_cl_solo(); (void)aln_warm_fast_rest(); (void)aln_warm_fast_rest_solo();
-        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile(); (void)aln_warm_msa(); (void)aln_warm_cigar(); (void)aln_warm_wordjoin(); (void)aln_warm_seedjoin();
+        (void)aln_warm_best(); (void)aln_warm_search(); (void)aln_warm_profile(); (void)aln_warm_msa(); (void)aln_warm_cigar(); (void)aln_warm_wordjoin(); (void)aln_warm_seedjoin(); (void)aln_warm_seedchain();
         aln_pair_result r;
         (void)aln_align_pair(c, &p, q.data(), L, t.data(), L, &r, qa.data(), ta.data(), nullptr, nullptr);   // devices in turn
     }
@@ -2804,16 +2805,17 @@ struct BestPass { uint32_t slots; uint32_t flags; double f_min; };
 #define ALN_SEQSET_CHUNK_PAIRS (1ull << 22)        // per chunk: the pair limit of a chunk of aln_align_batch
 
 // the host's copy of a set's candidate list: pair numbers of `block`, ascending, with their sequence numbers and shared counts (a seed
-// join: seeds, and the diagonals beside them).  live: there is a list
+// join: seeds, and the diagonals beside them).  live: there is a list; has_chain: a chain filter made it, and the kept entries' chain
+// records are resident (chain_rec)
 struct CandList {
-    bool live = false, has_diag = false;
+    bool live = false, has_diag = false, has_chain = false;
     aln_seqset_block block = {0, 0, 0, 0, 0, 0};
     std::vector<uint64_t> pair;
     std::vector<uint32_t> qs, ts, shared;
     std::vector<int32_t> diag;
     void clear()
     {
-        live = has_diag = false;
+        live = has_diag = has_chain = false;
         pair.clear(); qs.clear(); ts.clear(); shared.clear(); diag.clear();
     }
 };
@@ -2891,6 +2893,10 @@ struct aln_seqset : CallStats {
     uint32_t seed_k = 0, seed_alphabet = 0;
     uint64_t seed_entries = 0;
     DevBuf seed_key, seed_pos, sj_diag;
+    // the seed chains (aln_seedchain_rules.h).  ch_*: a call's tables -- the listed entries' records (q | t), their anchors (A | what
+    // is chained | the 64-bit offsets), their chain records, a run's anchors | states, a filter's kept places; chain_rec: the chain
+    // records of the entries a filter kept, resident while cands.has_chain
+    DevBuf ch_q, ch_t, ch_seeds, ch_chained, ch_off, ch_rec, ch_anchor, ch_state, ch_pos, chain_rec;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 0 .. 2: a chunk's launches; 4, 5: the best selection
     // pair sets made by aln_pairset_create_from_set read the residue buffer: a destroy with some of them alive releases everything
     // else, moves the buffer here and leaves the rest to the last of them
@@ -2920,7 +2926,8 @@ extern "C" void aln_seqset_destroy(aln_seqset *ss)
     DevBuf *d[] = {&ss->d_off, &ss->d_len, &ss->fbuf, &ss->stbuf, &ss->tiles, &ss->hit_k, &ss->hit_f, &ss->misc, &ss->cand_key, &ss->cand_t, &ss->cand_n,
                    &ss->run_key, &ss->run_t, &ss->run_n, &ss->rep_bits, &ss->reports, &ss->rep_pos, &ss->rep_out, &ss->cluster, &ss->kmer_bits, &ss->kmer_n,
                    &ss->cand_k, &ss->pf_shared, &ss->pf_keep, &ss->pf_out, &ss->row_first, &ss->profile, &ss->msa, &ss->msa_out, &ss->cigar,
-                   &ss->cigar_out, &ss->strand_map, &ss->cigar_rev, &ss->word_e, &ss->word_n, &ss->wj_first, &ss->wj_len, &ss->wj_off, &ss->wj_occ, &ss->wj_a, &ss->wj_b, &ss->wj_temp, &ss->seed_key, &ss->seed_pos, &ss->sj_diag};
+                   &ss->cigar_out, &ss->strand_map, &ss->cigar_rev, &ss->word_e, &ss->word_n, &ss->wj_first, &ss->wj_len, &ss->wj_off, &ss->wj_occ, &ss->wj_a, &ss->wj_b, &ss->wj_temp, &ss->seed_key, &ss->seed_pos, &ss->sj_diag,
+                   &ss->ch_q, &ss->ch_t, &ss->ch_seeds, &ss->ch_chained, &ss->ch_off, &ss->ch_rec, &ss->ch_anchor, &ss->ch_state, &ss->ch_pos, &ss->chain_rec};
     for (DevBuf *b : d) dev_free(*b);
     pin_free(ss->h_out);
     if (ss->derived && ss->slot) { ss->residues = ss->slot->seqs; ss->slot->seqs = DevBuf{}; }
@@ -4098,6 +4105,232 @@ extern "C" int aln_seqset_candidate_diags(aln_seqset *ss, uint64_t first, uint64
     if (n && !diag) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
     for (uint64_t i = 0; i < n; ++i) diag[i] = ss->cands.diag[first + i];
     return ALN_OK;                       // (no byte moves and no kernel runs: the stats stay as they are)
+}
+
+// ---------------------------------------------------------------- seed chains (include/aligner_hip_seedchain.h)
+// The colinear chain over ALL seeds of every listed candidate, from the seed index alone: count the anchors per candidate, cut the
+// list into runs of whole candidates of at most chunk_anchors, expand and chain run by run.  The records of a call lie in ch_rec; a
+// filter compacts the list by them into a new pair-number buffer and a new record buffer and changes places only when all is there.
+static const char *const SEEDCHAIN_REFUSALS[] = {
+    "", "max_gap must lie in 1 .. 2^31 - 1", "max_skew must lie in 0 .. 2^31 - 1", "gap_scale must lie in 0 .. 255",
+    "max_pair_seeds must lie in 0 .. 2^20", "chunk_anchors must lie in 0 .. 2^26", "the spec's flags and reserved words must be 0",
+    "max_pair_seeds (0: 2^16) may not exceed chunk_anchors (0: 2^24): a pair that is chained must fit one chunk"};
+#define ALN_SEEDCHAIN_CHUNK_CANDIDATES (1ull << 22)      // per run: what one launch takes a block each of
+
+static int seqset_chain_check(aln_seqset *ss, const aln_seedchain_spec *sp)
+{
+    if (!aln_seedjoin_words(sp->k, sp->alphabet)) { g_err = SEEDJOIN_RANGE; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!ss->seed_k || sp->k != ss->seed_k || sp->alphabet != ss->seed_alphabet) { g_err = "no seed index of this k and alphabet: aln_seqset_seed_index builds it"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint32_t why = aln_seedchain_spec_refusal(*sp);
+    if (why) { g_err = SEEDCHAIN_REFUSALS[why]; return ALN_ERR_INVALID_ARGUMENT; }
+    return seqset_cand_check(ss);
+}
+
+struct ChainRun {
+    aln_seedchain_summary sum = {0, 0, 0, 0};
+    uint64_t up = 0, down = 0;
+    double kernels = 0;
+};
+
+// the chain records of entries first .. first + n - 1 of the list into ss->ch_rec (n >= 1; the stream is idle before and after).
+// Nothing of the set's state but the ch_* tables is touched
+static int seqset_chain_run(aln_seqset *ss, const aln_seedchain_spec *sp, uint64_t first, uint64_t n, ChainRun *run)
+{
+    hipStream_t q = ss->slot->stream;
+    uint32_t *misc = ss->misc.as<uint32_t>() + ALN_SEQSET_MISC_CHAIN;
+    const uint64_t cap = aln_seedchain_chunk_anchors(*sp);
+    const aln_seedchain_index x = {ss->slot->seqs.as<uint8_t>(), ss->d_off.as<uint64_t>(), ss->d_len.as<uint32_t>(), ss->n, ss->total,
+                                   ss->seed_key.as<uint64_t>(), ss->seed_pos.as<uint32_t>(), ss->seed_entries};
+    std::vector<uint32_t> seeds_h(n), chained_h(n);
+    std::vector<uint64_t> per(n), run_first, run_count, run_base, run_sum;
+    return run_queued(q, [&]() -> int {
+        int st;
+        for (DevBuf *d : {&ss->ch_q, &ss->ch_t, &ss->ch_seeds, &ss->ch_chained})
+            if ((st = dev_ensure(*d, 4 * n, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->ch_off, 8 * n, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->ch_rec, sizeof(aln_chain_record) * n, false)) != ALN_OK) return st;
+        HIPCHK(hipMemcpyAsync(ss->ch_q.p, ss->cands.qs.data() + first, 4 * n, hipMemcpyHostToDevice, q));
+        HIPCHK(hipMemcpyAsync(ss->ch_t.p, ss->cands.ts.data() + first, 4 * n, hipMemcpyHostToDevice, q));
+        run->up += 8 * n;
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        HIPCHK(hipMemsetAsync(misc, 0, 4 * ALN_SEQSET_MISC_CHAIN_WORDS, q));
+        aln_seedchain_launch_count(&x, sp, ss->ch_q.as<uint32_t>(), ss->ch_t.as<uint32_t>(), n, ss->ch_seeds.as<uint32_t>(), ss->ch_chained.as<uint32_t>(),
+                                   ss->ch_off.as<uint64_t>(), reinterpret_cast<uint64_t *>(misc + ALN_CHAIN_MISC_TOTAL), ss->ch_rec.as<aln_chain_record>(),
+                                   misc + ALN_CHAIN_MISC_ERRORS, q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        uint32_t h[ALN_SEQSET_MISC_CHAIN_WORDS] = {};
+        HIPCHK(hipMemcpyAsync(seeds_h.data(), ss->ch_seeds.p, 4 * n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(chained_h.data(), ss->ch_chained.p, 4 * n, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(h, misc, sizeof h, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        run->kernels += ev_ms(ss->ev[0], ss->ev[1]);
+        run->down += 8 * n + sizeof h;
+        if (h[ALN_CHAIN_MISC_ERRORS]) { g_err = "a listed candidate names no record of the set"; return ALN_ERR_DEVICE; }
+        const uint32_t pair_cap = aln_seedchain_pair_seeds(*sp);
+        uint64_t total = 0;
+        for (uint64_t c = 0; c < n; ++c) {
+            if (chained_h[c] != aln_seedchain_chained(seeds_h[c], pair_cap)) { g_err = "a candidate chains other anchors than the rule gives it"; return ALN_ERR_DEVICE; }
+            per[c] = chained_h[c];
+            total += per[c];
+            run->sum.with_anchor += seeds_h[c] != 0u;
+            run->sum.overflowed += seeds_h[c] > pair_cap;
+        }
+        if (total != ((uint64_t)h[ALN_CHAIN_MISC_TOTAL + 1] << 32 | h[ALN_CHAIN_MISC_TOTAL])) { g_err = "the anchors' offsets differ from their counts"; return ALN_ERR_DEVICE; }
+        // the runs of whole candidates: decided before anything is expanded
+        uint64_t most = 0, base = 0;
+        for (uint64_t c = 0; c < n;) {
+            uint64_t m = aln_wordjoin_cut(per.data(), n, c, cap), sum = 0;
+            if (!m) { g_err = "one candidate has more anchors than chunk_anchors allows"; return ALN_ERR_CAPACITY; }
+            m = std::min<uint64_t>(m, ALN_SEEDCHAIN_CHUNK_CANDIDATES);
+            for (uint64_t r = c; r < c + m; ++r) sum += per[r];
+            if (sum) { run_first.push_back(c); run_count.push_back(m); run_base.push_back(base); run_sum.push_back(sum); most = std::max(most, sum); }
+            base += sum;
+            c += m;
+        }
+        if (!most) return ALN_OK;
+        if ((st = dev_ensure(ss->ch_anchor, 8 * most, false)) != ALN_OK) return st;
+        if ((st = dev_ensure(ss->ch_state, sizeof(aln_seedchain_state) * most, false)) != ALN_OK) return st;
+        HIPCHK(hipEventRecord(ss->ev[0], q));
+        for (size_t r = 0; r < run_first.size(); ++r) {
+            aln_seedchain_launch_chunk(&x, sp, ss->ch_q.as<uint32_t>(), ss->ch_t.as<uint32_t>(), run_first[r], run_count[r], ss->ch_seeds.as<uint32_t>(),
+                                       ss->ch_chained.as<uint32_t>(), ss->ch_off.as<uint64_t>(), run_base[r], run_sum[r], ss->ch_anchor.as<uint64_t>(),
+                                       ss->ch_state.p, ss->ch_rec.as<aln_chain_record>(), misc + ALN_CHAIN_MISC_ERRORS, q);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(ss->ev[1], q));
+        HIPCHK(hipMemcpyAsync(h, misc, 4, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipStreamSynchronize(q));
+        run->kernels += ev_ms(ss->ev[0], ss->ev[1]);
+        run->down += 4;
+        if (h[ALN_CHAIN_MISC_ERRORS]) { g_err = "the anchors of a candidate differ from their count, or do not ascend"; return ALN_ERR_DEVICE; }
+        run->sum.anchors = total;
+        run->sum.chunks = run_first.size();
+        return ALN_OK;
+    });
+}
+
+static int seqset_candidate_chains(aln_seqset *ss, const aln_seedchain_spec *sp, uint64_t first, uint64_t n, aln_chain_record *records,
+                                   aln_seedchain_summary *summary)
+{
+    if (!ss || !sp) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    int st = seqset_chain_check(ss, sp);
+    if (st != ALN_OK) return st;
+    const uint64_t have = ss->cands.pair.size();
+    if (first > have || n > have - first) { g_err = "range beyond the candidate list"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && !records) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    ChainRun run;
+    if (n) {
+        if ((st = seqset_chain_run(ss, sp, first, n, &run)) != ALN_OK) return st;
+        HIPCHK(hipMemcpy(records, ss->ch_rec.p, sizeof(aln_chain_record) * n, hipMemcpyDeviceToHost));
+        run.down += sizeof(aln_chain_record) * n;
+    }
+    if (summary) *summary = run.sum;
+    seqset_done(ss, t0, run.up, run.down, run.kernels);
+    return ALN_OK;
+}
+
+// a device buffer that goes with its scope: what a filter allocates before it knows that everything else can be had
+struct ScopedDev {
+    DevBuf b;
+    ~ScopedDev() { dev_free(b); }
+};
+
+static int seqset_candidate_chain_filter(aln_seqset *ss, const aln_seedchain_spec *sp, int32_t min_score, uint32_t min_span,
+                                         aln_seedchain_summary *summary, uint64_t *count)
+{
+    if (!ss || !sp || !count) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    int st = seqset_chain_check(ss, sp);
+    if (st != ALN_OK) return st;
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    hipStream_t q = ss->slot->stream;
+    HIPCHK(hipStreamSynchronize(q));
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t n = ss->cands.pair.size();
+    ChainRun run;
+    ScopedDev new_k, new_rec;                          // everything new first: a failure leaves the list as it was
+    CandList kept;
+    uint32_t got = 0;
+    if ((st = dev_ensure(new_k.b, 8 * std::max<uint64_t>(n, 1), false)) != ALN_OK) return st;
+    if ((st = dev_ensure(new_rec.b, sizeof(aln_chain_record) * std::max<uint64_t>(n, 1), false)) != ALN_OK) return st;
+    if (n) {
+        if ((st = seqset_chain_run(ss, sp, 0, n, &run)) != ALN_OK) return st;
+        std::vector<uint32_t> pos;
+        st = run_queued(q, [&]() -> int {
+            int st;
+            uint32_t *tile_count = nullptr, *tile_off = nullptr, *d_count = ss->misc.as<uint32_t>() + ALN_SEQSET_MISC_CHAIN + ALN_CHAIN_MISC_KEPT;
+            if ((st = dev_ensure(ss->ch_pos, 4 * n, false)) != ALN_OK) return st;
+            if ((st = tiles_ensure(ss->tiles, aln_seqset_tiles(n), &tile_count, &tile_off)) != ALN_OK) return st;
+            HIPCHK(hipEventRecord(ss->ev[0], q));
+            aln_seedchain_launch_filter(ss->ch_rec.as<aln_chain_record>(), ss->cand_k.as<uint64_t>(), n, min_score, min_span, tile_count, tile_off, d_count, n,
+                                        ss->ch_pos.as<uint32_t>(), new_k.b.as<uint64_t>(), new_rec.b.as<aln_chain_record>(), q);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ss->ev[1], q));
+            HIPCHK(hipMemcpyAsync(&got, d_count, 4, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipStreamSynchronize(q));
+            run.kernels += ev_ms(ss->ev[0], ss->ev[1]);
+            if (got > n) { g_err = "the filter kept more entries than the list holds"; return ALN_ERR_DEVICE; }
+            pos.resize(got);
+            if (got) HIPCHK(hipMemcpy(pos.data(), ss->ch_pos.p, 4ull * got, hipMemcpyDeviceToHost));
+            run.down += 4 + 4ull * got;
+            return ALN_OK;
+        });
+        if (st != ALN_OK) return st;
+        // the kept entries of the host's copy, by their places: ascending places of the list
+        kept.pair.resize(got); kept.qs.resize(got); kept.ts.resize(got); kept.shared.resize(got);
+        if (ss->cands.has_diag) kept.diag.resize(got);
+        for (uint64_t o = 0; o < got; ++o) {
+            const uint64_t c = pos[o];
+            if (c >= n || (o && c <= pos[o - 1])) { g_err = "the kept places are not an ascending list of the list's places"; return ALN_ERR_DEVICE; }
+            kept.pair[o] = ss->cands.pair[c]; kept.qs[o] = ss->cands.qs[c]; kept.ts[o] = ss->cands.ts[c]; kept.shared[o] = ss->cands.shared[c];
+            if (ss->cands.has_diag) kept.diag[o] = ss->cands.diag[c];
+        }
+    }
+    // all is there: the list, the resident pair numbers and the resident records change places
+    ss->cands.pair.swap(kept.pair); ss->cands.qs.swap(kept.qs); ss->cands.ts.swap(kept.ts); ss->cands.shared.swap(kept.shared); ss->cands.diag.swap(kept.diag);
+    ss->cands.has_chain = true;
+    std::swap(ss->cand_k, new_k.b);
+    std::swap(ss->chain_rec, new_rec.b);
+    if (summary) *summary = run.sum;
+    *count = got;
+    seqset_done(ss, t0, run.up, run.down, run.kernels);
+    return ALN_OK;
+}
+
+static int seqset_candidate_chain_records(aln_seqset *ss, uint64_t first, uint64_t n, aln_chain_record *records)
+{
+    const int st = seqset_cand_check(ss);
+    if (st != ALN_OK) return st;
+    if (!ss->cands.has_chain) { g_err = "the candidate list holds no chain records: aln_seqset_candidate_chain_filter makes the lists that do"; return ALN_ERR_INVALID_ARGUMENT; }
+    const uint64_t have = ss->cands.pair.size();
+    if (first > have || n > have - first) { g_err = "range beyond the candidate list"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (n && !records) { g_err = "null argument"; return ALN_ERR_INVALID_ARGUMENT; }
+    if (!n) return ALN_OK;
+    HIPCHK(hipSetDevice(ss->ctx->device));
+    HIPCHK(hipStreamSynchronize(ss->slot->stream));
+    HIPCHK(hipMemcpy(records, ss->chain_rec.as<aln_chain_record>() + first, sizeof(aln_chain_record) * n, hipMemcpyDeviceToHost));
+    return ALN_OK;                       // (no kernel runs: the stats stay the filter's, as aln_seqset_candidates leaves them the join's)
+}
+
+extern "C" int aln_seqset_candidate_chains(aln_seqset *ss, const aln_seedchain_spec *spec, uint64_t first, uint64_t n, aln_chain_record *records,
+                                           aln_seedchain_summary *summary)
+{
+    ALN_GUARDED(seqset_live(ss), seqset_candidate_chains(ss, spec, first, n, records, summary))
+}
+
+extern "C" int aln_seqset_candidate_chain_filter(aln_seqset *ss, const aln_seedchain_spec *spec, int32_t min_score, uint32_t min_span,
+                                                 aln_seedchain_summary *summary, uint64_t *count)
+{
+    ALN_GUARDED(seqset_live(ss), seqset_candidate_chain_filter(ss, spec, min_score, min_span, summary, count))
+}
+
+extern "C" int aln_seqset_candidate_chain_records(aln_seqset *ss, uint64_t first, uint64_t n, aln_chain_record *records)
+{
+    ALN_GUARDED(seqset_live(ss), seqset_candidate_chain_records(ss, first, n, records))
 }
 
 static int seqset_held_check(aln_seqset *ss)

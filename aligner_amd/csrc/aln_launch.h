@@ -1,6 +1,6 @@
 // aln_launch.h -- the launchers and code-object warm-ups that the kernel files (aln_kernels.hip, aln_traceback.hip, aln_scan.hip,
 // aln_shuffle.hip, aln_signif.hip, aln_pairset.hip, aln_seqset.hip, aln_loop.hip, aln_best.hip, aln_cluster.hip, aln_prefilter.hip,
-// aln_search.hip, aln_profile.hip, aln_msa.hip, aln_cigar.hip, aln_wordjoin.hip, aln_seedjoin.hip and aln_strand.hip) define and
+// aln_search.hip, aln_profile.hip, aln_msa.hip, aln_cigar.hip, aln_wordjoin.hip, aln_seedjoin.hip, aln_seedchain.hip and aln_strand.hip) define and
 // aln_host.hip calls.  Every one of those files includes this header, so the compiler holds each definition against the
 // declaration the host compiles against: they are extern "C", and a signature that drifted would still link.
 #pragma once
@@ -15,6 +15,7 @@
 #include "aln_profile_rules.h"
 #include "aln_msa_rules.h"
 #include "aln_cigar_rules.h"
+#include "../../include/aligner_hip_seedchain.h"
 
 // what every kernel of aln_cluster.hip takes: n label slots (node numbers 0 .. n - 1, those of `nodes` being nodes), m listed edges
 struct ClusterArgs {
@@ -342,6 +343,30 @@ void aln_seedjoin_launch_expand(const uint64_t *keys, const uint32_t *pos, const
 void aln_seedjoin_launch_append(const uint64_t *sorted, uint64_t n, uint64_t k_lo, uint64_t chunk_pairs, uint32_t band, uint32_t min_seeds,
                                 uint64_t *slots, uint32_t *errors, uint32_t *tile_count, uint32_t *tile_off, uint32_t *pairs_seen, uint32_t *count,
                                 uint64_t room, uint64_t *out_k, uint32_t *out_seeds, int32_t *out_diag, hipStream_t s);
+
+// ---- aln_seedchain.hip: the seed chains of a sequence set's candidate list (aln_seedchain_rules.h)
+int aln_warm_seedchain(void);
+// the resident set (n_seqs records, `total` residues) and its seed index P (n occurrences: keys ascending, pos beside them)
+struct aln_seedchain_index {
+    const uint8_t *seqs; const uint64_t *seq_off; const uint32_t *seq_len; uint64_t n_seqs, total;
+    const uint64_t *keys; const uint32_t *pos; uint64_t n;
+};
+// candidates 0 .. n - 1 (cand_q / cand_t: their records): seeds[c] = A, chained[c] = the anchors it chains (0 where it overflows),
+// offsets[c] = the chained anchors in front of it, total[0] = all of them; records[c]: the record of a pair that chains nothing (the
+// chunks write the others).  errors[0] counts what never happens on a sound index
+void aln_seedchain_launch_count(const aln_seedchain_index *x, const aln_seedchain_spec *sp, const uint32_t *cand_q, const uint32_t *cand_t, uint64_t n,
+                                uint32_t *seeds, uint32_t *chained, uint64_t *offsets, uint64_t *total, aln_chain_record *records, uint32_t *errors,
+                                hipStream_t s);
+// candidates c0 .. c0 + m - 1, at most 2^22 of them: expand their anchors (8 bytes each) into `anchors` and chain them with `state`
+// (16 bytes each) beside; both hold `room` = the run's chained anchors, the run's first at offset `base`
+void aln_seedchain_launch_chunk(const aln_seedchain_index *x, const aln_seedchain_spec *sp, const uint32_t *cand_q, const uint32_t *cand_t, uint64_t c0,
+                                uint64_t m, const uint32_t *seeds, const uint32_t *chained, const uint64_t *offsets, uint64_t base, uint64_t room,
+                                uint64_t *anchors, void *state, aln_chain_record *records, uint32_t *errors, hipStream_t s);
+// the kept entries of n in list order: their places, pair numbers and records, `room` each; count[0]: how many.  tile_count /
+// tile_off: aln_select_tiles(n) words each
+void aln_seedchain_launch_filter(const aln_chain_record *records, const uint64_t *cand_k, uint64_t n, int32_t min_score, uint32_t min_span,
+                                 uint32_t *tile_count, uint32_t *tile_off, uint32_t *count, uint64_t room, uint32_t *out_pos, uint64_t *out_k,
+                                 aln_chain_record *out_records, hipStream_t s);
 
 // ---- aln_strand.hip: the mirrors of a stranded sequence set (aln_strand_rules.h)
 // seqs: 2 * total + 256 bytes, the first `total` the n records packed in order; off, len: theirs; map: 256 bytes

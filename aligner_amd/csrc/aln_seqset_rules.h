@@ -48,6 +48,12 @@
 #define ALN_JOIN_MISC_SCANNED 2u       // occurrences (seeds) the chunk's offsets summed
 #define ALN_JOIN_MISC_PAIRS_SEEN 3u    // seed join: the chunk's pairs with a seed
 #define ALN_JOIN_MISC_DROPPED 4u       // seed join: the words max_occ dropped, counted by the plan
+// the seed chains: ALN_SEQSET_MISC_CHAIN + ...  A call zeroes the four before its first launch
+#define ALN_SEQSET_MISC_CHAIN 32u
+#define ALN_SEQSET_MISC_CHAIN_WORDS 4u
+#define ALN_CHAIN_MISC_ERRORS 0u       // what the kernels found that a sound index never shows
+#define ALN_CHAIN_MISC_KEPT 1u         // the entries a filter kept (written by the compaction's offsets step)
+#define ALN_CHAIN_MISC_TOTAL 2u        // words 2, 3: the chained anchors of the call, 64 bits (written by the offsets step)
 
 // pairs of a block over a set of n_seqs sequences; 0 for an invalid block (a range past the set, upper with unequal ranges, a
 // reserved word that is not 0, no pairs)

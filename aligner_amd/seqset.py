@@ -332,7 +332,7 @@ class SeqSet:
         runtime.raise_for_status(st, "aln_seqset_seed_join")
         return Candidates(self, int(count.value), diags=True,
                           summary=dict(seeds=int(summ.seeds), pairs_with_seed=int(summ.pairs_with_seed), words_dropped=int(summ.words_dropped),
-                                       chunks=int(summ.chunks)))
+                                       chunks=int(summ.chunks)), seed=(int(k), int(alphabet_size)))
 
     def stats(self):
         """(after best, fetch_kernel_ms is the selection kernels' time until a held fetch overwrites it; after kmer_index and
@@ -342,16 +342,33 @@ class SeqSet:
         return dict(fill_ms=ms[0], refill_ms=ms[1], fetch_kernel_ms=ms[2], wall_ms=ms[3], bytes_up=int(by[0]), bytes_down=int(by[1]))
 
 
+# aln_chain_record (include/aligner_hip_seedchain.h)
+CHAIN_RECORD = np.dtype([("score", "<i4"), ("anchors", "<u4"), ("q_start", "<u4"), ("q_end", "<u4"), ("t_start", "<u4"), ("t_end", "<u4"),
+                         ("seeds", "<u4"), ("flags", "<u4")])
+
+
+def _chain_summary(summ):
+    return dict(anchors=int(summ.anchors), with_anchor=int(summ.with_anchor), overflowed=int(summ.overflowed), chunks=int(summ.chunks))
+
+
 class Candidates:
     """The candidate list of SeqSet.prefilter: .index (pair numbers in the block), .q, .t (sequence numbers) and .shared (distinct
     words both sequences hold) in ascending pair order.  .score(...) aligns the candidates only, .hits(...) holds those at or above
     a threshold as SeqSet.hits would, .best(...) the k best of every query's candidates as SeqSet.best would.  A list of
     SeqSet.seed_join holds the seeds of the pair's best band in .shared, and has .diag (int32, the band's least diagonal) and .summary;
-    on the other routes both are None."""
+    on the other routes both are None.  .chains(...) gives every candidate's seed chain (CHAIN_RECORD), .chain_filter(...) the list
+    of those whose chain is good enough, which carries the kept records in .chain.  .chain_summary is None until .chains has run, then
+    the counts of its last call (anchors, with_anchor, overflowed, chunks)."""
 
-    def __init__(self, owner, count, diags=False, summary=None):
+    def __init__(self, owner, count, diags=False, summary=None, seed=None, chain=False):
         self.owner, self.count = owner, count
-        self.diag, self.summary = None, summary
+        self.diag, self.summary, self.chain, self.chain_summary = None, summary, None, None
+        self._seed = seed                 # (k, alphabet_size) of the seed index a seed-join list was made from
+        if chain:
+            self.chain = np.zeros(count, dtype=CHAIN_RECORD)
+            if count:
+                st = owner.lib.aln_seqset_candidate_chain_records(owner.handle, 0, count, self.chain.ctypes.data)
+                runtime.raise_for_status(st, "aln_seqset_candidate_chain_records")
         if diags:
             self.diag = np.zeros(count, dtype=np.int32)
             if count:
@@ -368,6 +385,57 @@ class Candidates:
 
     def __len__(self):
         return self.count
+
+    def _chain_spec(self, max_gap, max_skew, gap_scale, max_occ, max_pair_seeds, chunk_anchors, k, alphabet_size):
+        """the spec of a chaining call.  The set's seed index must be of (k, alphabet_size): it is built here only while the list is
+        empty, since building an index drops the list; otherwise ValueError asks for seed_index before the list is made"""
+        if k is None and alphabet_size is None and self._seed is not None:
+            k, alphabet_size = self._seed
+        if k is None or alphabet_size is None:
+            raise TypeError("a list of prefilter or word_join names no seed index: give k= and alphabet_size=")
+        o = self.owner
+        if getattr(o, "_seed", None) != (int(k), int(alphabet_size)):
+            if self.count:
+                raise ValueError("the set's seed index is not of (k, alphabet_size) = (%d, %d) and building it would drop this list: "
+                                 "call seed_index before the list is made" % (int(k), int(alphabet_size)))
+            o.seed_index(k, alphabet_size)
+        return _ffi.SeedchainSpec(int(k), int(alphabet_size), int(max_occ), int(max_gap), int(max_skew), int(gap_scale), int(max_pair_seeds),
+                                  int(chunk_anchors), 0, (C.c_uint32 * 3)(0, 0, 0))
+
+    def chains(self, max_gap=1000, max_skew=200, gap_scale=2, max_occ=0, max_pair_seeds=0, chunk_anchors=0, k=None, alphabet_size=None):
+        """aln_seqset_candidate_chains: the colinear chain over all seeds (anchors) of every candidate, on the device, as a structured
+        array (CHAIN_RECORD: score, anchors, q_start, q_end, t_start, t_end, seeds, flags) in list order.  An anchor may follow another
+        within max_gap on both records and max_skew of diagonal drift; a link gains min(the two distances, k) and costs
+        (drift * gap_scale) >> 4; the chain ends at the best anchor, the ends are half open.  A candidate with more than
+        max_pair_seeds anchors (0: 2 ** 16) is not chained: flags = CHAIN_OVERFLOW, seeds = its anchors.  The list stays as it is.  On
+        a list of prefilter or word_join, k and alphabet_size name the seed index and are required.  The seed index of that (k,
+        alphabet_size) must already be there: building one drops the candidate list, so on a list that is not empty this raises
+        ValueError instead of building it (call SeqSet.seed_index before the list is made; a seed_join list always has its index).
+        The call's counts (anchors, with_anchor, overflowed, chunks) are left in .chain_summary."""
+        spec = self._chain_spec(max_gap, max_skew, gap_scale, max_occ, max_pair_seeds, chunk_anchors, k, alphabet_size)
+        out = np.zeros(self.count, dtype=CHAIN_RECORD)
+        summ = _ffi.SeedchainSummary()
+        o = self.owner
+        st = o.lib.aln_seqset_candidate_chains(o.handle, C.byref(spec), 0, self.count, out.ctypes.data if self.count else None, C.byref(summ))
+        runtime.raise_for_status(st, "aln_seqset_candidate_chains")
+        self.chain_summary = _chain_summary(summ)
+        return out
+
+    def chain_filter(self, min_score, min_span=0, max_gap=1000, max_skew=200, gap_scale=2, max_occ=0, max_pair_seeds=0, chunk_anchors=0, k=None,
+                     alphabet_size=None):
+        """aln_seqset_candidate_chain_filter: replaces the set's candidate list with the candidates that overflowed or whose chain has
+        score >= min_score and spans at least min_span on both records, in their order.  Returns the new Candidates: .chain holds the
+        kept records, .summary the call's counts, .diag is carried over.  This object is stale afterwards, as after any call that
+        replaces the list (kmer_index / prefilter / word_join / seed_join).  As with chains, the seed index of (k, alphabet_size) must
+        already be there: ValueError on a list that is not empty otherwise, since building the index would drop the list."""
+        spec = self._chain_spec(max_gap, max_skew, gap_scale, max_occ, max_pair_seeds, chunk_anchors, k, alphabet_size)
+        summ = _ffi.SeedchainSummary()
+        count = C.c_uint64(0)
+        o = self.owner
+        st = o.lib.aln_seqset_candidate_chain_filter(o.handle, C.byref(spec), int(min_score), int(min_span), C.byref(summ), C.byref(count))
+        runtime.raise_for_status(st, "aln_seqset_candidate_chain_filter")
+        return Candidates(o, int(count.value), diags=self.diag is not None, summary=_chain_summary(summ), seed=(int(spec.k), int(spec.alphabet)),
+                          chain=True)
 
     def score(self, matrix, del_, ext, semantics=_ffi.CORE_LOCAL, blank=98, **kw):
         """(f, status) of every candidate, in list order: what SeqSet.score gives for those pairs, bit for bit."""
